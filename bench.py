@@ -13,6 +13,7 @@ reassembles the [T, nj] trajectory: weak scaling.
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...            # no launcher: spawns its own N worker processes (one per GPU, RCCL over 127.0.0.1)
     python bench.py --gpus N --scaling strong --total-batches 1024   # ONE fixed stream of 32768 frames split over the N ranks
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR  # + the last timed step's mu / conf / idx as DIR/<name>.npy
 
 Rank 0 prints ONE JSON line.  Extra objects: "roofline" (conv kernel, MFMA-bound, fp32 matrix
 peak) from hipEvent pairs recorded around every launch inside the timed region, and
@@ -464,6 +465,8 @@ def main():
     ap.add_argument("--no-r101", action="store_true", help="skip the ResNet-101 1280x720 child run (BASELINE configs[4] per-GPU shape)")
     ap.add_argument("--no-train-step", action="store_true", help="skip the training-step child run (BASELINE configs[3]) after the timed region")
     ap.add_argument("--train-steps", type=int, default=60, help="timed steps of the training-step child run")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (mu, conf, idx of its batch) as DIR/<name>.npy")
     ap.add_argument("--strict-f32-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tier-f16-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -504,6 +507,8 @@ def main():
     ident = dict(ddist.device_identity(local_rank), rank=rank, **numa)
 
     B, K, Wm = args.batch, args.steps, args.warmup
+    if K < 1 and args.scaling == "weak":
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.scaling == "strong":      # one fixed stream, independent of N: rank r runs batches [r TB / N, (r + 1) TB / N)
         if args.total_batches % world:
             raise SystemExit("bench.py: --total-batches %d must be a multiple of --gpus %d" % (args.total_batches, world))
@@ -593,6 +598,17 @@ def main():
     barrier()
     t1 = time.perf_counter()
     n_prof, launches = net.profile_end()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's batch as a caller of the packed path receives it (dist.unpack_keypoints): soft-argmax coordinates, likelihoods,
+        # arg-max indices; the inputs are seeded, so two builds can be compared output for output
+        mu, conf, idx = ddist.unpack_keypoints(traj[(K - 1) * B:K * B])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = {"mu": mu.cpu().numpy().astype(np.float32), "conf": conf.cpu().numpy().astype(np.float32),
+                  "idx": idx.cpu().numpy().astype(np.float64)}
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        dumped = {"dir": args.dump_outputs, "step": K - 1, "arrays": {name: list(a.shape) for name, a in dumped.items()}}
 
     # sustained segment (untimed for `value`): >= 5 s of back-to-back steps so that clocks, power and the driver's SMI sampler see
     # a loaded GPU; reports the rate and the shader clock sysfs shows while it runs
@@ -711,6 +727,8 @@ def main():
         "collective": collective,
         "activation_format": "H2 (fp16 high/low cells, calibrated per-tensor scales; include/dgp_hip.h)" if n_calib else "fp32",
     }
+    if dumped:
+        out["dump_outputs"] = dumped
 
     if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
         from oracle import dgp_oracle as O      # checker / baseline only

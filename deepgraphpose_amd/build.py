@@ -18,6 +18,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libdgp_hip.so")
+# the same sources with -DDGP_TUNING (the A/B switches read from the environment, the opt-in paths that measured slower): loaded only
+# through DGP_HIP_LIB, by the tests of those paths
+TUNING_LIB = os.path.join(HERE, "libdgp_hip_tuning.so")
 SOURCES = ["dgp_kernels.hip", "dgp_ops.hip", "dgp_chain.hip", "dgp_loss.hip", "dgp_net.hip", "dgp_train.hip"]
 HEADERS = ["dgp_internal.h", "dgp_device.h", "dgp_engine.h", os.path.join("..", "..", "include", "dgp_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
@@ -50,27 +53,35 @@ def _extra_flags() -> list:
     return os.environ.get("DGP_BUILD_FLAGS", "").split()
 
 
-def source_hash() -> str:
+def _variant(tuning: bool):
+    """(object directory, library, compile flags) of the product build or of the -DDGP_TUNING one"""
+    if tuning:
+        return os.path.join(OBJDIR, "tuning"), TUNING_LIB, FLAGS + _extra_flags() + ["-DDGP_TUNING"]
+    return OBJDIR, LIB, FLAGS + _extra_flags()
+
+
+def source_hash(tuning: bool = False) -> str:
     """sha256 over every source, every header and the compile flags: what libdgp_hip.so.sha must hold for the library to be current"""
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
-    return _sha(deps, " ".join(FLAGS + _extra_flags()))
+    return _sha(deps, " ".join(_variant(tuning)[2]))
 
 
-def needs_build() -> bool:
-    return not os.path.exists(LIB) or _read(LIB + ".sha") != source_hash()
+def needs_build(tuning: bool = False) -> bool:
+    lib = _variant(tuning)[1]
+    return not os.path.exists(lib) or _read(lib + ".sha") != source_hash(tuning)
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
-    if not force and not needs_build():
-        return LIB
+def build(force: bool = False, verbose: bool = True, tuning: bool = False) -> str:
+    objdir, lib, flags = _variant(tuning)
+    if not force and not needs_build(tuning):
+        return lib
     hipcc = _hipcc()
-    os.makedirs(OBJDIR, exist_ok=True)
-    flags = FLAGS + _extra_flags()
+    os.makedirs(objdir, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
 
     def compile_one(src: str) -> str:
         path = os.path.join(CSRC, src)
-        obj = os.path.join(OBJDIR, src + ".o")
+        obj = os.path.join(objdir, src + ".o")
         want = _sha([path] + hdrs, " ".join(flags))
         if not force and os.path.exists(obj) and _read(obj + ".sha") == want:
             return obj
@@ -85,15 +96,14 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs = max(1, min(len(SOURCES), os.cpu_count() or 1))
     with ThreadPoolExecutor(jobs) as ex:
         objs = list(ex.map(compile_one, SOURCES))
-    cmd = [hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB] + objs
+    cmd = [hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", lib] + objs
     if verbose:
         print("[dgp build]", " ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    with open(LIB + ".sha", "w") as f:
-        f.write(source_hash())
-    return LIB
+    with open(lib + ".sha", "w") as f:
+        f.write(source_hash(tuning))
+    return lib
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
-    print(LIB)
+    print(build(force="--force" in sys.argv, tuning="--tuning" in sys.argv))

@@ -24,11 +24,13 @@ def eng(lib_built):
 _TUNING_ONLY = {"DGP_STEM_ROWS", "DGP_PRESPLIT_WEIGHTS", "DGP_STEM_FUSED", "DGP_DMA", "DGP_COMPUTE_SPLIT"}
 
 
-def _skip_unless_tuning_build(extra):
-    if _TUNING_ONLY & set(extra):
-        from deepgraphpose_amd import _lib
-        if not _lib.load().dgp_tuning_build():
-            pytest.skip("switch of -DDGP_TUNING builds: the product build compiles its default in")
+def _tuning_lib_env(extra, request):
+    """A child process that sets one of these switches runs the -DDGP_TUNING library (conftest.tuning_lib): the product build compiles
+    their defaults in and would ignore them."""
+    from deepgraphpose_amd import _lib
+    if not _TUNING_ONLY & set(extra) or _lib.load().dgp_tuning_build():
+        return {}
+    return {"DGP_HIP_LIB": request.getfixturevalue("tuning_lib")}
 
 
 def _rel_err(a, b):
@@ -602,12 +604,11 @@ def test_fp16_split_keeps_fp32_class_accuracy_over_wide_ranges(eng, monkeypatch)
                                         ("f16x3", {"DGP_FUSE_SHORTCUT": "0"}),               # H2 engine, shortcut convs as their own launches
                                         ("f16x3", {"DGP_STEM_FUSED": "0"}),                  # H2 engine, root block as three launches
                                         ("f16x3", {"DGP_H2": "0"})])                         # fp32 activations (round-1 path)
-def test_other_conv_modes_keep_parity(eng, mode, extra):
+def test_other_conv_modes_keep_parity(eng, mode, extra, request):
     """The conv path is chosen once per process (DGP_CONV_MODE and the A/B switches are read at first use), so the
     non-default paths -- fp32 MFMA, the range-free bf16x6 split, and fp16x3 without fused shortcut / row-walk stem /
     pre-split weights -- run in a child process: whole-network parity vs the oracle on a small ResNet-50."""
     import subprocess, sys, os, textwrap
-    _skip_unless_tuning_build(extra)
     code = textwrap.dedent('''
         import sys, numpy as np, torch
         sys.path.insert(0, %r)
@@ -623,7 +624,7 @@ def test_other_conv_modes_keep_parity(eng, mode, extra):
         ok = np.array_equal(idx.cpu().numpy(), ref["idx"])
         print("RESULT", d, ok)
     ''') % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DGP_CONV_MODE=mode, **extra)
+    env = dict(os.environ, DGP_CONV_MODE=mode, **extra, **_tuning_lib_env(extra, request))
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")]
     assert line, out.stdout[-2000:] + out.stderr[-2000:]
@@ -755,13 +756,12 @@ def test_calculate_motion_energy_hip_backend_matches_host(eng):
 
 
 @pytest.mark.parametrize("extra", [{}, {"DGP_DMA": "0"}, {"DGP_COMPUTE_SPLIT": "0"}])
-def test_cell_kernels_match_fp64_per_layer(eng, extra):
+def test_cell_kernels_match_fp64_per_layer(eng, extra, request):
     """Single layers on the engine's pre-split-cell kernels (compute-side split, LDS-DMA loaders, 16x16x32 pipelined loop;
     DGP_CONV2D_CELLS=1 is read once per process, so this runs in a child): pointwise / 3x3 / dilated / strided shapes with ragged
     row counts and several K depths against an fp64 reference, plus an exact selection-matrix case that catches any row / column /
     k permutation (operands chosen so that every product is exact)."""
     import subprocess, sys, os, textwrap
-    _skip_unless_tuning_build(extra)
     code = textwrap.dedent('''
         import sys, numpy as np, torch
         sys.path.insert(0, %r)
@@ -794,7 +794,7 @@ def test_cell_kernels_match_fp64_per_layer(eng, extra):
         exact = bool(np.array_equal(y, x.reshape(M, Cin)[:, np.arange(Cout) %% Cin]))
         print("RESULT", worst, exact)
     ''') % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DGP_CONV2D_CELLS="1", **extra)
+    env = dict(os.environ, DGP_CONV2D_CELLS="1", **extra, **_tuning_lib_env(extra, request))
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")]
     assert line, out.stdout[-2000:] + out.stderr[-2000:]

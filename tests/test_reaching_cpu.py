@@ -1,8 +1,9 @@
 """SURVEY.md 8(c) fixture (5) and BASELINE configs[0] plumbing on the reference's own demo project (Reaching-Mackenzie-2018-08-30).
 
 tests/golden/reaching_vectors.npz was produced by RUNNING the reference loader and the reference's own lines on the shipped .mat
-(tests/golden/make_reaching_golden.py); the .mat itself is kept beside it as an input data file.  The last test opens the real
-project tree and only runs where /root/reference exists (the build container).
+(tests/golden/make_reaching_golden.py); the .mat itself is kept beside it as an input data file.  The last test assembles the
+project tree from the project's own files stored under tests/golden: its config.yaml and both pose_cfg.yaml (reaching_project/),
+its 55 labeled PNGs (reaching_frames/) and its training .mat.
 """
 import os
 import shutil
@@ -12,7 +13,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MAT = os.path.join(HERE, "golden", "Reaching_Mackenzie95shuffle1.mat")
-REF_PROJ = "/root/reference/data/Reaching-Mackenzie-2018-08-30"
+PROJ_FILES = os.path.join(HERE, "golden", "reaching_project")
+FRAMES = os.path.join(HERE, "golden", "reaching_frames")
 BODYPARTS = ["Hand", "Finger1", "Tongue", "Joystick1", "Joystick2"]
 SKELETON = [["Hand", "Finger1"], ["Joystick1", "Joystick2"]]
 
@@ -76,10 +78,18 @@ def test_dlc_pose_dataset_loads_the_mat_like_the_reference(G, tmp_path):
     np.testing.assert_array_equal(flat, G["joints_flat"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PROJ), reason="the reference tree only exists in the build container")
+def _reaching_project(dst):
+    """The Reaching demo project as it ships (no video), from the files stored under tests/golden."""
+    shutil.copytree(PROJ_FILES, dst)
+    shutil.copytree(FRAMES, os.path.join(dst, "labeled-data", "reachingvideo1"))
+    ts = os.path.join(dst, "training-datasets", "iteration-0", "UnaugmentedDataSet_ReachingAug30")
+    os.makedirs(ts)
+    shutil.copy(MAT, ts)
+
+
 def test_real_reaching_project_plumbing(G, tmp_path, monkeypatch):
     """BASELINE configs[0] without a GPU: the demo script's config rewriting on a copy of the real project, both pose_cfg.yaml,
-    the 55 labeled PNGs (57 directory entries) as a pseudo-video, the batch bookkeeping and the loss pre-computation (5 bodyparts / 2 limbs)."""
+    the 55 labeled PNGs as a pseudo-video, the batch bookkeeping and the loss pre-computation (5 bodyparts / 2 limbs)."""
     import sys
     import yaml
     sys.path.insert(0, os.path.join(os.path.dirname(HERE), "demo"))
@@ -93,10 +103,7 @@ def test_real_reaching_project_plumbing(G, tmp_path, monkeypatch):
 
     work = tmp_path / "work"
     dst = work / demo.DEMO_PROJECT
-    shutil.copytree(REF_PROJ, dst)
-    for root, dirs, files in os.walk(dst):                    # the reference tree is read-only
-        for n in dirs + files:
-            os.chmod(os.path.join(root, n), 0o755)
+    _reaching_project(dst)
     monkeypatch.chdir(work)
     before = {p: open(p).read() for p in (str(dst / "config.yaml"), demo.get_model_cfg_path(str(work), demo.DEMO_PROJECT, "train"),
                                           demo.get_model_cfg_path(str(work), demo.DEMO_PROJECT, "test"))}
