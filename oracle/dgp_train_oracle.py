@@ -337,6 +337,7 @@ def dlc_loss(pred, locref_pred, part_targets, locref_targets, locref_mask, part_
     if part_weights is None:
         part = ce.mean()
     else:
+        part_weights = part_weights.expand_as(ce)             # TF's _num_present counts the weights broadcast to the loss's shape
         nz = (part_weights != 0).sum()
         part = (ce * part_weights).sum() / nz if nz > 0 else ce.sum() * 0
     out = {"part_loss": part, "total_loss": part}
@@ -344,6 +345,7 @@ def dlc_loss(pred, locref_pred, part_targets, locref_targets, locref_mask, part_
         d = locref_pred - locref_targets
         ad = d.abs()
         el = torch.where(ad < 1.0, 0.5 * d * d, ad - 0.5) if huber else d * d
+        locref_mask = locref_mask.expand_as(el)
         nz = (locref_mask != 0).sum()
         loc = locref_loss_weight * ((el * locref_mask).sum() / nz if nz > 0 else el.sum() * 0)
         out["locref_loss"] = loc

@@ -50,3 +50,52 @@ def brute_force(in_shape, f_shape, stride, padding):
                     if 0 <= r < h and 0 <= c < wd:
                         y[:, i, j] += x[:, r, c] @ w[a, b]
     return y
+
+
+# ---- the training step's tail: losses and optimiser -------------------------------------------------------------------------
+# Closed forms of the TF ops fit_dgp / pose_net.train build their loss and update from.  Every number is derived by hand beside it,
+# so they pin the oracle (tests/test_oracle_cpu.py) and the kernels (tests/test_optimizer_gpu.py, tests/test_loss_edges_gpu.py) to
+# the definitions instead of to each other.
+
+# tf.losses.sigmoid_cross_entropy, reduction SUM_BY_NONZERO_WEIGHTS (losses_test.py SigmoidCrossEntropyLossTest).
+# Per element ce = max(x, 0) - x z + log1p(exp(-|x|)); at |x| = 100 the log1p term is 4e-44, so a right element costs 0 and a
+# wrong one costs 100.
+CE_LOGITS = np.array([[100.0, -100.0, -100.0], [-100.0, 100.0, -100.0], [-100.0, -100.0, 100.0]])
+CE_LABELS_RIGHT = np.eye(3)
+CE_LABELS_WRONG = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+CE_KNOWN_ANSWERS = [
+    # (name, labels, weights or None, expected loss)
+    ("all right", CE_LABELS_RIGHT, None, 0.0),                               # every element right: 0 / 9
+    ("all wrong", CE_LABELS_WRONG, None, 600.0 / 9.0),                       # two wrong elements per row, 100 each: 600 / 9
+    # per-element weights: wrong elements (0,0) (0,2) (1,0) (1,1) (2,1) (2,2) weigh 3+5+2+6+0+1 = 17 -> 1700; 7 weights are non-zero
+    ("all wrong, element weights", CE_LABELS_WRONG, np.array([[3.0, 4.0, 5.0], [2.0, 6.0, 0.0], [8.0, 0.0, 1.0]]), 1700.0 / 7.0),
+    ("all wrong, all weights zero", CE_LABELS_WRONG, np.zeros((3, 3)), 0.0),  # no non-zero weight: 0, not 0 / 0
+]
+# One weight per marker, broadcast over its H x W map ([n, 1, 1]): two markers (the 3 x 3 map above, all wrong, 600 each) weighing 3
+# and 0.  Sum 3 * 600 = 1800; the denominator counts the BROADCAST weights, H * W = 9 per non-zero marker: 1800 / 9 = 200.
+CE_MARKER_WEIGHTS = np.array([3.0, 0.0])
+CE_MARKER_WEIGHTS_LOSS = 200.0
+
+# tf.losses.huber_loss, delta 1: 0.5 d^2 for |d| <= 1, |d| - 0.5 beyond (both give 0.5 at |d| = 1)
+HUBER_D = np.array([0.0, 0.5, 1.0, 3.0, -2.0])
+HUBER_EL = np.array([0.0, 0.125, 0.5, 2.5, 1.5])                           # 0; .5 * .25; .5 * 1; 3 - .5; 2 - .5
+HUBER_MASK = np.array([1.0, 1.0, 0.0, 1.0, 0.0])
+HUBER_MEAN = 4.625 / 5.0                                                   # mask all ones: (0 + .125 + .5 + 2.5 + 1.5) / 5
+HUBER_MASKED = 2.625 / 3.0                                                 # mask above: (0 + .125 + 2.5) / 3 non-zero
+# tf.losses.mean_squared_error with the same mask (the locref_huber_loss=False branch): (0 + .25 + 9) / 3
+MSE_MASKED = 9.25 / 3.0
+
+# tf.clip_by_global_norm (clip_ops_test.py testClipByGlobalNorm / ...NotClipped): global norm sqrt(4 + 16 + 1 + 4) = 5
+CLIP_T0 = np.array([[-2.0, 0.0, 0.0], [4.0, 0.0, 0.0]])
+CLIP_T1 = np.array([1.0, -2.0])
+CLIP_NORM = 5.0
+CLIP_AT_4 = (np.array([[-1.6, 0.0, 0.0], [3.2, 0.0, 0.0]]), np.array([0.8, -1.6]))     # scale 4 / 5
+CLIP_AT_6 = (CLIP_T0, CLIP_T1)                                                           # 5 <= 6: unchanged
+
+# tf.train.MomentumOptimizer (momentum_test.py testBasic): lr 2, momentum 0.9, accum = m accum + g, var -= lr accum.
+# var0 [1, 2] with g 0.1: accum 0.1 -> var 1 - 0.2; accum 0.9 * 0.1 + 0.1 = 0.19 -> var 0.8 - 0.38
+# var1 [3, 4] with g 0.01: accum 0.01 -> var 3 - 0.02; accum 0.019 -> var 2.98 - 0.038
+MOMENTUM_LR, MOMENTUM_M = 2.0, 0.9
+MOMENTUM_VAR0, MOMENTUM_G0 = np.array([1.0, 2.0]), 0.1
+MOMENTUM_VAR1, MOMENTUM_G1 = np.array([3.0, 4.0]), 0.01
+MOMENTUM_STEPS = [(np.array([0.8, 1.8]), np.array([2.98, 3.98])), (np.array([0.42, 1.42]), np.array([2.942, 3.942]))]

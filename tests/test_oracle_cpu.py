@@ -397,3 +397,100 @@ def test_tf_max_pool_same_known_answer():
     for n, want in ((4, [[10, 11], [14, 15]]), (5, [[6, 8, 9], [16, 18, 19], [21, 23, 24]])):
         z = np.arange(n * n, dtype=np.float32).reshape(1, n, n, 1)
         np.testing.assert_array_equal(O.max_pool_same(_nchw(z), 3, 2)[0, 0].numpy(), want)
+
+
+# ---- the training step's tail against TF's closed forms (tests/_tf_kat.py) ---------------------------------------------------
+def _t(a):
+    return torch.as_tensor(np.asarray(a, np.float64))
+
+
+@pytest.mark.parametrize("case", __import__("_tf_kat").CE_KNOWN_ANSWERS, ids=lambda c: c[0])
+def test_sigmoid_cross_entropy_known_answers(case):
+    """tf.losses.sigmoid_cross_entropy with SUM_BY_NONZERO_WEIGHTS on TF's own 3 x 3 logits: _sigmoid_ce element by element, and
+    dlc_loss (the 3 x 3 map as nt=1, H=3, W=3, nj=1) for the reduction -- weighted sum over the number of non-zero weights, 0 when none."""
+    import _tf_kat as K
+    from oracle import dgp_train_oracle as T
+    name, labels, weights, want = case
+    ce = T._sigmoid_ce(_t(labels), _t(K.CE_LOGITS)).numpy()
+    np.testing.assert_allclose(ce, 100.0 * (labels != np.eye(3)), rtol=0, atol=1e-40)
+    w = None if weights is None else _t(weights).reshape(1, 3, 3, 1)
+    L = T.dlc_loss(_t(K.CE_LOGITS).reshape(1, 3, 3, 1), None, _t(labels).reshape(1, 3, 3, 1), None, None, w)
+    assert abs(float(L["part_loss"]) - want) <= 1e-12 * max(1.0, want), (float(L["part_loss"]), want)
+
+
+def test_sigmoid_cross_entropy_broadcast_marker_weights_count_every_cell():
+    """A weight per marker ([n, 1, 1, 1] against [n, H, W, 1]): TF's _num_present broadcasts the weights to the loss's shape before it
+    counts them, so the denominator is H * W per non-zero marker (3 * 600 / 9 = 200), not the number of markers (1800)."""
+    import _tf_kat as K
+    from oracle import dgp_train_oracle as T
+    x = _t(np.stack([K.CE_LOGITS] * 2)).reshape(2, 3, 3, 1)
+    z = _t(np.stack([K.CE_LABELS_WRONG] * 2)).reshape(2, 3, 3, 1)
+    w = _t(K.CE_MARKER_WEIGHTS).reshape(2, 1, 1, 1)
+    assert abs(float(T.dlc_loss(x, None, z, None, None, w)["part_loss"]) - K.CE_MARKER_WEIGHTS_LOSS) <= 1e-12 * K.CE_MARKER_WEIGHTS_LOSS
+    # the same weights written out in full: the same loss
+    L = T.dlc_loss(x, None, z, None, None, w.expand(2, 3, 3, 1).clone())
+    assert abs(float(L["part_loss"]) - K.CE_MARKER_WEIGHTS_LOSS) <= 1e-12 * K.CE_MARKER_WEIGHTS_LOSS
+
+
+def _locref_only(d, mask, huber):
+    """dgp_loss on one visible marker of a 1 x 5 map whose locref residuals (both channels) are d: -> (visible_loss_locref, d loss / d d)"""
+    from oracle import dgp_train_oracle as T
+    W = d.size
+    lp = torch.tensor(np.repeat(d, 2).reshape(1, 1, W, 2), requires_grad=True)
+    batch = dict(targets=np.array([[[0.0, 2.0]]]), locref_map=np.zeros((1, 1, W, 2)), locref_mask=np.repeat(mask, 2).reshape(1, 1, W, 2),
+                 visible_marker=np.array([0]), hidden_marker=np.array([], np.int64), visible_marker_in_targets=np.array([0]), nt=1)
+    cfg = dict(nj=1, S0=np.zeros((0, 1)), ws=np.zeros(0), ws_max=np.zeros(0), stride=8.0, gamma=1.0, gauss_len=1, lengthscale=1.0,
+               gm2=0, gm3=0, wn_visible=5.0, wn_hidden=3.0, locref_loss_weight=1.0, locref_huber_loss=huber, n_frames_total=10.0,
+               n_visible_frames_total=5.0)
+    L = T.dgp_loss(torch.zeros((1, 1, W, 1), dtype=torch.float64), lp, batch, cfg)
+    L["visible_loss_locref"].backward()
+    return float(L["visible_loss_locref"].detach()), lp.grad.numpy()[0, 0, :, 0]
+
+
+def test_huber_and_squared_error_known_answers():
+    """tf.losses.huber_loss (delta 1) and tf.losses.mean_squared_error with SUM_BY_NONZERO_WEIGHTS, as the locref term of dgp_loss
+    (locref_huber_loss True / False) and as dlc_loss (huber 1 / 0): the values of _tf_kat, and the gradients by hand -- clip(d, -1, 1)
+    and 2 d, times the mask, over the number of non-zero mask entries."""
+    import _tf_kat as K
+    from oracle import dgp_train_oracle as T
+    d, m = K.HUBER_D, K.HUBER_MASK
+    ones = np.ones_like(d)
+    for mask, huber, want in ((ones, True, K.HUBER_MEAN), (m, True, K.HUBER_MASKED), (m, False, K.MSE_MASKED)):
+        v, g = _locref_only(d, mask, huber)
+        assert abs(v - want) <= 1e-15, (huber, v, want)
+        de = np.clip(d, -1, 1) if huber else 2 * d
+        np.testing.assert_allclose(g, mask * de / (2 * mask.sum()), rtol=0, atol=1e-15)        # two channels: twice the count
+        pred = torch.zeros((1, 1, d.size, 1), dtype=torch.float64)
+        lp = _t(d).reshape(1, 1, d.size, 1)
+        L = T.dlc_loss(pred, lp, pred, torch.zeros_like(lp), _t(mask).reshape(1, 1, d.size, 1), None, 1.0, huber=huber)
+        assert abs(float(L["locref_loss"]) - want) <= 1e-15
+    # element by element: the quadratic and linear branches meet at |d| = 1
+    v = [_locref_only(np.array([x]), np.ones(1), True)[0] for x in d]
+    np.testing.assert_allclose(v, K.HUBER_EL, rtol=0, atol=1e-15)
+
+
+def test_clip_by_global_norm_known_answers():
+    """tf.clip_by_global_norm through momentum_step (lr 1, momentum 0, so -var is the clipped gradient): norm 5; clip 4 scales by 0.8,
+    clip 6 and clip 0 (no clipping) leave the gradients alone."""
+    import _tf_kat as K
+    from oracle import dgp_train_oracle as T
+    for clip, want in ((4.0, K.CLIP_AT_4), (6.0, K.CLIP_AT_6), (0.0, K.CLIP_AT_6)):
+        P = {"t0": torch.zeros(2, 3, dtype=torch.float64, requires_grad=True), "t1": torch.zeros(2, dtype=torch.float64, requires_grad=True)}
+        P["t0"].grad, P["t1"].grad = _t(K.CLIP_T0), _t(K.CLIP_T1)
+        gn = T.momentum_step(P, {}, 1.0, momentum=0.0, clip=clip)
+        assert gn == K.CLIP_NORM
+        np.testing.assert_allclose(-P["t0"].detach().numpy(), want[0], rtol=0, atol=1e-15)
+        np.testing.assert_allclose(-P["t1"].detach().numpy(), want[1], rtol=0, atol=1e-15)
+
+
+def test_momentum_optimizer_known_answer():
+    """tf.train.MomentumOptimizer testBasic: two steps of lr 2, momentum 0.9 through momentum_step (the norm is far below the clip)."""
+    import _tf_kat as K
+    from oracle import dgp_train_oracle as T
+    P = {"v0": _t(K.MOMENTUM_VAR0).requires_grad_(), "v1": _t(K.MOMENTUM_VAR1).requires_grad_()}
+    V = {}
+    for want0, want1 in K.MOMENTUM_STEPS:
+        P["v0"].grad, P["v1"].grad = torch.full((2,), K.MOMENTUM_G0, dtype=torch.float64), torch.full((2,), K.MOMENTUM_G1, dtype=torch.float64)
+        T.momentum_step(P, V, K.MOMENTUM_LR, K.MOMENTUM_M, clip=10.0)
+        np.testing.assert_allclose(P["v0"].detach().numpy(), want0, rtol=0, atol=1e-14)
+        np.testing.assert_allclose(P["v1"].detach().numpy(), want1, rtol=0, atol=1e-14)
