@@ -44,7 +44,7 @@ def _im2col64(x, k, stride, rate, pad_t, pad_l, Ho, Wo):
 
 
 # (N, H, W, Cin, Cout, k, stride, rate) -- the config-4 layer shapes (nt = 11)
-WGRAD_CASES = [
+CONFIG4_WGRAD_CASES = [
     (11, 30, 40, 512, 512, 3, 1, 2),        # block4 conv2 (dilated): wgrad_h3, 128 x 128 tiles, 1024-workgroup grid
     (11, 30, 40, 1024, 256, 1, 1, 1),       # block3 conv1
     (11, 30, 40, 2048, 512, 1, 1, 1),       # block4 conv1 (deepest K)
@@ -54,6 +54,18 @@ WGRAD_CASES = [
     (11, 120, 160, 64, 64, 3, 1, 1),        # block1 conv2: Cout = 64
     (3, 480, 640, 4, 64, 7, 2, 1),          # stem (4-channel padded input)
 ]
+# stride-2 layers on odd grids (frames 33 x 65, 75 x 101 and the Reaching demo's 747 x 832): the last output row / column of a
+# stride-2 conv reads one padded input row / column, and the stem's 7 x 7 window hangs over both edges
+ODD_WGRAD_CASES = [
+    (3, 19, 26, 64, 64, 3, 2, 1),           # block1 unit_3 conv2 at 75 x 101 (odd rows)
+    (3, 10, 13, 128, 128, 3, 2, 1),         # block2 unit_4 conv2 at 75 x 101 (odd columns)
+    (3, 5, 9, 128, 128, 3, 2, 1),           # block2 unit_4 conv2 at 33 x 65 (odd on both axes, 3 x 5 output)
+    (2, 187, 208, 64, 64, 3, 2, 1),         # block1 unit_3 conv2 at 747 x 832
+    (3, 19, 13, 256, 512, 1, 2, 1),         # strided 1 x 1 on an odd grid
+    (2, 75, 101, 4, 64, 7, 2, 1),           # stem on an odd input
+    (2, 33, 65, 4, 64, 7, 2, 1),            # stem, odd at every stage
+]
+WGRAD_CASES = CONFIG4_WGRAD_CASES + ODD_WGRAD_CASES
 
 
 @pytest.mark.parametrize("ranged", [True, False])
@@ -77,11 +89,15 @@ def test_wgrad_layer_matches_float64(lib_built, case, ranged):
 
 
 # the LDS-DMA tile of the training step (wgrad_dma): 128 x 128 layers only
-DMA_CASES = [c for c in WGRAD_CASES if c[4] >= 128 and c[3] * c[5] * c[5] >= 128] + [
+_RAGGED_DMA = (3, 13, 17, 64, 136, 3, 1, 1)      # ragged everything: Wo < 16 (several row wraps per step), Cout % 128 != 0, M % 16 != 0, two taps per k-tile
+_dma_able = lambda cases: [c for c in cases if c[4] >= 128 and c[3] * c[5] * c[5] >= 128]
+DMA_CASES = _dma_able(CONFIG4_WGRAD_CASES) + [
     (11, 30, 40, 256, 1024, 1, 1, 1),       # block3 conv3
     (11, 60, 80, 128, 512, 1, 1, 1),        # block2 conv3 (one k-tile)
-    (3, 13, 17, 64, 136, 3, 1, 1),          # ragged everything: Wo < 16 (several row wraps per step), Cout % 128 != 0, M % 16 != 0, two taps per k-tile
+    _RAGGED_DMA,
     (2, 9, 11, 32, 128, 3, 2, 1),           # stride 2, four taps per k-tile, K = 288 (the last k-tile is part empty)
+] + _dma_able(ODD_WGRAD_CASES) + [
+    (2, 47, 52, 128, 128, 3, 2, 1),         # stride 2 on odd rows at the Reaching geometry's block3 size
 ]
 
 
@@ -89,7 +105,7 @@ _DMA_RATIOS = [(1.0, 1.0), (0.4, 3.0), (2.0 ** -6, 1.0), (1.0, 2.0 ** 8), (0.0, 
 
 
 # (failed-prediction ratios: one large and one ragged shape only)
-@pytest.mark.parametrize("case,ratio", [(c, r) for c in DMA_CASES for r in _DMA_RATIOS if r == (1.0, 1.0) or c in (DMA_CASES[0], DMA_CASES[-2])])
+@pytest.mark.parametrize("case,ratio", [(c, r) for c in DMA_CASES for r in _DMA_RATIOS if r == (1.0, 1.0) or c in (DMA_CASES[0], _RAGGED_DMA)])
 def test_wgrad_dma_tile_matches_float64(lib_built, case, ratio):
     """Both operands as fp16 high / low copies with predicted scales.  ratio = (previous / current maximum) of (x, dy): inside the
     usable window the LDS-DMA path runs, outside it (or with no previous range) the fp32-MFMA path of the same kernel -- same tolerance."""
@@ -151,6 +167,16 @@ DGRAD_CASES = [
     (11, 60, 80, 512, 128, 1, 1, 1, -2),       # conv1 of the strided unit: + subsample-shortcut gradient from the coarse grid
     (11, 120, 160, 256, 64, 1, 1, 1, 1),
     (11, 120, 160, 64, 64, 3, 1, 1, 0),
+    # odd grids: a stride-2 conv's last input row / column (odd H / W) is reached by one tap row only, the zero-stuffed grid is
+    # 2 Ho x 2 Wo and one row / column longer than H / W, and the subsample shortcut's coarse grid is (H + 1) / 2
+    (2, 187, 208, 64, 64, 3, 2, 1, 0),         # block1 unit_3 conv2 at 747 x 832 (odd rows)
+    (3, 19, 26, 64, 64, 3, 2, 1, 0),           # block1 unit_3 conv2 at 75 x 101 (odd rows)
+    (3, 10, 13, 128, 128, 3, 2, 1, 0),         # block2 unit_4 conv2 at 75 x 101 (odd columns)
+    (3, 5, 9, 128, 128, 3, 2, 1, 0),           # block2 unit_4 conv2 at 33 x 65 (odd on both axes)
+    (3, 19, 13, 256, 512, 1, 2, 1, 0),         # strided 1 x 1 shortcut on an odd grid
+    (3, 19, 26, 256, 64, 1, 1, 1, -2),         # block1 unit_3 conv1 at 75 x 101: + subsample-shortcut gradient from the 10 x 13 grid
+    (3, 5, 9, 512, 128, 1, 1, 1, -2),          # block2 unit_4 conv1 at 33 x 65: coarse grid 3 x 5
+    (3, 5, 7, 512, 512, 3, 1, 2, 0),           # block4 conv2 at 75 x 101: dilated, most taps land in the padding
 ]
 
 
