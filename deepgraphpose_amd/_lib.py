@@ -29,6 +29,11 @@ class DgpLossDesc(C.Structure):
                [(n, C.c_int32) for n in ("use_wt", "Hin", "Win")] + [("wt_max", C.c_float)]
 
 
+class DgpFlowParams(C.Structure):
+    _fields_ = [("pyr_scale", C.c_double), ("levels", C.c_int32), ("winsize", C.c_int32), ("iterations", C.c_int32),
+                ("poly_n", C.c_int32), ("poly_sigma", C.c_double), ("flags", C.c_int32)]
+
+
 class DgpConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "N", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "rate", "pad_t", "pad_l", "Ho", "Wo", "relu",
@@ -112,6 +117,8 @@ SYMBOLS = {
     "dgp_motion_energy": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "dgp_maxpool_3x3s2_same": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dgp_preprocess_u8": (C.c_int, [_vp, C.c_int64, C.POINTER(_f32), _vp, _vp]),
+    "dgp_optical_flow_scratch_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(DgpFlowParams), C.POINTER(_sz), C.POINTER(_i32)]),
+    "dgp_optical_flow": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(DgpFlowParams), _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

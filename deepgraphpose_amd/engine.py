@@ -777,3 +777,37 @@ def motion_energy(frames: torch.Tensor, prev: Optional[torch.Tensor] = None) -> 
     sums = torch.empty(T, dtype=torch.int64, device=frames.device)
     _lib.check(lib.dgp_motion_energy(_ptr(frames), fb, T, _ptr(prev), _ptr(sums), _stream(frames.device)), "dgp_motion_energy")
     return sums.cpu().numpy().astype(np.float64) / float(fb)
+
+
+FLOW_OUTPUTS = ("magnitude", "flow", "both")
+
+
+def optical_flow(frames: torch.Tensor, *, pyr_scale: float = 0.5, levels: int = 3, winsize: int = 15, iterations: int = 3,
+                 poly_n: int = 5, poly_sigma: float = 1.2, output: str = "magnitude"):
+    """Farneback flow between consecutive frames of a device uint8 BGR sequence [T, H, W, 3] (dgp_optical_flow; replaces
+    cv2.calcOpticalFlowFarneback in learn_wt, DGP/models/fitdgp_util.py:454-467, whose parameters are the defaults here).
+    output "magnitude": [T-1, H, W] fp32 = |dx| + |dy| (the temporal clique's vector_field); "flow": [T-1, H, W, 2] (dx, dy); "both": the
+    pair (magnitude, flow).  Enqueued on the current stream, no host synchronisation; T < 2 gives empty tensors."""
+    lib = _lib.load()
+    if output not in FLOW_OUTPUTS:
+        raise ValueError("optical_flow: output must be one of %s, not %r" % ("|".join(FLOW_OUTPUTS), output))
+    _need_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise _lib.DgpError("optical_flow: frames must be [T, H, W, 3], got %s" % (tuple(frames.shape),))
+    T, H, W = (int(v) for v in frames.shape[:3])
+    P = max(T - 1, 0)
+    dev = frames.device
+    mag = torch.empty((P, H, W), dtype=torch.float32, device=dev) if output in ("magnitude", "both") else None
+    flow = torch.empty((P, H, W, 2), dtype=torch.float32, device=dev) if output in ("flow", "both") else None
+    if P > 0:
+        prm = _lib.DgpFlowParams(float(pyr_scale), int(levels), int(winsize), int(iterations), int(poly_n), float(poly_sigma), 0)
+        nb, used = C.c_size_t(), C.c_int32()
+        _lib.check(lib.dgp_optical_flow_scratch_bytes(T, H, W, C.byref(prm), C.byref(nb), C.byref(used)), "dgp_optical_flow_scratch_bytes")
+        scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.dgp_optical_flow(_ptr(frames), T, H, W, C.byref(prm), _ptr(flow), _ptr(mag), _ptr(scratch), nb.value,
+                                        _stream(dev)), "dgp_optical_flow")
+    if output == "magnitude":
+        return mag
+    if output == "flow":
+        return flow
+    return mag, flow

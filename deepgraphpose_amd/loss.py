@@ -124,14 +124,31 @@ def dgp_loss_prepare(nt: int, H: int, W: int, nj: int, batch: dict, hyper: DGPHy
     use_wt = hyper.wt > 0 and nt > 1 and batch.get("vector_field") is not None
     host = [vm_h.astype(np.int32), hm_h.astype(np.int32), vt_h.astype(np.int32), tg_h.astype(np.float32), lmap_h, lmask_h, S0, np.atleast_1d(f32(ws)), np.atleast_1d(f32(ws_max))]
     hin = win = 0
+    vf_dev = None
     if use_wt:          # temporal clique: flow magnitude [nt-1,Hin,Win] (learn_wt) and wt * batch_mask (fitdgp.py:774,905)
-        vf_h = f32(batch["vector_field"])
-        hin, win = int(vf_h.shape[1]), int(vf_h.shape[2])
+        vf = batch["vector_field"]
+        if isinstance(vf, torch.Tensor) and vf.is_cuda:       # computed on the device (engine.optical_flow): used in place
+            _need_cuda(vf, torch.float32, "vector_field")
+            if vf.dim() != 3 or vf.shape[0] != nt - 1:
+                raise ValueError("vector_field %s must be [nt-1, Hin, Win] with nt = %d" % (tuple(vf.shape), nt))
+            cur = torch.cuda.current_stream(vf.device)
+            ev = getattr(vf, "_dgp_ready", None)
+            if ev is not None:
+                cur.wait_event(ev)
+            vf.record_stream(cur)
+            vf_dev = vf
+            hin, win = int(vf.shape[1]), int(vf.shape[2])
+        else:
+            vf_h = f32(vf)
+            hin, win = int(vf_h.shape[1]), int(vf_h.shape[2])
+            host += [vf_h]
         mask = np.asarray(batch.get("wt_batch_mask", np.ones(nt - 1)), dtype=np.float32)
-        host += [vf_h, np.ones(nt - 1, dtype=np.float32) * hyper.wt * mask]
+        host += [np.ones(nt - 1, dtype=np.float32) * hyper.wt * mask]
     up = _upload_all(host, dev)          # one staging buffer, one asynchronous copy
     li.vm, li.hm, li.vt, li.targets, li.lmap, li.lmask, li.S0, li.ws, li.ws_max = up[:9]
-    li.vf, li.wtb = (up[9], up[10]) if use_wt else (None, None)
+    li.vf, li.wtb = (None, None)
+    if use_wt:
+        li.vf, li.wtb = (vf_dev, up[9]) if vf_dev is not None else (up[9], up[10])
     li.desc = _lib.DgpLossDesc(nt, H, W, nj, nl, li.vm.numel(), li.hm.numel(), hyper.gm2, hyper.gm3, hyper.gauss_len,
                                int(hyper.locref_huber_loss), hyper.gamma, hyper.lengthscale, hyper.stride, hyper.wn_visible,
                                hyper.wn_hidden, hyper.locref_loss_weight, float(n_frames_total), float(n_visible_frames_total),

@@ -11,8 +11,9 @@ TensorFlow V2 bundles `snapshot-step{k}--{it}.{index,data-00000-of-00001}`, `sna
 `snapshot-step{k}-final--0.*` plus the `checkpoint` state file, written without TensorFlow (weights_io.Saver,
 tf_checkpoint.py); DGP_SNAPSHOT_FORMAT=npz writes `.npz` files of the same names instead.
 Host-side hooks: augmentation of the labeled frames (`aug`; deepgraphpose_amd/augment.py: imgaug's pipeline when imgaug is
-installed, the numpy / scipy restatement of the same seven augmenters otherwise) and the cv2 Farneback
-optical flow feeding the temporal clique (`wt > 0`; raises ImportError without OpenCV -- the loss term itself is a HIP kernel).
+installed, the numpy / scipy restatement of the same seven augmenters otherwise) and the Farneback optical flow feeding the
+temporal clique (`wt > 0`): OpenCV's on the host when cv2 is importable, otherwise the HIP kernels (csrc/dgp_flow.hip) on the
+device -- fit_dgp(flow_backend="cv2" | "hip" | "auto").
 """
 from __future__ import annotations
 
@@ -179,6 +180,25 @@ class _FrameUploader:
         dev._dgp_ready = ev
         self.copied[k] = ev
         return dev
+
+
+def _device_flow(uploader, device, images):
+    """fit_dgp's temporal clique on the device: the batch's frames are uploaded (by the uploader, on its stream, when prefetching) and
+    learn_wt's flow magnitude [nt-1, H, W] is computed from them on the same stream (engine.optical_flow, the reference's parameters).
+    -> (device frames, device magnitude); the magnitude carries the event dgp_loss_prepare waits on."""
+    import torch
+    from .. import engine
+    if uploader is None:
+        dev = torch.from_numpy(np.ascontiguousarray(np.asarray(images).astype(np.uint8))).to(device)
+        return dev, engine.optical_flow(dev)
+    dev = uploader(images)
+    with torch.cuda.stream(uploader.stream):
+        mag = engine.optical_flow(dev)
+        ev = torch.cuda.Event()
+        ev.record(uploader.stream)
+    mag._dgp_ready = ev
+    dev._dgp_ready = ev                 # (the frames are ready no later than the flow that read them)
+    return dev, mag
 
 
 def _frames_to_device(trainer, images):
@@ -525,9 +545,13 @@ def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, di
 
 def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000, displayiters=5, maxiters=200000, ns=10,
             nc=2048, n_max_frames=2000, gm2=0, gm3=0, nepoch=100, wt=0, aug=True, debug="", trainingsetindex=0,
-            frame_sources=None):
+            frame_sources=None, flow_backend="auto"):
     """Run DGP (fitdgp.py:549-845): batches of `batch_size` consecutive frames of the selected windows, at least
-    one labeled frame per batch, loss = total_loss (visible + hidden CE, locref, spatial clique)."""
+    one labeled frame per batch, loss = total_loss (visible + hidden CE, locref, spatial clique; + the temporal clique when wt > 0).
+    flow_backend (wt > 0): "cv2" | "hip" | "auto" as learn_wt's backend.  With "hip" the flow magnitude is computed on the device from
+    the batch's uploaded frames (engine.optical_flow) and handed to the loss as a device tensor: it never crosses to the host."""
+    from .fitdgp_util import resolve_flow_backend
+    flow_backend = resolve_flow_backend(flow_backend) if wt > 0 else None
     rank, world, local_rank = _dp_setup()
     data_batcher, init_weights = _setup(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources)
     dgp_cfg = data_batcher.dlc_config
@@ -583,13 +607,17 @@ def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000,
             from ..augment import data_aug
             images, joint_loc = data_aug(images, vis_within, joint_loc, pipeline, dgp_cfg)
         lmap, lmask = _locref_targets(joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
-        vector_field = None
-        if dgp_cfg.wt > 0:                                            # temporal clique: flow field from the host hook
+        vector_field, dev_images = None, None
+        if dgp_cfg.wt > 0 and flow_backend == "hip":                  # temporal clique: flow magnitude on the device
+            dev_images, vector_field = _device_flow(uploader, trainer.device, images)
+        elif dgp_cfg.wt > 0:                                          # temporal clique: flow field from the host hook
             from .fitdgp_util import learn_wt
-            vector_field = learn_wt(images)
+            vector_field = learn_wt(images, backend=flow_backend)
         feed_dict = _feed(placeholders, images, joint_loc, lmap, lmask, addn, wt_mask, vector_field, dgp_cfg.wt, d.nx_out,
                           d.ny_out, learning_rate, dgp_cfg.lr)
-        if uploader is not None:
+        if dev_images is not None:
+            feed_dict[placeholders["inputs"]] = dev_images
+        elif uploader is not None:
             feed_dict[placeholders["inputs"]] = uploader(images)
         return dataset_i, vis_b, hid_b, feed_dict
 

@@ -107,14 +107,57 @@ def gen_batch(visible_frame_total, hidden_frame_total, all_frame_total, dgp_cfg,
     return random.sample(out, len(out))
 
 
-def learn_wt(all_data_batch):
-    """Optical-flow magnitude fields between consecutive frames of a batch, [nt-1, H, W] (fitdgp_util.py:454-467).
-    The flow itself is third-party host code (cv2 Farneback, untouched); without OpenCV this raises."""
+FLOW_BACKENDS = ("auto", "cv2", "hip")
+
+
+def _cv2_available() -> bool:
+    try:
+        import cv2  # noqa: F401
+    except ImportError:
+        return False
+    return True
+
+
+def resolve_flow_backend(backend: str = "auto") -> str:
+    """"cv2" | "hip" for learn_wt / fit_dgp(flow_backend=...): "auto" keeps OpenCV when it is importable (the reference's flow) and
+    otherwise uses the HIP Farneback (engine.optical_flow); neither available is an error naming both."""
+    if backend not in FLOW_BACKENDS:
+        raise ValueError("flow backend must be one of %s, not %r" % (" | ".join(FLOW_BACKENDS), backend))
+    if backend != "auto":
+        return backend
+    if _cv2_available():
+        return "cv2"
+    try:
+        from .. import _lib
+        _lib.load()
+        import torch
+        if torch.cuda.is_available():
+            return "hip"
+    except Exception:
+        pass
+    raise ImportError("the temporal clique (wt > 0) needs an optical flow: neither OpenCV (cv2, calcOpticalFlowFarneback) is "
+                      "installed nor is the HIP Farneback (libdgp_hip.so on a visible GPU) usable; run with wt=0 or pass "
+                      "batch['vector_field'] yourself")
+
+
+def learn_wt(all_data_batch, backend="auto"):
+    """Optical-flow magnitude fields between consecutive frames of a batch, [nt-1, H, W] float32 (fitdgp_util.py:454-467).
+    backend "cv2": OpenCV's Farneback on the host (the reference's code); "hip": the same algorithm on the GPU (dgp_optical_flow, same
+    parameters); "auto": cv2 when importable, else hip (resolve_flow_backend)."""
+    backend = resolve_flow_backend(backend)
+    if backend == "hip":
+        import torch
+        from .. import engine
+        if not torch.cuda.is_available():
+            from .._lib import DgpError
+            raise DgpError("learn_wt(backend='hip') needs a HIP device (there is no CPU fallback)")
+        frames = torch.from_numpy(np.ascontiguousarray(np.asarray(all_data_batch).astype(np.uint8))).cuda()
+        return engine.optical_flow(frames, pyr_scale=0.5, levels=3, winsize=15, iterations=3, poly_n=5, poly_sigma=1.2,
+                                   output="magnitude").cpu().numpy()
     try:
         import cv2
     except ImportError as e:
-        raise ImportError("the temporal clique (wt > 0) needs OpenCV's Farneback optical flow on the host "
-                          "(cv2 is not installed); run with wt=0 or pass batch['vector_field'] yourself") from e
+        raise ImportError("learn_wt(backend='cv2') needs OpenCV's Farneback optical flow on the host (cv2 is not installed)") from e
     fields = []
     for ff in range(all_data_batch.shape[0] - 1):
         prvs = cv2.cvtColor(all_data_batch[ff].astype(np.uint8), cv2.COLOR_BGR2GRAY)

@@ -416,6 +416,31 @@ int  dgp_preprocess_u8(const uint8_t* frames, int64_t n_pixels, const float mean
 int  dgp_motion_energy(const uint8_t* frames, int64_t frame_bytes, int32_t n_frames, const uint8_t* prev_frame,
                        uint64_t* sums, void* stream);
 
+/* ---- Farneback optical flow (replaces cv2.calcOpticalFlowFarneback in learn_wt, DGP/models/fitdgp_util.py:454-467, called from
+ * DGP/models/fitdgp.py:771-775: the flow magnitude the temporal clique reads as vector_field).  Parameters as OpenCV's
+ * calcOpticalFlowFarneback(prev, next, None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags); the reference uses
+ * (0.5, 3, 15, 3, 5, 1.2, 0).  Rules: 0 < pyr_scale < 1, levels >= 0, winsize odd 3..31, iterations >= 1, poly_n 5 | 7,
+ * poly_sigma > 0, flags 0 (no Gaussian window, no initial flow), frames >= 16 x 16, n_frames >= 2; anything else is DGP_ERR_INVALID. */
+typedef struct dgp_flow_params {
+    double  pyr_scale;
+    int32_t levels, winsize, iterations, poly_n;
+    double  poly_sigma;
+    int32_t flags;
+} dgp_flow_params;
+
+/* Host only (no GPU): validates the parameters and gives the device scratch dgp_optical_flow needs for n_frames frames of H x W, and
+ * the pyramid levels it builds (levels clamped as OpenCV does: a level narrower or lower than 32 pixels is not built).
+ * Reference call site: DGP/models/fitdgp_util.py:454-467. */
+int  dgp_optical_flow_scratch_bytes(int32_t n_frames, int32_t H, int32_t W, const dgp_flow_params* p, size_t* bytes,
+                                    int32_t* levels_used);
+/* Flow of the n_frames - 1 consecutive pairs of a uint8 BGR frame sequence (channel 0 = B: the reference's COLOR_BGR2GRAY), all pairs
+ * in every launch.  frames: device [n_frames][H][W][3]; flow: device fp32 [n_frames-1][H][W][2] (dx, dy) or NULL; magnitude: device
+ * fp32 [n_frames-1][H][W] = |dx| + |dy| (learn_wt's np.abs(flow).sum(2), dgp_loss_fwd_bwd's vector_field layout) or NULL; at least
+ * one of the two.  scratch: dgp_optical_flow_scratch_bytes device bytes.  fp32, no atomics: bit-identical from run to run.
+ * Reference call site: DGP/models/fitdgp_util.py:454-467. */
+int  dgp_optical_flow(const uint8_t* frames, int32_t n_frames, int32_t H, int32_t W, const dgp_flow_params* p, float* flow,
+                      float* magnitude, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
