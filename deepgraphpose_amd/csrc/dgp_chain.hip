@@ -82,10 +82,6 @@ __device__ unsigned long long g_unit_diag[16];
 template <int RES, int RB, bool H1 = false>
 __device__ __forceinline__ void chain_fetch_res(const ChainArgs& p, uint4 (&res)[RB][2], const unsigned (&roff)[RB],
                                                 const __amdgpu_buffer_rsrc_t rs_s2, int jp) {
-#if defined(DGP_UX) && (DGP_UX & 1)      // timing-only ablation (scripts/diag_unit.sh): no residual loads
-    for (int rb = 0; rb < RB; ++rb) { res[rb][0] = make_uint4(0, 0, 0, 0); res[rb][1] = make_uint4(0, 0, 0, 0); }
-    return;
-#endif
     if constexpr (RES != 0) {
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -197,18 +193,12 @@ __device__ __forceinline__ void chain_tail(const ChainArgs& p, const uint4* ring
                 }
                 if constexpr (H1) { xh[rb] = h1_pack8(o, p.xout_scale); xl[rb] = xh[rb]; }
                 else h2_pack8(o, p.xout_scale, xh[rb], xl[rb]);
-#if defined(DGP_UX) && (DGP_UX & 2)      // timing-only ablation: no X' stores
-                if (p.nt == 77) {
-#else
                 if (p.nt & 2) {
-#endif
                     st16nt(rs_xo, xh[rb], xoff[rb], jp * CB);
                     if constexpr (!H1) st16nt(rs_xo, xl[rb], xoff[rb], jp * CB + 16);
                 } else {
-#if !(defined(DGP_UX) && (DGP_UX & 2))
                     st16(rs_xo, xh[rb], xoff[rb], jp * CB);
                     if constexpr (!H1) st16(rs_xo, xl[rb], xoff[rb], jp * CB + 16);
-#endif
                 }
                 if (xoff[rb] != OOB) {
 #pragma unroll
@@ -437,7 +427,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW + HWV)) void unit_kernel(const Chai
     // NLW weight-loader waves + HWV (0 / 1) halo wave.  Round 4: with the halo pieces in the weight loaders' queues (HWV = 0) the weight
     // stream waits behind them -- a wave's vector-memory operations return in order, the halo pieces come from HBM / the Infinity Cache,
     // the weight chunks from L2: a timing-only build without the halo DMA ran unit_c64_n64_sc 21 % faster, unit_c64_n64_id 7 %
-    // (scripts/ablate_unit.sh).  The halo wave gets a part of that back where the launch is not HBM-bound (launch_unit).
+    // (EXPERIMENTS.md section 6a'').  The halo wave gets a part of that back where the launch is not HBM-bound (launch_unit).
     constexpr int NS = 3;
     constexpr int TH = NCW, TW = 16, HW = TW + 2, HPIX = (TH + 2) * HW;
     constexpr int EB = H1 ? 2 : 4;
@@ -491,12 +481,10 @@ __global__ __launch_bounds__(64 * (NCW + NLW + HWV)) void unit_kernel(const Chai
         };
         // the pointwise stage of a tile no longer reads the halo buffer (every wave passed barrier 8): the next tile's is fetched then
         auto halo_step = [&](int cur_st, int tile, int hl) {
-#if !(defined(DGP_UX) && (DGP_UX & 32))     // (timing-only ablation: no halo tiles after the first)
             if (cur_st >= 9 && tile + G < p.ntiles) {
                 const int i0 = (cur_st - 9) * HPP, i1 = i0 + HPP < NHI ? i0 + HPP : NHI;
                 halo_issue(tile + G, i0, i1, hl);
             }
-#endif
         };
         const int lw_rt = wave - NCW;
         if (HWV && lw_rt == NLW) {
@@ -522,11 +510,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW + HWV)) void unit_kernel(const Chai
         constexpr int N2 = lw < NF2 % NLW ? (NF2 + NLW - 1) / NLW : NF2 / NLW, NJ = lw < NFJ % NLW ? (NFJ + NLW - 1) / NLW : NFJ / NLW;
         auto issue = [&]() {
             char* dst = ringb + slot * CHUNK;
-#if defined(DGP_UX) && (DGP_UX & 4)      // timing-only ablation: every workgroup walks the chunks in its own rotation (results are garbage)
-            const int st2 = (st + (int)blockIdx.x) % 9, stj = (st - 9 + (int)blockIdx.x) % NJP;
-#else
-            const int st2 = st, stj = st - 9;
-#endif
+            const int st2 = st, stj = st - 9;                          // chunk of conv2's weights / of the pointwise stage's
             if (st < 9) {
 #pragma unroll
                 for (int k = 0; k < N2; ++k)
@@ -660,13 +644,8 @@ __global__ __launch_bounds__(64 * (NCW + NLW + HWV)) void unit_kernel(const Chai
             }
             constexpr int NW2 = KS2 * NCB2 * PL;
             uint4 wq[WR];
-#if defined(DGP_UX) && (DGP_UX & 8)      // timing-only ablation: the weight fragments are not read from LDS
-#define UX_W(i) make_uint4(lane, i, slot, t)
-#else
-#define UX_W(i) W[(i) * 64]
-#endif
 #pragma unroll
-            for (int f = 0; f < WR && f < NW2; ++f) wq[f] = UX_W(f);
+            for (int f = 0; f < WR && f < NW2; ++f) wq[f] = W[f * 64];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int ks = 0; ks < KS2; ++ks) {
@@ -674,22 +653,17 @@ __global__ __launch_bounds__(64 * (NCW + NLW + HWV)) void unit_kernel(const Chai
                 for (int cb = 0; cb < NCB2; ++cb) {
                     const int f0 = (ks * NCB2 + cb) * PL;
                     const uint4 wh = wq[f0 % WR], wl = wq[(f0 + PL - 1) % WR];
-#if defined(DGP_UX) && (DGP_UX & 16)     // timing-only ablation: no MFMAs
-                    acc[cb][0] += __builtin_bit_cast(float, wh.x ^ wl.y ^ ah[ks].x ^ al[ks].y);
-#else
                     if constexpr (!H1) {
                     acc[cb] = mma16(wl, ah[ks], acc[cb]);
                     acc[cb] = mma16(wh, al[ks], acc[cb]);
                     }
                     acc[cb] = mma16(wh, ah[ks], acc[cb]);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
-                    if (f0 + WR < NW2) wq[f0 % WR] = UX_W(f0 + WR);
-                    if (PL == 2 && f0 + 1 + WR < NW2) wq[(f0 + 1) % WR] = UX_W(f0 + 1 + WR);
+                    if (f0 + WR < NW2) wq[f0 % WR] = W[(f0 + WR) * 64];
+                    if (PL == 2 && f0 + 1 + WR < NW2) wq[(f0 + 1) % WR] = W[(f0 + 1 + WR) * 64];
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#undef UX_W
             if (t == 8) {                                              // conv2's BN affine rides in the last tap's chunk
 #pragma unroll
                 for (int q = 0; q < KS2; ++q) {

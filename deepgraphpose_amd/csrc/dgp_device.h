@@ -101,14 +101,6 @@ __device__ __forceinline__ float h2_res_inv_scale(const ConvArgs& p, int lane) {
 }
 
 __device__ __forceinline__ void split2_f16(const float4 v, const float s, uint2& ph, uint2& pl) {
-#if defined(DGP_SPLIT_PK)
-    const float2v x01 = {v.x * s, v.y * s}, x23 = {v.z * s, v.w * s};
-    const half2v h01 = __builtin_convertvector(x01, half2v), h23 = __builtin_convertvector(x23, half2v);
-    const float2v r01 = x01 - __builtin_convertvector(h01, float2v), r23 = x23 - __builtin_convertvector(h23, float2v);   // exact
-    const half2v l01 = __builtin_convertvector(r01, half2v), l23 = __builtin_convertvector(r23, half2v);
-    ph.x = __builtin_bit_cast(unsigned, h01); ph.y = __builtin_bit_cast(unsigned, h23);
-    pl.x = __builtin_bit_cast(unsigned, l01); pl.y = __builtin_bit_cast(unsigned, l23);
-#else
     // 10 VALU per 4 values, written out because hipcc computes the high parts twice (16): h = f16(s x) straight into its half of
     // the packed register (v_fma_mixlo/hi_f16), r = s x - h exactly in fp32 with h read as an fp16 operand (v_fma_mix_f32),
     // l = f16(r) packed (v_cvt_pk_f16_f32).  Scalar fp32 arithmetic on purpose: packed fp32 VALU ops are slow beside MFMAs.
@@ -126,7 +118,6 @@ __device__ __forceinline__ void split2_f16(const float4 v, const float s, uint2&
     const half2v l01 = __builtin_convertvector(r01, half2v), l23 = __builtin_convertvector(r23, half2v);
     ph.x = h01; ph.y = h23;
     pl.x = __builtin_bit_cast(unsigned, l01); pl.y = __builtin_bit_cast(unsigned, l23);
-#endif
 }
 
 // ---- H2 activation format helpers -------------------------------------------------------------------------------------------

@@ -203,8 +203,8 @@ hipError_t launch_chain_pack(const float* src, int n_chunks, int f1_pairs, int f
 // Run-time switches of the native code, two classes (README "Switches"):
 //  * dgp_env(): the shipped ones -- the precision tiers (DGP_CONV_MODE, DGP_H2) and the A/B switches between paths that all ship
 //    and that the tests exercise (<= 20 in all); read from the environment once per process;
-//  * dgp_tune(): knobs of measured-and-settled choices and the opt-ins that measured SLOWER (the 256-row tile DGP_TALL, the C = 256
-//    chain instance DGP_CHAIN_WIDE, the trainer's fast pass, the non-pipelined weight-gradient tile).  The product binary compiles
+//  * dgp_tune(): knobs of measured-and-settled choices and the opt-ins that measured SLOWER (the C = 256 chain instance
+//    DGP_CHAIN_WIDE, the trainer's fast pass).  The product binary compiles
 //    the default in; they read the environment only in a tuning build (DGP_BUILD_FLAGS=-DDGP_TUNING python -m deepgraphpose_amd.build),
 //    which is also the only build that carries the kernels behind the opt-ins.
 inline int dgp_env(const char* name, int dflt) {

@@ -400,9 +400,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm_f32(const C
 // barriers: the loader waves are gone).  acc -> scale/bias/residual/ReLU/mask -> 16-byte stores.
 // M16: the caller's accumulators are the 2 x 8 blocks of v_mfma_f32_16x16x32 and it has staged them into the wave's LDS tile itself
 // (block (i, j) register r of lane l = row 16 i + 4 (l >> 4) + r, column 16 j + (l & 15)); `acc` is not read
-#ifndef DGP_SHADOW_AUX
-#define DGP_SHADOW_AUX 0
-#endif
 template <int TM, int TN, int WN, bool M16 = false>
 __device__ __forceinline__ void ls_epilogue(const ConvArgs& p, floatx16 (&acc)[TM][TN], char* smem, int wave, int lane,
                                             int m0, int n0, int wave_m0, int wave_n0, float post = 1.f) {
@@ -530,7 +527,7 @@ __device__ __forceinline__ void ls_epilogue(const ConvArgs& p, floatx16 (&acc)[T
                 // H1 copy (the 16-bit trainer): this lane's 4 channels are 8 bytes of the tensor at half the fp32 offset
                 uint2 sh, sl;
                 split2_f16(o, sh_scale, sh, sl);
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{sh.x, sh.y}, rs_sh, (int)(ooff[slot][u] >> 1), 0, DGP_SHADOW_AUX);
+                __builtin_amdgcn_raw_buffer_store_b64(u32x2{sh.x, sh.y}, rs_sh, (int)(ooff[slot][u] >> 1), 0, 0);
             } else if (sh_scale > 0.f) {
                 // this lane holds 4 of a cell's 8 channels: trade halves with the neighbour (quad_perm 1,0,3,2) so that the even lane
                 // stores the whole high chunk and the odd lane the whole low chunk -- one 16-byte store per lane, whole cells per pair
@@ -541,7 +538,7 @@ __device__ __forceinline__ void ls_epilogue(const ConvArgs& p, floatx16 (&acc)[T
                 const unsigned r0 = (unsigned)__builtin_amdgcn_mov_dpp((int)g0, 0xB1, 0xF, 0xF, true);
                 const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)g1, 0xB1, 0xF, 0xF, true);
                 const u32x4 cell = odd ? u32x4{r0, r1, sl.x, sl.y} : u32x4{sh.x, sh.y, r0, r1};
-                __builtin_amdgcn_raw_buffer_store_b128(cell, rs_sh, (int)((ooff[slot][u] & ~31u) + (odd ? 16u : 0u)), 0, DGP_SHADOW_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(cell, rs_sh, (int)((ooff[slot][u] & ~31u) + (odd ? 16u : 0u)), 0, 0);
             }
             if (ooff[slot][u] != OOB) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
         }
@@ -890,8 +887,8 @@ __device__ __forceinline__ void ls_epilogue_h2(const ConvArgs& p, floatx16 (&acc
     constexpr int CPP = NV / VC, NQ = TM * CPP;
     const int half = lane >> 5, l31 = lane & 31;
     const int HoWo = p.Ho * p.Wo;
-    // (16x16x32 loops: the caller staged the wave's WHOLE tile, TM x 32 rows; the 32x32x16 loops stage one 32-row pass at a time below)
-    float* sC = reinterpret_cast<float*>(smem) + wave * ((M16 ? TM : 1) * 32 * LDC);
+    // (16x16x32 loops: the caller staged the wave's 32 rows; the 32x32x16 loops stage one 32-row pass at a time below)
+    float* sC = reinterpret_cast<float*>(smem) + wave * (32 * LDC);
     const __amdgpu_buffer_rsrc_t rs_res =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.in), 0, p.res ? (int)p.res_bytes : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
@@ -984,7 +981,7 @@ __device__ __forceinline__ void ls_epilogue_h2(const ConvArgs& p, floatx16 (&acc
 #pragma unroll
         for (int u = 0; u < VC; ++u) {
             const int row = my_r0 + (v0 + u) * RPI;
-            const float* srow = sC + ((M16 ? 32 * i : 0) + row) * LDC + 8 * my_c8;
+            const float* srow = sC + row * LDC + 8 * my_c8;
             const float4 a0 = *reinterpret_cast<const float4*>(srow);
             const float4 a1 = *reinterpret_cast<const float4*>(srow + 4);
             float o[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -1071,20 +1068,8 @@ __device__ __forceinline__ void ls_epilogue_h2(const ConvArgs& p, floatx16 (&acc
 //   (high, low) cell pair of k-group g is now the pair of k-groups (2 g, 2 g + 1): the compute waves issue a_even b_even + a_odd b_odd --
 //   TWO MFMAs per 64 channels where the parity tier issues three per 32 -- on the same LDS reads.  A third of the matrix work and half the
 //   operand bytes per FLOP; 11-bit operands: NOT inside the 1e-3 px gate (bench.py reports what it measures).  O1 = H1 output.
-//   BM = 256 (round 6; the 16-bit tier only, MODE 1 / 2): FOUR compute waves of 64 rows x 128 columns each on a 256 x 128 tile, ONE
-//   workgroup per CU (256 registers per wave: 128 accumulators).  At one MFMA per product the 128 x 128 tile needs 32 KB of operands
-//   per 32 MFMAs and wave -- two co-resident workgroups pull 64 KB through the L2 -> LDS path per 1 024 matrix cycles, which is that
-//   path's rate (EXPERIMENTS.md R5 (6): the loaders need as long to ISSUE a step's LDS-DMA pieces as the MFMAs of the step take) --
-//   and every wave reads 20 fragments from LDS per 32 MFMAs.  A 64 x 128 wave tile reads 24 fragments per 64 MFMAs (-40 % LDS bytes
-//   per MFMA), the workgroup moves 48 KB per 64 MFMAs and wave (-25 % L2 -> LDS bytes per MFMA) and meets at half as many barriers.
-//   (The round-3 / round-5 "tall" tile -- 256 rows as EIGHT waves of 32 x 128 -- kept the per-wave tile and measured slower; removed.)
-//   MEASURED (round 6, profiles/r6_w64_*.txt): correct -- the network's outputs are bit-identical on either tile -- and SLOWER on every
-//   layer: 1 530-1 640 cycles per K-step where the 64 MFMAs take 1 053, with the loaders idle (barrier wait ~ 100 cycles): the tile is
-//   not operand-bound any more, it is bound by its ONE compute wave per SIMD.  scripts/micro/mfma_w64.hip / mfma_w64b.hip rebuild the
-//   loop piece by piece: MFMA stream 1 053 cycles per step, + weight-fragment reads 1 088, + A-cell reads and the ra -> ah / al copies
-//   1 220, + one workgroup barrier per step 1 375 -- every stall two co-resident 128-row workgroups hide from each other is exposed --
-//   and prologue + epilogue (12-18 k cycles per tile) have nothing to run under.  Instantiated for the parity tier's H2 cells too (three
-//   MFMAs per product: 96 per K-step, so the fixed per-step cost weighs a third as much): still +8..+34 % slower per layer.  Opt-in only (DGP_W64).
+//   BM = 256 (round 6: four compute waves of 64 x 128) measured slower than 128 x 128 on every layer in both tiers and was removed, like the
+//   round-3 / round-5 "tall" tile (eight waves of 32 x 128) before it: EXPERIMENTS.md R6 (1), profiles/r6_w64_*.txt.
 //   MODE 3 (round 4; H2 DMA kernels, 3x3 / stride 1 / any dilation: the "halo walk").  With MODE 1 the A rows of a 3x3 conv cross the
 //   L2 -> LDS path NINE times, once per tap (16 KB per K-step and workgroup, as much as the weight cells).  On a stride-1 conv the tap
 //   (kh, kw) of output pixel m reads input pixel m + d ((kh - 1) W + (kw - 1)) of the FLATTENED [N H W] pixel list -- a constant
@@ -1113,11 +1098,11 @@ constexpr int HALO_TBL = HALO_ZERO + 1024;        // three stages of the address
 constexpr int HALO_B0 = HALO_TBL + 2048;          // two stages of weight cells behind it: 49 152 + 32 768 = 80 KB, two workgroups per CU
 static_assert(HALO_B0 == 49152, "80 KB per workgroup");
 template <int BM, int BN, int NT, int BK, int CW, bool PB = false, int MODE = 0, bool CS = false, bool DMA = false, bool AH2 = false, bool OH2 = false, bool DEEP = false, bool H1 = false>
-__global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK == 16 || NT == 2) ? 4 : 2)) void conv_igemm_split_ls(const ConvArgs p) {
+__global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : ((BK == 16 || NT == 2) ? 4 : 2)) void conv_igemm_split_ls(const ConvArgs p) {
     static_assert(MODE != 3 || (DMA && AH2 && OH2 && BM == 128 && BN == 128 && CW == 4 && !DEEP), "halo walk: H2 / H1 tensors, LDS-DMA, 128 x 128 tiles");
     static_assert(!DEEP || (DMA && BN == 128 && BM == 128), "deep ring: LDS-DMA kernels with 128 x 128 tiles");
     static_assert(!H1 || (AH2 && DMA && !DEEP), "16-bit tier: cell input, LDS-DMA kernels");
-    static_assert(BM == 128 || (BM == 256 && AH2 && OH2 && DMA && CW == 4 && BN == 128 && MODE != 3), "256-row tile: cell tensors, 64 x 128 wave tiles");
+    static_assert(BM == 128, "128-row tiles");
     static_assert(!AH2 || CS, "pre-split A operand: compute-side-split kernels only");
     static_assert(!OH2 || AH2, "H2 output: kernels with H2 input only (the stem writes fp32, the pool converts)");
     // compute waves: 2 x (CW / 2) over the tile; with the compute-side split 4 x 1 (each wave owns 32 rows and ALL columns, so no
@@ -1140,7 +1125,7 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
     constexpr int NSA = DEEP ? 5 : (DMA ? 3 : 2);  // A stages
     constexpr int NSB = DEEP ? 4 : 2;              // B stages
     static_assert(!DMA || (CS && MODE != 0 && (BN == 128 || BN == 64) && CW == 4),
-                  "LDS-DMA loaders: CS kernels, plain or pointwise walk, 4 compute waves of 32 (128-row tile) or 64 rows (256-row tile)");
+                  "LDS-DMA loaders: CS kernels, plain or pointwise walk, 4 compute waves of 32 rows");
     static_assert(!CS || (PB && NT == 2 && BK == 32), "compute-side split: fp16 path, pre-split weights, BK 32");
     constexpr int LDC = WN + 4;
     static_assert(NT == 2 || NT == 3 || NT == 6, "6 / 3 bf16 products, or NT = 2: fp16 high/low pair (3 products)");
@@ -1324,11 +1309,7 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                 for (int it = -1; it < nks; ++it) {
                     if (it + 1 < nks) issue_cells();                     // step it + 1
                     if (lw < 2 && it >= 0 && ws < nks) write_table();    // step it + 2: read by the compute waves behind barrier it + 1
-#if defined(DGP_X) && DGP_X == 10      // timing only: this step's weight cells are not waited for (what a second step of lookahead would buy)
-                    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-#else
                     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
                     __builtin_amdgcn_s_barrier();
                 }
                 return;
@@ -1357,9 +1338,7 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
 #endif
             for (int it = -2; it < nks; ++it) {
                 DIAG_STAMP(h0);
-#if !(defined(DGP_X) && DGP_X == 10)
                 if (it + 1 >= 0 && it + 1 < nks) issue_cells();          // weight cells of step it + 1 first
-#endif
                 if (it > -2) {                                           // ring bookkeeping
                     if (ws + 1 < nks) {
                         wl += wt == 8 ? d_ch : ((wt == 2 || wt == 5) ? d_kh : d);
@@ -1380,9 +1359,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                 int n_far = end_g - G;
                 n_far = n_far < 0 ? 0 : n_far;
                 while (G < end_g) issue_group();
-#if defined(DGP_X) && DGP_X == 10
-                if (it + 1 >= 0 && it + 1 < nks) { issue_cells(); n_far += 4; }
-#endif
                 DIAG_STAMP(h1);
                 if (it >= -1) {
                     switch (n_far) {                                     // everything but this iteration's lookahead pieces has landed
@@ -1395,14 +1371,7 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                         case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
                         case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
                         case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-#if defined(DGP_X) && DGP_X == 10
-                        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-                        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-                        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-                        default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-#else
                         default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-#endif
                     }
                     DIAG_STAMP(h2);
                     __builtin_amdgcn_s_barrier();
@@ -1445,9 +1414,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                     char* dst = smB + sb * (B_CELLS * 16) + b_dst0;
 #pragma unroll
                     for (int i = 0; i < BSLOTS; ++i)
-#if defined(DGP_FEEDX) && (DGP_FEEDX & 2)
-                        if (it < 0)
-#endif
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w3, (lds_void*)(dst + i * (PB_KG_STEP * LDB * 16)), 16, (int)pb_goff0,
                                                                  (int)kgbase + i * pb_gstride, 0, 0);
                     if (p.tap_minor) {
@@ -1473,21 +1439,14 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                         const unsigned base_a = second ? rowbase2 + (unsigned)d2 : rowbase + (unsigned)doff;
                         const int stride_a = second ? rstride2 : rstride;
 #pragma unroll
-                        for (int i = 0; i < AROWS; ++i) {
-#if defined(DGP_FEEDX) && (DGP_FEEDX & 1)
-                            if (it < 0)
-#endif
+                        for (int i = 0; i < AROWS; ++i)
                             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_void*)(dst + i * (32 * 128)), 16, (int)(base_a + (unsigned)(i * stride_a)), 0, 0, 0);
-                        }
                     } else {
                         const bool tapok = DGP_RFL(a_tap) < p.ntaps;
 #pragma unroll
                         for (int i = 0; i < AROWS; ++i) {
                             const int hi = hi0[i] + dh, wi = wi0[i] + dw;
                             const bool ok = tapok && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-#if defined(DGP_FEEDX) && (DGP_FEEDX & 1)
-                            if (it < 0)
-#endif
                             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(dst + i * (32 * 128)), 16,
                                                                      (int)(ok ? (unsigned)(rowoff[i] + doff) : OOB), 0, 0, 0);
                         }
@@ -1508,13 +1467,8 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                 }
                 if (it >= -1) {
                     if constexpr (!DEEP) {
-#if defined(DGP_X) && DGP_X == 10
-                        if (moreA) { if constexpr (AROWS == 8) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
-                        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#else
                         if (moreA) { if constexpr (AROWS == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
                         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
                     } else {
                         // step it + 1 must have landed; what may stay in flight was issued after its cells: the A rows of steps
                         // it + 2 .. min(it + LA, nks - 1) and the cells of steps it + 2 .. min(it + LB, nks - 1), 4 instructions each
@@ -1537,15 +1491,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
         }
         float4 ra0[AROWS], rb0[BSLOTS], ra1[AROWS], rb1[BSLOTS];
         auto gload = [&](int ks, float4 (&ra)[AROWS], float4 (&rb)[BSLOTS]) {
-#if defined(DGP_X) && DGP_X == 4
-            if (CS) {
-#pragma unroll
-                for (int i = 0; i < AROWS; ++i) asm volatile("" : "+v"(ra[i].x), "+v"(ra[i].y), "+v"(ra[i].z), "+v"(ra[i].w));
-#pragma unroll
-                for (int i = 0; i < BSLOTS; ++i) asm volatile("" : "+v"(rb[i].x), "+v"(rb[i].y), "+v"(rb[i].z), "+v"(rb[i].w));
-                return;
-            }
-#endif
             const int dh = DGP_RFL(w_kh * p.dil), dw = DGP_RFL(w_kw * p.dil);
             const int doff = DGP_RFL(((dh * p.W + dw) * p.Cin + w_ch) * 4);
             const bool tapok = DGP_RFL(w_tap) < p.ntaps;
@@ -1611,15 +1556,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
             }
         };
         auto lstore = [&](int buf, float4 (&ra)[AROWS], float4 (&rb)[BSLOTS]) {
-#if defined(DGP_X) && DGP_X == 3
-            if (CS) {
-#pragma unroll
-                for (int i = 0; i < AROWS; ++i) asm volatile("" :: "v"(ra[i].x), "v"(ra[i].y), "v"(ra[i].z), "v"(ra[i].w));
-#pragma unroll
-                for (int i = 0; i < BSLOTS; ++i) asm volatile("" :: "v"(rb[i].x), "v"(rb[i].y), "v"(rb[i].z), "v"(rb[i].w));
-                return;
-            }
-#endif
             if (CS) {
 #pragma unroll
                 for (int i = 0; i < AROWS; ++i) sA[buf * A_CELLS + c * LDAF + rg + RG * i] = __builtin_bit_cast(uint4, ra[i]);
@@ -1726,8 +1662,8 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
 #endif
     // 16x16x32 MFMAs in the pipelined loop of the 32 x 128 wave tile: the same FLOPs, LDS bytes and register reads as the 32x32x16
     // shape in twice as many, half as long matrix instructions -- +5.3 % end to end (block4 3x3: 0.499 -> 0.453 ms)
-    constexpr bool M16 = CS && (TM == 1 || (TM == 2 && AH2 && DMA)) && (TN == 4 || (TN == 2 && DMA)) && NT == 2 && BK == 32;      // (32 x 64 wave tiles: DMA images only)
-    static_assert(!DMA || ((TM == 1 || (TM == 2 && AH2)) && (TN == 4 || TN == 2)), "DMA image is read by the pipelined loops only");
+    constexpr bool M16 = CS && TM == 1 && (TN == 4 || (TN == 2 && DMA)) && NT == 2 && BK == 32;      // (32 x 64 wave tiles: DMA images only)
+    static_assert(!DMA || (TM == 1 && (TN == 4 || TN == 2)), "DMA image is read by the pipelined loops only");
     static_assert(!(DMA && AH2) || M16, "pre-split A + DMA image: 16x16x32 loop only");
     if constexpr (MODE == 3) {
         // The 16x16x32 loop of the branch below on the pixel ring: same fragment ring, same barrier placement; the A cells of the NEXT
@@ -1819,99 +1755,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                     for (int r = 0; r < 4; ++r) sCw[(16 * i + 4 * g + r) * LDCW + 16 * j + l15] = c[i][j][r];
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
-    } else if constexpr (M16 && TM == 2) {
-        // 64 x 128 wave tile of the 256-row tile (16-bit tier): four row blocks x eight column blocks of 16x16x32 MFMAs, 64 per K-step
-        // of 64 channels; a weight fragment feeds FOUR MFMAs, so a wave reads 16 + 8 cells per 64 MFMAs where the 32 x 128 tile reads
-        // 16 + 4 per 32.  ONE compute wave per SIMD: nothing hides an exposed LDS round trip (the first version -- the 32 x 128 loop's
-        // four-fragment ring, the barrier before the last two fragments -- ran 1 530 cycles per K-step for 1 024 cycles of MFMAs), so
-        // the fragment ring is EIGHT quads deep (fragment F + 8 is read behind the MFMAs of fragment F: seven fragments = 448 matrix
-        // cycles of cover) and the barrier sits before the last FOUR fragments, whose 16 MFMAs cover the next step's A cells.
-        typedef float floatx4 __attribute__((ext_vector_type(4)));
-        const int l15 = lane & 15, g = lane >> 4;
-        constexpr int NJ = 8, NF = 16;
-        floatx4 c[4][NJ];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) c[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-        // DMA image: row-major, chunk ch of row r in slot ch ^ ((r >> 1) & 7) (the same for r + 16 i); this lane wants chunks 2 g, 2 g + 1
-        const unsigned a_row0 = (unsigned)((wave_m0 + l15) * 128 + (((2 * g) ^ (((wave_m0 + l15) >> 1) & 7)) << 4));
-        unsigned a_cur = a_row0;
-        int sa_c = 0;
-        const uint4* B = sB + wave_n0 + l15 + g * LDB;
-        int db = B_CELLS;
-        uint4 ra[4][2], ah[4], al[4], bq[8];
-        auto mma = [](const uint4& x, const uint4& y, floatx4 cc) {
-            return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, x), __builtin_bit_cast(half8, y), cc, 0, 0, 0);
-        };
-#define DGP_FENCE() __builtin_amdgcn_sched_barrier(0)
-#if defined(DGP_X) && (DGP_X == 8 || DGP_X == 9)      // timing-only: no A cell reads
-#define DGP_RA(I) do { asm volatile("" : "+v"(ra[I][0].x), "+v"(ra[I][0].y), "+v"(ra[I][0].z), "+v"(ra[I][0].w), "+v"(ra[I][1].x), "+v"(ra[I][1].y), "+v"(ra[I][1].z), "+v"(ra[I][1].w)); } while (0)
-#else
-#define DGP_RA(I) do { ra[I][0] = *reinterpret_cast<const uint4*>(smem + a_cur + (I) * 2048);                        \
-                       ra[I][1] = *reinterpret_cast<const uint4*>(smem + (a_cur ^ 16u) + (I) * 2048); } while (0)
-#endif
-#if defined(DGP_X) && (DGP_X == 6 || DGP_X == 8)      // timing-only: no B fragment reads
-#define DGP_RB(F) do { asm volatile("" : "+v"(bq[(F) & 7].x), "+v"(bq[(F) & 7].y), "+v"(bq[(F) & 7].z), "+v"(bq[(F) & 7].w)); } while (0)
-#else
-#define DGP_RB(F) do { bq[(F) & 7] = B[((((F) & 1) ? 0 : 1) * KG) * LDB + 16 * (((F) % NF) >> 1)]; } while (0)
-#endif
-        // H1: fragment F even = plane 1 = the odd k-groups' weights x the odd chunks `al`; F odd = plane 0 x the even chunks `ah`.
-        // H2 (parity tier): chunk 2 g = the HIGH cell `ah` of k-group g, chunk 2 g + 1 its LOW cell `al`; F even = the low weight plane x ah,
-        // F odd = the high plane x al, then x ah -- per accumulator the same order as the 32 x 128 loop (a_hi b_lo, a_lo b_hi, a_hi b_hi).
-#define DGP_MM4(X, F, J) do { c[0][J] = mma(X[0], bq[(F) & 7], c[0][J]); c[1][J] = mma(X[1], bq[(F) & 7], c[1][J]);                     \
-                              c[2][J] = mma(X[2], bq[(F) & 7], c[2][J]); c[3][J] = mma(X[3], bq[(F) & 7], c[3][J]); } while (0)
-#define DGP_MM(F) do { constexpr int j_ = (F) >> 1;                                                                 \
-        if constexpr (H1) { if (((F) & 1) == 0) DGP_MM4(al, F, j_); else DGP_MM4(ah, F, j_); }                      \
-        else if (((F) & 1) == 0) DGP_MM4(ah, F, j_);                                                                \
-        else { DGP_MM4(al, F, j_); DGP_MM4(ah, F, j_); } } while (0)
-#define DGP_STEP(F) do { DGP_MM(F); DGP_FENCE(); DGP_RB((F) + 8); DGP_FENCE(); } while (0)
-#define DGP_TAIL(F) do { DGP_MM(F); DGP_FENCE(); if (more) DGP_RB((F) - 8); DGP_FENCE(); } while (0)
-        DGP_RA(0); DGP_RA(1); DGP_RA(2); DGP_RA(3);
-        DGP_RB(0); DGP_RB(1); DGP_RB(2); DGP_RB(3); DGP_RB(4); DGP_RB(5); DGP_RB(6); DGP_RB(7);
-        DGP_FENCE();
-        for (int ks = 0; ks < nks; ++ks) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { ah[i] = ra[i][0]; al[i] = ra[i][1]; }
-            DGP_FENCE();
-            DGP_STEP(0); DGP_STEP(1); DGP_STEP(2); DGP_STEP(3); DGP_STEP(4); DGP_STEP(5); DGP_STEP(6); DGP_STEP(7);
-            DGP_MM(8); DGP_FENCE();
-            DGP_MM(9); DGP_FENCE();
-            DGP_MM(10); DGP_FENCE();
-            DGP_MM(11); DGP_FENCE();
-            DIAG_STAMP(e2);
-            __syncthreads();
-            DIAG_STAMP(e3);
-#ifdef DGP_DIAG
-            acc_mf += e2 - e1; acc_ba += e3 - e2; e1 = e3;
-#endif
-            sa_c = sa_c == NSA - 1 ? 0 : sa_c + 1; a_cur = a_row0 + (unsigned)(sa_c * (A_CELLS * 16));
-            static_assert(NSB == 2, "256-row tile: two weight stages");
-            B += db; db = -db;
-            const bool more = ks + 1 < nks;
-            if (more) { DGP_RA(0); DGP_RA(1); DGP_RA(2); DGP_RA(3); DGP_RB(0); DGP_RB(1); DGP_RB(2); DGP_RB(3); }
-            DGP_FENCE();
-            DGP_TAIL(12); DGP_TAIL(13); DGP_TAIL(14); DGP_TAIL(15);
-        }
-#undef DGP_FENCE
-#undef DGP_RA
-#undef DGP_RB
-#undef DGP_MM
-#undef DGP_MM4
-#undef DGP_STEP
-#undef DGP_TAIL
-        {      // stage the wave's 64 x 128 tile (its own LDS slice: the ring is dead behind the last barrier)
-            constexpr int LDCW = WN + 4;
-            float* sCw = reinterpret_cast<float*>(smem) + wave * (64 * LDCW);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) sCw[(16 * i + 4 * g + r) * LDCW + 16 * j + l15] = c[i][j][r];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
     } else if constexpr (M16) {
         // One K-step = one MFMA depth (32).  Per step a wave splits its 2 x 16 rows (A: two fp32 chunks per lane and row block ->
         // a_hi / a_lo), and walks 16 B fragments f = (column block j = f / 2, plane: low first) through a ring of four register
@@ -1937,32 +1780,20 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
         int da = A_CELLS, db = B_CELLS;            // to the other buffer and back (deep ring: to the next stage, wrapping)
         int sb_c = 0; (void)sb_c;
         uint4 ra[2][2], ah[2], al[2], bq[4];
-#if defined(DGP_X) && DGP_X == 7      // timing-only: no MFMAs in the 16x16x32 loop
-        auto mma = [](const uint4& x, const uint4& y, floatx4 cc) { asm volatile("" :: "v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w), "v"(y.x), "v"(y.y), "v"(y.z), "v"(y.w)); return cc; };
-#else
         auto mma = [](const uint4& x, const uint4& y, floatx4 cc) {
             return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, x), __builtin_bit_cast(half8, y), cc, 0, 0, 0);
         };
-#endif
 #define DGP_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define DGP_RA(I) do { if constexpr (DMA) {                                                                         \
             ra[I][0] = *reinterpret_cast<const uint4*>(smem + a_cur + (I) * 2048);                                 \
             ra[I][1] = *reinterpret_cast<const uint4*>(smem + (a_cur ^ 16u) + (I) * 2048);                         \
         } else { ra[I][0] = A[16 * (I)]; ra[I][1] = A[LDAF + 16 * (I)]; } } while (0)
-#if defined(DGP_X) && DGP_X == 6      // timing-only: no B fragment reads in the 16x16x32 loop
-#define DGP_RB(F) do { asm volatile("" : "+v"(bq[(F) & 3].x), "+v"(bq[(F) & 3].y), "+v"(bq[(F) & 3].z), "+v"(bq[(F) & 3].w)); } while (0)
-#else
 #define DGP_RB(F) do { bq[(F) & 3] = B[((((F) & 1) ? 0 : 1) * KG) * LDB + 16 * (((F) % NF) >> 1)]; } while (0)
-#endif
-#if defined(DGP_X) && DGP_X == 1      // timing-only stand-in: the A operand as if it arrived pre-split (no split arithmetic)
-#define DGP_SPLIT(I) do { ah[I] = ra[I][0]; al[I] = ra[I][1]; } while (0)
-#else
 #define DGP_SPLIT(I) do { if constexpr (AH2) { ah[I] = ra[I][0]; al[I] = ra[I][1]; break; }                       \
         uint2 h0_, l0_, h1_, l1_;                                                                                  \
         split2_f16(__builtin_bit_cast(float4, ra[I][0]), scA_c, h0_, l0_);                                         \
         split2_f16(__builtin_bit_cast(float4, ra[I][1]), scA_c, h1_, l1_);                                         \
         ah[I] = make_uint4(h0_.x, h0_.y, h1_.x, h1_.y); al[I] = make_uint4(l0_.x, l0_.y, l1_.x, l1_.y); } while (0)
-#endif
 #define DGP_MM(F) do { constexpr int j_ = (F) >> 1;                                                                \
         if constexpr (H1) { if (((F) & 1) == 0) { c[0][j_] = mma(al[0], bq[(F) & 3], c[0][j_]); c[1][j_] = mma(al[1], bq[(F) & 3], c[1][j_]); } \
                             else { c[0][j_] = mma(ah[0], bq[(F) & 3], c[0][j_]); c[1][j_] = mma(ah[1], bq[(F) & 3], c[1][j_]); } }              \
@@ -1970,27 +1801,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
         else { c[0][j_] = mma(al[0], bq[(F) & 3], c[0][j_]); c[1][j_] = mma(al[1], bq[(F) & 3], c[1][j_]);         \
                c[0][j_] = mma(ah[0], bq[(F) & 3], c[0][j_]); c[1][j_] = mma(ah[1], bq[(F) & 3], c[1][j_]); } } while (0)
 #define DGP_STEP(F) do { DGP_MM(F); DGP_FENCE(); DGP_RB((F) + 4); DGP_FENCE(); } while (0)
-#ifdef DGP_M16_SIMPLE      // debugging aid: the same arithmetic without any software pipelining
-        for (int ks = 0; ks < nks; ++ks) {
-            DGP_RA(0); DGP_RA(1);
-            DGP_SPLIT(0); DGP_SPLIT(1);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const uint4 bl = B[(1 * KG) * LDB + 16 * j], bh = B[16 * j];
-#if DGP_M16_SIMPLE != 2
-                c[0][j] = mma(ah[0], bl, c[0][j]); c[1][j] = mma(ah[1], bl, c[1][j]);
-#endif
-#if DGP_M16_SIMPLE != 3
-                c[0][j] = mma(al[0], bh, c[0][j]); c[1][j] = mma(al[1], bh, c[1][j]);
-#endif
-                c[0][j] = mma(ah[0], bh, c[0][j]); c[1][j] = mma(ah[1], bh, c[1][j]);
-            }
-            __syncthreads();
-            if constexpr (DMA) { sa_c = sa_c == NSA - 1 ? 0 : sa_c + 1; a_cur = a_row0 + (unsigned)(sa_c * (A_CELLS * 16)); }
-            else { A += da; da = -da; }
-            if constexpr (NSB == 2) { B += db; db = -db; } else { B += db; if (++sb_c == NSB) { sb_c = 0; B -= NSB * B_CELLS; } }
-        }
-#else
         DGP_RA(0); DGP_RA(1);
         DGP_RB(0); DGP_RB(1); DGP_RB(2); DGP_RB(3);
         DGP_FENCE();
@@ -2040,7 +1850,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
             if (more) DGP_RB(3);
             DGP_FENCE();
         }
-#endif
 #undef DGP_FENCE
 #undef DGP_RA
 #undef DGP_RB
@@ -2086,15 +1895,9 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
         } else { ra[0] = (A)[(4 * (KK)) * LDAF]; ra[1] = (A)[(4 * (KK) + 1) * LDAF]; } } while (0)
 #define DGP_RB(B, S, KK, PL, J0) do { bq[S][0] = (B)[((PL) * KG + 2 * (KK)) * LDB + 32 * (J0)];        \
                                       bq[S][1] = (B)[((PL) * KG + 2 * (KK)) * LDB + 32 * ((J0) + 1)]; } while (0)
-#if defined(DGP_X) && DGP_X == 1
-#define DGP_SPLIT_HALF(KK, C) do { uint2 h_, l_; h_.x = ra[C].x; h_.y = ra[C].y; l_.x = ra[C].z; l_.y = ra[C].w;   \
-        if ((C) == 0) { ah[0].x = h_.x; ah[0].y = h_.y; al[0].x = l_.x; al[0].y = l_.y; }                         \
-        else { ah[0].z = h_.x; ah[0].w = h_.y; al[0].z = l_.x; al[0].w = l_.y; } } while (0)
-#else
 #define DGP_SPLIT_HALF(KK, C) do { uint2 h_, l_; split2_f16(__builtin_bit_cast(float4, ra[C]), scA_c, h_, l_);    \
         if ((C) == 0) { ah[0].x = h_.x; ah[0].y = h_.y; al[0].x = l_.x; al[0].y = l_.y; }                         \
         else { ah[0].z = h_.x; ah[0].w = h_.y; al[0].z = l_.x; al[0].w = l_.y; } } while (0)
-#endif
 #define DGP_GL(KK, J0, S) do { acc[0][J0] = mma(ah[0], bq[S][0], acc[0][J0]); acc[0][(J0) + 1] = mma(ah[0], bq[S][1], acc[0][(J0) + 1]); } while (0)
 #define DGP_GH(KK, J0, S) do { acc[0][J0] = mma(al[0], bq[S][0], acc[0][J0]); acc[0][(J0) + 1] = mma(al[0], bq[S][1], acc[0][(J0) + 1]); \
                                acc[0][J0] = mma(ah[0], bq[S][0], acc[0][J0]); acc[0][(J0) + 1] = mma(ah[0], bq[S][1], acc[0][(J0) + 1]); } while (0)
@@ -2102,15 +1905,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
         DGP_RA(a_lane, 0);
         DGP_RB(b_lane, 0, 0, 1, 0);
         DGP_RB(b_lane, 1, 0, 0, 0);
-#if defined(DGP_X) && DGP_X == 2
-        DGP_RB(b_lane, 2, 0, 0, 2);
-#undef DGP_RB
-#define DGP_RB(B, S, KK, PL, J0) do { asm volatile("" : "+v"(bq[S][0].x), "+v"(bq[S][0].y), "+v"(bq[S][0].z), "+v"(bq[S][0].w), "+v"(bq[S][1].x), "+v"(bq[S][1].y), "+v"(bq[S][1].z), "+v"(bq[S][1].w)); } while (0)
-#endif
-#if defined(DGP_X) && DGP_X == 5
-        auto mma5 = [](const uint4& x, const uint4& y, floatx16 c) { asm volatile("" :: "v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w), "v"(y.x), "v"(y.y), "v"(y.z), "v"(y.w)); return c; };
-#define mma mma5
-#endif
         DGP_FENCE();
         const uint4* A = a_lane;
         const uint4* B = b_lane;
@@ -2171,7 +1965,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
             DGP_FENCE();
         }
 #undef DGP_RA
-#undef mma
 #undef DGP_RB
 #undef DGP_SPLIT_HALF
 #undef DGP_GL
@@ -2199,10 +1992,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                 for (int i = 0; i < TM; ++i) {
                     const float4 f0 = __builtin_bit_cast(float4, a_base[(2 * kg) * LDAF + 32 * i]);
                     const float4 f1 = __builtin_bit_cast(float4, a_base[(2 * kg + 1) * LDAF + 32 * i]);
-#if defined(DGP_X) && DGP_X == 1
-                    af[0][i] = __builtin_bit_cast(uint4, f0);
-                    af[1][i] = __builtin_bit_cast(uint4, f1);
-#else
                     if constexpr (AH2) {       // chunk 2 kg = high cell, chunk 2 kg + 1 = low cell of this row's k-group
                         af[0][i] = __builtin_bit_cast(uint4, f0);
                         af[1][i] = __builtin_bit_cast(uint4, f1);
@@ -2213,7 +2002,6 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : BM == 256 ? 2 : ((BK =
                     split2_f16(f1, scA_c, h1, l1);
                     af[0][i] = make_uint4(h0.x, h0.y, h1.x, h1.y);
                     af[1][i] = make_uint4(l0.x, l0.y, l1.x, l1.y);
-#endif
                 }
             }
             auto mma = [](const uint4& x, const uint4& y, floatx16 c) {
@@ -2681,79 +2469,6 @@ static hipError_t launch_conv_split(ConvArgs a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// The 256 x 128 tile (see conv_igemm_split_ls, "BM = 256"): cell -> cell convolutions of either tier (H1 -> H1, H2 -> H2), pointwise (incl. the
-// K-concatenated shortcut) or plain taps.  `a` holds REAL channels here (before to_h1_units): conv_kernel_name and launch_conv ask the same
-// question.  DGP_W64: 0 (default) never -- it measured SLOWER than the 128 x 128 tile on every layer of the bench workload in BOTH tiers
-// (one stream, profiles/r6_w64_ab_layers.txt / r6_w64_h2_ab_layers.txt: 16-bit tier block4 +6..+26 %, block3 +14..+28 %; parity tier
-// block4 +8..+19 %, block3 +12..+34 %; EXPERIMENTS.md R6 (1) has the stamps and the micro-benchmarks that say why); any other value:
-// wherever the kernel can run (the layer tests, the bit-identity tests of both tiers).
-static int w64_env() { static const int v = dgp_env("DGP_W64", 0); return v; }
-static bool conv_w64_eligible(const ConvArgs& a) {
-    const int fmt = a.in_fmt;
-    if (!w64_env() || (fmt != 1 && fmt != 2) || a.out_fmt != fmt || !a.wh3 || a.up || a.stem || a.out_mode != 0 || a.shadow) return false;
-    if (a.res && a.res_fmt != fmt && !(fmt == 1 && a.res_fmt == 0)) return false;
-    if (a.in_scale_dev || a.out_scale_dev || a.res_scale_dev) { if (fmt == 1) return false; }      // (the parity trainer's predicted scales: 128-row kernels)
-    if (a.mask && !(fmt == 2 && a.mask_fmt == 2)) return false;
-    const int cq = fmt == 2 ? 63 : 31;                                 // channels per K-step - 1
-    if (a.CoutP % 128 != 0 || (a.Cout % 8) || (a.Cin & cq) || (fmt == 2 && (a.nk & 1))) return false;
-    const bool pointwise = a.ntaps == 1 && a.stride == 1 && a.pad_t == 0 && a.pad_l == 0 && a.H == a.Ho && a.W == a.Wo;
-    if (a.in2 && (!pointwise || (a.cin_split & cq) || ((a.Cin - a.cin_split) & cq))) return false;
-    if (pointwise && ((unsigned long long)a.M * (a.in2 ? a.cin_split : a.Cin) * 4ull != a.in_bytes ||
-                      (a.in2 && (unsigned long long)a.M * (a.Cin - a.cin_split) * 4ull != a.in2_bytes) || a.in_bytes >= 4200000000u)) return false;
-    if (!pointwise && a.nk * 32 != a.ntaps * a.Cin) return false;      // (plain taps: whole channel chunks per tap)
-    return true;
-}
-
-static hipError_t launch_conv_w64(ConvArgs a, hipStream_t s) {       // (`a` already in H1 units where the tensors are H1)
-    constexpr int BM = 256, BN = 128, NT = 2, BK = 32, CW = 4, NP = 2, KG = 4;
-    static const int tap_minor = dgp_tune("DGP_TAP_MINOR", 1);
-    a.tap_minor = (tap_minor && a.ntaps > 1 && a.nk * 32 == a.ntaps * a.Cin) ? 1 : 0;
-    a.mtiles = (a.M + BM - 1) / BM;
-    a.ntiles = a.CoutP / BN;
-    if (a.tap_rows == 0) a.tap_rows = a.Cin >> 2;
-    static const int epi_nt_env = dgp_tune("DGP_EPI_NT", 2);
-    a.epi_nt = epi_nt_env == 1 ? 3 : (a.ntiles >= 8 ? (epi_nt_env == 2 ? 3 : epi_nt_env == 3 ? 1 : epi_nt_env == 4 ? 2 : 0) : 0);
-    a.tail_ksplit = 0; a.st_gn = 0;
-    const bool pointwise = a.ntaps == 1 && a.stride == 1 && a.pad_t == 0 && a.pad_l == 0 && a.H == a.Ho && a.W == a.Wo;
-    const int mode = pointwise ? 2 : 1;
-    const bool h1 = a.in_fmt == 2;
-    auto kern = h1 ? (mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, true, 2, true, true, true, true, false, true>
-                                : conv_igemm_split_ls<BM, BN, NT, BK, CW, true, 1, true, true, true, true, false, true>)
-                   : (mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, true, 2, true, true, true, true, false, false>
-                                : conv_igemm_split_ls<BM, BN, NT, BK, CW, true, 1, true, true, true, true, false, false>);
-    size_t smem = (size_t)(3 * BM * 8 + 2 * NP * KG * BN) * 16;                // 3 A stages + 2 B stages = 128 KB
-    const size_t smem_epi = (size_t)CW * 64 * (BN + 4) * 4;                    // 132 KB: the four 64-row wave tiles of the epilogue
-    if (smem < smem_epi) smem = smem_epi;
-    static bool attr_dev[16][2][3] = {};
-    bool& attr = attr_dev[dgp_device_slot()][h1 ? 1 : 0][mode];
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    a.n_main = a.mtiles * a.ntiles;
-#ifdef DGP_DIAG
-    static unsigned long long* dbg_buf = nullptr;
-    if (!dbg_buf) (void)hipMalloc(&dbg_buf, 10 * 8 * 65536);
-    a.dbg = a.n_main <= 65536 ? dbg_buf : nullptr;
-#endif
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.n_main), dim3(64 * (CW + 4)), smem, s, a);
-#ifdef DGP_DIAG
-    if (a.dbg) {
-        (void)hipStreamSynchronize(s);
-        const long long nwg = a.n_main;
-        std::vector<unsigned long long> h(10 * nwg);
-        (void)hipMemcpy(h.data(), a.dbg, 80 * nwg, hipMemcpyDeviceToHost);
-        double v[10] = {0};
-        for (long long b = 0; b < nwg; ++b) for (int k = 0; k < 10; ++k) v[k] += (double)h[10 * b + k];
-        for (int k = 0; k < 10; ++k) v[k] /= (double)nwg;
-        printf("[diag w64 256x128 mode %d] tiles %lld K-steps %d | compute wave 0: first barrier %.0f cyc, staging %.0f, epilogue %.0f | per K-step: "
-               "ldsread+mfma %.0f barrier-wait %.0f\n", mode, nwg, a.nk, v[0], v[9], v[2], v[4] / a.nk, v[7] / a.nk);
-    }
-#endif
-    return hipGetLastError();
-}
-
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool WIDE>
 static hipError_t launch_conv_t(ConvArgs a, hipStream_t s) {
     size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
@@ -2858,8 +2573,7 @@ const char* conv_kernel_name(const ConvArgs& a, int tile_cfg) {
             case TILE_128x128_S6K16W8: return "split6_128x128_k16w8";
             case TILE_128x128_H3K16:   return "splith3_128x128_k16";
             case TILE_128x128_H3K16W8: return "splith3_128x128_k16w8";
-            case TILE_128x128_H3K32:   return a.in_fmt == 2 ? (conv_w64_eligible(a) ? "h1_256x128_k64" : "h1_128x128_k64")
-                                              : (conv_w64_eligible(a) ? "splith3_256x128_k32" : "splith3_128x128_k32");
+            case TILE_128x128_H3K32:   return a.in_fmt == 2 ? "h1_128x128_k64" : "splith3_128x128_k32";
             case TILE_128x64_H3:       return a.in_fmt == 2 ? "h1_128x64_k64" : "splith3_128x64_k32";
             case TILE_128x128_S6:    return "split6_128x128_k32";
             case TILE_128x64_S6:     return "split6_128x64_k32";
@@ -2911,9 +2625,7 @@ hipError_t launch_conv(const ConvArgs& a_in, int tile_cfg, hipStream_t s) {
         case TILE_128x128_S6K16W8: return a.out_mode == 0 ? launch_conv_split<128, 128, 6, 16, 8>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
         case TILE_128x128_H3K16:   return a.out_mode == 0 ? launch_conv_split<128, 128, 2, 16>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
         case TILE_128x128_H3K16W8: return a.out_mode == 0 ? launch_conv_split<128, 128, 2, 16, 8>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_H3K32:
-            if (conv_w64_eligible(a_in)) return launch_conv_w64(a, s);
-            return a.out_mode == 0 ? launch_conv_split<128, 128, 2, 32>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
+        case TILE_128x128_H3K32:   return a.out_mode == 0 ? launch_conv_split<128, 128, 2, 32>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
         case TILE_128x64_H3:       return a.out_mode == 0 ? launch_conv_split<128, 64, 2, 32>(a, s) : launch_conv_t<128, 64, 2, 2, true>(a, s);
         case TILE_128x64_S6:  return a.out_mode == 0 ? launch_conv_split<128, 64, 6, 32>(a, s) : launch_conv_t<128, 64, 2, 2, true>(a, s);
         default:          return launch_conv_t<128, 128, 2, 2, true>(a, s);

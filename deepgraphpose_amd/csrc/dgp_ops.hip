@@ -473,14 +473,12 @@ struct StemPoolArgs {
     int B, H, W, H1, W1, HP, WP, pbh, pbw, tiles_h, tiles_w, ntiles;
 };
 
-#ifndef DGP_STEM_PH
-#define DGP_STEM_PH 5      // pool rows per tile of the parity tier's kernel.  5: the conv1 tile aliases the input planes, four barriers per tile; 4 / 3: own
-                           // buffers, two barriers -- same-box A/B (scripts/r6_stem_ph.sh): 255-261 us at 4 against 256-259 at 5, 297-301 at 3: with ONE workgroup per
-                           // CU the phases are serial either way
-#endif
+// Pool rows per tile: 5 in the parity tier's kernel, whose conv1 tile aliases the input planes (four barriers per tile).  4 or 3 rows with
+// buffers of their own and two barriers measured no faster (EXPERIMENTS.md R6: 255-261 us at 4 against 256-259 at 5, 297-301 at 3):
+// with ONE workgroup per CU the phases are serial either way.
 template <bool H1T>
 __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolArgs p) {
-    constexpr int PH = H1T ? 3 : DGP_STEM_PH, PW = 16, SR = 2 * PH + 1, SC = 2 * PW + 1, MS = SR * SC, NRB = (MS + 15) / 16;     // 11, 33, 363, 23 (H1T: 7, 33, 231, 15)
+    constexpr int PH = H1T ? 3 : 5, PW = 16, SR = 2 * PH + 1, SC = 2 * PW + 1, MS = SR * SC, NRB = (MS + 15) / 16;     // 11, 33, 363, 23 (H1T: 7, 33, 231, 15)
     constexpr int IR = 2 * SR + 5, IC = 72;                                                                   // 27 x 72 input pixels (H1T: 19 x 72)
     static_assert(NRB <= 24 && NRB > 8, "one to three row blocks per wave");
     constexpr int NPL = H1T ? 1 : 2;                                                                          // weight planes in LDS
@@ -492,7 +490,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
     uint4* sW = reinterpret_cast<uint4*>(smem);
     char* sU = smem + WCELLS * 16;
     uint2* sHi = reinterpret_cast<uint2*>(sU);                     // [IR][IC]
-    constexpr bool ALIAS = !H1T && PH >= 5;                         // the conv1 tile aliases the planes where both do not fit (5 x 16 tiles of the parity tier)
+    constexpr bool ALIAS = !H1T;                                    // the conv1 tile aliases the planes where both do not fit (5 x 16 tiles of the parity tier)
     float* sC = reinterpret_cast<float*>(sU + (ALIAS ? 0 : IR * IC * 8));      // [NRB * 16][LDC]
     _Float16* sCh = reinterpret_cast<_Float16*>(sU + IR * IC * 8); // H1T: [NRB * 16][LDH], BEHIND the planes (not aliased: two barriers per tile instead of four)
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -543,18 +541,14 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
             for (int w = 0; w < 3; ++w) pix[w] = b[4 * w] | (b[4 * w + 1] << 8) | (b[4 * w + 2] << 16) | (b[4 * w + 3] << 24);
         }
     };
-#ifndef DGP_SX
-#define DGP_SX 0      // timing-only ablations of the phases (scripts/ablate_stem.sh; results are garbage): 1 no input fetch, 2 no phase 1,
-#endif                // 4 no MFMAs, 8 no phase-3 tile store, 16 no pooling reads, 32 no global stores
-    if (!(DGP_SX & 1) && (int)blockIdx.x < p.ntiles) fetch(blockIdx.x);
-    if (DGP_SX & 1) { pix[0] = t; pix[1] = wave; pix[2] = lane; }
+    if ((int)blockIdx.x < p.ntiles) fetch(blockIdx.x);
     for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
         const int n = tile / (p.tiles_h * p.tiles_w), rem = tile - n * (p.tiles_h * p.tiles_w);
         const int ph0 = (rem / p.tiles_w) * PH, pw0 = (rem % p.tiles_w) * PW;
         const int r0 = 2 * ph0 - p.pbh, c0 = 2 * pw0 - p.pbw;      // first conv1 pixel of the tile
         const int ir0 = 2 * r0 - 3, ic0 = 2 * c0 - 3;              // first input pixel
         // ---- phase 1: input pixels (already in registers) -> fp16 high / low planes
-        if (!(DGP_SX & 2) && fr_on) {
+        if (fr_on) {
             const int gr = ir0 + fr_r, gc = ic0 + fr_c;
             const bool rok = (unsigned)gr < (unsigned)p.H;
             unsigned w[8];
@@ -575,7 +569,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
             dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
         }
         __syncthreads();
-        if (!(DGP_SX & 1) && tile + (int)gridDim.x < p.ntiles) fetch(tile + gridDim.x);
+        if (tile + (int)gridDim.x < p.ntiles) fetch(tile + gridDim.x);
         // ---- phase 2: GEMM
         floatx4 acc[3][4];
 #pragma unroll
@@ -604,7 +598,6 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
                     const uint4 ah = *reinterpret_cast<const uint4*>(sHi + abase[i] + kh * IC);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        if (DGP_SX & 4) { acc[i][j][0] += __builtin_bit_cast(float, ah.x ^ bh[j].y ^ bh[j].z); continue; }
                         if constexpr (!H1T)
                             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ah), __builtin_bit_cast(half8, bl[j]), acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ah), __builtin_bit_cast(half8, bh[j]), acc[i][j], 0, 0, 0);
@@ -635,13 +628,12 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
                         asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h01) : "v"(oscale), "v"(v4[1]));
                         asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h23) : "v"(oscale), "v"(v4[2]));
                         asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h23) : "v"(oscale), "v"(v4[3]));
-                        if (!(DGP_SX & 8)) *reinterpret_cast<uint2*>(sCh + m * LDH + 4 * l15) = make_uint2(h01, h23);
+                        *reinterpret_cast<uint2*>(sCh + m * LDH + 4 * l15) = make_uint2(h01, h23);
                         continue;
                     }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const float v = fmaxf(acc[i][j][r] * sc4[j][0] + bi4[j][0], 0.f);
-                        if (DGP_SX & 8) { amax = fmaxf(amax, v); continue; }
                         sC[m * LDC + 16 * j + l15] = ok ? v : 0.f;
                     }
                 }
@@ -669,18 +661,15 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
 #pragma unroll
                 for (int a = 0; a < 3; ++a)
 #pragma unroll
-                    for (int b = 0; b < 3; ++b) {
-                        if (DGP_SX & 16) { mx[0] = (_Float16)(float)(a + b + q); continue; }
+                    for (int b = 0; b < 3; ++b)
                         mx = __builtin_elementwise_max(mx, *reinterpret_cast<const half8*>(sCh + ((2 * ph + a) * SC + 2 * pw + b) * LDH + 8 * cg));
-                    }
                 }
                 if (ph0 + ph < p.HP && pw0 + pw < p.WP) {
                     const size_t cell = (((size_t)n * p.HP + ph0 + ph) * p.WP + pw0 + pw) * 8 + cg;
                     if (p.idx)
                         *reinterpret_cast<uint2*>(p.idx + cell * 8) = make_uint2(kk[0] | (kk[1] << 8) | (kk[2] << 16) | (kk[3] << 24),
                                                                                  kk[4] | (kk[5] << 8) | (kk[6] << 16) | (kk[7] << 24));
-                    if (!(DGP_SX & 32)) reinterpret_cast<uint4*>(p.out)[cell] = __builtin_bit_cast(uint4, mx);
-                    else amax = fmaxf(amax, (float)mx[0]);
+                    reinterpret_cast<uint4*>(p.out)[cell] = __builtin_bit_cast(uint4, mx);
                 }
                 continue;
             }
@@ -706,7 +695,6 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
 #pragma unroll
                 for (int b = 0; b < 3; ++b) {
                     const float* src = sC + ((2 * ph + a) * SC + 2 * pw + b) * LDC + 8 * cg;
-                    if (DGP_SX & 16) { v[0] = fmaxf(v[0], (float)(a + b + q)); continue; }
                     const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
                     v[0] = fmaxf(v[0], x0.x); v[1] = fmaxf(v[1], x0.y); v[2] = fmaxf(v[2], x0.z); v[3] = fmaxf(v[3], x0.w);
                     v[4] = fmaxf(v[4], x1.x); v[5] = fmaxf(v[5], x1.y); v[6] = fmaxf(v[6], x1.z); v[7] = fmaxf(v[7], x1.w);
@@ -720,7 +708,8 @@ __global__ __launch_bounds__(512, 2) void stem_pool_fused_kernel(const StemPoolA
                     *reinterpret_cast<uint2*>(p.idx + cell * 8) = make_uint2(kk[0] | (kk[1] << 8) | (kk[2] << 16) | (kk[3] << 24),
                                                                              kk[4] | (kk[5] << 8) | (kk[6] << 16) | (kk[7] << 24));
                 uint4* dst = reinterpret_cast<uint4*>(p.out) + (p.out_h1 ? cell : 2 * cell);
-                if (!(DGP_SX & 32)) { dst[0] = hi; if (!p.out_h1) dst[1] = lo; } else amax = fmaxf(amax, __builtin_bit_cast(float, hi.x ^ lo.y));
+                dst[0] = hi;
+                if (!p.out_h1) dst[1] = lo;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) amax = fmaxf(amax, v[k]);
             }
@@ -748,9 +737,9 @@ hipError_t launch_stem_pool_fused(const unsigned char* frames, int B, int H, int
     static const int h1t_env = dgp_tune("DGP_STEM_H1T", 1);
     static const int h1t_train_env = dgp_tune("DGP_STEM_H1T_TRAIN", 1);
     const bool h1t = h1t_env && out_h1 && (!idx || h1t_train_env);      // (training: the pool's first-maximum record is taken on the tier's own fp16 values)
-    const int ph = h1t ? 3 : DGP_STEM_PH;
+    const int ph = h1t ? 3 : 5;
     a.tiles_h = (a.HP + ph - 1) / ph; a.tiles_w = (a.WP + 15) / 16; a.ntiles = B * a.tiles_h * a.tiles_w;
-    const size_t smem = h1t ? (size_t)7 * 4 * 64 * 16 + (size_t)19 * 72 * 8 + (size_t)15 * 16 * 72 * 2 : (size_t)7 * 4 * 2 * 64 * 16 + (DGP_STEM_PH >= 5 ? (size_t)23 * 16 * 68 * 4 : (size_t)(4 * DGP_STEM_PH + 7) * 72 * 8 + (size_t)(((2 * DGP_STEM_PH + 1) * 33 + 15) / 16) * 16 * 68 * 4);
+    const size_t smem = h1t ? (size_t)7 * 4 * 64 * 16 + (size_t)19 * 72 * 8 + (size_t)15 * 16 * 72 * 2 : (size_t)7 * 4 * 2 * 64 * 16 + (size_t)23 * 16 * 68 * 4;
     static bool attr_dev[16][2] = {};
     bool& attr = attr_dev[dgp_device_slot()][h1t ? 1 : 0];
     if (!attr) {

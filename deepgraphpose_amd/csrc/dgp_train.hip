@@ -398,13 +398,7 @@ __device__ __forceinline__ void wgrad_f32_body(const WgradArgs& p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int k = q0 * 4 + wm * 32 * T + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (k < p.kchunks * 4) {
-#if defined(DGP_WX) && DGP_WX == 6
-                    p.dw[(long long)k * p.Cdy + co] = acc[i][j][r];
-#else
-                    atomicAdd(p.dw + (long long)k * p.Cdy + co, acc[i][j][r]);
-#endif
-                }
+                if (k < p.kchunks * 4) atomicAdd(p.dw + (long long)k * p.Cdy + co, acc[i][j][r]);
             }
     }
 }
@@ -454,228 +448,11 @@ __device__ __forceinline__ void split_hl(const float4 v, const float s, uint2& p
     pl.x = __builtin_bit_cast(unsigned, l01); pl.y = __builtin_bit_cast(unsigned, l23);
 }
 
-// byte offset of 16-byte chunk ch (0..15) of pixel row `row` in a [32][128 halves] plane (conflict-free for the 8-byte
-// row-wise writes and the transposed reads: cdna_hip_programming.md T10, image (b))
-__device__ __forceinline__ unsigned swz_off(int row, int ch) { return 256u * row + 16u * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
 struct WgradRanges { const float* x_absmax; const float* dy_absmax; };
 
-#ifdef DGP_DIAG
-// diagnostic build only: s_memtime stamps fence the schedule; read SHARES, not totals (scripts/diag_wgrad.py)
-#define WG_STAMP(x)                                                                     \
-    do {                                                                                \
-        __builtin_amdgcn_sched_barrier(0);                                              \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x)::"memory");       \
-        __builtin_amdgcn_sched_barrier(0);                                              \
-    } while (0)
-__device__ unsigned long long g_wgrad_diag[16];
-#else
-#define WG_STAMP(x)
-#endif
-
-__global__ __launch_bounds__(256) void wgrad_h3(const WgradArgs p, const WgradRanges rg) {
-    constexpr int BR = 128, CH = 32, NLD = 4;
-    constexpr unsigned PLANE = 32 * 256;          // bytes of one fp16 plane of a 32-pixel tile
-    extern __shared__ __attribute__((aligned(16))) char smem[];     // [2 buffers][A hi, A lo, B hi, B lo][PLANE]
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, half = lane >> 5, l31 = lane & 31;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int q0 = blockIdx.x * CH;
-    const int n0 = blockIdx.y * BR;
-    const int m_lo = blockIdx.z * p.m_per_block;
-    const int m_hi = min(p.M, m_lo + p.m_per_block);
-    const int nsteps = (m_hi - m_lo + 31) / 32;
-    if (nsteps <= 0) return;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dy), 0, (int)p.dy_bytes, 0x00020000);
-    const float sx = rng_scale(rg.x_absmax, lane), sy = rng_scale(rg.dy_absmax, lane);
-    const float post = 1.f / (sx * sy);           // exact power of two
-
-    const int cc = t % CH, pr = t / CH;           // this thread stages 4-channel chunk cc of pixel rows pr + 8 i
-    const int q = q0 + cc;
-    const int cin4m1 = (p.Cin >> 2) - 1;
-    const int tap = q >> p.log2cin4, ch = (q & cin4m1) << 2;
-    const bool qok = q < p.kchunks && tap < p.ntaps;
-    const int kh = tap / p.KW, kw = tap - kh * p.KW;
-    const int dh = kh * p.dil - p.pad_t, dw = kw * p.dil - p.pad_l;
-    const int cob = n0 + 4 * cc;
-    const bool cok = cob < p.Cdy;
-    const int HoWo = p.Ho * p.Wo;
-
-    float4 ra[NLD], rb[NLD];
-    // pixel coordinates of this thread's NLD rows, advanced by 32 pixels per step (no integer divisions in the loop: with three
-    // 16-bit MFMAs per product the staging arithmetic, not the matrix pipe, sets the pace of this kernel)
-    const bool pointwise = p.ntaps == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.H == p.Ho && p.W == p.Wo;
-    int pn[NLD], pho[NLD], pwo[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int m = m_lo + pr + 8 * i;
-        pn[i] = m / HoWo;
-        const int rem = m - pn[i] * HoWo;
-        pho[i] = rem / p.Wo;
-        pwo[i] = rem - pho[i] * p.Wo;
-    }
-    auto gload = [&](int step) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int m = m_lo + step * 32 + pr + 8 * i;
-            unsigned offa = OOBT, offb = OOBT;
-            if (m < m_hi) {
-                if (pointwise) {
-                    if (qok) offa = (unsigned)(m * p.Cin + ch) << 2;
-                } else {
-                    const int hi = pho[i] * p.stride + dh, wi = pwo[i] * p.stride + dw;
-                    if (qok && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
-                        offa = (unsigned)(((pn[i] * p.H + hi) * p.W + wi) * p.Cin + ch) << 2;
-                }
-                if (cok) offb = (unsigned)(m * p.Cdy + cob) << 2;
-            }
-            ra[i] = bload16(rs_x, offa);
-            rb[i] = bload16(rs_dy, offb);
-            if (!pointwise) {                      // next step: 32 pixels further
-                pwo[i] += 32;
-                while (pwo[i] >= p.Wo) { pwo[i] -= p.Wo; if (++pho[i] == p.Ho) { pho[i] = 0; ++pn[i]; } }
-            }
-        }
-    };
-    float4 cs4 = make_float4(0.f, 0.f, 0.f, 0.f);          // column sums of dY (d beta / d bias) from the staging registers
-    const bool do_colsum = p.colsum != nullptr && blockIdx.x == 0;
-    auto lstore = [&](int buf) {
-        char* base = smem + buf * (4 * PLANE);
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int row = pr + 8 * i;
-            const unsigned o = swz_off(row, cc >> 1) + 8u * (cc & 1);
-            uint2 h, l;
-            split_hl(ra[i], sx, h, l);
-            *reinterpret_cast<uint2*>(base + o) = h;
-            *reinterpret_cast<uint2*>(base + PLANE + o) = l;
-            split_hl(rb[i], sy, h, l);
-            *reinterpret_cast<uint2*>(base + 2 * PLANE + o) = h;
-            *reinterpret_cast<uint2*>(base + 3 * PLANE + o) = l;
-            if (do_colsum) { cs4.x += rb[i].x; cs4.y += rb[i].y; cs4.z += rb[i].z; cs4.w += rb[i].w; }
-        }
-    };
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // transposed-read addressing: 16-lane group g: columns 16 (g & 1) .. +15 of the 32-wide block, pixel group g >> 1
-    const int g16 = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;
-    const unsigned smem_base = (unsigned)(size_t)smem;
-    auto tr_addr = [&](int buf, int plane, int col0 /* first channel of the 32-wide block */, int pix0) {
-        const int row = pix0 + 8 * (g16 >> 1) + qq;
-        const int col = col0 + 16 * (g16 & 1) + 4 * pp;             // in halves
-        return smem_base + (unsigned)(buf * 4 * PLANE + plane * PLANE) + swz_off(row, col >> 3) + 8u * ((col >> 2) & 1);
-    };
-
-#ifdef DGP_DIAG
-    unsigned long long T0 = 0, T1 = 0, T2[2] = {0, 0}, T3[2] = {0, 0}, T4 = 0, T5 = 0, TB = 0, TE = 0, dsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    WG_STAMP(TB);
-#endif
-    gload(0);
-    lstore(0);
-    __syncthreads();
-    for (int s = 0; s < nsteps; ++s) {
-        const int buf = s & 1;
-        WG_STAMP(T0);
-        if (s + 1 < nsteps) gload(s + 1);
-        WG_STAMP(T1);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            // operands: [operand A/B][block][piece hi/lo] = 8 halves = two transposed reads of 4 pixels each
-            unsigned long long lo4[2][2][2], hi4[2][2][2];
-#pragma unroll
-            for (int op = 0; op < 2; ++op)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int pc = 0; pc < 2; ++pc) {
-                        const int col0 = (op == 0 ? wm : wn) * 64 + 32 * b;
-                        const unsigned a0 = tr_addr(buf, 2 * op + pc, col0, 16 * kk);          // pixels 0-3 of this lane's k-group
-                        const unsigned a1 = tr_addr(buf, 2 * op + pc, col0, 16 * kk + 4);      // pixels 4-7 (the row enters the swizzle)
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo4[op][b][pc]) : "v"(a0) : "memory");
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi4[op][b][pc]) : "v"(a1) : "memory");
-                    }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int op = 0; op < 2; ++op)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int pc = 0; pc < 2; ++pc) asm volatile("" : "+v"(lo4[op][b][pc]), "+v"(hi4[op][b][pc]));
-            WG_STAMP(T2[kk]);
-            auto frag = [&](int op, int b, int pc) {
-                const uint4 u = make_uint4((unsigned)lo4[op][b][pc], (unsigned)(lo4[op][b][pc] >> 32), (unsigned)hi4[op][b][pc],
-                                           (unsigned)(hi4[op][b][pc] >> 32));
-                return __builtin_bit_cast(half8t, u);
-            };
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    floatx16 a = acc[i][j];
-                    a = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(0, i, 1), frag(1, j, 0), a, 0, 0, 0);      // lo * hi
-                    a = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(0, i, 0), frag(1, j, 1), a, 0, 0, 0);      // hi * lo
-                    a = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag(0, i, 0), frag(1, j, 0), a, 0, 0, 0);      // hi * hi
-                    acc[i][j] = a;
-                }
-            WG_STAMP(T3[kk]);
-        }
-        if (s + 1 < nsteps) lstore(buf ^ 1);
-        WG_STAMP(T4);
-        __syncthreads();
-#ifdef DGP_DIAG
-        WG_STAMP(T5);
-        dsum[0] += T1 - T0; dsum[1] += T2[0] - T1; dsum[2] += T3[0] - T2[0]; dsum[3] += T2[1] - T3[0];
-        dsum[4] += T3[1] - T2[1]; dsum[5] += T4 - T3[1]; dsum[6] += T5 - T4;
-#endif
-    }
-#ifdef DGP_DIAG
-    WG_STAMP(TE);
-#endif
-    if (do_colsum && cok) {
-        atomicAdd(p.colsum + cob, cs4.x); atomicAdd(p.colsum + cob + 1, cs4.y);
-        atomicAdd(p.colsum + cob + 2, cs4.z); atomicAdd(p.colsum + cob + 3, cs4.w);
-    }
-    // C/D layout: col = lane&31 (co), row = (r&3) + 8*(r>>2) + 4*half (k)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int co = n0 + wn * 64 + 32 * j + l31;
-        if (co >= p.Cdy) continue;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int k = q0 * 4 + wm * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (k < p.kchunks * 4) {
-#if defined(DGP_WX) && DGP_WX == 6
-                    p.dw[(long long)k * p.Cdy + co] = acc[i][j][r] * post;
-#else
-                    atomicAdd(p.dw + (long long)k * p.Cdy + co, acc[i][j][r] * post);
-#endif
-                }
-            }
-    }
-#ifdef DGP_DIAG
-    if (lane == 0 && wave == 0) {
-        unsigned long long TF;
-        WG_STAMP(TF);
-        for (int k = 0; k < 7; ++k) atomicAdd(&g_wgrad_diag[k], dsum[k]);
-        atomicAdd(&g_wgrad_diag[7], T0 ? (unsigned long long)nsteps : 0ull);
-        atomicAdd(&g_wgrad_diag[8], TE - TB);        // prologue + loop
-        atomicAdd(&g_wgrad_diag[9], TF - TE);        // atomics epilogue (issue + colsum)
-        atomicAdd(&g_wgrad_diag[10], 1ull);
-    }
-#endif
-}
-
 // ------------------------------------------------------------------------------------------------
-// wgrad_h3p: wgrad_h3 as an explicit software pipeline.  scripts/diag_wgrad.py stamps on wgrad_h3 (b4.conv2, cycles per 32-pixel
-// step of 4400): staging-load issue 1630, transposed reads 690, the 24 MFMAs 850, split + LDS stores 1100, barrier 130 -- the
+// wgrad_h3p: the weight-gradient tile as an explicit software pipeline.  Diagnostic-build stamps of the plain, non-pipelined version it
+// replaced (b4.conv2, cycles per 32-pixel step of 4400): staging-load issue 1630, transposed reads 690, the 24 MFMAs 850, split + LDS stores 1100, barrier 130 -- the
 // phases of a wave ran one after the other and the four waves of a workgroup ran them in lock-step, so each shared unit (texture
 // addresser, LDS, matrix pipe) was busy in bursts and idle between them (PMC: TA busy 22 %, L2 hit 83 %, L1->L2 latency 173 cycles,
 // MFMA busy 23 %).  Here every MFMA is followed by a fixed slice of the other work:
@@ -855,23 +632,6 @@ __global__ __launch_bounds__(256) void wgrad_h3p(const WgradArgs p, const WgradR
     WG_WAIT_LDS();
     WG_FENCE();
 
-#if defined(DGP_WX)      // timing-only ablations (results are garbage): scripts/ablate_wgrad.sh
-#if DGP_WX == 1         // no global loads inside the loop
-#undef WG_LOAD
-#define WG_LOAD(U) do { if ((U) < 4) asm volatile("" : "+v"(ra[(U) & 3].x), "+v"(ra[(U) & 3].y), "+v"(ra[(U) & 3].z), "+v"(ra[(U) & 3].w)); else asm volatile("" : "+v"(rb[(U) & 3].x), "+v"(rb[(U) & 3].y), "+v"(rb[(U) & 3].z), "+v"(rb[(U) & 3].w)); } while (0)
-#elif DGP_WX == 2       // no MFMAs
-#undef WG_MMA
-#define WG_MMA(F, G) do { asm volatile("" :: "v"(F[0][0].v[0][0]), "v"(F[0][1].v[0][0]), "v"(F[1][0].v[0][0]), "v"(F[1][1].v[0][0]), "v"(F[0][0].v[1][1]), "v"(F[0][1].v[1][1]), "v"(F[1][0].v[1][1]), "v"(F[1][1].v[1][1])); } while (0)
-#elif DGP_WX == 3       // no transposed reads inside the loop
-#undef WG_READ2
-#define WG_READ2(F, BUFI, KK, R) do { constexpr int op_ = ((R) >> 2) & 1, b_ = ((R) >> 1) & 1, pc_ = (R) & 1; asm volatile("" : "+v"(F[op_][b_].v[pc_][0]), "+v"(F[op_][b_].v[pc_][1])); } while (0)
-#elif DGP_WX == 4       // no split + store inside the loop
-#undef WG_UNIT
-#define WG_UNIT(SB, U) do { asm volatile("" :: "v"(ra[(U) & 3].x), "v"(rb[(U) & 3].x)); } while (0)
-#elif DGP_WX == 5       // no mid-step barrier
-#define __syncthreads() do { } while (0)
-#endif
-#endif
     // one step on compute buffer CB: stores go to the other buffer, the next step's first fragments come from it
 #define WG_STEP(CB)                                                                                                  \
     do {                                                                                                             \
@@ -932,13 +692,7 @@ __global__ __launch_bounds__(256) void wgrad_h3p(const WgradArgs p, const WgradR
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int k = q0 * 4 + wm * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (k < p.kchunks * 4) {
-#if defined(DGP_WX) && DGP_WX == 6
-                    p.dw[(long long)k * p.Cdy + co] = acc[i][j][r] * post;
-#else
-                    atomicAdd(p.dw + (long long)k * p.Cdy + co, acc[i][j][r] * post);
-#endif
-                }
+                if (k < p.kchunks * 4) atomicAdd(p.dw + (long long)k * p.Cdy + co, acc[i][j][r] * post);
             }
     }
 }
@@ -2343,7 +2097,7 @@ hipError_t wgrad_launch(const float* x, int N, int H, int W, int Cin, const floa
     if (mpb < 256) mpb = 256;
     split = (a.M + mpb - 1) / mpb;
     a.m_per_block = mpb;
-    static bool attr_dev[16][4] = {};
+    static bool attr_dev[16][3] = {};
     auto& attr = attr_dev[dgp_device_slot()];
     static const bool h3_env = (dgp_tune("DGP_WGRAD_F16", 1) != 0);       // A/B switch
     const float* rx = rx_given ? rx_given : range_of(x);
@@ -2363,10 +2117,10 @@ hipError_t wgrad_launch(const float* x, int N, int H, int W, int Cin, const floa
     }
     if (big && h3_env && g_wgrad_dma && rx && rdy && xs && dys && x_prev && dy_prev && Cin % 16 == 0 && ((Cin / 8) & (Cin / 8 - 1)) == 0 && Cdy % 8 == 0 &&
         (double)a.x_bytes + 160.0 * Cin * 4 < 4294967000.0 && (double)a.dy_bytes + 160.0 * Cdy * 4 < 4294967000.0) {
-        if (!attr[3]) {
+        if (!attr[2]) {
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
             if (e != hipSuccess) return e;
-            attr[3] = true;
+            attr[2] = true;
         }
         a.xs = xs; a.dys = dys; a.x_prev = x_prev; a.x_cur = rx; a.dy_prev = dy_prev; a.dy_cur = rdy;
         if (x_h2_only_flag) { a.x = nullptr; a.fail_flag = x_h2_only_flag; }
@@ -2375,35 +2129,12 @@ hipError_t wgrad_launch(const float* x, int N, int H, int W, int Cin, const floa
     }
     if (x_h2_only_flag) return hipErrorInvalidValue;       // (no other kernel reads H2 cells)
     if (big && h3_env && rx && rdy && Cin % 4 == 0) {      // both operand ranges known: 16-bit matrix pipe
-        if (!attr[2]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_h3), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        if (!attr[0]) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_h3p), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
             if (e != hipSuccess) return e;
-            attr[2] = true;
+            attr[0] = true;
         }
-        WgradRanges rg{rx, rdy};
-        static const bool pipe_env = (dgp_tune("DGP_WGRAD_PIPE", 1) != 0);      // A/B switch
-        if (pipe_env) {
-            if (!attr[0]) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_h3p), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-                if (e != hipSuccess) return e;
-                attr[0] = true;
-            }
-            hipLaunchKernelGGL(wgrad_h3p, dim3(kt, nt, split), dim3(256), 2 * 4 * 32 * 256, s, a, rg);
-            return hipGetLastError();
-        }
-#ifdef DGP_DIAG
-        unsigned long long hz[16] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_diag), hz, sizeof(hz));
-#endif
-        hipLaunchKernelGGL(wgrad_h3, dim3(kt, nt, split), dim3(256), 2 * 4 * 32 * 256, s, a, rg);
-#ifdef DGP_DIAG
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpyFromSymbol(hz, HIP_SYMBOL(g_wgrad_diag), sizeof(hz));
-        const double ns = (double)hz[7], nw = (double)hz[10];
-        printf("[diag wgrad_h3] K %d Cdy %d M %d grid %dx%dx%d steps/wg %.1f | per step (wave 0, 100 MHz ticks): gload-issue %.1f tr-read0 %.1f "
-               "mfma0 %.1f tr-read1 %.1f mfma1 %.1f split+store %.1f barrier %.1f | per wg: loop %.0f epilogue %.0f\n", a.kchunks * 4, Cdy, a.M,
-               kt, nt, split, ns / nw, hz[0] / ns, hz[1] / ns, hz[2] / ns, hz[3] / ns, hz[4] / ns, hz[5] / ns, hz[6] / ns, hz[8] / nw, hz[9] / nw);
-#endif
+        hipLaunchKernelGGL(wgrad_h3p, dim3(kt, nt, split), dim3(256), 2 * 4 * 32 * 256, s, a, WgradRanges{rx, rdy});
         return hipGetLastError();
     }
     if (big) {
@@ -3716,7 +3447,7 @@ int dgp_trainer_fast_status(dgp_trainer* tr, int32_t* was_fast, int32_t* failed)
 /* ---- single-layer backward entry points (layer-level parity tests at the real shapes; the trainer calls the same launchers) ---- */
 
 /* dWraw[(tap, ci)][co] = sum_m x[m + tap][ci] * dy[m][co] (HWIO order, Cin rows per tap), colsum[co] = sum_m dy[m][co].
- * With both ranges (DGP_ABSMAX_SLOTS floats each) the fp16-split kernel wgrad_h3 runs where the tile is 128 x 128, else wgrad_f32. */
+ * With both ranges (DGP_ABSMAX_SLOTS floats each) the fp16-split kernel wgrad_h3p runs where the tile is 128 x 128, else wgrad_f32. */
 int dgp_conv2d_wgrad(const dgp_conv_desc* d, const float* x, const float* dy, const float* x_absmax, const float* dy_absmax,
                      float* dw_raw, float* colsum, void* stream) {
     g_ctx = nullptr;              // layer-level call: explicit ranges only

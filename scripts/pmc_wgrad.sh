@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes over scripts/diag_wgrad.py (normal build): L2 hit rate, fabric bytes, L1 / TA busy of the weight-gradient kernels
+# PMC passes over scripts/bench_wgrad_layers.py: L2 hit rate, fabric bytes, L1 / TA busy of the weight-gradient kernels (wgrad_h3p, wgrad_dma)
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/pmc_wgrad
@@ -9,7 +9,7 @@ grep -o "TCP_[A-Z_0-9a-z]*\|TA_[A-Z_0-9a-z]*\|TCC_[A-Z_0-9a-z]*\|TD_[A-Z_0-9a-z]
 i=0
 for set in "TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum" "TA_BUSY_avr TA_TA_BUSY_sum GRBM_GUI_ACTIVE" "TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_TCR_TCP_STALL_CYCLES_sum" "TCC_REQ_sum TCC_EA0_RDREQ_sum TCC_TAG_STALL_sum" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_LATENCY_sum"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$OUT/p$i" -- python3 scripts/diag_wgrad.py > "$OUT/p$i.log" 2>&1
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$OUT/p$i" -- python3 scripts/bench_wgrad_layers.py > "$OUT/p$i.log" 2>&1
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, os

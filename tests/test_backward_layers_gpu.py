@@ -3,7 +3,7 @@
 dense-skeleton shapes of config 5.
 
 The forward kernels have per-layer float64 tests in test_parity_gpu.py; these are the same for the backward kernels
-(`wgrad_h3`, `wgrad_f32<1|2>`, the data-gradient convs incl. the zero-stuffed stride-2 gather, ReLU gate and shortcut adds).
+(`wgrad_h3p`, `wgrad_f32<1|2>`, the data-gradient convs incl. the zero-stuffed stride-2 gather, ReLU gate and shortcut adds).
 Reference arithmetic: float64 im2col + matmul written out below (torch is only the float64 calculator).
 Tolerance: 1e-5 relative (max-abs error over max |reference|) -- fp32 accumulation noise of a 13 200-pixel reduction.
 """
@@ -45,7 +45,7 @@ def _im2col64(x, k, stride, rate, pad_t, pad_l, Ho, Wo):
 
 # (N, H, W, Cin, Cout, k, stride, rate) -- the config-4 layer shapes (nt = 11)
 CONFIG4_WGRAD_CASES = [
-    (11, 30, 40, 512, 512, 3, 1, 2),        # block4 conv2 (dilated): wgrad_h3, 128 x 128 tiles, 1024-workgroup grid
+    (11, 30, 40, 512, 512, 3, 1, 2),        # block4 conv2 (dilated): wgrad_h3p, 128 x 128 tiles, 1024-workgroup grid
     (11, 30, 40, 1024, 256, 1, 1, 1),       # block3 conv1
     (11, 30, 40, 2048, 512, 1, 1, 1),       # block4 conv1 (deepest K)
     (11, 60, 80, 128, 128, 3, 2, 1),        # block2 unit_4 conv2: stride 2, conv2d_same padding
