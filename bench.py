@@ -14,11 +14,15 @@ reassembles the [T, nj] trajectory: weak scaling.
     python bench.py --gpus N ...            # no launcher: spawns its own N worker processes (one per GPU, RCCL over 127.0.0.1)
     python bench.py --gpus N --scaling strong --total-batches 1024   # ONE fixed stream of 32768 frames split over the N ranks
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR  # + the last timed step's mu / conf / idx as DIR/<name>.npy
+    python bench.py --gpus 1 --steps K --warmup W --full              # + everything that is not the headline figure (below)
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (conv kernel, MFMA-bound, fp32 matrix
-peak) from hipEvent pairs recorded around every launch inside the timed region, and
-"cpu_baseline" (the CPU oracle = fp32 torch-CPU restatement of the TF1 reference path, timed
-on this box's host cores on a bounded sample; TF1 itself cannot be installed here).
+Rank 0 prints ONE JSON line.  A plain run sets up, pre-warms, runs the W warm-up and K timed steps and
+prints the line: `value` / `ms_per_step` and the "roofline" object (conv kernel, MFMA-bound, fp32 matrix
+peak) from hipEvent pairs recorded around every launch inside the timed region.  `--full` adds what
+takes runs of its own: the "sustained" segment, "cpu_baseline" with "accuracy_vs_oracle" (the CPU
+oracle = fp32 torch-CPU restatement of the TF1 reference path, timed on the host cores on a bounded
+sample; TF1 itself cannot be installed here) and, at N = 1, the child-process legs (strict_f32, tier_f16,
+r101_1280x720(_f16), train_step(_f16), host_pipeline(_f16)).
 """
 from __future__ import annotations
 
@@ -447,6 +451,9 @@ def main():
     ap.add_argument("--steps", type=int, default=64)      # (0.44 s of timed region at 6.9 ms per step; round 2 timed 20 steps = 0.15 s)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the sustained segment, the CPU baseline and oracle check, and (N = 1) the "
+                         "child-process legs; the options below that shape those parts act only with --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=64, help="size of the bounded CPU-baseline sample (batch-1 leg: a quarter of it)")
     ap.add_argument("--cpu-threads", type=int, default=16,
@@ -610,10 +617,10 @@ def main():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         dumped = {"dir": args.dump_outputs, "step": K - 1, "arrays": {name: list(a.shape) for name, a in dumped.items()}}
 
-    # sustained segment (untimed for `value`): >= 5 s of back-to-back steps so that clocks, power and the driver's SMI sampler see
-    # a loaded GPU; reports the rate and the shader clock sysfs shows while it runs
+    # sustained segment (--full; untimed for `value`): >= 5 s of back-to-back steps so that clocks, power and the driver's SMI sampler
+    # see a loaded GPU; reports the rate and the shader clock sysfs shows while it runs
     sustained = None
-    if rank == 0 or use_pg:
+    if args.full and (rank == 0 or use_pg):
         s_steps, s0 = 0, time.perf_counter()
         sclk = None
         while True:
@@ -712,6 +719,7 @@ def main():
                    "frames_per_step_per_gpu": B, "sharding": "contiguous frame shards, 1 RCCL all-gather per run",
                    "total_frames": world * n_local},
         "roofline": roofline,
+        "full": bool(args.full),          # plain run: no sustained segment, CPU baseline or child legs in this line
         "sustained": sustained,
         "shard_check": shard_check,
         "prewarm_seconds": args.prewarm_seconds,
@@ -730,7 +738,7 @@ def main():
     if dumped:
         out["dump_outputs"] = dumped
 
-    if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only
         from oracle import dgp_oracle as O      # checker / baseline only
         nthreads = max(1, min(args.cpu_threads, os.cpu_count() or 1))
         torch.set_num_threads(nthreads)
@@ -781,7 +789,7 @@ def main():
                     "CPU oracle on the same frames",
         }
         assert idx_ok and float(err.max()) < 1e-3, "timed trajectory outside the parity gate"
-    if world == 1 and not args.no_strict_f32:
+    if args.full and world == 1 and not args.no_strict_f32:
         # the IEEE-fp32 tier beside the fp32-class one, timed in THIS run: a fresh child process (the conv mode is read once per
         # process) runs the same workload on the fp32 MFMA kernels for a few steps
         import subprocess
@@ -807,7 +815,7 @@ def main():
                 out[key] = json.loads(ln[-1]) if cp.returncode == 0 and ln else {"error": (cp.stderr or cp.stdout)[-300:]}
             except Exception as e:      # noqa: BLE001 -- the main line must still be printed
                 out[key] = {"error": repr(e)[:300]}
-    if world == 1 and not args.no_strict_f32 and not args.no_r101:
+    if args.full and world == 1 and not args.no_strict_f32 and not args.no_r101:
         # BASELINE configs[4]'s per-GPU shape (ResNet-101, 1280 x 720, 20 keypoints) in a fresh child process: block3 has 23 units there
         import subprocess
         env = dict(os.environ)
@@ -825,7 +833,7 @@ def main():
             out["r101_1280x720_f16"] = json.loads(ln[-1]) if cp.returncode == 0 and ln else {"error": (cp.stderr or cp.stdout)[-300:]}
         except Exception as e:      # noqa: BLE001
             out.setdefault("r101_1280x720", {"error": repr(e)[:300]})
-    if world == 1 and not args.no_train_step and not args.no_strict_f32:
+    if args.full and world == 1 and not args.no_train_step and not args.no_strict_f32:
         # BASELINE configs[3] next to the headline number, driver-timed: the semi-supervised fit_dgp step (1 labeled + 10 unlabeled 640 x 480
         # frames, gm2 = 1, gm3 = 3, skeleton clique; forward + loss + backward + clip + momentum) -- the call that replaces
         # sess.run([loss, train_op]) (DGP/models/fitdgp.py:801-818) -- in a fresh child process (scripts/bench_train.py), never a re-exec
@@ -865,7 +873,7 @@ def main():
                     frac_basis="3 x forward conv FLOPs / step time / 2500 TFLOP/s (one MFMA per product)")
         except Exception as e:      # noqa: BLE001 -- the main line must still be printed
             out.setdefault("train_step", {"error": repr(e)[:300]})
-    if world == 1 and not args.no_host_pipeline and not args.no_strict_f32:
+    if args.full and world == 1 and not args.no_host_pipeline and not args.no_strict_f32:
         # the PCIe-inclusive rate of the boundary that takes HOST frames (A0 estimate_pose: decode thread -> pinned ring -> copy stream -> engines
         # -> one D2H), in a fresh child process; reported beside `value`, never as it
         import subprocess

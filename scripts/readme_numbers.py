@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """README.md's table of numbers, generated from the committed bench lines (profiles/r<N>_bench_line*.json: one JSON line of `python
-bench.py` each, one box per file) -- never typed by hand.  `readme_numbers.py` rewrites the block between the two markers in
+bench.py --full` each, one box per file) -- never typed by hand.  `readme_numbers.py` rewrites the block between the two markers in
 README.md; `--check` exits 1 when the block is out of date (tests/test_host_new_cpu.py)."""
 import glob, json, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -6,7 +6,7 @@ TAG=${1:-r5}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/refresh_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"; export TMPDIR=/tmp; cd "$ROOT"
-python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
+python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
 # parity tier: kernel trace + PMC passes of the bench command, per-launch table, every launch against both roofs
 bash scripts/profile.sh "$TAG" > "$OUT/profile_sh.log" 2>&1
 cp gpurun_out/prof_$TAG/kernel_stats.csv "$OUT/kernel_stats.csv"

@@ -253,9 +253,11 @@ def _run_bench(args, **env_extra):
 
 def test_bench_through_its_own_spawner(lib_built):
     """`python bench.py --gpus N` with no launcher around it spawns its N workers itself (the parent never touches the GPU) and relays
-    rank 0's line.  Here N = 1 through the spawner (DGP_BENCH_FORCE_SPAWN=1): RCCL group of one rank, the strict-fp32 child run included."""
-    d = _run_bench(["--gpus", "1", "--steps", "6", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--sustain-seconds", "0.3",
+    rank 0's line.  Here N = 1 through the spawner (DGP_BENCH_FORCE_SPAWN=1): RCCL group of one rank, with --full the strict-fp32 child run
+    included."""
+    d = _run_bench(["--gpus", "1", "--steps", "6", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline", "--sustain-seconds", "0.3",
                     "--prewarm-seconds", "0.2", "--train-steps", "3", "--no-r101", "--host-frames", "128"], DGP_BENCH_FORCE_SPAWN=1)
+    assert d["full"] and d["sustained"]["steps"] > 0
     hp = d["host_pipeline"]                                 # the PCIe-inclusive estimate_pose leg, also a fresh child
     assert "error" not in hp and hp["frames"] == 128 and hp["frames_per_s"] > 0 and hp["host_seconds"]["drain_s"] >= 0
     ts = d["train_step"]                                    # BASELINE configs[3], timed by a fresh child of the same run
@@ -268,6 +270,25 @@ def test_bench_through_its_own_spawner(lib_built):
     kern = d["roofline"]["kernels"]
     assert any(k.startswith("chain_") or k.startswith("unit_") for k in kern)       # the fused bottleneck launches are in the table
     assert all(v["bound"] in ("hbm", "mfma") for v in kern.values())
+
+
+def test_bench_plain_run_reports_the_headline_only(lib_built, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the timed steps, the roofline of their instrumented launches and the
+    dumped outputs, but no sustained segment, CPU baseline, oracle check or child-process leg."""
+    d = _run_bench(["--gpus", "1", "--steps", "6", "--warmup", "1", "--batch", "8", "--prewarm-seconds", "0.2", "--dump-outputs", str(tmp_path)])
+    assert d["metric"] == "frames_per_sec" and d["unit"] == "frames/s" and d["higher_is_better"] and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 1 and d["value"] > 0
+    assert abs(d["value"] - 6 * 8 / (d["ms_per_step"] * 6 / 1e3)) <= 1e-3 * d["value"]
+    assert d["roofline"]["frac"] > 0 and d["shard_check"]["indices_identical"]
+    assert not d["full"] and d["sustained"] is None
+    for key in ("cpu_baseline", "accuracy_vs_oracle", "strict_f32", "tier_f16", "r101_1280x720", "r101_1280x720_f16", "train_step", "train_step_f16",
+                "host_pipeline", "host_pipeline_f16"):
+        assert key not in d, key
+    shapes = {"mu": (8, 4, 2), "conf": (8, 4), "idx": (8, 4, 2)}
+    assert d["dump_outputs"]["step"] == 5 and {k: tuple(v) for k, v in d["dump_outputs"]["arrays"].items()} == shapes
+    for name, shape in shapes.items():
+        a = np.load(str(tmp_path / (name + ".npy")))
+        assert a.shape == shape and np.isfinite(a).all(), name
 
 
 def test_bench_under_torch_distributed_run_exactly_as_the_driver_launches_it(lib_built):
