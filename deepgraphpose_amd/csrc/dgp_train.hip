@@ -27,7 +27,6 @@ __device__ __forceinline__ float4 bload16(__amdgpu_buffer_rsrc_t r, unsigned off
 // ------------------------------------------------------------------------------------------------
 // weight (re)packing on the device, from the flat master parameter buffer
 // ------------------------------------------------------------------------------------------------
-// forward panels [nk*8][CoutP][4] from HWIO [KH*KW][Cin_real][Cout]
 // max |v| of what a pack kernel wrote -> the panel's range slots (fp16-split convs of the training step); non-negative floats
 // order like their bit patterns, slots spread the atomics
 __device__ __forceinline__ void pack_track(float* rng, float m) {
@@ -39,27 +38,6 @@ __device__ __forceinline__ void pack_track(float* rng, float m) {
 }
 __device__ __forceinline__ float amax4(float m, const float4& v) {
     return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-}
-
-__global__ void pack_fwd_kernel(const float* __restrict__ w, int taps, int cin_real, int cin, int cout, int coutP,
-                                int nchunks, float* __restrict__ packed, float* __restrict__ rng) {
-    float mx = 0.f;
-    const long long total = (long long)nchunks * coutP;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
-        const int co = (int)(g % coutP);
-        const int q = (int)(g / coutP);
-        const int cin4 = cin >> 2;
-        const int tap = q / cin4, ch = (q - tap * cin4) << 2;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tap < taps && co < cout) {
-            float* pv = &v.x;
-            for (int e = 0; e < 4; ++e)
-                if (ch + e < cin_real) pv[e] = w[((long long)tap * cin_real + ch + e) * cout + co];
-        }
-        *reinterpret_cast<float4*>(packed + g * 4) = v;
-        mx = amax4(mx, v);
-    }
-    pack_track(rng, mx);
 }
 
 // head forward panels: W'[khp][kwp][ci][(a,b),c] = w[a+2-2khp][b+2-2kwp][c][ci] (w is [3,3,njt,Cin])
@@ -109,17 +87,6 @@ __global__ void pack_head_pw_kernel(const float* __restrict__ w, int njt, int ci
     pack_track(rng, mx);
 }
 
-__global__ void fold_bn_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                               const float* __restrict__ mean, const float* __restrict__ var, float eps, int C,
-                               float* __restrict__ scale, float* __restrict__ bias) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) {
-        const float inv = gamma[c] / sqrtf(var[c] + eps);
-        scale[c] = inv;
-        bias[c] = beta[c] - mean[c] * inv;
-    }
-}
-
 __global__ void head_bias_kernel(const float* __restrict__ b, int njt, float* __restrict__ bias4) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < 4 * njt) bias4[i] = b[i % njt];
@@ -147,9 +114,10 @@ __global__ void pack_dgrad_kernel(const float* __restrict__ w, const float* __re
     pack_track(rng, mx);
 }
 
-// All non-head layers in ONE launch (the per-layer kernels above cost ~180 dispatches of 4 us + their gaps per step):
-// blockIdx.y = layer, blockIdx.z = job (0: forward panel, 1: data-gradient panel, 2: folded BN).  The data-gradient job folds
-// scale = gamma / sqrt(var + eps) itself (the same expression as fold_bn_kernel, so the same bits) instead of waiting for job 2.
+// All non-head layers in ONE launch (a launch per layer and job costs ~180 dispatches of 4 us + their gaps per step):
+// blockIdx.y = layer, blockIdx.z = job (0: forward panel [nk*8][CoutP][4] from HWIO [KH*KW][Cin_real][Cout], 1: data-gradient panel
+// as pack_dgrad_kernel lays it out, 2: folded BN: scale = gamma / sqrtf(var + eps), bias = beta - mean * scale).  The data-gradient
+// job evaluates the same expression for scale itself (so the same bits) instead of waiting for job 2.
 struct PackDesc {
     long long w_off, g_off, b_off, mean_off, var_off;
     int taps, cin_real, cin, cout, coutP, nchunks_f, cinP, nchunks_b;
@@ -1073,47 +1041,11 @@ __global__ __launch_bounds__(256) void h1_zero_stuff_kernel(const uint4* __restr
     }
 }
 
-// dW = scale * dWraw (HWIO, real Cin) and dot[co] += sum_k W[k][co] * dWraw[k][co]   (grid: k-chunks x co-tiles of 64)
-__global__ __launch_bounds__(256) void scale_dw_dot_kernel(const float* __restrict__ dwraw, const float* __restrict__ w,
-                                                           const float* __restrict__ scale, int taps, int cin, int cin_real,
-                                                           int cout, int rows_per_block, float* __restrict__ dW,
-                                                           float* __restrict__ dot) {
-    __shared__ float part[4][64];
-    const int co = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
-    const int krows = taps * cin_real;
-    const int k0 = blockIdx.y * rows_per_block, k1 = min(krows, k0 + rows_per_block);
-    float acc = 0.f;
-    if (co < cout) {
-        const float s = scale[co];
-        for (int k = k0 + rl; k < k1; k += 4) {
-            const int tp = k / cin_real, ci = k - tp * cin_real;
-            const float g = dwraw[((long long)tp * cin + ci) * cout + co];
-            const long long o = (long long)k * cout + co;
-            acc += w[o] * g;
-            dW[o] = s * g;
-        }
-    }
-    part[rl][threadIdx.x & 63] = acc;
-    __syncthreads();
-    if (rl == 0 && co < cout)
-        atomicAdd(dot + co, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
-}
-
-// dgamma = r * (dot - mean * dbeta), dbeta = colsum           (r = rsqrt(var + eps))
-__global__ void bn_param_grads_kernel(const float* __restrict__ dot, const float* __restrict__ colsum,
-                                      const float* __restrict__ mean, const float* __restrict__ var, float eps, int cout,
-                                      float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    const int co = blockIdx.x * blockDim.x + threadIdx.x;
-    if (co >= cout) return;
-    const float r = 1.f / sqrtf(var[co] + eps);
-    const float db = colsum[co];
-    dbeta[co] = db;
-    dgamma[co] = r * (dot[co] - mean[co] * db);
-}
-
-// The two kernels above for ALL non-head layers in one launch each (blockIdx.z = layer; offsets are relative to the workspace,
-// which the caller may move between steps): every layer keeps its own dWraw / colsum region, so nothing has to be finalised
-// between two layers' weight-gradient GEMMs.
+// Finalisation of the parameter gradients of ALL non-head layers in two launches (blockIdx.z / .y = layer; offsets are relative to the
+// workspace, which the caller may move between steps): every layer keeps its own dWraw / colsum region, so nothing has to be
+// finalised between two layers' weight-gradient GEMMs.
+//   scale_dw_dot_all_kernel:   dW = scale * dWraw (HWIO, real Cin) and dot[co] += sum_k W[k][co] * dWraw[k][co]
+//   bn_param_grads_all_kernel: dgamma = r * (dot - mean * dbeta), dbeta = colsum           (r = rsqrt(var + eps))
 struct FinDesc {
     long long dw_off, cs_off;              // bytes from the workspace base
     long long w_off, g_off, b_off, mean_off, var_off;
@@ -1255,7 +1187,7 @@ __global__ __launch_bounds__(256) void head_gather_h1_kernel(const float* __rest
 // max-pool 3x3/2 SAME backward fused with the stem's ReLU gate: dC1 = (C1 > 0) * sum over windows whose first
 // maximum is this element of dPool.
 // Training forward pool: the same maxima as maxpool3x3s2_same plus, per window and channel, the position (a * 3 + b) of its FIRST
-// maximum in row-major order -- the element TF's MaxPoolGrad (and the re-scan of maxpool_bwd_kernel below) routes the gradient to.
+// maximum in row-major window order -- the element TF's MaxPoolGrad routes the gradient to.
 __global__ __launch_bounds__(256) void maxpool_fwd_idx_kernel(const float* __restrict__ x, int N, int H, int W, int C4, int Ho, int Wo,
                                                               int pt, int pl, float* __restrict__ y, uchar4* __restrict__ idx,
                                                               uint2* __restrict__ y_h1 = nullptr, const float* __restrict__ h1_prev = nullptr) {
@@ -1298,7 +1230,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_idx_kernel(const float* __res
 }
 
 // Backward of that pool (+ the stem's ReLU gate): a pixel collects the gradient of every window (<= 4) whose recorded first maximum it
-// is, in the same window order as maxpool_bwd_kernel below -- bitwise the same result with ~5 loads per pixel instead of ~33.
+// is (ties: the first maximum in row-major window order, as TF's MaxPoolGrad), windows added in ascending (ho, wo) order: ~5 loads
+// per pixel.
 __global__ __launch_bounds__(256) void maxpool_bwd_idx_kernel(const float* __restrict__ c1, const float* __restrict__ dpool,
                                                               const uchar4* __restrict__ idx, int N, int H, int W, int C, int Ho, int Wo,
                                                               int pt, int pl, float* __restrict__ dc1) {
@@ -1326,55 +1259,6 @@ __global__ __launch_bounds__(256) void maxpool_bwd_idx_kernel(const float* __res
                     if (k.y == me) acc.y += d.y;
                     if (k.z == me) acc.z += d.z;
                     if (k.w == me) acc.w += d.w;
-                }
-            if (!(v.x > 0.f)) acc.x = 0.f;        // ReLU gate of the stem
-            if (!(v.y > 0.f)) acc.y = 0.f;
-            if (!(v.z > 0.f)) acc.z = 0.f;
-            if (!(v.w > 0.f)) acc.w = 0.f;
-        }
-        *reinterpret_cast<float4*>(dc1 + g * 4) = acc;
-    }
-}
-
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ c1, const float* __restrict__ dpool, int N, int H,
-                                                          int W, int C, int Ho, int Wo, int pt, int pl, float* __restrict__ dc1) {
-    // one thread per pixel and 4 channels (16-byte loads); <= 4 windows contain a pixel, each re-scanned for its first maximum
-    const int C4 = C >> 2;
-    const long long total = (long long)N * H * W * C4;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(g % C4);
-        long long r = g / C4;
-        const int wi = (int)(r % W);
-        r /= W;
-        const int hi = (int)(r % H);
-        const int n = (int)(r / H);
-        const float4 v = *reinterpret_cast<const float4*>(c1 + g * 4);
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (v.x > 0.f || v.y > 0.f || v.z > 0.f || v.w > 0.f) {
-            for (int ho = max(0, (hi + pt - 2 + 1) / 2); ho <= min(Ho - 1, (hi + pt) / 2); ++ho)
-                for (int wo = max(0, (wi + pl - 2 + 1) / 2); wo <= min(Wo - 1, (wi + pl) / 2); ++wo) {
-                    // is this pixel the FIRST maximum (row-major) of window (ho, wo), per channel?  It is iff no earlier
-                    // element is >= it and no later element is > it.
-                    bool fx = true, fy = true, fz = true, fw = true;
-                    for (int a = 0; a < 3; ++a) {
-                        const int hh = ho * 2 - pt + a;
-                        if ((unsigned)hh >= (unsigned)H) continue;
-                        for (int b = 0; b < 3; ++b) {
-                            const int ww = wo * 2 - pl + b;
-                            if ((unsigned)ww >= (unsigned)W || (hh == hi && ww == wi)) continue;
-                            const float4 u = *reinterpret_cast<const float4*>(c1 + ((((long long)n * H + hh) * W + ww) * C4 + c4) * 4);
-                            const bool before = hh < hi || (hh == hi && ww < wi);
-                            fx = fx && (before ? u.x < v.x : u.x <= v.x);
-                            fy = fy && (before ? u.y < v.y : u.y <= v.y);
-                            fz = fz && (before ? u.z < v.z : u.z <= v.z);
-                            fw = fw && (before ? u.w < v.w : u.w <= v.w);
-                        }
-                    }
-                    const float4 d = *reinterpret_cast<const float4*>(dpool + ((((long long)n * Ho + ho) * Wo + wo) * C4 + c4) * 4);
-                    if (fx) acc.x += d.x;
-                    if (fy) acc.y += d.y;
-                    if (fz) acc.z += d.z;
-                    if (fw) acc.w += d.w;
                 }
             if (!(v.x > 0.f)) acc.x = 0.f;        // ReLU gate of the stem
             if (!(v.y > 0.f)) acc.y = 0.f;
@@ -1632,7 +1516,6 @@ __global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const StemWgradA
     else if (p.colsum) atomicAdd(p.colsum + (i - 196 * 64), s);
 }
 
-bool pool_idx_on() { static const bool v = (dgp_tune("DGP_POOL_IDX", 1) != 0); return v; }
 int grid_for(long long n) {
     long long b = (n + 255) / 256;
     return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
@@ -1648,7 +1531,7 @@ struct TLayer {
     long long mean_off = -1, var_off = -1;            // offsets into the frozen-statistics buffer
     int cin_real = 0;
     float* d_wT = nullptr;                            // data-gradient panels
-    float* d_wTh3 = nullptr;                          // ... pre-split into fp16 high/low cells (launch_pack_h3), per sync
+    void* d_wTh3 = nullptr;                           // ... pre-split into fp16 high/low cells (launch_pack_h3), per sync
     void* d_wTh1 = nullptr;                           // ... as high-only H1 cells (tier 1)
     int nkT = 0, cinP = 0, cpad = 0;                  // cpad: padded phase-major channel count (heads)
 };
@@ -1674,7 +1557,7 @@ struct TrainCtx {
     RangeCtx rng;
     std::unordered_map<const float*, const float*> cells;      // weight panel -> the same panel pre-split into fp16 cells
     std::unordered_map<const float*, const void*> cells1;      // ... -> its high-only H1 cells (16-bit tier, launch_pack_h1)
-    const void* defer_plan = nullptr;            // TPlan of the running backward pass when weight-gradient finalisation is deferred
+    const void* defer_plan = nullptr;            // TPlan of the running backward pass: every layer's dWraw / colsum region (layer_param_grads)
     char* defer_ws = nullptr;
     // Weight gradients on a second stream (EXPERIMENTS.md section 6a (8)): the data-gradient chain is the critical path of the backward pass
     // and its 11-frame grids leave CUs idle; a layer's weight gradient only needs (x, dY) and is not needed before the finalisation
@@ -2309,177 +2192,136 @@ int dgp_trainer_sync_weights(dgp_trainer* tr, void* stream) {
     const float eps = net->desc.bn_eps;
     const size_t nl_all = net->layers.size();
     if (tr->d_wrng) TRY_HIP(hipMemsetAsync(tr->d_wrng, 0, 2 * nl_all * ABSMAX_SLOTS * sizeof(float), s));
-    // one launch for the panels / folded BN of all non-head layers (DGP_PACK_MERGED=0: one launch per layer and job, as before)
-    static const bool merged_env = (dgp_tune("DGP_PACK_MERGED", 1) != 0);
-    const bool merged = merged_env;
-    // tier 1, every sync after the first: the parity-only panels wait for a plain pass (A/B switch DGP_TRAIN_LAZY_PARITY=0)
-    static const bool lazy_env = (dgp_tune("DGP_TRAIN_LAZY_PARITY", 1) != 0);
-    const bool lazy = lazy_env && merged && g_train_cells && tr->tier == 1 && tr->d_h3_table && tr->d_h1_table && tr->d_wrng;
+    // tier 1, every sync after the first: the parity-only panels wait for a plain pass
+    const bool lazy = g_train_cells && tr->tier == 1 && tr->d_h3_table && tr->d_h1_table && tr->d_wrng;
     tr->parity_stale = lazy;
-    for (size_t li = 0; li < net->layers.size(); ++li) {
-        ConvLayer& l = net->layers[li];
-        TLayer& t = tr->tl[li];
-        float* rng_f = tr->d_wrng ? tr->d_wrng + li * ABSMAX_SLOTS : nullptr;          // ranges of the panels packed below
-        float* rng_b = tr->d_wrng ? tr->d_wrng + (nl_all + li) * ABSMAX_SLOTS : nullptr;
-        const bool head = ((int)li == net->head_part || (int)li == net->head_locref);
-        const size_t nfl = (size_t)l.nk * 8 * l.CoutP * 4;
-        if (!l.d_w) TRY_HIP(hipMalloc(&l.d_w, nfl * sizeof(float)));
+    for (ConvLayer& l : net->layers) {
+        if (!l.d_w) TRY_HIP(hipMalloc(&l.d_w, (size_t)l.nk * 8 * l.CoutP * 4 * sizeof(float)));
         if (!l.d_scale) TRY_HIP(hipMalloc(&l.d_scale, l.Cout * sizeof(float)));
         if (!l.d_bias) TRY_HIP(hipMalloc(&l.d_bias, l.Cout * sizeof(float)));
+    }
+    for (int hd : {net->head_part, net->head_locref}) {
+        ConvLayer& l = net->layers[hd];
+        TLayer& t = tr->tl[hd];
+        float* rng_f = tr->d_wrng ? tr->d_wrng + (size_t)hd * ABSMAX_SLOTS : nullptr;          // range of the pointwise panel packed below
         const float* w = tr->params + t.w_off;
         const long long tot = (long long)l.nk * 8 * l.CoutP;
-        if (!head && merged) continue;        // packed by pack_all_kernel below
-        if (head) {
-            const int njt = l.Cout / 4;
-            if (!lazy) hipLaunchKernelGGL(pack_head_fwd_kernel, dim3(grid_for(tot)), dim3(256), 0, s, w, njt, l.Cin, l.CoutP, l.nk * 8, l.d_w);
-            if (g_train_cells && merged && rng_f) {      // pointwise form of the same head for the forward pass (cells built below)
-                l.coutp_pw = head_pw_coutp(16 * njt);      // same width as dgp_net_load_weights gives the shared buffers
-                const size_t npw = (size_t)nk_for(1, 1, l.Cin) * 8 * l.coutp_pw * 4;
-                if (!l.d_w_pw) TRY_HIP(hipMalloc(&l.d_w_pw, npw * sizeof(float)));
-                if (!l.d_wh3_pw) TRY_HIP(hipMalloc(&l.d_wh3_pw, npw * sizeof(float)));
-                hipLaunchKernelGGL(pack_head_pw_kernel, dim3(grid_for((long long)(l.Cin >> 2) * l.coutp_pw)), dim3(256), 0, s, w, njt,
-                                   l.Cin, l.coutp_pw, l.d_w_pw, rng_f);
-            }
-            hipLaunchKernelGGL(head_bias_kernel, dim3(1), dim3(256), 0, s, tr->params + t.b_off, njt, l.d_bias);
-            const long long totT = (long long)t.nkT * 8 * t.cinP;
-            if (!lazy) hipLaunchKernelGGL(pack_head_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, w, njt, l.Cin, t.cpad, t.cinP,
-                                          t.nkT * 8, t.d_wT);
-        } else {
-            hipLaunchKernelGGL(pack_fwd_kernel, dim3(grid_for(tot)), dim3(256), 0, s, w, l.KH * l.KW, t.cin_real, l.Cin, l.Cout,
-                               l.CoutP, l.nk * 8, l.d_w, rng_f);
-            if (g_train_cells && rng_f && l.Cin >= 32) {          // cells of the forward panel, scaled by the range tracked just above
-                if (!l.d_wh3) TRY_HIP(hipMalloc(&l.d_wh3, nfl * sizeof(float)));
-                TRY_HIP(launch_pack_h3(l.d_w, l.nk, l.CoutP, rng_f, l.d_wh3, s));
-                g_ctx->cells[l.d_w] = reinterpret_cast<const float*>(l.d_wh3);
-            }
-            hipLaunchKernelGGL(fold_bn_kernel, dim3((l.Cout + 255) / 256), dim3(256), 0, s, tr->params + t.g_off,
-                               tr->params + t.b_off, tr->stats + t.mean_off, tr->stats + t.var_off, eps, l.Cout, l.d_scale,
-                               l.d_bias);
-            if (t.d_wT) {
-                const long long totT = (long long)t.nkT * 8 * t.cinP;
-                hipLaunchKernelGGL(pack_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, w, l.d_scale, l.KH * l.KW, l.Cin,
-                                   l.Cout, t.cinP, t.nkT * 8, t.d_wT, rng_b);
-                if (g_train_cells && rng_b && l.Cout >= 32) {
-                    if (!t.d_wTh3) TRY_HIP(hipMalloc(&t.d_wTh3, (size_t)t.nkT * 8 * t.cinP * 16));
-                    TRY_HIP(launch_pack_h3(t.d_wT, t.nkT, t.cinP, rng_b, t.d_wTh3, s));
-                    g_ctx->cells[t.d_wT] = t.d_wTh3;
-                }
-            }
+        const int njt = l.Cout / 4;
+        if (!lazy) hipLaunchKernelGGL(pack_head_fwd_kernel, dim3(grid_for(tot)), dim3(256), 0, s, w, njt, l.Cin, l.CoutP, l.nk * 8, l.d_w);
+        if (g_train_cells && rng_f) {      // pointwise form of the same head for the forward pass (cells built below)
+            l.coutp_pw = head_pw_coutp(16 * njt);      // same width as dgp_net_load_weights gives the shared buffers
+            const size_t npw = (size_t)nk_for(1, 1, l.Cin) * 8 * l.coutp_pw * 4;
+            if (!l.d_w_pw) TRY_HIP(hipMalloc(&l.d_w_pw, npw * sizeof(float)));
+            if (!l.d_wh3_pw) TRY_HIP(hipMalloc(&l.d_wh3_pw, npw * sizeof(float)));
+            hipLaunchKernelGGL(pack_head_pw_kernel, dim3(grid_for((long long)(l.Cin >> 2) * l.coutp_pw)), dim3(256), 0, s, w, njt,
+                               l.Cin, l.coutp_pw, l.d_w_pw, rng_f);
         }
+        hipLaunchKernelGGL(head_bias_kernel, dim3(1), dim3(256), 0, s, tr->params + t.b_off, njt, l.d_bias);
+        const long long totT = (long long)t.nkT * 8 * t.cinP;
+        if (!lazy) hipLaunchKernelGGL(pack_head_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, w, njt, l.Cin, t.cpad, t.cinP,
+                                      t.nkT * 8, t.d_wT);
     }
-    if (merged) {
-        if (!tr->d_pack_table) {
-            std::vector<PackDesc> tab;
+    // one launch for the panels / folded BN of all non-head layers
+    if (!tr->d_pack_table) {
+        std::vector<PackDesc> tab;
+        for (size_t li = 0; li < net->layers.size(); ++li) {
+            if ((int)li == net->head_part || (int)li == net->head_locref) continue;
+            const ConvLayer& l = net->layers[li];
+            const TLayer& t = tr->tl[li];
+            PackDesc d{};
+            d.w_off = t.w_off; d.g_off = t.g_off; d.b_off = t.b_off; d.mean_off = t.mean_off; d.var_off = t.var_off;
+            d.taps = l.KH * l.KW; d.cin_real = t.cin_real; d.cin = l.Cin; d.cout = l.Cout; d.coutP = l.CoutP;
+            d.nchunks_f = l.nk * 8; d.cinP = t.cinP; d.nchunks_b = t.nkT * 8;
+            d.d_w = l.d_w; d.rng_f = tr->d_wrng ? tr->d_wrng + li * ABSMAX_SLOTS : nullptr;
+            d.d_wT = t.d_wT; d.rng_b = tr->d_wrng ? tr->d_wrng + (nl_all + li) * ABSMAX_SLOTS : nullptr;
+            d.d_scale = l.d_scale; d.d_bias = l.d_bias;
+            tab.push_back(d);
+        }
+        tr->n_pack = (int)tab.size();
+        TRY_HIP(hipMalloc(&tr->d_pack_table, tab.size() * sizeof(PackDesc)));
+        TRY_HIP(hipMemcpy(tr->d_pack_table, tab.data(), tab.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(pack_all_kernel, dim3(256, (unsigned)tr->n_pack, 3), dim3(256), 0, s,
+                       reinterpret_cast<const PackDesc*>(tr->d_pack_table), tr->params, tr->stats, eps);
+    if (g_train_cells && tr->d_wrng) {        // the panels' fp16 cells, split with the ranges the launch above has just tracked
+        // The table of one cell format (`bytes` of cells per float4 of panel): per non-head layer the forward panel, then the data-gradient
+        // panel, each where takes(K, nk, NP) holds, then the heads' pointwise panels (range slot of the layer).  fwd / bwd / pw: the member
+        // that owns a panel's cells, allocated here; reg(panel, cells) enters a non-head panel's cells into the trainer's lookup.
+        auto cell_table = [&](int bytes, auto takes, void* ConvLayer::*fwd, void* TLayer::*bwd, void* ConvLayer::*pw, auto reg, void** d_table,
+                              int* n) -> int {
+            std::vector<PackH3Desc> tab;
             for (size_t li = 0; li < net->layers.size(); ++li) {
                 if ((int)li == net->head_part || (int)li == net->head_locref) continue;
-                const ConvLayer& l = net->layers[li];
-                const TLayer& t = tr->tl[li];
-                PackDesc d{};
-                d.w_off = t.w_off; d.g_off = t.g_off; d.b_off = t.b_off; d.mean_off = t.mean_off; d.var_off = t.var_off;
-                d.taps = l.KH * l.KW; d.cin_real = t.cin_real; d.cin = l.Cin; d.cout = l.Cout; d.coutP = l.CoutP;
-                d.nchunks_f = l.nk * 8; d.cinP = t.cinP; d.nchunks_b = t.nkT * 8;
-                d.d_w = l.d_w; d.rng_f = tr->d_wrng ? tr->d_wrng + li * ABSMAX_SLOTS : nullptr;
-                d.d_wT = t.d_wT; d.rng_b = tr->d_wrng ? tr->d_wrng + (nl_all + li) * ABSMAX_SLOTS : nullptr;
-                d.d_scale = l.d_scale; d.d_bias = l.d_bias;
-                tab.push_back(d);
+                ConvLayer& l = net->layers[li];
+                TLayer& t = tr->tl[li];
+                if (takes(l.Cin, l.nk, l.CoutP)) {
+                    if (!(l.*fwd)) TRY_HIP(hipMalloc(&(l.*fwd), (size_t)l.nk * 8 * l.CoutP * bytes));
+                    tab.push_back(PackH3Desc{l.d_w, l.nk * 4, l.CoutP, tr->d_wrng + li * ABSMAX_SLOTS, l.*fwd});
+                    reg(l.d_w, l.*fwd);
+                }
+                if (t.d_wT && takes(l.Cout, t.nkT, t.cinP)) {
+                    if (!(t.*bwd)) TRY_HIP(hipMalloc(&(t.*bwd), (size_t)t.nkT * 8 * t.cinP * bytes));
+                    tab.push_back(PackH3Desc{t.d_wT, t.nkT * 4, t.cinP, tr->d_wrng + (nl_all + li) * ABSMAX_SLOTS, t.*bwd});
+                    reg(t.d_wT, t.*bwd);
+                }
             }
-            tr->n_pack = (int)tab.size();
-            TRY_HIP(hipMalloc(&tr->d_pack_table, tab.size() * sizeof(PackDesc)));
-            TRY_HIP(hipMemcpy(tr->d_pack_table, tab.data(), tab.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
-        }
-        hipLaunchKernelGGL(pack_all_kernel, dim3(256, (unsigned)tr->n_pack, 3), dim3(256), 0, s,
-                           reinterpret_cast<const PackDesc*>(tr->d_pack_table), tr->params, tr->stats, eps);
-        if (g_train_cells && tr->d_wrng) {        // the panels' fp16 cells, split with the ranges the launch above has just tracked
-            if (!tr->d_h3_table) {
-                std::vector<PackH3Desc> tab;
-                for (size_t li = 0; li < net->layers.size(); ++li) {
-                    if ((int)li == net->head_part || (int)li == net->head_locref) continue;
-                    ConvLayer& l = net->layers[li];
-                    TLayer& t = tr->tl[li];
-                    if (l.Cin >= 32) {
-                        if (!l.d_wh3) TRY_HIP(hipMalloc(&l.d_wh3, (size_t)l.nk * 8 * l.CoutP * 16));
-                        tab.push_back(PackH3Desc{l.d_w, l.nk * 4, l.CoutP, tr->d_wrng + li * ABSMAX_SLOTS, l.d_wh3});
-                        g_ctx->cells[l.d_w] = reinterpret_cast<const float*>(l.d_wh3);
-                    }
-                    if (t.d_wT && l.Cout >= 32) {
-                        if (!t.d_wTh3) TRY_HIP(hipMalloc(&t.d_wTh3, (size_t)t.nkT * 8 * t.cinP * 16));
-                        tab.push_back(PackH3Desc{t.d_wT, t.nkT * 4, t.cinP, tr->d_wrng + (nl_all + li) * ABSMAX_SLOTS, t.d_wTh3});
-                        g_ctx->cells[t.d_wT] = t.d_wTh3;
-                    }
-                }
-                for (int hd : {net->head_part, net->head_locref}) {         // the heads' pointwise panels (range slot of the layer)
-                    ConvLayer& l = net->layers[hd];
-                    if (l.d_w_pw && l.d_wh3_pw)
-                        tab.push_back(PackH3Desc{l.d_w_pw, nk_for(1, 1, l.Cin) * 4, l.coutp_pw, tr->d_wrng + (size_t)hd * ABSMAX_SLOTS, l.d_wh3_pw});
-                }
-                tr->n_h3 = (int)tab.size();
-                TRY_HIP(hipMalloc(&tr->d_h3_table, tab.size() * sizeof(PackH3Desc)));
-                TRY_HIP(hipMemcpy(tr->d_h3_table, tab.data(), tab.size() * sizeof(PackH3Desc), hipMemcpyHostToDevice));
+            for (int hd : {net->head_part, net->head_locref}) {
+                ConvLayer& l = net->layers[hd];
+                if (!l.d_w_pw) continue;
+                const int nk = nk_for(1, 1, l.Cin);
+                if (!(l.*pw)) TRY_HIP(hipMalloc(&(l.*pw), (size_t)nk * 8 * l.coutp_pw * bytes));
+                tab.push_back(PackH3Desc{l.d_w_pw, nk * 4, l.coutp_pw, tr->d_wrng + (size_t)hd * ABSMAX_SLOTS, l.*pw});
             }
-            if (!lazy) TRY_HIP(launch_pack_h3_all(reinterpret_cast<const PackH3Desc*>(tr->d_h3_table), tr->n_h3, s));
-            if (tr->tier == 1) {              // 16-bit tier: the same panels as high-only H1 cells (K-steps of 64 channels: K % 64 == 0)
-                if (!tr->d_h1_table) {
-                    std::vector<PackH3Desc> tab;
-                    for (size_t li = 0; li < net->layers.size(); ++li) {
-                        if ((int)li == net->head_part || (int)li == net->head_locref) continue;
-                        ConvLayer& l = net->layers[li];
-                        TLayer& t = tr->tl[li];
-                        if (l.Cin >= 64 && (l.Cin % 64) == 0 && (l.nk % 2) == 0 && l.CoutP % 64 == 0) {
-                            if (!l.d_wh1) TRY_HIP(hipMalloc(&l.d_wh1, (size_t)l.nk * 8 * l.CoutP * 8));
-                            tab.push_back(PackH3Desc{l.d_w, l.nk * 4, l.CoutP, tr->d_wrng + li * ABSMAX_SLOTS, l.d_wh1});
-                            g_ctx->cells1[l.d_w] = l.d_wh1;
-                        }
-                        if (t.d_wT && l.Cout >= 64 && (l.Cout % 64) == 0 && (t.nkT % 2) == 0 && t.cinP % 64 == 0) {
-                            if (!t.d_wTh1) TRY_HIP(hipMalloc(&t.d_wTh1, (size_t)t.nkT * 8 * t.cinP * 8));
-                            tab.push_back(PackH3Desc{t.d_wT, t.nkT * 4, t.cinP, tr->d_wrng + (nl_all + li) * ABSMAX_SLOTS, t.d_wTh1});
-                            g_ctx->cells1[t.d_wT] = t.d_wTh1;
-                        }
-                    }
-                    for (int hd : {net->head_part, net->head_locref}) {
-                        ConvLayer& l = net->layers[hd];
-                        if (l.d_w_pw) {
-                            if (!l.d_wh1_pw) TRY_HIP(hipMalloc(&l.d_wh1_pw, (size_t)nk_for(1, 1, l.Cin) * 8 * l.coutp_pw * 8));
-                            tab.push_back(PackH3Desc{l.d_w_pw, nk_for(1, 1, l.Cin) * 4, l.coutp_pw, tr->d_wrng + (size_t)hd * ABSMAX_SLOTS, l.d_wh1_pw});
-                        }
-                    }
-                    tr->n_h1 = (int)tab.size();
-                    TRY_HIP(hipMalloc(&tr->d_h1_table, tab.size() * sizeof(PackH3Desc)));
-                    TRY_HIP(hipMemcpy(tr->d_h1_table, tab.data(), tab.size() * sizeof(PackH3Desc), hipMemcpyHostToDevice));
+            *n = (int)tab.size();
+            TRY_HIP(hipMalloc(d_table, tab.size() * sizeof(PackH3Desc)));
+            TRY_HIP(hipMemcpy(*d_table, tab.data(), tab.size() * sizeof(PackH3Desc), hipMemcpyHostToDevice));
+            return DGP_OK;
+        };
+        int rc;
+        if (!tr->d_h3_table &&
+            (rc = cell_table(16, [](int K, int, int) { return K >= 32; }, &ConvLayer::d_wh3, &TLayer::d_wTh3, &ConvLayer::d_wh3_pw,
+                             [&](const float* panel, void* c) { g_ctx->cells[panel] = static_cast<const float*>(c); }, &tr->d_h3_table, &tr->n_h3)))
+            return rc;
+        if (!lazy) TRY_HIP(launch_pack_h3_all(reinterpret_cast<const PackH3Desc*>(tr->d_h3_table), tr->n_h3, s));
+        if (tr->tier == 1) {              // 16-bit tier: the same panels as high-only H1 cells (K-steps of 64 channels: K % 64 == 0)
+            if (!tr->d_h1_table &&
+                (rc = cell_table(8, [](int K, int nk, int NP) { return K >= 64 && K % 64 == 0 && nk % 2 == 0 && NP % 64 == 0; }, &ConvLayer::d_wh1,
+                                 &TLayer::d_wTh1, &ConvLayer::d_wh1_pw, [&](const float* panel, void* c) { g_ctx->cells1[panel] = c; },
+                                 &tr->d_h1_table, &tr->n_h1)))
+                return rc;
+            TRY_HIP(launch_pack_h1_all(reinterpret_cast<const PackH3Desc*>(tr->d_h1_table), tr->n_h1, s));
+            // both heads' data-gradient panels as one panel + its H1 cells (one launch gives d features of both heads)
+            static const bool heads_h1_env = (dgp_env("DGP_TRAIN_HEADS_H1", 1) != 0);      // A/B switch
+            {
+                const ConvLayer &l0 = net->layers[net->head_part], &l1 = net->layers[net->head_locref];
+                const TLayer &t0 = tr->tl[net->head_part], &t1 = tr->tl[net->head_locref];
+                const int CT = heads_ct(net->desc.num_joints), nkT = nk_for(2, 2, CT);
+                if (heads_h1_env && l0.Cin == l1.Cin && t0.cinP == t1.cinP && t0.cpad + t1.cpad <= CT && (nkT % 2) == 0 && t0.cinP % 64 == 0) {
+                    const size_t pbytes = (size_t)nkT * 8 * t0.cinP * 16;
+                    if (!tr->d_hmT) TRY_HIP(hipMalloc(&tr->d_hmT, pbytes));
+                    if (!tr->d_hmT_h1) TRY_HIP(hipMalloc(&tr->d_hmT_h1, pbytes / 2));
+                    if (!tr->d_hm_rng) TRY_HIP(hipMalloc(&tr->d_hm_rng, ABSMAX_SLOTS * sizeof(float)));
+                    tr->hm_ct = CT; tr->hm_nk = nkT;
+                    TRY_HIP(hipMemsetAsync(tr->d_hm_rng, 0, ABSMAX_SLOTS * sizeof(float), s));
+                    const long long totT = (long long)nkT * 8 * t0.cinP;
+                    hipLaunchKernelGGL(pack_heads_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, tr->params + t0.w_off, l0.Cout / 4, t0.cpad,
+                                       tr->params + t1.w_off, l1.Cout / 4, t1.cpad, l0.Cin, CT, t0.cinP, nkT * 8, tr->d_hmT, tr->d_hm_rng);
+                    TRY_HIP(launch_pack_h1(tr->d_hmT, nkT, t0.cinP, tr->d_hm_rng, tr->d_hmT_h1, s));
+                    g_ctx->cells1[tr->d_hmT] = tr->d_hmT_h1;
                 }
-                TRY_HIP(launch_pack_h1_all(reinterpret_cast<const PackH3Desc*>(tr->d_h1_table), tr->n_h1, s));
-                // both heads' data-gradient panels as one panel + its H1 cells (one launch gives d features of both heads)
-                static const bool heads_h1_env = (dgp_env("DGP_TRAIN_HEADS_H1", 1) != 0);      // A/B switch
-                {
-                    const ConvLayer &l0 = net->layers[net->head_part], &l1 = net->layers[net->head_locref];
-                    const TLayer &t0 = tr->tl[net->head_part], &t1 = tr->tl[net->head_locref];
-                    const int CT = heads_ct(net->desc.num_joints), nkT = nk_for(2, 2, CT);
-                    if (heads_h1_env && l0.Cin == l1.Cin && t0.cinP == t1.cinP && t0.cpad + t1.cpad <= CT && (nkT % 2) == 0 && t0.cinP % 64 == 0) {
-                        const size_t pbytes = (size_t)nkT * 8 * t0.cinP * 16;
-                        if (!tr->d_hmT) TRY_HIP(hipMalloc(&tr->d_hmT, pbytes));
-                        if (!tr->d_hmT_h1) TRY_HIP(hipMalloc(&tr->d_hmT_h1, pbytes / 2));
-                        if (!tr->d_hm_rng) TRY_HIP(hipMalloc(&tr->d_hm_rng, ABSMAX_SLOTS * sizeof(float)));
-                        tr->hm_ct = CT; tr->hm_nk = nkT;
-                        TRY_HIP(hipMemsetAsync(tr->d_hm_rng, 0, ABSMAX_SLOTS * sizeof(float), s));
-                        const long long totT = (long long)nkT * 8 * t0.cinP;
-                        hipLaunchKernelGGL(pack_heads_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, tr->params + t0.w_off, l0.Cout / 4, t0.cpad,
-                                           tr->params + t1.w_off, l1.Cout / 4, t1.cpad, l0.Cin, CT, t0.cinP, nkT * 8, tr->d_hmT, tr->d_hm_rng);
-                        TRY_HIP(launch_pack_h1(tr->d_hmT, nkT, t0.cinP, tr->d_hm_rng, tr->d_hmT_h1, s));
-                        g_ctx->cells1[tr->d_hmT] = tr->d_hmT_h1;
-                    }
-                }
-                // the fused root block's weight cells (stem_pool_fused_kernel): row panel of conv1 from the panel pack_all_kernel just wrote
-                static const bool stem_fused_env = (dgp_tune("DGP_TRAIN_STEM_FUSED", 1) != 0);      // A/B switch
-                ConvLayer& lc = net->layers[net->conv1];
-                if (stem_fused_env && lc.CoutP == 64 && lc.Cin == 4 && lc.KH == 7 && lc.KW == 7) {
-                    const size_t nrow = (size_t)56 * lc.CoutP * 4;
-                    if (!tr->d_stem_rows) TRY_HIP(hipMalloc(&tr->d_stem_rows, nrow * sizeof(float)));
-                    if (!tr->d_stem_cells) TRY_HIP(hipMalloc(&tr->d_stem_cells, nrow * sizeof(float)));
-                    const float* mp = net->desc.mean_pixel;
-                    hipLaunchKernelGGL(stem_rows_kernel, dim3((56 * lc.CoutP + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float4*>(lc.d_w),
-                                       lc.CoutP, roundf(mp[0]) - mp[0], roundf(mp[1]) - mp[1], roundf(mp[2]) - mp[2],
-                                       reinterpret_cast<float4*>(tr->d_stem_rows));
-                    TRY_HIP(launch_pack_h3(tr->d_stem_rows, 7, lc.CoutP, tr->d_wrng + (size_t)net->conv1 * ABSMAX_SLOTS, tr->d_stem_cells, s));
-                }
+            }
+            // the fused root block's weight cells (stem_pool_fused_kernel): row panel of conv1 from the panel pack_all_kernel just wrote
+            static const bool stem_fused_env = (dgp_tune("DGP_TRAIN_STEM_FUSED", 1) != 0);      // A/B switch
+            ConvLayer& lc = net->layers[net->conv1];
+            if (stem_fused_env && lc.CoutP == 64 && lc.Cin == 4 && lc.KH == 7 && lc.KW == 7) {
+                const size_t nrow = (size_t)56 * lc.CoutP * 4;
+                if (!tr->d_stem_rows) TRY_HIP(hipMalloc(&tr->d_stem_rows, nrow * sizeof(float)));
+                if (!tr->d_stem_cells) TRY_HIP(hipMalloc(&tr->d_stem_cells, nrow * sizeof(float)));
+                const float* mp = net->desc.mean_pixel;
+                hipLaunchKernelGGL(stem_rows_kernel, dim3((56 * lc.CoutP + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float4*>(lc.d_w),
+                                   lc.CoutP, roundf(mp[0]) - mp[0], roundf(mp[1]) - mp[1], roundf(mp[2]) - mp[2],
+                                   reinterpret_cast<float4*>(tr->d_stem_rows));
+                TRY_HIP(launch_pack_h3(tr->d_stem_rows, 7, lc.CoutP, tr->d_wrng + (size_t)net->conv1 * ABSMAX_SLOTS, tr->d_stem_cells, s));
             }
         }
     }
@@ -2515,7 +2357,7 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
     for (size_t ui = 1; ui < net->units.size(); ++ui)
         if (net->units[ui].depth_bn >= 128 && pl.sh_xo[ui - 1]) { ub = ui; break; }
     // (16-bit tier: EVERY unit -- block1 included -- keeps H1 tensors; the first one reads the H1 copy of the pool output)
-    if (tr->tier == 1 && pl.sh_pool && pool_idx_on()) ub = 0;
+    if (tr->tier == 1 && pl.sh_pool) ub = 0;
     const bool fast = tr->fast_next && g_wgrad_dma && g_train_cells && g_ctx->rng.on && ub < net->units.size() && pl.feat32 &&
                       (tr->tier != 1 || tr->d_h1_table);
     const int FMT = tr->tier == 1 ? 2 : 1;       // cell format of this pass's H2 / H1 tensors
@@ -2549,8 +2391,7 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
     const bool two = side_env && g_ctx->s2 && chains_env >= 2 && B >= 4;
     const int n1 = two ? (B + 1) / 2 : B;
     const ConvLayer& c1 = net->layers[net->conv1];
-    static const bool pool_idx = (dgp_tune("DGP_POOL_IDX", 1) != 0);       // A/B switch (0: re-scan in backward)
-    const bool stem_fused = fast && FMT == 2 && ub == 0 && pool_idx && tr->d_stem_cells && tr->d_wrng && c1.d_scale && c1.d_bias;
+    const bool stem_fused = fast && FMT == 2 && ub == 0 && tr->d_stem_cells && tr->d_wrng && c1.d_scale && c1.d_bias;
     tr->fwd_stem_fused = stem_fused;
     if (two) {
         hipEvent_t ready = g_ctx->take_event();
@@ -2595,25 +2436,21 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
         }
         TRY_HIP(conv_launch(c1, c1.d_w, c1.nk, c1.CoutP, at(pl.p0, px_in * 4), nB, d.in_h, d.in_w, 4, 3, 3, net->h1, net->w1, 64, 2, 0,
                             c1.d_scale, c1.d_bias, nullptr, 0, 0, 0, nullptr, true, 0, 0, at(pl.c1, px1 * 64), cs, F(pl.p0), F(pl.c1)));
-        if (pool_idx) {
-            int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
-            int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
-            const long long totp = (long long)nB * net->hp * net->wp * 16;
-            uint2* yh1 = nullptr;
-            const float* yprev = nullptr;
-            if (fast && FMT == 2 && ub == 0) {        // H1 copy of the pool output for the first unit (scale: conv1's range one step ago)
-                yprev = range_prev_of(range_of(F(pl.c1)));
-                if (!yprev) return fail(DGP_ERR_STATE, "16-bit tier: the root block's output has no predicted range");
-                yh1 = reinterpret_cast<uint2*>(reinterpret_cast<char*>(F(pl.sh_pool)) + (size_t)n0 * pxp * 64 * 2);
-                g_ctx->shadow_base[F(pl.pool)] = F(pl.sh_pool);
-                g_ctx->shadow_prev[F(pl.pool)] = yprev;
-            }
-            hipLaunchKernelGGL(maxpool_fwd_idx_kernel, dim3(grid_for(totp)), dim3(256), 0, cs, at(pl.c1, px1 * 64), nB, net->h1, net->w1, 16,
-                               net->hp, net->wp, pth / 2, ptw / 2, at(pl.pool, pxp * 64),
-                               reinterpret_cast<uchar4*>(ws + pl.pidx) + (size_t)n0 * pxp * 16, yh1, yprev);
-        } else {
-            TRY_HIP(launch_maxpool(at(pl.c1, px1 * 64), nB, net->h1, net->w1, 64, at(pl.pool, pxp * 64), cs));
+        int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
+        int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
+        const long long totp = (long long)nB * net->hp * net->wp * 16;
+        uint2* yh1 = nullptr;
+        const float* yprev = nullptr;
+        if (fast && FMT == 2 && ub == 0) {        // H1 copy of the pool output for the first unit (scale: conv1's range one step ago)
+            yprev = range_prev_of(range_of(F(pl.c1)));
+            if (!yprev) return fail(DGP_ERR_STATE, "16-bit tier: the root block's output has no predicted range");
+            yh1 = reinterpret_cast<uint2*>(reinterpret_cast<char*>(F(pl.sh_pool)) + (size_t)n0 * pxp * 64 * 2);
+            g_ctx->shadow_base[F(pl.pool)] = F(pl.sh_pool);
+            g_ctx->shadow_prev[F(pl.pool)] = yprev;
         }
+        hipLaunchKernelGGL(maxpool_fwd_idx_kernel, dim3(grid_for(totp)), dim3(256), 0, cs, at(pl.c1, px1 * 64), nB, net->h1, net->w1, 16,
+                           net->hp, net->wp, pth / 2, ptw / 2, at(pl.pool, pxp * 64),
+                           reinterpret_cast<uchar4*>(ws + pl.pidx) + (size_t)n0 * pxp * 16, yh1, yprev);
         range_set(F(pl.pool), range_of(F(pl.c1)));      // max-pooling cannot raise the maximum
         return DGP_OK;
     };
@@ -2756,59 +2593,45 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
 }
 
 // One conv layer's parameter gradients: dWraw = A^T dY, d beta = colsum(dY), then the BN-affine algebra.
-// Deferred finalisation (default; DGP_WGRAD_DEFER=0: per layer as before): every non-head layer accumulates dWraw / colsum in its
-// own region of the workspace (zeroed once per pass) and two launches at the end of dgp_train_backward turn them into dW, d gamma,
-// d beta for all layers -- ~150 dispatches fewer per step than fill + fill + wgrad + scale + bn per layer.
+// Every non-head layer accumulates dWraw / colsum in its own region of the workspace (zeroed once per pass; g_ctx->defer_plan holds the
+// running pass's plan) and two table launches of dgp_train_backward turn them into dW, d gamma, d beta for all layers -- ~150
+// dispatches fewer per step than fill + fill + wgrad + scale + bn per layer.
 
 static int layer_param_grads(dgp_trainer* tr, size_t li, const float* x, int N, int H, int W, const float* dy, int Ho,
-                             int Wo, int stride, int pad_t, int pad_l, float* dwraw, float* colsum, hipStream_t s) {
-    dgp_net* net = tr->net;
-    const ConvLayer& l = net->layers[li];
-    const TLayer& t = tr->tl[li];
-    if (g_ctx->defer_plan) {
-        hipStream_t ws_ = s;
-        hipEvent_t done = nullptr;
-        if (g_ctx->overlap) {                    // behind everything enqueued on the chain's stream so far (dY's producer included)
-            hipEvent_t ready = g_ctx->take_event();
-            done = g_ctx->take_event();
-            if (!ready || !done) return fail(DGP_ERR_HIP, "weight-gradient stream: hipEventCreate failed");
-            TRY_HIP(hipEventRecord(ready, s));
-            TRY_HIP(hipStreamWaitEvent(g_ctx->s2, ready, 0));
-            ws_ = g_ctx->s2;
-        }
-        const void *xs = nullptr, *dys = nullptr;
-        const float *xp = nullptr, *dyp = nullptr;
-        {
-            const auto px = g_ctx->shadow_prev.find(x), py = g_ctx->shadow_prev.find(dy);
-            const auto bx = g_ctx->shadow_base.find(x), by = g_ctx->shadow_base.find(dy);
-            if (px != g_ctx->shadow_prev.end() && py != g_ctx->shadow_prev.end() && bx != g_ctx->shadow_base.end() && by != g_ctx->shadow_base.end()) {
-                xs = bx->second; xp = px->second; dys = by->second; dyp = py->second;
-            }
-        }
-        int* h2_only = (xs && xs == (const void*)x) ? tr->d_fast_flag : nullptr;       // fast pass: the activation has no fp32 twin
-        const bool h1 = tr->fwd_fast && tr->fwd_fmt == 2 && xs && dys;                 // 16-bit tier: both operands are H1 tensors
-        if (h1) h2_only = tr->d_fast_flag;
-        if (!h2_only && tr->fwd_fast && g_ctx->shadow_base.count(x) && g_ctx->shadow_base[x] == x)
-            return fail(DGP_ERR_STATE, "weight gradient of an H2-only activation without a usable gradient copy");
-        TRY_HIP(wgrad_launch(x, N, H, W, l.Cin, dy, Ho, Wo, l.Cout, l.KH, l.KW, stride, l.rate, pad_t, pad_l,
-                             reinterpret_cast<float*>(g_ctx->defer_ws + ((const TPlan*)g_ctx->defer_plan)->dw_l[li]),
-                             reinterpret_cast<float*>(g_ctx->defer_ws + ((const TPlan*)g_ctx->defer_plan)->cs_l[li]), ws_, true,
-                             nullptr, nullptr, xs, xp, dys, dyp, h2_only, h1));
-        if (done) {
-            TRY_HIP(hipEventRecord(done, g_ctx->s2));
-            g_ctx->readers.emplace((const void*)dy, done);
-        }
-        return DGP_OK;
+                             int Wo, int stride, int pad_t, int pad_l, hipStream_t s) {
+    const ConvLayer& l = tr->net->layers[li];
+    hipStream_t ws_ = s;
+    hipEvent_t done = nullptr;
+    if (g_ctx->overlap) {                    // behind everything enqueued on the chain's stream so far (dY's producer included)
+        hipEvent_t ready = g_ctx->take_event();
+        done = g_ctx->take_event();
+        if (!ready || !done) return fail(DGP_ERR_HIP, "weight-gradient stream: hipEventCreate failed");
+        TRY_HIP(hipEventRecord(ready, s));
+        TRY_HIP(hipStreamWaitEvent(g_ctx->s2, ready, 0));
+        ws_ = g_ctx->s2;
     }
-    TRY_HIP(wgrad_launch(x, N, H, W, l.Cin, dy, Ho, Wo, l.Cout, l.KH, l.KW, stride, l.rate, pad_t, pad_l, dwraw, colsum, s));
-    float* dot = colsum + l.Cout;
-    const int krows = l.KH * l.KW * t.cin_real;
-    const int rpb = 64;
-    hipLaunchKernelGGL(scale_dw_dot_kernel, dim3((l.Cout + 63) / 64, (krows + rpb - 1) / rpb), dim3(256), 0, s, dwraw,
-                       tr->params + t.w_off, l.d_scale, l.KH * l.KW, l.Cin, t.cin_real, l.Cout, rpb, tr->grads + t.w_off, dot);
-    hipLaunchKernelGGL(bn_param_grads_kernel, dim3((l.Cout + 127) / 128), dim3(128), 0, s, dot, colsum, tr->stats + t.mean_off,
-                       tr->stats + t.var_off, net->desc.bn_eps, l.Cout, tr->grads + t.g_off, tr->grads + t.b_off);
-    TRY_HIP(hipGetLastError());
+    const void *xs = nullptr, *dys = nullptr;
+    const float *xp = nullptr, *dyp = nullptr;
+    {
+        const auto px = g_ctx->shadow_prev.find(x), py = g_ctx->shadow_prev.find(dy);
+        const auto bx = g_ctx->shadow_base.find(x), by = g_ctx->shadow_base.find(dy);
+        if (px != g_ctx->shadow_prev.end() && py != g_ctx->shadow_prev.end() && bx != g_ctx->shadow_base.end() && by != g_ctx->shadow_base.end()) {
+            xs = bx->second; xp = px->second; dys = by->second; dyp = py->second;
+        }
+    }
+    int* h2_only = (xs && xs == (const void*)x) ? tr->d_fast_flag : nullptr;       // fast pass: the activation has no fp32 twin
+    const bool h1 = tr->fwd_fast && tr->fwd_fmt == 2 && xs && dys;                 // 16-bit tier: both operands are H1 tensors
+    if (h1) h2_only = tr->d_fast_flag;
+    if (!h2_only && tr->fwd_fast && g_ctx->shadow_base.count(x) && g_ctx->shadow_base[x] == x)
+        return fail(DGP_ERR_STATE, "weight gradient of an H2-only activation without a usable gradient copy");
+    TRY_HIP(wgrad_launch(x, N, H, W, l.Cin, dy, Ho, Wo, l.Cout, l.KH, l.KW, stride, l.rate, pad_t, pad_l,
+                         reinterpret_cast<float*>(g_ctx->defer_ws + ((const TPlan*)g_ctx->defer_plan)->dw_l[li]),
+                         reinterpret_cast<float*>(g_ctx->defer_ws + ((const TPlan*)g_ctx->defer_plan)->cs_l[li]), ws_, true,
+                         nullptr, nullptr, xs, xp, dys, dyp, h2_only, h1));
+    if (done) {
+        TRY_HIP(hipEventRecord(done, g_ctx->s2));
+        g_ctx->readers.emplace((const void*)dy, done);
+    }
     return DGP_OK;
 }
 
@@ -2832,19 +2655,17 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
     const dgp_net_desc& d = net->desc;
     const int B = nt, nj = d.num_joints;
     const int nu = (int)net->units.size();
-    static const bool defer_env = (dgp_tune("DGP_WGRAD_DEFER", 1) != 0);
-    g_ctx->defer_plan = defer_env ? &pl : nullptr;
+    g_ctx->defer_plan = &pl;
     g_ctx->defer_ws = ws;
-    if (defer_env) TRY_HIP(hipMemsetAsync(ws + pl.dwall, 0, pl.dwall_bytes, s));
+    TRY_HIP(hipMemsetAsync(ws + pl.dwall, 0, pl.dwall_bytes, s));
     // weight gradients on their own stream beside the data-gradient chain (DGP_WGRAD_OVERLAP=0: one stream, A/B)
     static const bool overlap_env = (dgp_tune("DGP_WGRAD_OVERLAP", 1) != 0);
     TrainCtx* const ctx = g_ctx;
-    if (defer_env && overlap_env) {
+    if (overlap_env) {
         if (!ctx->s2) {
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);         // lo: numerically greatest = least urgent
-            static const int prio_mode = dgp_tune("DGP_WGRAD_PRIO", 0);      // 0 least urgent, 1 default, 2 most urgent
-            TRY_HIP(hipStreamCreateWithPriority(&ctx->s2, hipStreamNonBlocking, prio_mode == 0 ? lo : prio_mode == 2 ? hi : 0));
+            TRY_HIP(hipStreamCreateWithPriority(&ctx->s2, hipStreamNonBlocking, lo));
         }
         ctx->overlap = true;
         ctx->ev_next = 0;
@@ -2893,11 +2714,10 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
     // them in place, and the heads use the fp32 copy of the features the forward pass left in feat32
     const bool fast = tr->fwd_fast;
     const bool h1p = fast && tr->fwd_fmt == 2;          // 16-bit tier: the gradient tensors of units >= ub are H1-only as well
-    if (h1p && !defer_env) return fail(DGP_ERR_STATE, "the 16-bit tier needs the deferred weight-gradient finalisation (DGP_WGRAD_DEFER)");
     int ub = nu;
     for (int ui = 1; ui < nu; ++ui)
         if (net->units[ui].depth_bn >= 128 && pl.sh_xo[ui - 1]) { ub = ui; break; }
-    if (h1p && pl.sh_pool && pool_idx_on()) ub = 0;      // (as dgp_train_forward decided)
+    if (h1p && pl.sh_pool) ub = 0;      // (as dgp_train_forward decided)
     g_h2 = H2Launch();
     g_shadow_fmt = h1p ? 2 : 1;
     if (h1p) g_ctx->h2_slots.clear();                   // this pass's H1 gradient tensors, checked against their predicted scales at its end
@@ -3021,40 +2841,38 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
     // 16-bit tier with the fused root block: the stem's weight gradient reads d pool as the H1 tensor unit 0 leaves (stem_wgrad_h1_kernel:
     // pool backward fused, no d conv1 map); A/B switch DGP_TRAIN_STEM_WGRAD_H1=0
     static const bool stem_wgrad_env = (dgp_tune("DGP_TRAIN_STEM_WGRAD_H1", 1) != 0);
-    const bool stem_wgrad_h1 = stem_wgrad_env && h1p && ub == 0 && tr->fwd_stem_fused && pool_idx_on() && g_ctx->defer_plan &&
+    const bool stem_wgrad_h1 = stem_wgrad_env && h1p && ub == 0 && tr->fwd_stem_fused &&
                                net->layers[net->conv1].Cout == 64 && net->layers[net->conv1].KH == 7 && net->layers[net->conv1].Cin == 4;
     const float* stem_g = nullptr;
     const float* stem_g_prev = nullptr;
-    // deferred finalisation: table of every non-head layer, conv1 LAST (its weight gradient is the last launch of the pass: the other
+    // finalisation: table of every non-head layer, conv1 LAST (its weight gradient is the last launch of the pass: the other
     // layers are finalised beside it)
     int max_cout = 0, max_krows = 0;
-    if (g_ctx->defer_plan) {
-        if (!tr->d_fin_table || tr->fin_B != B || tr->fin_h != d.in_h || tr->fin_w != d.in_w) {      // offsets follow the plan
-            std::vector<FinDesc> tab;
-            tr->fin_of_layer.assign(net->layers.size(), -1);
-            auto entry = [&](size_t li) {
-                tr->fin_of_layer[li] = (int)tab.size();
-                const ConvLayer& l = net->layers[li];
-                const TLayer& t = tr->tl[li];
-                FinDesc f{};
-                f.dw_off = (long long)pl.dw_l[li]; f.cs_off = (long long)pl.cs_l[li];
-                f.w_off = t.w_off; f.g_off = t.g_off; f.b_off = t.b_off; f.mean_off = t.mean_off; f.var_off = t.var_off;
-                f.taps = l.KH * l.KW; f.cin = l.Cin; f.cin_real = t.cin_real; f.cout = l.Cout; f.d_scale = l.d_scale;
-                tab.push_back(f);
-            };
-            for (size_t li = 0; li < net->layers.size(); ++li)
-                if ((int)li != net->head_part && (int)li != net->head_locref && (int)li != net->conv1) entry(li);
-            entry((size_t)net->conv1);
-            if (!tr->d_fin_table) TRY_HIP(hipMalloc(&tr->d_fin_table, tab.size() * sizeof(FinDesc)));
-            TRY_HIP(hipStreamSynchronize(s));        // (a previous pass may still read the old table)
-            TRY_HIP(hipMemcpy(tr->d_fin_table, tab.data(), tab.size() * sizeof(FinDesc), hipMemcpyHostToDevice));
-            tr->n_fin = (int)tab.size(); tr->fin_B = B; tr->fin_h = d.in_h; tr->fin_w = d.in_w;
-        }
-        for (size_t li = 0; li < net->layers.size(); ++li) {
-            if ((int)li == net->head_part || (int)li == net->head_locref) continue;
-            max_cout = std::max(max_cout, net->layers[li].Cout);
-            max_krows = std::max(max_krows, net->layers[li].KH * net->layers[li].KW * tr->tl[li].cin_real);
-        }
+    if (!tr->d_fin_table || tr->fin_B != B || tr->fin_h != d.in_h || tr->fin_w != d.in_w) {      // offsets follow the plan
+        std::vector<FinDesc> tab;
+        tr->fin_of_layer.assign(net->layers.size(), -1);
+        auto entry = [&](size_t li) {
+            tr->fin_of_layer[li] = (int)tab.size();
+            const ConvLayer& l = net->layers[li];
+            const TLayer& t = tr->tl[li];
+            FinDesc f{};
+            f.dw_off = (long long)pl.dw_l[li]; f.cs_off = (long long)pl.cs_l[li];
+            f.w_off = t.w_off; f.g_off = t.g_off; f.b_off = t.b_off; f.mean_off = t.mean_off; f.var_off = t.var_off;
+            f.taps = l.KH * l.KW; f.cin = l.Cin; f.cin_real = t.cin_real; f.cout = l.Cout; f.d_scale = l.d_scale;
+            tab.push_back(f);
+        };
+        for (size_t li = 0; li < net->layers.size(); ++li)
+            if ((int)li != net->head_part && (int)li != net->head_locref && (int)li != net->conv1) entry(li);
+        entry((size_t)net->conv1);
+        if (!tr->d_fin_table) TRY_HIP(hipMalloc(&tr->d_fin_table, tab.size() * sizeof(FinDesc)));
+        TRY_HIP(hipStreamSynchronize(s));        // (a previous pass may still read the old table)
+        TRY_HIP(hipMemcpy(tr->d_fin_table, tab.data(), tab.size() * sizeof(FinDesc), hipMemcpyHostToDevice));
+        tr->n_fin = (int)tab.size(); tr->fin_B = B; tr->fin_h = d.in_h; tr->fin_w = d.in_w;
+    }
+    for (size_t li = 0; li < net->layers.size(); ++li) {
+        if ((int)li == net->head_part || (int)li == net->head_locref) continue;
+        max_cout = std::max(max_cout, net->layers[li].Cout);
+        max_krows = std::max(max_krows, net->layers[li].KH * net->layers[li].KW * tr->tl[li].cin_real);
     }
     const int rpb = 128;
     const FinDesc* fin_tab = reinterpret_cast<const FinDesc*>(tr->d_fin_table);
@@ -3083,44 +2901,37 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             acc(t.b_off, bsz_);
         };
         std::vector<dgp_trainer::GradGroup> gs;
-        const bool can = g_ctx->defer_plan != nullptr && !tr->fin_of_layer.empty();
-        if (can) {
-            dgp_trainer::GradGroup cur_g;
-            long long lo = tr->n_train, hi = 0;
-            int f_lo = tr->n_fin, f_n = 0;
-            layer_range(net->head_part, lo, hi);
-            layer_range(net->head_locref, lo, hi);
-            for (int ui = nu - 1; ui >= 1; --ui) {
-                const Unit& u = net->units[ui];
-                for (int li : {u.sc, u.c1, u.c2, u.c3}) {
-                    if (li < 0) continue;
-                    layer_range(li, lo, hi);
-                    f_lo = std::min(f_lo, tr->fin_of_layer[li]); ++f_n;
-                }
-                if (hi - lo >= tr->n_train / 4 && gs.size() < 6) {
-                    cur_g.cut_ui = ui; cur_g.fin_first = f_lo; cur_g.fin_count = f_n; cur_g.lo = lo; cur_g.hi = hi;
-                    gs.push_back(cur_g);
-                    lo = tr->n_train; hi = 0; f_lo = tr->n_fin; f_n = 0;
-                }
+        dgp_trainer::GradGroup cur_g;
+        long long lo = tr->n_train, hi = 0;
+        int f_lo = tr->n_fin, f_n = 0;
+        layer_range(net->head_part, lo, hi);
+        layer_range(net->head_locref, lo, hi);
+        for (int ui = nu - 1; ui >= 1; --ui) {
+            const Unit& u = net->units[ui];
+            for (int li : {u.sc, u.c1, u.c2, u.c3}) {
+                if (li < 0) continue;
+                layer_range(li, lo, hi);
+                f_lo = std::min(f_lo, tr->fin_of_layer[li]); ++f_n;
             }
-            // the last group: everything in front of the last cut (its table rows are [0, first cut row) + the stem's row, finalised at the end)
-            dgp_trainer::GradGroup last;
-            last.cut_ui = -1; last.lo = 0; last.hi = gs.empty() ? tr->n_train : gs.back().lo;
-            last.fin_first = 0; last.fin_count = gs.empty() ? tr->n_fin - 1 : gs.back().fin_first;
-            bool ok = true;                              // the groups must tile the flat buffer and the table, back to front
-            long long expect_hi = tr->n_train;
-            int expect_f = tr->n_fin - 1;
-            for (const auto& g : gs) {
-                ok = ok && g.hi == expect_hi && g.fin_first + g.fin_count == expect_f && g.lo < g.hi;
-                expect_hi = g.lo; expect_f = g.fin_first;
+            if (hi - lo >= tr->n_train / 4 && gs.size() < 6) {
+                cur_g.cut_ui = ui; cur_g.fin_first = f_lo; cur_g.fin_count = f_n; cur_g.lo = lo; cur_g.hi = hi;
+                gs.push_back(cur_g);
+                lo = tr->n_train; hi = 0; f_lo = tr->n_fin; f_n = 0;
             }
-            if (!ok) gs.clear(), last.hi = tr->n_train, last.fin_count = tr->n_fin - 1;
-            gs.push_back(last);
-        } else {
-            dgp_trainer::GradGroup all;
-            all.cut_ui = -1; all.lo = 0; all.hi = tr->n_train;
-            gs.push_back(all);
         }
+        // the last group: everything in front of the last cut (its table rows are [0, first cut row) + the stem's row, finalised at the end)
+        dgp_trainer::GradGroup last;
+        last.cut_ui = -1; last.lo = 0; last.hi = gs.empty() ? tr->n_train : gs.back().lo;
+        last.fin_first = 0; last.fin_count = gs.empty() ? tr->n_fin - 1 : gs.back().fin_first;
+        bool ok = true;                              // the groups must tile the flat buffer and the table, back to front
+        long long expect_hi = tr->n_train;
+        int expect_f = tr->n_fin - 1;
+        for (const auto& g : gs) {
+            ok = ok && g.hi == expect_hi && g.fin_first + g.fin_count == expect_f && g.lo < g.hi;
+            expect_hi = g.lo; expect_f = g.fin_first;
+        }
+        if (!ok) gs.clear(), last.hi = tr->n_train, last.fin_count = tr->n_fin - 1;
+        gs.push_back(last);
         for (auto& g : gs)
             if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) return fail(DGP_ERR_HIP, "gradient groups: hipEventCreate failed");
         tr->groups = gs;
@@ -3172,14 +2983,14 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
                 g_h2.in_fmt = 2; g_h2.out_fmt = 2; g_h2.mask_fmt = gate ? 2 : 0;
                 if (res_key) { g_h2.res_fmt = 2; g_h2.res_key = res_key; }
             };
-            rc = layer_param_grads(tr, u.c3, F(pl.r2[ui]), B, ho, wo, GoutH, ho, wo, 1, 0, 0, dwraw, colsum, s);
+            rc = layer_param_grads(tr, u.c3, F(pl.r2[ui]), B, ho, wo, GoutH, ho, wo, 1, 0, 0, s);
             if (rc) return rc;
             TRY_HIP(before_write(DR2H));
             fmt(true, nullptr);
             TRY_HIP(conv_launch(l3, t3.d_wT, t3.nkT, t3.cinP, GoutH, B, ho, wo, l3.Cout, 0, 0, ho, wo, l3.Cin, 1, 0, nullptr, nullptr,
                                 nullptr, 0, 0, 0, F(pl.r2[ui]), false, 0, 0, DR2H, s));
             const int pb_h = pad_before_for(h, 3, u.stride, u.rate, true), pb_w = pad_before_for(w, 3, u.stride, u.rate, true);
-            rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2H, ho, wo, u.stride, pb_h, pb_w, dwraw, colsum, s);
+            rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2H, ho, wo, u.stride, pb_h, pb_w, s);
             if (rc) return rc;
             const int keff = 2 * u.rate + 1;
             TRY_HIP(before_write(DR1H));
@@ -3208,7 +3019,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
                 const ConvLayer& ls = net->layers[u.sc];
                 const TLayer& ts = tr->tl[u.sc];
                 if (u.stride != 1) return fail(DGP_ERR_STATE, "16-bit tier: strided shortcut conv");
-                rc = layer_param_grads(tr, u.sc, xin, B, h, w, GoutH, ho, wo, 1, 0, 0, dwraw, colsum, s);
+                rc = layer_param_grads(tr, u.sc, xin, B, h, w, GoutH, ho, wo, 1, 0, 0, s);
                 if (rc) return rc;
                 TRY_HIP(before_write(DXAH));
                 fmt(false, nullptr);
@@ -3218,7 +3029,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             } else if (u.stride > 1) {
                 dxa_mode = -2;
             }
-            rc = layer_param_grads(tr, u.c1, xin, B, h, w, DR1H, h, w, 1, 0, 0, dwraw, colsum, s);
+            rc = layer_param_grads(tr, u.c1, xin, B, h, w, DR1H, h, w, 1, 0, 0, s);
             if (rc) return rc;
             TRY_HIP(before_write(GinH));
             fmt(true, dxa);
@@ -3252,7 +3063,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
         float* const DR1 = F((ui & 1) ? pl.dr1_b : pl.dr1);
         float* const DXA = F((ui & 1) ? pl.dxa_b : pl.dxa);
         // conv3: params, then dR2 = convT(G) gated by R2 > 0
-        rc = layer_param_grads(tr, u.c3, F(pl.r2[ui]), B, ho, wo, Gout, ho, wo, 1, 0, 0, dwraw, colsum, s);
+        rc = layer_param_grads(tr, u.c3, F(pl.r2[ui]), B, ho, wo, Gout, ho, wo, 1, 0, 0, s);
         if (rc) return rc;
         TRY_HIP(before_write(DR2));
         g_shadow_want = u.depth_bn >= 128;       // dR2 -> conv2's weight gradient (9 C1 x C1)
@@ -3261,7 +3072,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
                             nullptr, 0, 0, 0, F(pl.r2[ui]), false, 0, 0, DR2, s));
         // conv2: params, then dR1 = convT(dR2) gated by R1 > 0
         const int pb_h = pad_before_for(h, 3, u.stride, u.rate, true), pb_w = pad_before_for(w, 3, u.stride, u.rate, true);
-        rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2, ho, wo, u.stride, pb_h, pb_w, dwraw, colsum, s);
+        rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2, ho, wo, u.stride, pb_h, pb_w, s);
         if (rc) return rc;
         const int keff = 2 * u.rate + 1;
         TRY_HIP(before_write(DR1));
@@ -3277,7 +3088,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
         if (u.sc >= 0) {
             const ConvLayer& ls = net->layers[u.sc];
             const TLayer& ts = tr->tl[u.sc];
-            rc = layer_param_grads(tr, u.sc, xin, B, h, w, Gout, ho, wo, u.stride, 0, 0, dwraw, colsum, s);
+            rc = layer_param_grads(tr, u.sc, xin, B, h, w, Gout, ho, wo, u.stride, 0, 0, s);
             if (rc) return rc;
             TRY_HIP(before_write(DXA));
             g_shadow_want = false;                // (dXa is only added to the next data gradient)
@@ -3288,7 +3099,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             dxa_mode = -2;                      // subsample shortcut: gradient lives on the coarser grid
         }
         // conv1: params, then dX = (convT(dR1) + dXa) gated by X_in > 0  -> G for the previous unit
-        rc = layer_param_grads(tr, u.c1, xin, B, h, w, DR1, h, w, 1, 0, 0, dwraw, colsum, s);
+        rc = layer_param_grads(tr, u.c1, xin, B, h, w, DR1, h, w, 1, 0, 0, s);
         if (rc) return rc;
         TRY_HIP(before_write(Gin));              // (the G of two units ago: its conv3 / shortcut weight gradients)
         g_shadow_want = ui > 0 && net->units[ui - 1].depth_bn >= 128;      // G of unit ui - 1 -> its conv3 / shortcut weight gradients
@@ -3299,13 +3110,11 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
         TRY_HIP(close_groups_at(ui));
     }
     // ---- root block: max-pool backward (+ stem ReLU gate), stem weight gradient
-    static const bool fin_split_env = (dgp_tune("DGP_FIN_SPLIT", 1) != 0);       // A/B switch
-    const bool fin_split = fin_split_env && g_ctx->defer_plan && ctx->overlap && tr->n_fin > 1;
+    const bool fin_split = ctx->overlap && tr->n_fin > 1;
     {
         int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
         int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
         const long long tot = (long long)B * net->h1 * net->w1 * 16;
-        static const bool pool_idx = (dgp_tune("DGP_POOL_IDX", 1) != 0);
         if (stem_g) {
             if (fin_split) finalise(0, tr->groups.back().fin_count, ctx->s2);      // (what the gradient groups have not finalised yet)
             StemWgradArgs sa{};
@@ -3321,13 +3130,10 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             sa.slab = F(pl.dc1);                  // (the d conv1 map's region: unused on this path; grid x 50 KB)
             hipLaunchKernelGGL(stem_wgrad_h1_kernel, dim3((unsigned)grid), dim3(256), 0, s, sa);
             hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((STEM_SLAB_ROW + 255) / 256, (grid + 31) / 32), dim3(256), 0, s, sa, grid);
-        } else if (pool_idx)          // (fused root block in the forward pass: no conv1 map -- unit 0's data gradient is already gated by pool > 0)
+        } else          // (fused root block in the forward pass: no conv1 map -- unit 0's data gradient is already gated by pool > 0)
             hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_for(tot)), dim3(256), 0, s, (h1p && tr->fwd_stem_fused) ? (const float*)nullptr : F(pl.c1), G[cur],
                                reinterpret_cast<const uchar4*>(ws + pl.pidx), B, net->h1, net->w1, 64, net->hp, net->wp, pth / 2, ptw / 2,
                                F(pl.dc1));
-        else
-            hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(tot)), dim3(256), 0, s, F(pl.c1), G[cur], B, net->h1, net->w1, 64,
-                               net->hp, net->wp, pth / 2, ptw / 2, F(pl.dc1));
         if (stem_g) {
             rc = DGP_OK;
         } else if (fin_split) {
@@ -3336,10 +3142,10 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             // their weight gradients, the stem's weight gradient to this stream
             finalise(0, tr->groups.back().fin_count, ctx->s2);
             ctx->overlap = false;
-            rc = layer_param_grads(tr, net->conv1, F(pl.p0), B, d.in_h, d.in_w, F(pl.dc1), net->h1, net->w1, 2, 3, 3, dwraw, colsum, s);
+            rc = layer_param_grads(tr, net->conv1, F(pl.p0), B, d.in_h, d.in_w, F(pl.dc1), net->h1, net->w1, 2, 3, 3, s);
             ctx->overlap = true;
         } else {
-            rc = layer_param_grads(tr, net->conv1, F(pl.p0), B, d.in_h, d.in_w, F(pl.dc1), net->h1, net->w1, 2, 3, 3, dwraw, colsum, s);
+            rc = layer_param_grads(tr, net->conv1, F(pl.p0), B, d.in_h, d.in_w, F(pl.dc1), net->h1, net->w1, 2, 3, 3, s);
         }
         if (rc) return rc;
     }
@@ -3352,14 +3158,12 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
         if (cl.n) hipLaunchKernelGGL(h2_pred_check_kernel, dim3(cl.n), dim3(64), 0, s, cl, g_ctx->rng.pool, g_ctx->rng.prev, tr->d_fast_flag);
     }
     join();                                      // every weight gradient has landed before the finalisation reads them
-    if (g_ctx->defer_plan) {
-        g_ctx->defer_plan = nullptr;
-        const int rest = tr->groups.back().fin_count;      // rows [0, rest) + the stem's row: the last gradient group
-        if (!fin_split) finalise(0, rest, s);
-        finalise(tr->n_fin - 1, 1, s);
-        bn_grads(0, rest, s);
-        bn_grads(tr->n_fin - 1, 1, s);
-    }
+    g_ctx->defer_plan = nullptr;
+    const int rest = tr->groups.back().fin_count;      // rows [0, rest) + the stem's row: the last gradient group
+    if (!fin_split) finalise(0, rest, s);
+    finalise(tr->n_fin - 1, 1, s);
+    bn_grads(0, rest, s);
+    bn_grads(tr->n_fin - 1, 1, s);
     if (grp_next + 1 != tr->groups.size()) return fail(DGP_ERR_STATE, "backward: a gradient group was not closed");
     TRY_HIP(hipEventRecord(tr->groups.back().ev, s));
     TRY_HIP(hipGetLastError());
