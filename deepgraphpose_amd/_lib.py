@@ -119,6 +119,9 @@ SYMBOLS = {
     "dgp_preprocess_u8": (C.c_int, [_vp, C.c_int64, C.POINTER(_f32), _vp, _vp]),
     "dgp_optical_flow_scratch_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(DgpFlowParams), C.POINTER(_sz), C.POINTER(_i32)]),
     "dgp_optical_flow": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(DgpFlowParams), _vp, _vp, _vp, _sz, _vp]),
+    "dgp_resize_plan_size": (C.c_int, [_i32, _i32, C.POINTER(_i32)]),
+    "dgp_resize_plan": (C.c_int, [_i32, _i32, _vp, _vp]),
+    "dgp_resize_crop_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _vp, _vp, _vp, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -811,3 +811,79 @@ def optical_flow(frames: torch.Tensor, *, pyr_scale: float = 0.5, levels: int = 
     if output == "flow":
         return flow
     return mag, flow
+
+
+# resize plans kept on the device: (device, H, W, rows, cols) -> (plan_x, plan_y, ksize_x, ksize_y); a project's videos share one frame size
+_RESIZE_PLANS: Dict[tuple, tuple] = {}
+
+
+def resize_plan(in_size: int, out_size: int) -> Tuple[int, np.ndarray, np.ndarray]:
+    """Pillow's bicubic tables of one axis (dgp_resize_plan, host only): (ksize, bounds int32 [out, 2] = (first input, taps),
+    coeffs int32 [out, ksize], zero-padded)."""
+    lib = _lib.load()
+    ks = C.c_int32()
+    _lib.check(lib.dgp_resize_plan_size(int(in_size), int(out_size), C.byref(ks)), "dgp_resize_plan_size")
+    bounds = np.empty((int(out_size), 2), np.int32)
+    coeffs = np.empty((int(out_size), ks.value), np.int32)
+    _lib.check(lib.dgp_resize_plan(int(in_size), int(out_size), bounds.ctypes.data_as(C.c_void_p), coeffs.ctypes.data_as(C.c_void_p)),
+               "dgp_resize_plan")
+    return ks.value, bounds, coeffs
+
+
+def _device_resize_plans(dev, H: int, W: int, rh: int, rw: int):
+    key = (str(dev), H, W, rh, rw)
+    if key not in _RESIZE_PLANS:
+        plans = []
+        for n_in, n_out in ((W, rw), (H, rh)):
+            ks, bounds, coeffs = resize_plan(n_in, n_out)
+            plans.append((torch.from_numpy(np.concatenate([bounds.ravel(), coeffs.ravel()])).to(dev), ks))
+        if len(_RESIZE_PLANS) >= 16:               # a handful of sizes per process; never grows without bound
+            # drop the oldest entry only.  Its tables were allocated on the default stream and a resize queued on any other stream may
+            # still read them, so the device is drained before the block can go back to the allocator (the 17th size of a process: rare)
+            old = next(iter(_RESIZE_PLANS))
+            torch.cuda.synchronize(_RESIZE_PLANS[old][0].device)
+            del _RESIZE_PLANS[old]
+        _RESIZE_PLANS[key] = (plans[0][0], plans[1][0], plans[0][1], plans[1][1])
+    return _RESIZE_PLANS[key]
+
+
+def resize_output_shape(H: int, W: int, new_size=None, crop_size=None) -> Tuple[int, int]:
+    """(rows, cols) of a frame after Image.resize(size=(new_size[1], new_size[0])) and Image.crop(crop_size)"""
+    oh, ow = (int(new_size[0]), int(new_size[1])) if new_size is not None else (int(H), int(W))
+    if crop_size is not None:
+        l, u, r, b = (int(round(v)) for v in crop_size)
+        oh, ow = b - u, r - l
+    return oh, ow
+
+
+def resize_frames(frames: torch.Tensor, new_size=None, crop_size=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Resize and / or crop a device uint8 RGB batch [B, H, W, 3] as estimate_pose's host preparation does per frame
+    (DGP/models/eval.py:307-326): Image.resize(size=(new_size[1], new_size[0])) -- Pillow's antialiased BICUBIC -- then
+    Image.crop(crop_size), crop_size = (left, upper, right, lower) in the resized image, zeros outside it.  One dgp_resize_crop_u8 launch
+    on the current stream, no host synchronisation after the first call of a size (the tables are built on the host and uploaded once);
+    the bytes are Pillow's.  Returns uint8 [B, oh, ow, 3]; `out` (that shape, contiguous) is filled in place and returned."""
+    lib = _lib.load()
+    _need_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise _lib.DgpError("resize_frames: frames must be [B, H, W, 3], got %s" % (tuple(frames.shape),))
+    if new_size is not None and len(new_size) != 2:
+        raise ValueError("resize_frames: new_size must be (rows, cols), not %r" % (new_size,))
+    if crop_size is not None and len(crop_size) != 4:
+        raise ValueError("resize_frames: crop_size must be (left, upper, right, lower), not %r" % (crop_size,))
+    B, H, W = (int(v) for v in frames.shape[:3])
+    rh, rw = (int(new_size[0]), int(new_size[1])) if new_size is not None else (H, W)
+    oh, ow = resize_output_shape(H, W, new_size, crop_size)
+    if min(rh, rw, oh, ow) <= 0:
+        raise ValueError("resize_frames: empty result for new_size %r, crop_size %r" % (new_size, crop_size))
+    dev = frames.device
+    if out is None:
+        out = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=dev)
+    else:
+        _need_cuda(out, torch.uint8, "out")
+        if tuple(out.shape) != (B, oh, ow, 3) or out.device != dev:
+            raise _lib.DgpError("resize_frames: out must be %s on %s, got %s on %s" % ((B, oh, ow, 3), dev, tuple(out.shape), out.device))
+    plan_x, plan_y, ksx, ksy = _device_resize_plans(dev, H, W, rh, rw)
+    box = (C.c_int32 * 4)(*(int(round(v)) for v in crop_size)) if crop_size is not None else None
+    _lib.check(lib.dgp_resize_crop_u8(_ptr(frames), B, H, W, rh, rw, box, _ptr(out), _ptr(plan_x), _ptr(plan_y), ksx, ksy, _stream(dev)),
+               "dgp_resize_crop_u8")
+    return out

@@ -190,7 +190,11 @@ def clear_session_cache():
 
 # counters of the last estimate_pose call (tests, soak runs): chunks processed and chunks re-run after a range overflow
 RUN_STATS = {"chunks": 0, "chunk_reruns": 0, "strict_passes": 0, "stage_s": 0.0, "wait_frames_s": 0.0, "wait_h2d_s": 0.0, "drain_s": 0.0,
-             "setup_s": 0.0, "alloc_s": 0.0, "calibrate_s": 0.0, "finish_s": 0.0}
+             "setup_s": 0.0, "alloc_s": 0.0, "calibrate_s": 0.0, "finish_s": 0.0, "prep_backend": "none"}
+
+# who resizes / crops the frames of estimate_pose(new_size=, crop_size=): "hip" = engine.resize_frames on the copy stream (source-size
+# frames cross PCIe), "pil" = Pillow per frame on the host (the reference's code), "auto" = "hip" unless the kernel refuses the shape
+RESIZE_BACKENDS = ("auto", "pil", "hip")
 
 # The host pipeline's geometry (measured settings, not run-time switches; tests patch the module attributes): engines / HIP streams the
 # batches are dealt to, pinned staging slots, host threads staging an in-memory stack, copy streams the uploads alternate on, bytes of
@@ -212,11 +216,14 @@ def _pinned_ring(nslots: int, shape):
 
 
 def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle=1, save_pose=True, save_str="",
-                  new_size=None, crop_size=None, batch_size: int = 32, tier: Optional[str] = None):
+                  new_size=None, crop_size=None, batch_size: int = 32, tier: Optional[str] = None, resize_backend: str = "auto"):
     """Estimate pose on an arbitrary video (eval.py:217-372).  Returns {'x','y','likelihoods'} [T,nj] float64,
     or the csv path if labels already exist (:247-249).  `batch_size` is new: frames go through the GPU in
     batches instead of one sess.run per frame.  `tier` is new (resolve_tier): None = DGP_EVAL_TIER or the parity tier; "f16" = the
-    16-bit tier (reported error band, ~2 x the frames/s).
+    16-bit tier (reported error band, ~2 x the frames/s).  `resize_backend` is new (RESIZE_BACKENDS): who runs the reference's per-frame
+    PIL resize / crop of eval.py:307-326 when `new_size` / `crop_size` are given -- "hip": engine.resize_frames (Pillow's bytes, computed on
+    the GPU behind the upload of the source-size frames), "pil": Pillow on the host, "auto": "hip", and "pil" (with one printed line) only
+    for a shape the kernel refuses or frames that are not uint8 RGB.  RUN_STATS["prep_backend"] names the one that ran ("none": no resize).
 
     Multi-GPU: under torchrun (one process per GPU; RANK / WORLD_SIZE / LOCAL_RANK in the environment, or an
     already initialised torch.distributed group) rank r decodes and infers only the contiguous frame block
@@ -227,6 +234,8 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     from .. import dist as ddist
     import torch.distributed as tdist
     t_entry = time.perf_counter()
+    if resize_backend not in RESIZE_BACKENDS:
+        raise ValueError("estimate_pose: resize_backend must be one of %s, not %r" % ("|".join(RESIZE_BACKENDS), resize_backend))
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not tdist.is_initialized():
         ddist.init_from_env()                      # before anything touches the GPU
@@ -264,10 +273,33 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     markers = np.zeros((n_frames, nj, 2))
     likelihoods = np.zeros((n_frames, nj))
     scale_x = scale_y = 1
+    resizing = new_size is not None or crop_size is not None
+    prep_backend = "pil" if resizing and resize_backend == "pil" else None if resizing else "none"      # None: decided on the first frame
+
+    def choose_prep_backend(first, dev):
+        """"hip" when dgp_resize_crop_u8 takes the video's frames (tried on the first one, which also uploads the tables)"""
+        nonlocal prep_backend, scale_x, scale_y
+        import torch
+        from .. import engine, _lib
+        first = np.asarray(first)
+        try:
+            if first.dtype != np.uint8 or first.ndim != 3 or first.shape[2] != 3:
+                raise _lib.DgpError("frames are %s %s, not uint8 RGB" % (first.dtype, first.shape))
+            engine.resize_frames(torch.from_numpy(np.ascontiguousarray(first[None])).to(dev), new_size, crop_size)
+        except _lib.DgpError as e:
+            if resize_backend == "hip":
+                raise
+            print("resize_backend auto: frames of %s are resized with Pillow on the host (%s)" % (video_file, e), flush=True)
+            prep_backend = "pil"
+            return
+        prep_backend = "hip"
+        if new_size is not None:
+            scale_x = first.shape[1] / new_size[1]
+            scale_y = first.shape[0] / new_size[0]
 
     def prep(frame):
         nonlocal scale_x, scale_y
-        if new_size is None and crop_size is None:
+        if not resizing or prep_backend == "hip":
             return np.asarray(frame)
         from PIL import Image
         im = Image.fromarray(frame)
@@ -288,6 +320,7 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         import queue
         import threading
         import torch
+        from .. import engine
         dev = torch.device("cuda", sess.device)
         if world > 1 and hasattr(video_clip, "frame_at"):          # a shard starts in the middle of the video: seek
             frames_it = (video_clip.frame_at(t) for t in range(lo, hi))
@@ -301,8 +334,12 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
                 first = next(frames_it, None)
         if first is None:
             raise ValueError("no frames in %s" % video_file)
+        if prep_backend is None:
+            choose_prep_backend(first, dev)
+        on_gpu = prep_backend == "hip"                 # source-size frames are staged and uploaded, engine.resize_frames fills dchunk
         f0 = prep(first)
-        hh, ww = f0.shape[:2]
+        sh, sw = f0.shape[:2]                          # the staged frames' size; (hh, ww): the network's
+        hh, ww = engine.resize_output_shape(sh, sw, new_size, crop_size) if on_gpu else (sh, sw)
         # two engines on two HIP streams, batches dealt in turn (engine.DGPPipeline)
         t_ = time.perf_counter()
         net = net_used = sess.pipe_for(hh, ww, n_streams=EVAL_STREAMS)
@@ -310,7 +347,7 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         RUN_STATS["setup_s"] += time.perf_counter() - t_      # the engines of this frame size: weights re-packed and uploaded (first call of a size)
         t_ = time.perf_counter()
         nslots = PINNED_SLOTS                     # pinned staging ring: batches being staged / copied + slack for bursts
-        pinned = _pinned_ring(nslots, (batch_size, hh, ww, 3))
+        pinned = _pinned_ring(nslots, (batch_size, sh, sw, 3))
         # The frames of a CHUNK of batches stay on the device until the chunk's range check has come back clean: a chunk whose
         # activations outgrew the calibrated H2 scales is re-run from HBM, without decoding anything again (DGP_EVAL_CHUNK_BATCHES,
         # default 64 batches, capped at 4 GB of frames)
@@ -322,6 +359,8 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         chunk_cap = int(CHUNK_BYTES // max(batch_bytes, 1)) or 1
         chunk_batches = max(1, min(int(os.environ.get("DGP_EVAL_CHUNK_BATCHES", "64")), chunk_cap, per_rank_batches))
         dchunk = torch.empty((chunk_batches, batch_size, hh, ww, 3), dtype=torch.uint8, device=dev)
+        # one source-size batch per copy stream: the upload lands here and the resize kernel behind it, on the same stream, fills dchunk
+        dsrc = [torch.empty((batch_size, sh, sw, 3), dtype=torch.uint8, device=dev) for _ in range(COPY_STREAMS)] if on_gpu else []
         RUN_STATS["alloc_s"] += time.perf_counter() - t_        # pinned ring (kept between calls) + the chunk's device buffer
         strict = os.environ.get("DGP_EVAL_STRICT", "0") == "1"
         stale = False                             # an earlier chunk holds results of narrower scales than the video ended with
@@ -336,6 +375,8 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
             for t in range(nb0):
                 np.copyto(pinned[0][t].numpy(), prep(video_clip.frame_at(t)))
             cal_batch = pinned[0][:nb0].to(dev)
+            if on_gpu:
+                cal_batch = engine.resize_frames(cal_batch, new_size, crop_size)
             net.calibrate(cal_batch, sess.gamma, sess.gauss_len)
             torch.cuda.synchronize(dev)
         # ---- staging: N host threads fill the pinned ring (a batch is ONE GIL-free copy when the source is an in-memory stack; decoders
@@ -344,7 +385,7 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         # hold a slot at once: no thread can starve an earlier batch of its slot); total = number of batches once known; err = a decode error.
         cv = threading.Condition()
         st = {"staged": {}, "n_freed": 0, "total": None, "err": None, "free": list(range(nslots))}
-        whole_batches = new_size is None and crop_size is None and hasattr(video_clip, "iter_batches") and hasattr(video_clip, "frames")
+        whole_batches = prep_backend != "pil" and hasattr(video_clip, "iter_batches") and hasattr(video_clip, "frames")
         n_stage = STAGE_THREADS if whole_batches else 1
 
         def take_slot(k):
@@ -466,7 +507,12 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
                     k = len(entries)
                     cs = copy_streams[kb % len(copy_streams)]
                     with torch.cuda.stream(cs):
-                        dchunk[k][:nb].copy_(pinned[slot][:nb], non_blocking=True)
+                        if on_gpu:
+                            src = dsrc[kb % len(copy_streams)]      # (this stream's: the next upload into it queues behind this resize)
+                            src[:nb].copy_(pinned[slot][:nb], non_blocking=True)
+                            engine.resize_frames(src[:nb], new_size, crop_size, out=dchunk[k][:nb])
+                        else:
+                            dchunk[k][:nb].copy_(pinned[slot][:nb], non_blocking=True)
                         copied = torch.cuda.Event()
                         copied.record(cs)
                     compute.wait_event(copied)
@@ -548,6 +594,7 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
             break
         RUN_STATS["strict_passes"] += 1
         print("DGP_EVAL_STRICT: scales were widened after the first chunk; computing %s again on the final scales" % video_file, flush=True)
+    RUN_STATS["prep_backend"] = prep_backend
     sess.close()
     video_clip.close()
 

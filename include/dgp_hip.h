@@ -441,6 +441,31 @@ int  dgp_optical_flow_scratch_bytes(int32_t n_frames, int32_t H, int32_t W, cons
 int  dgp_optical_flow(const uint8_t* frames, int32_t n_frames, int32_t H, int32_t W, const dgp_flow_params* p, float* flow,
                       float* magnitude, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Resize + crop of uint8 RGB frames, bit-exact with Pillow (replaces the per-frame PIL.Image.resize + .crop of estimate_pose,
+ * DGP/models/eval.py:307-326).  The contract is Pillow's ImagingResample at 8 bits per channel with the BICUBIC filter -- what
+ * Image.resize(size=...) runs by default.  Per axis, in_size -> out_size, PRECISION_BITS = 22:
+ *   scale = in / out, filterscale = max(scale, 1), support = 2 * filterscale, ksize = (int)ceil(support) * 2 + 1;
+ *   output xx: center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0),
+ *              n = min((int)(center + support + 0.5), in) - xmin, w[x] = bicubic((x + xmin - center + 0.5) / filterscale), a = -0.5,
+ *              divided by their left-to-right sum, in double; k[x] = (int)(w * 2^22 +- 0.5), rounded away from zero;
+ *   a pass is clip((2^21 + sum k[x] * pixel[xmin + x]) >> 22, 0, 255) on int32.  The horizontal pass runs first and its result is clipped
+ *   to uint8 before the vertical pass.  crop(left, upper, right, lower) selects that box of the resized image; what lies outside is 0. */
+
+/* Host only (no GPU): the table width of one axis.  Non-positive sizes (or sizes above 2^24) are DGP_ERR_INVALID. */
+int  dgp_resize_plan_size(int32_t in_size, int32_t out_size, int32_t* ksize);
+/* Host only (no GPU): one axis' tables.  bounds: int32 [out_size][2] = (xmin, n); coeffs: int32 [out_size][ksize], zero-padded past n.
+ * Double arithmetic in Pillow's operation order with contraction off: the integers are Pillow's. */
+int  dgp_resize_plan(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* coeffs);
+/* src: device uint8 [B][H][W][3] -> resized to RH x RW -> box (left, upper, right, lower; host int32[4], NULL = the whole resized
+ * image) -> dst: device uint8 [B][OH][OW][3], OH = lower - upper, OW = right - left (RH, RW without a box).  Only the box is computed;
+ * its parts outside the resized image are written as zeros.  d_plan_x (W -> RW) and d_plan_y (H -> RH): device int32 arrays holding
+ * dgp_resize_plan's bounds followed by its coeffs ([out][2] then [out][ksize]); ksize_x / ksize_y: dgp_resize_plan_size's.  One launch,
+ * integer arithmetic, no atomics, no scratch: bit-identical from run to run.  A horizontal reduction whose row segment for 64 output
+ * pixels does not fit the kernel's LDS (about 20 x) is DGP_ERR_INVALID before anything is launched; the vertical factor is unbounded.
+ * Reference call site: DGP/models/eval.py:307-326. */
+int  dgp_resize_crop_u8(const uint8_t* src, int32_t B, int32_t H, int32_t W, int32_t RH, int32_t RW, const int32_t* box, uint8_t* dst,
+                        const int32_t* d_plan_x, const int32_t* d_plan_y, int32_t ksize_x, int32_t ksize_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

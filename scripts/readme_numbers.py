@@ -8,7 +8,7 @@ BEGIN, END = "<!-- numbers:begin (scripts/readme_numbers.py) -->", "<!-- numbers
 
 
 def lines_of_latest_round():
-    files = glob.glob(os.path.join(ROOT, "profiles", "r*_bench_line*.json"))
+    files = glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*_bench_line*.json"))      # (not resize_bench_line.json: bench_resize.py's)
     rounds = sorted({int(re.match(r"r(\d+)_", os.path.basename(f)).group(1)) for f in files})
     if not rounds:
         return 0, []
