@@ -15,8 +15,9 @@
 // The temporal term follows the reference's specification of intent (its TF code passes float crop sizes to
 // tf.image.crop_and_resize and cannot build): frame-to-frame displacement of every marker,
 // weighted by min(1/mean-flow, 1)^3 of the optical-flow magnitude inside the +-10 px box of the two positions
-// (bilinear crop_and_resize to the full frame, then mean), Frobenius norm.  The flow weight is treated as a
-// constant in the backward pass (no gradient through the crop boxes).
+// (bilinear crop_and_resize to the full frame, then mean), Frobenius norm.  The flow weight is differentiated too:
+// the crop boxes follow the hidden targets and tf.image.crop_and_resize has a gradient with respect to its boxes
+// (loss_temporal_weights below; include/dgp_hip.h).
 #include "dgp_internal.h"
 
 namespace dgp {

@@ -140,9 +140,13 @@ def dgp_loss_prepare(nt: int, H: int, W: int, nj: int, batch: dict, hyper: DGPHy
             hin, win = int(vf.shape[1]), int(vf.shape[2])
         else:
             vf_h = f32(vf)
+            if vf_h.ndim != 3 or vf_h.shape[0] != nt - 1:      # the kernel reads frame pair n at vf + n * Hin * Win
+                raise ValueError("vector_field %s must be [nt-1, Hin, Win] with nt = %d" % (tuple(vf_h.shape), nt))
             hin, win = int(vf_h.shape[1]), int(vf_h.shape[2])
             host += [vf_h]
-        mask = np.asarray(batch.get("wt_batch_mask", np.ones(nt - 1)), dtype=np.float32)
+        mask = np.asarray(batch.get("wt_batch_mask", np.ones(nt - 1)), dtype=np.float32).ravel()
+        if mask.size not in (1, nt - 1):                       # one value for every pair, or one per pair
+            raise ValueError("wt_batch_mask has %d entries, expected 1 or nt-1 = %d" % (mask.size, nt - 1))
         host += [np.ones(nt - 1, dtype=np.float32) * hyper.wt * mask]
     up = _upload_all(host, dev)          # one staging buffer, one asynchronous copy
     li.vm, li.hm, li.vt, li.targets, li.lmap, li.lmask, li.S0, li.ws, li.ws_max = up[:9]

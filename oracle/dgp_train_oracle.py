@@ -228,17 +228,30 @@ def dgp_loss(pred, locref_pred, batch: dict, cfg: dict):
         total = total + loss["ws_loss"]
     if cfg.get("wt", 0) > 0 and nt > 1 and batch.get("vector_field") is not None:        # :1079-1124
         P_t = t3 * cfg["stride"] + 0.5 * cfg["stride"]
-        dif = torch.sqrt(((P_t[:-1] - P_t[1:]) ** 2).sum(2))                             # [nt-1, nj]
+        sq = ((P_t[:-1] - P_t[1:]) ** 2).sum(2)                                          # [nt-1, nj]
+        if cfg.get("wt_zero_dist_grad", False):
+            # a pair that does not move: d sqrt / d 0 is infinite and autograd (like TF) yields NaN; this option gives such a pair the
+            # zero distance gradient the HIP kernel documents
+            pos = sq > 0
+            dif = torch.where(pos, torch.sqrt(torch.where(pos, sq, torch.ones_like(sq))), torch.zeros_like(sq))
+        else:
+            dif = torch.sqrt(sq)
         vf = np.asarray(batch["vector_field"], dtype=np.float64)
         mask = np.asarray(batch.get("wt_batch_mask", np.ones(nt - 1)), dtype=np.float64)
         wt_batch = np.ones(nt - 1) * cfg["wt"] * mask
         # the crop boxes are functions of the (differentiable) targets and tf.image.crop_and_resize has a gradient with respect to
         # its boxes (python/ops/image_grad.py _CropAndResizeGrad -> CropAndResizeGradBoxes), so the weight is differentiated too;
-        # cfg["wt_weight_grad"] = False gives the weight as a constant (stop-gradient), for comparison
+        # cfg["wt_weight_grad"] = False gives the weight as a constant (stop-gradient), for comparison.  cfg["wt_coord_dtype"] =
+        # np.float32 takes the crop's coordinates and decisions in float32, as TensorFlow's op does (crop_and_resize_mean)
+        cdt = cfg.get("wt_coord_dtype", np.float64)
+        P_np = P_t.detach().numpy().astype(np.float64)
+        info = {}
+        w_np = temporal_flow_weights(P_np, vf, wt_batch, H, W, coord_dtype=cdt, info=info)
         if cfg.get("wt_weight_grad", True):
-            w = temporal_flow_weights_torch(P_t.to(torch.float64), vf, wt_batch, H, W).to(dt)
+            w = temporal_flow_weights_torch(P_t.to(torch.float64), vf, wt_batch, H, W, coord_dtype=cdt).to(dt)
         else:
-            w = torch.as_tensor(temporal_flow_weights(P_t.detach().numpy().astype(np.float64), vf, wt_batch, H, W)).to(dt)
+            w = torch.as_tensor(w_np).to(dt)
+        loss["_wt_info"] = dict(info, P=P_np, D=dif.detach().numpy().astype(np.float64), w=w.detach().numpy().astype(np.float64))
         v = (F.relu(dif - cfg["wt_max"]) + cfg["wt_max"]) * w
         loss["wt_loss"] = torch.sqrt((v ** 2).sum()) * n_vis_total / n_v_eff / (n_vis_total + n_hid_total) / cfg["wn_visible"]
         total = total + loss["wt_loss"]
@@ -248,71 +261,155 @@ def dgp_loss(pred, locref_pred, batch: dict, cfg: dict):
     return loss
 
 
-def crop_and_resize_mean(img: np.ndarray, box, crop_hw):
+def _crop_axis(a1, a2, n_img, n_crop, coord_dtype):
+    """Sample coordinates of one axis of crop_and_resize and their in-range mask, every operation in `coord_dtype` and in the order of
+    crop_and_resize_op.cc: scale = (a2 - a1) * (n_img - 1) / (n_crop - 1); in = a1 * (n_img - 1) + i * scale; kept while
+    0 <= in <= n_img - 1.
+
+    float32 is what TensorFlow's op and the HIP kernel work in.  There the sum's product i * scale is NOT rounded on its own: a GPU
+    compiler contracts `a + i * scale` into one fused multiply-add (hipcc and nvcc both do by default; loss_temporal_weights compiles to
+    fma(i, scale, round(a1 * (n_img - 1)))), and that is the float32 mode here.  It matters for a box that ends on the frame's edge
+    (a2 == 1): the last sample is n_img - 1 in exact arithmetic, the fused sum can land one ulp above it and the sample is then dropped
+    (1 to 2 % of such boxes for n_img in 83 .. 128).  With the product rounded first, as an x86 build without FMA evaluates the C++
+    expression, the two rounding errors cancel and the last sample is kept, as it is in float64 (tests/test_temporal_clique_cpu.py)."""
+    dt = np.dtype(coord_dtype).type
+    a1, a2, nm1 = dt(a1), dt(a2), dt(n_img - 1)
+    if n_crop > 1:
+        scale = (a2 - a1) * nm1 / dt(n_crop - 1)
+        i = np.arange(n_crop)
+        if dt is np.float32:
+            # one rounding: the product of two float32 is exact in the wide type, and so is its sum with a float32 of similar size
+            wide = np.longdouble if np.finfo(np.longdouble).nmant > 52 else np.float64
+            c = (i.astype(wide) * wide(scale) + wide(a1 * nm1)).astype(dt)
+        else:
+            c = a1 * nm1 + i.astype(dt) * scale
+    else:
+        c = np.array([dt(0.5) * (a1 + a2) * nm1], dtype=dt)
+    assert c.dtype == np.dtype(coord_dtype)
+    return c, (c >= 0) & (c <= nm1)
+
+
+def crop_axis_unfused_float32(a1, a2, n_img):
+    """_crop_axis in float32 with every operation rounded on its own (crop size = image size): for the comparison with the fused form."""
+    f = np.float32
+    a1, a2, nm1 = f(a1), f(a2), f(n_img - 1)
+    c = a1 * nm1 + np.arange(n_img).astype(f) * ((a2 - a1) * nm1 / nm1)
+    return c, (c >= 0) & (c <= nm1)
+
+
+def crop_and_resize_mean(img: np.ndarray, box, crop_hw, coord_dtype=np.float64, info: Optional[dict] = None):
     """mean of tf.image.crop_and_resize(img[None,...,None], [box], [0], crop_hw) (bilinear, extrapolation 0).
-    box = (y1, x1, y2, x2) normalised as TF defines it (y * (H-1) is the source row)."""
+    box = (y1, x1, y2, x2) normalised as TF defines it (y * (H-1) is the source row).  coord_dtype: the type the sample coordinates,
+    their in-range test, the corner indices and the lerp fractions are computed in (_crop_axis); the sampled values, the lerp and the
+    mean are float64 either way.  info (a dict) receives the number of rows / columns kept."""
     Himg, Wimg = img.shape
     ch, cw = crop_hw
     y1, x1, y2, x2 = box
-    hs = (y2 - y1) * (Himg - 1) / (ch - 1) if ch > 1 else 0.0
-    ws_ = (x2 - x1) * (Wimg - 1) / (cw - 1) if cw > 1 else 0.0
-    iy = y1 * (Himg - 1) + np.arange(ch) * hs if ch > 1 else np.array([0.5 * (y1 + y2) * (Himg - 1)])
-    ix = x1 * (Wimg - 1) + np.arange(cw) * ws_ if cw > 1 else np.array([0.5 * (x1 + x2) * (Wimg - 1)])
-    vy = (iy >= 0) & (iy <= Himg - 1)
-    vx = (ix >= 0) & (ix <= Wimg - 1)
+    iy, vy = _crop_axis(y1, y2, Himg, ch, coord_dtype)
+    ix, vx = _crop_axis(x1, x2, Wimg, cw, coord_dtype)
     iyc, ixc = np.clip(iy, 0, Himg - 1), np.clip(ix, 0, Wimg - 1)
     ty, by = np.floor(iyc).astype(int), np.ceil(iyc).astype(int)
     lx, rx = np.floor(ixc).astype(int), np.ceil(ixc).astype(int)
-    fy, fx = (iyc - ty)[:, None], (ixc - lx)[None, :]
+    fy, fx = (iyc - ty).astype(np.float64)[:, None], (ixc - lx).astype(np.float64)[None, :]
+    img = np.asarray(img, dtype=np.float64)
     top = img[ty][:, lx] + (img[ty][:, rx] - img[ty][:, lx]) * fx
     bot = img[by][:, lx] + (img[by][:, rx] - img[by][:, lx]) * fx
     out = (top + (bot - top) * fy) * (vy[:, None] & vx[None, :])
+    if info is not None:
+        info.update(rows=int(vy.sum()), cols=int(vx.sum()))
     return out.sum() / (ch * cw)
 
 
-def temporal_flow_weights(P_t: np.ndarray, vector_field: np.ndarray, wt_batch: np.ndarray, H: int, W: int, window=10.0):
+def temporal_box(r0, c0, r1, c1, Hin: int, Win: int, window=10.0, coord_dtype=np.float64):
+    """fitdgp.py:1092-1105 in `coord_dtype` -> (box (y1, x1, y2, x2), clamped (y1, x1, y2, x2)): the +-window box of the two positions,
+    clipped to the frame and normalised by the frame size.  clamped[k] is True where tf.math.maximum(0, .) / tf.math.minimum(n, .) does
+    NOT pass the gradient to the position (math_grad.py _MaximumMinimumGrad: the first argument, the constant, takes a tie)."""
+    dt = np.dtype(coord_dtype).type
+    r0, c0, r1, c1, win, Hf, Wf = dt(r0), dt(c0), dt(r1), dt(c1), dt(window), dt(Hin), dt(Win)
+    lo_r, lo_c, hi_r, hi_c = min(r0, r1) - win, min(c0, c1) - win, max(r0, r1) + win, max(c0, c1) + win
+    box = (max(dt(0), lo_r) / Hf, max(dt(0), lo_c) / Wf, min(Hf, hi_r) / Hf, min(Wf, hi_c) / Wf)
+    return box, (bool(lo_r <= 0), bool(lo_c <= 0), bool(hi_r >= Hf), bool(hi_c >= Wf))
+
+
+def temporal_flow_weights(P_t: np.ndarray, vector_field: np.ndarray, wt_batch: np.ndarray, H: int, W: int, window=10.0,
+                          coord_dtype=np.float64, info: Optional[dict] = None):
     """fitdgp.py:1085-1118: per (frame pair, joint) weight min(min(1/(mean flow + 1e-10), 1)^3, 1) * wt / H / W, the
-    mean flow taken over the +-10 px box of the two marker positions resampled to the full frame."""
+    mean flow taken over the +-10 px box of the two marker positions resampled to the full frame.  coord_dtype=np.float32 computes the
+    positions' box, the scales, the sample coordinates and the in-range decision in float32, as TensorFlow's op and the HIP kernel do.
+    info (a dict) receives per pair: m [ntm1, nj] (mean flow), clamped [ntm1, nj, 4] (y1, x1, y2, x2), rows / cols [ntm1, nj] kept."""
     ntm1, nj = P_t.shape[0] - 1, P_t.shape[1]
     Hin, Win = vector_field.shape[1:]
     w = np.zeros((ntm1, nj))
+    m_all, cl_all = np.zeros((ntm1, nj)), np.zeros((ntm1, nj, 4), dtype=bool)
+    rows, cols = np.zeros((ntm1, nj), dtype=int), np.zeros((ntm1, nj), dtype=int)
     for t in range(ntm1):
         for j in range(nj):
             r0, c0 = P_t[t, j]
             r1, c1 = P_t[t + 1, j]
-            box = (max(0.0, min(r0, r1) - window) / Hin, max(0.0, min(c0, c1) - window) / Win,
-                   min(float(Hin), max(r0, r1) + window) / Hin, min(float(Win), max(c0, c1) + window) / Win)
-            m = crop_and_resize_mean(vector_field[t], box, (Hin, Win))
+            box, cl_all[t, j] = temporal_box(r0, c0, r1, c1, Hin, Win, window, coord_dtype)
+            kept = {}
+            m = crop_and_resize_mean(vector_field[t], box, (Hin, Win), coord_dtype, kept)
+            m_all[t, j], rows[t, j], cols[t, j] = m, kept["rows"], kept["cols"]
             inv = min(1.0 / (m + 1e-10), 1.0)
             inv = min(np.exp(np.log(inv) * 3), 1.0)
             w[t, j] = inv * wt_batch[t] / H / W
+    if info is not None:
+        info.update(m=m_all, clamped=cl_all, rows=rows, cols=cols)
     return w
 
 
-def temporal_flow_weights_torch(P_t, vector_field: np.ndarray, wt_batch: np.ndarray, H: int, W: int, window=10.0):
+def temporal_flow_weights_torch(P_t, vector_field: np.ndarray, wt_batch: np.ndarray, H: int, W: int, window=10.0,
+                                coord_dtype=np.float64):
     """temporal_flow_weights with the autograd path TF has (fitdgp.py:1085-1118): P_t [nt, nj, 2] torch float64 (graph attached).
     crop_and_resize_op.cc: a sample at in_y = y1 (Hin - 1) + i (y2 - y1) (crop height = image height), bilinear between floor and
     ceil rows; CropAndResizeGradBoxes differentiates the LERP FRACTIONS with respect to the box (the integer corner indices are
     constants), which is what autograd does on `iy - floor(iy)` below.  reduce_min / reduce_max of the two positions share a tie's
-    gradient evenly (math_grad.py _MinOrMaxGrad); maximum(0, v) / minimum(n, v) pass the gradient to v where v is strictly inside."""
+    gradient evenly (math_grad.py _MinOrMaxGrad); maximum(0, v) / minimum(n, v) pass the gradient to v where v is strictly inside.
+    coord_dtype=np.float32: every DECISION (which position is the minimum, which clamp is active, which samples are in range, the corner
+    indices) and the value of the lerp fractions come from the float32 computation of temporal_box / _crop_axis; the fractions keep the float64 graph's derivative."""
     ntm1, nj = P_t.shape[0] - 1, P_t.shape[1]
     Hin, Win = vector_field.shape[1:]
     img_all = torch.as_tensor(np.asarray(vector_field, dtype=np.float64))
+    f32 = np.dtype(coord_dtype) == np.dtype(np.float32)
+    P_np = P_t.detach().numpy()
     rows = []
     for t in range(ntm1):
         row = []
         for j in range(nj):
             pair_r = torch.stack([P_t[t, j, 0], P_t[t + 1, j, 0]])
             pair_c = torch.stack([P_t[t, j, 1], P_t[t + 1, j, 1]])
-            y1 = torch.clamp(torch.amin(pair_r) - window, min=0.0) / Hin
-            y2 = torch.clamp(torch.amax(pair_r) + window, max=float(Hin)) / Hin
-            x1 = torch.clamp(torch.amin(pair_c) - window, min=0.0) / Win
-            x2 = torch.clamp(torch.amax(pair_c) + window, max=float(Win)) / Win
             img = img_all[t]
+            if f32:
+                box, cl = temporal_box(P_np[t, j, 0], P_np[t, j, 1], P_np[t + 1, j, 0], P_np[t + 1, j, 1], Hin, Win, window, np.float32)
+                zero, one = torch.zeros((), dtype=torch.float64), torch.ones((), dtype=torch.float64)
+
+                def lo_hi(pair, a32, b32):          # which position is the minimum is a float32 decision too; a float32 tie shares
+                    if a32 == b32:
+                        return 0.5 * (pair[0] + pair[1]), 0.5 * (pair[0] + pair[1])
+                    return (pair[0], pair[1]) if a32 < b32 else (pair[1], pair[0])
+                r_lo, r_hi = lo_hi(pair_r, np.float32(P_np[t, j, 0]), np.float32(P_np[t + 1, j, 0]))
+                c_lo, c_hi = lo_hi(pair_c, np.float32(P_np[t, j, 1]), np.float32(P_np[t + 1, j, 1]))
+                y1 = zero if cl[0] else (r_lo - window) / Hin
+                x1 = zero if cl[1] else (c_lo - window) / Win
+                y2 = one if cl[2] else (r_hi + window) / Hin
+                x2 = one if cl[3] else (c_hi + window) / Win
+                iy32, vy32 = _crop_axis(box[0], box[2], Hin, Hin, np.float32)
+                ix32, vx32 = _crop_axis(box[1], box[3], Win, Win, np.float32)
+            else:
+                y1 = torch.clamp(torch.amin(pair_r) - window, min=0.0) / Hin
+                y2 = torch.clamp(torch.amax(pair_r) + window, max=float(Hin)) / Hin
+                x1 = torch.clamp(torch.amin(pair_c) - window, min=0.0) / Win
+                x2 = torch.clamp(torch.amax(pair_c) + window, max=float(Win)) / Win
             iy = y1 * (Hin - 1) + torch.arange(Hin, dtype=torch.float64) * (y2 - y1) if Hin > 1 else (0.5 * (y1 + y2) * (Hin - 1)).reshape(1)
             ix = x1 * (Win - 1) + torch.arange(Win, dtype=torch.float64) * (x2 - x1) if Win > 1 else (0.5 * (x1 + x2) * (Win - 1)).reshape(1)
-            vy = ((iy >= 0) & (iy <= Hin - 1)).to(torch.float64)
-            vx = ((ix >= 0) & (ix <= Win - 1)).to(torch.float64)
+            if f32:
+                # value from the float32 coordinates, derivative from the float64 graph
+                iy = torch.as_tensor(iy32.astype(np.float64)) + (iy - iy.detach())
+                ix = torch.as_tensor(ix32.astype(np.float64)) + (ix - ix.detach())
+                vy, vx = torch.as_tensor(vy32.astype(np.float64)), torch.as_tensor(vx32.astype(np.float64))
+            else:
+                vy = ((iy >= 0) & (iy <= Hin - 1)).to(torch.float64)
+                vx = ((ix >= 0) & (ix <= Win - 1)).to(torch.float64)
             iyc, ixc = torch.clamp(iy, 0, Hin - 1), torch.clamp(ix, 0, Win - 1)
             ty, by = torch.floor(iyc).long(), torch.ceil(iyc).long()
             lx, rx = torch.floor(ixc).long(), torch.ceil(ixc).long()
