@@ -104,12 +104,13 @@ __device__ __forceinline__ void split2_f16(const float4 v, const float s, uint2&
     // 10 VALU per 4 values, written out because hipcc computes the high parts twice (16): h = f16(s x) straight into its half of
     // the packed register (v_fma_mixlo/hi_f16), r = s x - h exactly in fp32 with h read as an fp16 operand (v_fma_mix_f32),
     // l = f16(r) packed (v_cvt_pk_f16_f32).  Scalar fp32 arithmetic on purpose: packed fp32 VALU ops are slow beside MFMAs.
+    // The addend is -0: s x + (-0) keeps the sign of a zero product (x = -0.0 -> cell 0x8000, as fp16(s x) rounds); + 0 gave +0.
     unsigned h01, h23;
     float r0, r1, r2, r3;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h01) : "v"(s), "v"(v.x));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h01) : "v"(s), "v"(v.y));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h23) : "v"(s), "v"(v.z));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h23) : "v"(s), "v"(v.w));
+    asm("v_fma_mixlo_f16 %0, %1, %2, neg(0)" : "=v"(h01) : "v"(s), "v"(v.x));
+    asm("v_fma_mixhi_f16 %0, %1, %2, neg(0)" : "+v"(h01) : "v"(s), "v"(v.y));
+    asm("v_fma_mixlo_f16 %0, %1, %2, neg(0)" : "=v"(h23) : "v"(s), "v"(v.z));
+    asm("v_fma_mixhi_f16 %0, %1, %2, neg(0)" : "+v"(h23) : "v"(s), "v"(v.w));
     asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0) : "v"(s), "v"(v.x), "v"(h01));
     asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(s), "v"(v.y), "v"(h01));
     asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r2) : "v"(s), "v"(v.z), "v"(h23));
@@ -142,8 +143,8 @@ __device__ __forceinline__ uint4 h1_pack8(const float (&v)[8], float scale) {
     unsigned h[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h[k]) : "v"(scale), "v"(v[2 * k]));
-        asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h[k]) : "v"(scale), "v"(v[2 * k + 1]));
+        asm("v_fma_mixlo_f16 %0, %1, %2, neg(0)" : "=v"(h[k]) : "v"(scale), "v"(v[2 * k]));
+        asm("v_fma_mixhi_f16 %0, %1, %2, neg(0)" : "+v"(h[k]) : "v"(scale), "v"(v[2 * k + 1]));
     }
     return make_uint4(h[0], h[1], h[2], h[3]);
 }

@@ -1082,8 +1082,9 @@ int dgp_forward(dgp_net* net, const uint8_t* frames, int32_t batch, void* worksp
 int dgp_soft_argmax(const float* scmap, int32_t B, int32_t H, int32_t W, int32_t C, float gamma, int32_t gauss_len,
                     float* mu, float* conf, int32_t* idx, float* pmap, void* stream) {
     if (!scmap || !mu || !conf || !idx) return fail(DGP_ERR_INVALID, "dgp_soft_argmax: null argument");
-    if (B < 0 || H < 1 || W < 1 || C < 1 || gauss_len < 0 || gauss_len > 7)
-        return fail(DGP_ERR_INVALID, "dgp_soft_argmax: bad shape / gauss_len (0..7)");
+    if (B < 0 || H < 1 || W < 1 || C < 1) return fail(DGP_ERR_INVALID, "dgp_soft_argmax: bad shape");
+    if (gauss_len < 1 || gauss_len > 7)             // 2 gauss_len + 1 taps in a 16-float LDS array; gauss_len 0 would give 0/0 taps
+        return fail(DGP_ERR_INVALID, "dgp_soft_argmax: gauss_len must be 1..7");
     if (B == 0) return DGP_OK;
     hipError_t e = launch_soft_argmax(scmap, B, H, W, C, gamma, gauss_len, mu, conf, idx, pmap, (hipStream_t)stream);
     if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("soft_argmax: ") + hipGetErrorString(e));
@@ -1114,7 +1115,7 @@ static int infer_impl(dgp_net* net, const uint8_t* frames, int32_t batch, void* 
                       int32_t gauss_len, float* mu, float* conf, int32_t* idx, float* scmap_out, int record_stride, void* stream) {
     if (!net) return fail(DGP_ERR_INVALID, "dgp_infer: null net");
     if (!mu || !conf || !idx) return fail(DGP_ERR_INVALID, "dgp_infer: null output");
-    if (gauss_len < 0 || gauss_len > 7) return fail(DGP_ERR_INVALID, "dgp_infer: gauss_len (0..7)");
+    if (gauss_len < 1 || gauss_len > 7) return fail(DGP_ERR_INVALID, "dgp_infer: gauss_len must be 1..7");      // (as dgp_soft_argmax)
     // (the soft-argmax keeps one joint's map in LDS up to 38 400 cells -- frames up to ~1920 x 1280 -- and streams larger ones: launch_soft_argmax)
     net->prof_in_infer = true;
     int rc = dgp_forward(net, frames, batch, workspace, workspace_bytes, scmap_out, nullptr, nullptr, stream);

@@ -884,8 +884,10 @@ __global__ __launch_bounds__(SOFT_ARGMAX_THREADS) void soft_argmax_kernel(const 
         mu[om + 0] = mh;
         mu[om + 1] = mw;
         // likelihood window on raw logits
-        int h0 = (int)floorf(mh), h1 = (int)ceilf(mh) + 1;
-        int w0 = (int)floorf(mw), w1 = (int)ceilf(mw) + 1;
+        // (a NaN mu -- a +inf or NaN logit in the map -- has no window: cell (0, 0), never an index outside the map)
+        const bool mok = mh == mh && mw == mw;
+        int h0 = mok ? (int)floorf(mh) : 0, h1 = mok ? (int)ceilf(mh) + 1 : 1;
+        int w0 = mok ? (int)floorf(mw) : 0, w1 = mok ? (int)ceilf(mw) + 1 : 1;
         if (h1 > H) h1 = H;
         if (w1 > W) w1 = W;
         if (h0 < 0) h0 = 0;
@@ -931,7 +933,15 @@ hipError_t launch_soft_argmax(const float* scmap, int B, int H, int W, int C, fl
 // ------------------------------------------------------------------------------------
 // DLC hard arg-max (PET/nnet/predict.py:62-77): first row-major maximum of
 // sigmoid(scmap[:, :, j]); returns index, probability and the raw locref pair there.
+// np.argmax's order: a NaN is the maximum (an all-NaN map is what a 16-bit-tier pass leaves after an overflow), and among NaNs
+// or equal values the lower index wins.  Every candidate's index is a cell of the map or 0 (a thread without cells holds
+// (-1, 0), below every sigmoid), so the locref read below stays inside the tensor whatever the values are.
 // ------------------------------------------------------------------------------------
+__device__ __forceinline__ bool argmax_takes(float v, int i, float bv, int bi) {      // does (v, i) come before (bv, bi)?
+    const bool vn = v != v, bn = bv != bv;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > bv || (v == bv && i < bi);
+}
 __global__ __launch_bounds__(256) void hard_argmax_kernel(const float* __restrict__ scmap,
                                                           const float* __restrict__ locref, int H, int W, int C,
                                                           int* __restrict__ idx, float* __restrict__ prob,
@@ -944,23 +954,23 @@ __global__ __launch_bounds__(256) void hard_argmax_kernel(const float* __restric
     const float* src = scmap + (long long)b * HW * C + cj;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     float bv = -1.f;
-    int bi = 0x7fffffff;
+    int bi = 0;
     for (int i = t; i < HW; i += 256) {
         const float x = src[(long long)i * C];
         const float sg = 1.f / (1.f + expf(-x));      // tf.sigmoid in fp32 (pose_net.py:86)
-        if (sg > bv) { bv = sg; bi = i; }              // i increases: keeps the first maximum
+        if (sg > bv || (sg != sg && bv == bv)) { bv = sg; bi = i; }      // i increases: keeps the first maximum / the first NaN
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(bv, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        if (argmax_takes(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     if (lane == 0) { rv[wave] = bv; ri[wave] = bi; }
     __syncthreads();
     if (t == 0) {
         for (int k = 1; k < 4; ++k)
-            if (rv[k] > bv || (rv[k] == bv && ri[k] < bi)) { bv = rv[k]; bi = ri[k]; }
+            if (argmax_takes(rv[k], ri[k], bv, bi)) { bv = rv[k]; bi = ri[k]; }
         const long long o = (long long)b * C + cj;
         const int h = bi / W, w = bi - h * W;
         idx[o * 2 + 0] = h;

@@ -100,7 +100,9 @@ int  dgp_forward(dgp_net* net, const uint8_t* frames, int32_t batch, void* works
  * scmap [B,H,W,C] fp32 -> mu [B,C,2] (row, col) fp32, conf [B,C] fp32 (sigmoid of the raw
  * logit at the window arg-max), idx [B,C,2] int32 (row, col), pmap optional [B,H,W,C].
  * Any H x W (the reference's placeholders are [None, None, None, nj]): maps up to 38 400 cells are held in LDS, larger ones
- * stream from global memory with the same arithmetic. */
+ * stream from global memory with the same arithmetic.
+ * gauss_len must be 1..7 (here, in dgp_infer and in dgp_infer_packed; DGP_ERR_INVALID otherwise): the blur has 2 gauss_len + 1
+ * taps, and gauss_len 0 would make them 0/0.  A map whose mu is NaN (a +inf or NaN logit) reports idx (0, 0). */
 int  dgp_soft_argmax(const float* scmap, int32_t B, int32_t H, int32_t W, int32_t C,
                      float gamma, int32_t gauss_len, float* mu, float* conf, int32_t* idx,
                      float* pmap, void* stream);
@@ -112,7 +114,9 @@ int  dgp_pmap_threshold(float* pmap, int32_t B, int32_t H, int32_t W, int32_t C,
 
 /* DLC hard arg-max over sigmoid(scmap).  idx [B,C,2] (row, col), prob [B,C],
  * offs [B,C,2] = locref[b,row,col,2c..2c+1] (dx, dy; NOT yet scaled by locref_stdev) or
- * zeros when locref == NULL. */
+ * zeros when locref == NULL.
+ * Order of np.argmax: the first row-major maximum; a NaN counts as the maximum and the FIRST NaN wins (an all-NaN map gives
+ * idx (0, 0) and a NaN prob).  idx always lies inside the map, so the locref read does too. */
 int  dgp_hard_argmax(const float* scmap, const float* locref, int32_t B, int32_t H, int32_t W,
                      int32_t C, int32_t* idx, float* prob, float* offs, void* stream);
 

@@ -27,8 +27,8 @@ probe("soft_argmax on an empty batch [0, 8, 8, 3]", lambda: engine.soft_argmax(z
 probe("soft_argmax with zero joints [2, 8, 8, 0]", lambda: engine.soft_argmax(z(2, 8, 8, 0)), "ok")
 probe("soft_argmax on a 0 x 8 map", lambda: engine.soft_argmax(z(1, 0, 8, 2)), "error")
 probe("soft_argmax on a 1 x 1 map", lambda: engine.soft_argmax(z(1, 1, 1, 2)), "ok")
-probe("soft_argmax with gauss_len 0", lambda: engine.soft_argmax(z(1, 6, 6, 2), 1.0, 0))
-probe("soft_argmax with gauss_len 40 on a 6 x 6 map", lambda: engine.soft_argmax(z(1, 6, 6, 2), 1.0, 40))
+probe("soft_argmax with gauss_len 0", lambda: engine.soft_argmax(z(1, 6, 6, 2), 1.0, 0), "error")
+probe("soft_argmax with gauss_len 40 on a 6 x 6 map", lambda: engine.soft_argmax(z(1, 6, 6, 2), 1.0, 40), "error")
 probe("soft_argmax with gamma 0", lambda: engine.soft_argmax(z(1, 6, 6, 2), 0.0, 1), "ok")
 probe("soft_argmax with NaN scores", lambda: engine.soft_argmax(z(1, 6, 6, 2) + float("nan"), 1.0, 1))
 probe("hard_argmax on an empty batch", lambda: engine.hard_argmax(z(0, 8, 8, 3)), "ok")
