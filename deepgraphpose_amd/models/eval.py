@@ -21,6 +21,8 @@ from typing import Dict, Optional
 import numpy as np
 import yaml
 
+from . import staging
+
 
 class _Fetch:
     """Symbolic handle standing in for a TF tensor of the eval graph."""
@@ -215,6 +217,257 @@ def _pinned_ring(nslots: int, shape):
     return _PINNED["bufs"]
 
 
+class _PoseRun:
+    """estimate_pose's state for one video on one rank, and the steps of a pass over the rank's frames [lo, hi).
+
+    Host pipeline: host threads fill a ring of pinned staging buffers (models/staging.py: an in-memory stack is
+    staged by STAGE_THREADS threads, ONE GIL-free copy per batch; a decoder is sequential and keeps one thread), copy streams move
+    batch k+1 to the GPU while batch k runs through dgp_infer on the compute stream, and the keypoints of the whole video come back in
+    ONE device-to-host copy at the end (the reference fetched the full scoremap every frame)."""
+
+    def __init__(self, sess, clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend):
+        self.sess, self.clip, self.video_file = sess, clip, video_file
+        self.lo, self.hi, self.world, self.n_frames, self.batch_size = lo, hi, world, int(clip.n_frames), batch_size
+        self.new_size, self.crop_size, self.resize_backend = new_size, crop_size, resize_backend
+        resizing = new_size is not None or crop_size is not None
+        self.prep_backend = "pil" if resizing and resize_backend == "pil" else None if resizing else "none"      # None: decided on the first frame
+        self.scale_x = self.scale_y = 1
+        self.markers = np.zeros((self.n_frames, sess.nj, 2))
+        self.likelihoods = np.zeros((self.n_frames, sess.nj))
+
+    def choose_prep_backend(self, first):
+        """"hip" when dgp_resize_crop_u8 takes the video's frames (tried on the first one, which also uploads the tables)"""
+        import torch
+        from .. import engine, _lib
+        try:
+            if first.dtype != np.uint8 or first.ndim != 3 or first.shape[2] != 3:
+                raise _lib.DgpError("frames are %s %s, not uint8 RGB" % (first.dtype, first.shape))
+            engine.resize_frames(torch.from_numpy(np.ascontiguousarray(first[None])).to(self.dev), self.new_size, self.crop_size)
+        except _lib.DgpError as e:
+            if self.resize_backend == "hip":
+                raise
+            print("resize_backend auto: frames of %s are resized with Pillow on the host (%s)" % (self.video_file, e), flush=True)
+            return "pil"
+        return "hip"
+
+    def prep(self, frame):
+        """the frame as it is staged: the reference's PIL resize / crop (eval.py:307-326) on the "pil" backend, else the source frame"""
+        if self.prep_backend != "pil":
+            return np.asarray(frame)
+        from PIL import Image
+        im = Image.fromarray(frame)
+        if self.new_size is not None:
+            im = im.resize(size=(self.new_size[1], self.new_size[0]))
+        if self.crop_size is not None:
+            im = im.crop(self.crop_size)
+        return np.asarray(im)
+
+    def allocate(self, sh, sw):
+        """The engines, the pinned ring and the device buffers of a pass whose staged frames are sh x sw: dchunk keeps the frames of a
+        CHUNK of batches (staging.chunk_plan) on the device until the chunk's range check has come back clean -- a chunk whose activations
+        outgrew the calibrated H2 scales is re-run from HBM, without decoding anything again."""
+        import torch
+        from .. import engine
+        B, dev = self.batch_size, self.dev
+        self.on_gpu = self.prep_backend == "hip"       # source-size frames are staged and uploaded, engine.resize_frames fills dchunk
+        hh, ww = engine.resize_output_shape(sh, sw, self.new_size, self.crop_size) if self.on_gpu else (sh, sw)      # the network's frame size
+        t_ = time.perf_counter()
+        self.net = self.sess.pipe_for(hh, ww, n_streams=EVAL_STREAMS)      # two engines on two HIP streams, batches dealt in turn
+        torch.cuda.synchronize(dev)
+        RUN_STATS["setup_s"] += time.perf_counter() - t_      # the engines of this frame size: weights re-packed and uploaded (first call of a size)
+        t_ = time.perf_counter()
+        self.pinned = _pinned_ring(PINNED_SLOTS, (B, sh, sw, 3))      # batches being staged / copied + slack for bursts
+        self.chunk_batches, self.n_rounds = staging.chunk_plan(self.n_frames, self.world, B, B * hh * ww * 3,
+                                                               int(os.environ.get("DGP_EVAL_CHUNK_BATCHES", "64")), CHUNK_BYTES)
+        self.dchunk = torch.empty((self.chunk_batches, B, hh, ww, 3), dtype=torch.uint8, device=dev)
+        # one source-size batch per copy stream: the upload lands here and the resize kernel behind it, on the same stream, fills dchunk
+        self.dsrc = [torch.empty((B, sh, sw, 3), dtype=torch.uint8, device=dev) for _ in range(COPY_STREAMS)] if self.on_gpu else []
+        RUN_STATS["alloc_s"] += time.perf_counter() - t_        # pinned ring (kept between calls) + the chunk's device buffer
+        self.copy_streams = [torch.cuda.Stream(device=dev) for _ in range(COPY_STREAMS)]
+        self.compute = torch.cuda.current_stream(dev)
+        self.traj = torch.zeros((max(self.hi - self.lo, 1), self.sess.nj, 5), dtype=torch.float32, device=dev)      # packed (row, col, likelihood, iy, ix)
+
+    def calibrate_on_first_batch(self):
+        """Calibration: every engine of every rank calibrates its activation scales on the video's FIRST batch (not on its own shard's),
+        so the frozen scales -- and with them every output bit -- are those of a single-process run.  Sharded runs of a seekable source
+        do it here; a single process finds the video's first batch first in its ring, and upload_and_submit calibrates on that (as does
+        a sharded run of a source that cannot seek -- on its own shard's first batch)."""
+        import torch
+        from .. import engine
+        nb0 = min(self.batch_size, self.n_frames)
+        for t in range(nb0):
+            np.copyto(self.pinned[0][t].numpy(), self.prep(self.clip.frame_at(t)))
+        self.cal_batch = self.pinned[0][:nb0].to(self.dev)
+        if self.on_gpu:
+            self.cal_batch = engine.resize_frames(self.cal_batch, self.new_size, self.crop_size)
+        self.net.calibrate(self.cal_batch, self.sess.gamma, self.sess.gauss_len)
+        torch.cuda.synchronize(self.dev)
+
+    def start_staging(self, f0, rest):
+        """the ring over the pinned buffers and the started threads that fill it with this shard's batches"""
+        import itertools
+        import threading
+        B, clip = self.batch_size, self.clip
+        self.ring = ring = staging.StagingRing([p.numpy() for p in self.pinned])
+        if self.prep_backend != "pil" and hasattr(clip, "iter_batches") and hasattr(clip, "frames"):      # an in-memory stack: whole batches
+            ring.set_total(-(-(self.hi - self.lo) // B))
+            threads = [threading.Thread(target=staging.stage_stack, args=(ring, clip.frames, self.lo, self.hi, B, t, STAGE_THREADS), daemon=True)
+                       for t in range(STAGE_THREADS)]
+        else:
+            frames = itertools.chain([f0], (self.prep(x) for x in rest))
+            threads = [threading.Thread(target=staging.stage_decoded, args=(ring, frames, self.hi - self.lo, B), daemon=True)]
+        for th in threads:
+            th.start()
+        return threads
+
+    def release(self, block):
+        """Slot return: a pinned slot goes back to the ring only after its H2D event has completed, without the host waiting for every
+        copy; block: wait for the oldest copy when none has completed"""
+        freed = 0
+        while self.pending and self.pending[0][0].query():
+            freed += 1
+            self.ring.give_back(self.pending.pop(0)[1])
+        if block and not freed and self.pending:
+            t_ = time.perf_counter()
+            self.pending[0][0].synchronize()
+            RUN_STATS["wait_h2d_s"] += time.perf_counter() - t_
+            self.release(False)
+
+    def next_batch(self, k):
+        """(slot, frames) of batch k, or None when the shard has no batch k"""
+        t_ = time.perf_counter()
+        try:
+            return self.ring.get(k, lambda: self.release(True))
+        finally:
+            RUN_STATS["wait_frames_s"] += time.perf_counter() - t_
+
+    def upload_and_submit(self, kb, slot, nb, k, start):
+        """Batch number kb (1-based) of the shard, staged in pinned[slot]: into dchunk[k], through the engines, records to traj[start:].
+        Stream roles: the upload and its resize run on copy stream kb % COPY_STREAMS, and the compute stream waits on that event."""
+        import torch
+        from .. import engine
+        net, sess, dst = self.net, self.sess, self.dchunk[k][:nb]
+        cs = self.copy_streams[kb % len(self.copy_streams)]
+        with torch.cuda.stream(cs):
+            if self.on_gpu:
+                src = self.dsrc[kb % len(self.copy_streams)]      # (this stream's: the next upload into it queues behind this resize)
+                src[:nb].copy_(self.pinned[slot][:nb], non_blocking=True)
+                engine.resize_frames(src[:nb], self.new_size, self.crop_size, out=dst)
+            else:
+                dst.copy_(self.pinned[slot][:nb], non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record(cs)
+        self.compute.wait_event(copied)
+        self.pending.append((copied, slot))
+        if self.cal_batch is None:
+            self.cal_batch = dst.clone()
+            t_ = time.perf_counter()
+            net.calibrate(self.cal_batch, sess.gamma, sess.gauss_len)      # (what the first submit would do: timed apart)
+            RUN_STATS["calibrate_s"] += time.perf_counter() - t_
+        net.submit(dst, self.traj[start:start + nb], sess.gamma, sess.gauss_len)      # written in place by the soft-argmax kernel, on the next engine's stream
+        # the consumer blocks on its oldest pending copy once it holds all slots but one
+        self.release(len(self.pending) >= len(self.pinned) - 1)
+
+    def settle_chunk(self, entries, end, strict):
+        """Settle loop, on every rank every round; -> True when the scales were widened.  H2 activation scales (include/dgp_hip.h): a batch
+        that outgrew the scales calibrated on the first batch invalidates the results since the last clean check, i.e. THIS chunk's
+        (`entries`: (slot in dchunk, frames, offset in traj), ending at shard frame `end`).  All ranks decide together (any_rank, once per
+        attempt; the fifth failure raises); every engine of every rank then re-calibrates on the calibration batch with 3 more bits of
+        headroom (same scales everywhere again -- a rank that did not overflow widens first, to follow the one that did) and the ranks
+        whose chunk overflowed re-run it from the frames still resident in HBM; strict: every rank re-runs it on the new scales."""
+        import torch
+        from .. import dist as ddist
+        net, sess = self.net, self.sess
+        widened = False
+        for attempt in range(5):
+            t_ = time.perf_counter()
+            net.join()
+            torch.cuda.synchronize(self.dev)
+            RUN_STATS["drain_s"] += time.perf_counter() - t_
+            overflow = bool(net.range_status()[0])
+            if not ddist.any_rank(overflow, device="cuda:%d" % sess.device):
+                break
+            if attempt == 4:
+                raise RuntimeError("activation scales did not settle after 4 re-calibrations in %s" % self.video_file)
+            if not overflow:
+                net.widen()
+            net.calibrate(self.cal_batch, sess.gamma, sess.gauss_len)
+            widened = True
+            if overflow or strict:
+                print("activation ranges outgrew the calibrated scales: re-calibrated, re-running frames %d-%d of %s"
+                      % (self.lo + entries[0][2] if entries else self.lo, self.lo + end, self.video_file), flush=True)
+                RUN_STATS["chunk_reruns"] += 1
+                for k, nb, off in entries:
+                    net.submit(self.dchunk[k][:nb], self.traj[off:off + nb], sess.gamma, sess.gauss_len)
+        return widened
+
+    def gather(self, n_done):
+        """the trajectory into markers / likelihoods: ONE all-gather per video when sharded (20 bytes per (frame, joint)), ONE device-to-host copy"""
+        from .. import dist as ddist
+        t_ = time.perf_counter()
+        if self.world > 1:
+            mu_t, lik_t, _ = ddist.unpack_keypoints(ddist.gather_trajectory(self.traj[:self.hi - self.lo], self.n_frames))
+            n_done = self.n_frames
+        else:
+            mu_t, lik_t, _ = ddist.unpack_keypoints(self.traj[:n_done])
+        self.markers[:n_done] = mu_t.cpu().numpy()
+        self.likelihoods[:n_done] = lik_t.cpu().numpy()
+        RUN_STATS["finish_s"] += time.perf_counter() - t_
+
+    def run_pass(self, first_pass):
+        """One pass over the shard; -> True when an earlier chunk holds results of narrower scales than the video ended with."""
+        import torch
+        self.dev = torch.device("cuda", self.sess.device)
+        first, rest = staging.shard_frames(self.clip, self.lo, self.hi, self.world, self.video_file)
+        first = np.asarray(first)
+        if self.new_size is not None:                  # (all frames of a video have one size)
+            self.scale_x, self.scale_y = first.shape[1] / self.new_size[1], first.shape[0] / self.new_size[0]
+        if self.prep_backend is None:
+            self.prep_backend = self.choose_prep_backend(first)
+        f0 = self.prep(first)
+        self.allocate(*f0.shape[:2])
+        if first_pass:
+            self.net.reset_scales()               # engines kept from an earlier video: THIS video's first batch sets the scales, on the default
+                                                  # headroom -- the same bits as a fresh session (a strict re-pass keeps the widened scales)
+        self.cal_batch = None                     # the batch every engine (and every rank) calibrates its activation scales on
+        if self.world > 1 and hasattr(self.clip, "frame_at"):
+            self.calibrate_on_first_batch()
+        strict = os.environ.get("DGP_EVAL_STRICT", "0") == "1"
+        threads = self.start_staging(f0, rest)
+        self.pending = []                         # (H2D-complete event, pinned slot) of the uploads in flight, oldest first
+        stale = False
+        try:
+            start, finished, kb = 0, False, 0
+            # Chunk rounds: every rank runs the SAME number (a short shard ends with empty ones), because the decision to re-calibrate
+            # after a range overflow is a collective
+            for rnd in range(self.n_rounds):
+                entries = []
+                while len(entries) < self.chunk_batches and not finished:
+                    item = self.next_batch(kb)
+                    if item is None:
+                        finished = True
+                        break
+                    kb += 1
+                    self.upload_and_submit(kb, item[0], item[1], len(entries), start)
+                    entries.append((len(entries), item[1], start))
+                    start += item[1]
+                if self.settle_chunk(entries, start, strict) and rnd > 0:
+                    stale = True                  # chunks [0, rnd) were computed with the narrower scales (valid, but other bits)
+                RUN_STATS["chunks"] += 1 if entries else 0
+            if not finished:
+                assert self.next_batch(kb) is None, "more frames than the shard holds"
+            while self.pending:
+                self.release(True)
+            for th in threads:
+                th.join()
+        except BaseException as e:               # Error handling: a failure on this side must not leave the staging threads waiting for a slot for ever
+            self.ring.fail(e)
+            raise
+        RUN_STATS["stage_s"] += self.ring.stage_s
+        self.gather(start)
+        return stale
+
+
 def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle=1, save_pose=True, save_str="",
                   new_size=None, crop_size=None, batch_size: int = 32, tier: Optional[str] = None, resize_backend: str = "auto"):
     """Estimate pose on an arbitrary video (eval.py:217-372).  Returns {'x','y','likelihoods'} [T,nj] float64,
@@ -236,6 +489,8 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     t_entry = time.perf_counter()
     if resize_backend not in RESIZE_BACKENDS:
         raise ValueError("estimate_pose: resize_backend must be one of %s, not %r" % ("|".join(RESIZE_BACKENDS), resize_backend))
+    RUN_STATS.update(chunks=0, chunk_reruns=0, strict_passes=0, stage_s=0.0, wait_frames_s=0.0, wait_h2d_s=0.0, drain_s=0.0, setup_s=0.0,
+                     alloc_s=0.0, calibrate_s=0.0, finish_s=0.0)
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not tdist.is_initialized():
         ddist.init_from_env()                      # before anything touches the GPU
@@ -252,357 +507,40 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         return save_file + ".csv"
 
     video_clip = open_frame_source(video_file)
-    n_frames = int(video_clip.n_frames)
     with open(proj_cfg_file, "r") as stream:
         proj_config = yaml.safe_load(stream)
     proj_config["video_path"] = None
     dlc_cfg = get_train_config(proj_config, shuffle=shuffle)
-
     try:
         dlc_cfg.net_type = "resnet_50"
-        sess, mu_n, _, scmap, _, inputs = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, tier=tier)
+        sess = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, tier=tier)[0]
     except KeyError:
         dlc_cfg.net_type = "resnet_101"
-        sess, mu_n, _, scmap, _, inputs = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, tier=tier)
+        sess = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, tier=tier)[0]
     sess.max_batch = int(batch_size)
     sess.device = local_rank
-    lo, hi = ddist.shard_range(n_frames, rank, world)        # this rank's frames
-    n_local = hi - lo
-
-    nj = dlc_cfg.num_joints
-    markers = np.zeros((n_frames, nj, 2))
-    likelihoods = np.zeros((n_frames, nj))
-    scale_x = scale_y = 1
-    resizing = new_size is not None or crop_size is not None
-    prep_backend = "pil" if resizing and resize_backend == "pil" else None if resizing else "none"      # None: decided on the first frame
-
-    def choose_prep_backend(first, dev):
-        """"hip" when dgp_resize_crop_u8 takes the video's frames (tried on the first one, which also uploads the tables)"""
-        nonlocal prep_backend, scale_x, scale_y
-        import torch
-        from .. import engine, _lib
-        first = np.asarray(first)
-        try:
-            if first.dtype != np.uint8 or first.ndim != 3 or first.shape[2] != 3:
-                raise _lib.DgpError("frames are %s %s, not uint8 RGB" % (first.dtype, first.shape))
-            engine.resize_frames(torch.from_numpy(np.ascontiguousarray(first[None])).to(dev), new_size, crop_size)
-        except _lib.DgpError as e:
-            if resize_backend == "hip":
-                raise
-            print("resize_backend auto: frames of %s are resized with Pillow on the host (%s)" % (video_file, e), flush=True)
-            prep_backend = "pil"
-            return
-        prep_backend = "hip"
-        if new_size is not None:
-            scale_x = first.shape[1] / new_size[1]
-            scale_y = first.shape[0] / new_size[0]
-
-    def prep(frame):
-        nonlocal scale_x, scale_y
-        if not resizing or prep_backend == "hip":
-            return np.asarray(frame)
-        from PIL import Image
-        im = Image.fromarray(frame)
-        if new_size is not None:
-            scale_x = im.width / new_size[1]
-            scale_y = im.height / new_size[0]
-            im = im.resize(size=(new_size[1], new_size[0]))
-        if crop_size is not None:
-            im = im.crop(crop_size)
-        return np.asarray(im)
-
-    def _infer_once(video_clip, first_pass=True):
-        nonlocal net_used
-        # Host pipeline (SURVEY.md 8(f) N3): a decode thread fills pinned staging buffers, a copy stream moves batch k+1
-        # to the GPU while batch k runs through dgp_infer on the compute stream, and the keypoints of the whole video
-        # come back in ONE device-to-host copy at the end (the reference fetched the full scoremap every frame).
-        import itertools
-        import queue
-        import threading
-        import torch
-        from .. import engine
-        dev = torch.device("cuda", sess.device)
-        if world > 1 and hasattr(video_clip, "frame_at"):          # a shard starts in the middle of the video: seek
-            frames_it = (video_clip.frame_at(t) for t in range(lo, hi))
-            first = video_clip.frame_at(lo if n_local > 0 else 0)
-            if n_local > 0:
-                next(frames_it)
-        else:
-            frames_it = iter(video_clip.iter_frames())
-            first = next(frames_it, None)
-            for _ in range(lo):                                    # sources without random access: decode up to the shard
-                first = next(frames_it, None)
-        if first is None:
-            raise ValueError("no frames in %s" % video_file)
-        if prep_backend is None:
-            choose_prep_backend(first, dev)
-        on_gpu = prep_backend == "hip"                 # source-size frames are staged and uploaded, engine.resize_frames fills dchunk
-        f0 = prep(first)
-        sh, sw = f0.shape[:2]                          # the staged frames' size; (hh, ww): the network's
-        hh, ww = engine.resize_output_shape(sh, sw, new_size, crop_size) if on_gpu else (sh, sw)
-        # two engines on two HIP streams, batches dealt in turn (engine.DGPPipeline)
-        t_ = time.perf_counter()
-        net = net_used = sess.pipe_for(hh, ww, n_streams=EVAL_STREAMS)
-        torch.cuda.synchronize(dev)
-        RUN_STATS["setup_s"] += time.perf_counter() - t_      # the engines of this frame size: weights re-packed and uploaded (first call of a size)
-        t_ = time.perf_counter()
-        nslots = PINNED_SLOTS                     # pinned staging ring: batches being staged / copied + slack for bursts
-        pinned = _pinned_ring(nslots, (batch_size, sh, sw, 3))
-        # The frames of a CHUNK of batches stay on the device until the chunk's range check has come back clean: a chunk whose
-        # activations outgrew the calibrated H2 scales is re-run from HBM, without decoding anything again (DGP_EVAL_CHUNK_BATCHES,
-        # default 64 batches, capped at 4 GB of frames)
-        # -- never more batches than the shard holds, and at most CHUNK_BYTES (1 GiB) of frames: 34 batches of 32 at
-        # 640 x 480, 24 batches of 16 at 1280 x 720, next to the engines' workspaces.  Every term is the same on every rank (the chunk
-        # rounds below are collective), so nothing here may depend on a rank's free memory.
-        batch_bytes = batch_size * hh * ww * 3
-        per_rank_batches = max(1, -(-(-(-n_frames // world)) // batch_size))
-        chunk_cap = int(CHUNK_BYTES // max(batch_bytes, 1)) or 1
-        chunk_batches = max(1, min(int(os.environ.get("DGP_EVAL_CHUNK_BATCHES", "64")), chunk_cap, per_rank_batches))
-        dchunk = torch.empty((chunk_batches, batch_size, hh, ww, 3), dtype=torch.uint8, device=dev)
-        # one source-size batch per copy stream: the upload lands here and the resize kernel behind it, on the same stream, fills dchunk
-        dsrc = [torch.empty((batch_size, sh, sw, 3), dtype=torch.uint8, device=dev) for _ in range(COPY_STREAMS)] if on_gpu else []
-        RUN_STATS["alloc_s"] += time.perf_counter() - t_        # pinned ring (kept between calls) + the chunk's device buffer
-        strict = os.environ.get("DGP_EVAL_STRICT", "0") == "1"
-        stale = False                             # an earlier chunk holds results of narrower scales than the video ended with
-        cal_batch = None                          # the batch every engine (and every rank) calibrates its activation scales on
-        if first_pass:
-            net.reset_scales()                    # engines kept from an earlier video: THIS video's first batch sets the scales, on the default
-                                                  # headroom -- the same bits as a fresh session (a strict re-pass keeps the widened scales)
-        if world > 1 and hasattr(video_clip, "frame_at"):
-            # every rank calibrates the activation scales on the video's FIRST batch (not on its own shard's), so the frozen scales --
-            # and with them every output bit -- are those of a single-process run
-            nb0 = min(batch_size, n_frames)
-            for t in range(nb0):
-                np.copyto(pinned[0][t].numpy(), prep(video_clip.frame_at(t)))
-            cal_batch = pinned[0][:nb0].to(dev)
-            if on_gpu:
-                cal_batch = engine.resize_frames(cal_batch, new_size, crop_size)
-            net.calibrate(cal_batch, sess.gamma, sess.gauss_len)
-            torch.cuda.synchronize(dev)
-        # ---- staging: N host threads fill the pinned ring (a batch is ONE GIL-free copy when the source is an in-memory stack; decoders
-        # are sequential by nature and keep one thread), the consumer below takes the batches IN ORDER.  Protocol, all under `cv`:
-        # staged[k] = (slot, frames) of batch k; a thread may stage batch k only while k < n_freed + nslots (the window of batches that can
-        # hold a slot at once: no thread can starve an earlier batch of its slot); total = number of batches once known; err = a decode error.
-        cv = threading.Condition()
-        st = {"staged": {}, "n_freed": 0, "total": None, "err": None, "free": list(range(nslots))}
-        whole_batches = prep_backend != "pil" and hasattr(video_clip, "iter_batches") and hasattr(video_clip, "frames")
-        n_stage = STAGE_THREADS if whole_batches else 1
-
-        def take_slot(k):
-            with cv:
-                while not (k < st["n_freed"] + nslots and st["free"]) and st["err"] is None:
-                    cv.wait()
-                if st["err"] is not None:
-                    raise RuntimeError("staging stopped")
-                return st["free"].pop()
-
-        def publish(k, slot, nb):
-            with cv:
-                st["staged"][k] = (slot, nb)
-                cv.notify_all()
-
-        def stage_stack(tid):                     # in-memory stack: thread tid stages batches tid, tid + n_stage, ...
-            try:
-                src = video_clip.frames
-                nbat = -(-n_local // batch_size)
-                for k in range(tid, nbat, n_stage):
-                    a = lo + k * batch_size
-                    nb = min(batch_size, hi - a)
-                    slot = take_slot(k)
-                    t_ = time.perf_counter()
-                    np.copyto(pinned[slot][:nb].numpy(), src[a:a + nb])
-                    RUN_STATS["stage_s"] += time.perf_counter() - t_
-                    publish(k, slot, nb)
-            except BaseException as e:            # surface errors in the consumer
-                with cv:
-                    st["err"] = st["err"] or e
-                    cv.notify_all()
-
-        def stage_decoded():                      # frame by frame from the decoder (one thread: decoding is sequential)
-            try:
-                k, fill, count, slot = 0, 0, 0, None
-                for fr in itertools.chain([f0], (prep(x) for x in frames_it)):
-                    if count >= n_local:
-                        break
-                    if slot is None:
-                        slot = take_slot(k)
-                    np.copyto(pinned[slot][fill].numpy(), fr)
-                    fill += 1
-                    count += 1
-                    if fill == batch_size:
-                        publish(k, slot, fill)
-                        k, fill, slot = k + 1, 0, None
-                if fill:
-                    publish(k, slot, fill)
-                    k += 1
-                with cv:
-                    st["total"] = k
-                    cv.notify_all()
-            except BaseException as e:
-                with cv:
-                    st["err"] = st["err"] or e
-                    cv.notify_all()
-
-        if whole_batches:
-            st["total"] = -(-n_local // batch_size)
-            threads = [threading.Thread(target=stage_stack, args=(t,), daemon=True) for t in range(n_stage)]
-        else:
-            threads = [threading.Thread(target=stage_decoded, daemon=True)]
-        for th in threads:
-            th.start()
-        copy_streams = [torch.cuda.Stream(device=dev) for _ in range(COPY_STREAMS)]
-        compute = torch.cuda.current_stream(dev)
-        traj = torch.zeros((max(n_local, 1), nj, 5), dtype=torch.float32, device=dev)      # packed (row, col, likelihood, iy, ix)
-        pending = []                              # (H2D-complete event, pinned slot): slots go back to the ring without the host waiting for every copy
-
-        def release(block):
-            """pinned slots whose H2D copy has completed go back to the ring; block: wait for the oldest copy when none has"""
-            freed = 0
-            while pending and pending[0][0].query():
-                freed += 1
-                slot = pending.pop(0)[1]
-                with cv:
-                    st["free"].append(slot); st["n_freed"] += 1
-                    cv.notify_all()
-            if block and not freed and pending:
-                t_ = time.perf_counter()
-                pending[0][0].synchronize()
-                RUN_STATS["wait_h2d_s"] += time.perf_counter() - t_
-                release(False)
-
-        def next_batch(k):
-            """(slot, frames) of batch k, or None when the shard has no batch k"""
-            t_ = time.perf_counter()
-            try:
-                while True:
-                    with cv:
-                        if st["err"] is not None:
-                            raise st["err"]
-                        if k in st["staged"]:
-                            return st["staged"].pop(k)
-                        if st["total"] is not None and k >= st["total"]:
-                            return None
-                        if not pending:
-                            cv.wait(0.05)
-                            continue
-                    release(True)                 # the producers may be waiting for a slot this thread still holds
-            finally:
-                RUN_STATS["wait_frames_s"] += time.perf_counter() - t_
-
-        try:
-            start, finished, kb = 0, False, 0
-            # every rank runs the SAME number of chunk rounds (a short shard ends with empty ones): the decision to re-calibrate after a
-            # range overflow is a collective
-            per_rank = -(-n_frames // world)
-            n_rounds = max(1, -(-(-(-per_rank // batch_size)) // chunk_batches))
-            for rnd in range(n_rounds):
-                entries = []                          # (slot in dchunk, frames, offset in traj) of this chunk
-                while len(entries) < chunk_batches and not finished:
-                    item = next_batch(kb)
-                    if item is None:
-                        finished = True
-                        break
-                    kb += 1
-                    slot, nb = item
-                    k = len(entries)
-                    cs = copy_streams[kb % len(copy_streams)]
-                    with torch.cuda.stream(cs):
-                        if on_gpu:
-                            src = dsrc[kb % len(copy_streams)]      # (this stream's: the next upload into it queues behind this resize)
-                            src[:nb].copy_(pinned[slot][:nb], non_blocking=True)
-                            engine.resize_frames(src[:nb], new_size, crop_size, out=dchunk[k][:nb])
-                        else:
-                            dchunk[k][:nb].copy_(pinned[slot][:nb], non_blocking=True)
-                        copied = torch.cuda.Event()
-                        copied.record(cs)
-                    compute.wait_event(copied)
-                    pending.append((copied, slot))
-                    if cal_batch is None:
-                        cal_batch = dchunk[k][:nb].clone()
-                        t_ = time.perf_counter()
-                        net.calibrate(cal_batch, sess.gamma, sess.gauss_len)      # (what the first submit would do: timed apart)
-                        RUN_STATS["calibrate_s"] += time.perf_counter() - t_
-                    # written in place by the soft-argmax kernel, on the next engine's stream
-                    net.submit(dchunk[k][:nb], traj[start:start + nb], sess.gamma, sess.gauss_len)
-                    entries.append((k, nb, start))
-                    start += nb
-                    release(len(pending) >= nslots - 1)
-                # H2 activation scales (include/dgp_hip.h): a batch that outgrew the scales calibrated on the first batch invalidates the
-                # results since the last clean check, i.e. THIS chunk's.  All ranks decide together; every engine of every rank then
-                # re-calibrates on the calibration batch with 3 more bits of headroom (same scales everywhere again) and the ranks whose
-                # chunk overflowed re-run it from the frames still resident in HBM.
-                for attempt in range(5):
-                    t_ = time.perf_counter()
-                    net.join()
-                    torch.cuda.synchronize(dev)
-                    RUN_STATS["drain_s"] += time.perf_counter() - t_
-                    overflow = bool(net.range_status()[0])
-                    anywhere = ddist.any_rank(overflow, device="cuda:%d" % sess.device)
-                    if not anywhere:
-                        break
-                    if attempt == 4:
-                        raise RuntimeError("activation scales did not settle after 4 re-calibrations in %s" % video_file)
-                    if not overflow:
-                        net.widen()                   # follow the rank that overflowed: same headroom everywhere
-                    net.calibrate(cal_batch, sess.gamma, sess.gauss_len)
-                    if rnd > 0:
-                        stale = True                  # chunks [0, rnd) were computed with the narrower scales (valid, but other bits)
-                    if overflow or strict:            # strict: every rank re-runs this chunk on the new scales, not only the one that overflowed
-                        print("activation ranges outgrew the calibrated scales: re-calibrated, re-running frames %d-%d of %s"
-                              % (lo + entries[0][2] if entries else lo, lo + start, video_file), flush=True)
-                        RUN_STATS["chunk_reruns"] += 1
-                        for k, nb, off in entries:
-                            net.submit(dchunk[k][:nb], traj[off:off + nb], sess.gamma, sess.gauss_len)
-                RUN_STATS["chunks"] += 1 if entries else 0
-            if not finished:
-                assert next_batch(kb) is None, "more frames than the shard holds"
-            while pending:
-                release(True)
-            for th in threads:
-                th.join()
-        except BaseException as e:               # a failure on this side must not leave the staging threads waiting for a slot for ever
-            with cv:
-                st["err"] = st["err"] or e
-                cv.notify_all()
-            raise
-        t_ = time.perf_counter()
-        if world > 1:                                  # ONE all-gather per video: 20 bytes per (frame, joint)
-            full = ddist.gather_trajectory(traj[:n_local], n_frames)
-            mu_t, lik_t, _ = ddist.unpack_keypoints(full)
-            markers[:] = mu_t.cpu().numpy()
-            likelihoods[:] = lik_t.cpu().numpy()
-        else:
-            mu_t, lik_t, _ = ddist.unpack_keypoints(traj[:start])
-            markers[:start] = mu_t.cpu().numpy()
-            likelihoods[:start] = lik_t.cpu().numpy()
-        RUN_STATS["finish_s"] += time.perf_counter() - t_       # the trajectory's gather / ONE device-to-host copy
-        return stale
+    lo, hi = ddist.shard_range(int(video_clip.n_frames), rank, world)        # this rank's frames
+    run = _PoseRun(sess, video_clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend)
 
     # Bit-identity of a sharded run with a single-process run holds as long as no chunk overflows (or only the first one does).  After an
     # overflow in a LATER chunk the earlier chunks keep the (valid) results of the narrower scales, which a run that started with the
     # wide scales would not reproduce bit for bit.  DGP_EVAL_STRICT=1 restores the guarantee at the cost of a second pass over the video:
     # the engines keep the widened headroom and everything is computed again on those scales (the decision is collective).
-    net_used = None
-    RUN_STATS["chunks"] = RUN_STATS["chunk_reruns"] = RUN_STATS["strict_passes"] = 0
-    # where the host side of the call spent its time: staging copies of in-memory frames (producer thread), the consumer waiting for a
-    # decoded batch / for an H2D copy / for the engines at a chunk boundary
-    RUN_STATS["stage_s"] = RUN_STATS["wait_frames_s"] = RUN_STATS["wait_h2d_s"] = RUN_STATS["drain_s"] = 0.0
-    RUN_STATS["alloc_s"] = RUN_STATS["calibrate_s"] = RUN_STATS["finish_s"] = 0.0
     RUN_STATS["setup_s"] = time.perf_counter() - t_entry      # config, snapshot -> engine (read, re-pack, upload): before the first frame moves
     for _pass in range(4):
-        if not (_infer_once(video_clip, _pass == 0) and os.environ.get("DGP_EVAL_STRICT", "0") == "1"):
+        if not (run.run_pass(_pass == 0) and os.environ.get("DGP_EVAL_STRICT", "0") == "1"):
             break
         RUN_STATS["strict_passes"] += 1
         print("DGP_EVAL_STRICT: scales were widened after the first chunk; computing %s again on the final scales" % video_file, flush=True)
-    RUN_STATS["prep_backend"] = prep_backend
+    RUN_STATS["prep_backend"] = run.prep_backend
     sess.close()
     video_clip.close()
 
-    xr = markers[:, :, 1] * dlc_cfg.stride + 0.5 * dlc_cfg.stride      # eval.py:352-353
-    yr = markers[:, :, 0] * dlc_cfg.stride + 0.5 * dlc_cfg.stride
-    xr *= scale_x
-    yr *= scale_y
-    labels = {"x": xr, "y": yr, "likelihoods": likelihoods}
+    xr = run.markers[:, :, 1] * dlc_cfg.stride + 0.5 * dlc_cfg.stride      # eval.py:352-353
+    yr = run.markers[:, :, 0] * dlc_cfg.stride + 0.5 * dlc_cfg.stride
+    xr *= run.scale_x
+    yr *= run.scale_y
+    labels = {"x": xr, "y": yr, "likelihoods": run.likelihoods}
     if save_pose and rank == 0:
         if not Path(save_file).parent.exists():
             os.makedirs(os.path.dirname(save_file))

@@ -561,6 +561,32 @@ def test_estimate_pose_edge_cases_vs_oracle(lib_built, tmp_path):
     check(run(big, "cropped", batch_size=2, crop_size=crop), O.infer(cropped, wts, 50, 8.0, 1.0, 1))
 
 
+def test_estimate_pose_stack_and_decoded_staging_agree_on_a_recycled_ring(lib_built, tmp_path, monkeypatch):
+    """The two producers of the staging ring through the public call: 7 frames in batches of 3 (3 + 3 + 1) as a .npy stack (two staging
+    threads) and as a directory of PNGs of the same frames (the decoding thread), each on a ring of TWO pinned slots, so every slot is
+    handed back and staged again -- bit for bit the run on the default 8 slots, in one chunk and without a re-run."""
+    from PIL import Image
+    from deepgraphpose_amd.models import eval as E
+    from deepgraphpose_amd.synthetic import make_frames
+    proj, snap, _, wts = _tiny_project(tmp_path)
+    frames = make_frames(7, 64, 96, 3, seed=5)
+    np.save(tmp_path / "seven.npy", frames)
+    (tmp_path / "seven_png").mkdir()
+    for i, f in enumerate(frames):
+        Image.fromarray(f).save(tmp_path / "seven_png" / ("img%03d.png" % i))
+
+    def run(video, tag):
+        out = E.estimate_pose(str(proj / "config.yaml"), snap, str(tmp_path / video), str(tmp_path / tag), shuffle=1, save_pose=False, batch_size=3)
+        assert E.RUN_STATS["chunks"] == 1 and E.RUN_STATS["chunk_reruns"] == 0, E.RUN_STATS
+        return out
+    assert E.PINNED_SLOTS == 8
+    wide = run("seven.npy", "slots8")
+    monkeypatch.setattr(E, "PINNED_SLOTS", 2)
+    stack, decoded = run("seven.npy", "stack2"), run("seven_png", "png2")
+    for k in ("x", "y", "likelihoods"):
+        assert stack[k].shape == (7, 3) and np.array_equal(stack[k], decoded[k]) and np.array_equal(stack[k], wide[k]), k
+
+
 def test_pipeline_two_engines_equal_single_engine(lib_built):
     """engine.DGPPipeline (two engines on two HIP streams, batches dealt in turn): every batch's packed records equal what ONE engine
     calibrated on the same first batch computes, bit for bit, whichever engine they landed on; ragged last batch; a re-calibration
