@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -48,6 +49,9 @@ struct Unit {
     int sc = -1, c1 = -1, c2 = -1, c3 = -1;
     int stride = 1, rate = 1;
     int depth_in = 0, depth = 0, depth_bn = 0;
+    // the unit's grid at the net's frame size (set_geometry): input h x w, output ho x wo (conv2 and the shortcut conv carry the stride),
+    // conv2's padding-before
+    int h = 0, w = 0, ho = 0, wo = 0, pb_h = 0, pb_w = 0;
 };
 
 // conv3 of unit k (+ shortcut, ReLU) and conv1 of unit k + 1 as ONE launch (dgp_chain.hip): the weight fragments of both convs in
@@ -81,6 +85,25 @@ int nk_for(int kh, int kw, int cin);
 void tf_same(int n, int k, int s, int d, int* out, int* pad_before);
 int pad_before_for(int n, int k, int stride, int rate, bool conv2d_same_explicit);
 
+inline bool fits_descriptor(std::initializer_list<double> bytes) {      // a tensor addressed through a buffer descriptor stays under 4 GiB
+    for (double b : bytes) if (b > 4294967000.0) return false;
+    return true;
+}
+
+// A head as ONE pointwise GEMM (ConvLayer::d_w_pw), T[pixel][(tap, phase, joint)] = feat[pixel][:] . W'.  The callers (inference engine,
+// training step) add their activation formats, the 16-bit tier's cells and the K-split slab
+inline ConvArgs head_pointwise_args(const ConvLayer& l, const float* feat, int B, int h, int w, float* T, const float* feat_absmax,
+                                    const float* w_absmax) {
+    ConvArgs a{};
+    a.in = feat; a.wpk = l.d_w_pw; a.wh3 = l.d_wh3_pw; a.out = T; a.in_absmax = feat_absmax; a.w_absmax = w_absmax;
+    a.N = B; a.H = h; a.W = w; a.Cin = l.Cin; a.log2cin4 = ilog2(l.Cin / 4);
+    a.Ho = h; a.Wo = w; a.Cout = l.coutp_pw; a.CoutP = l.coutp_pw;
+    a.KH = 1; a.KW = 1; a.stride = 1; a.dil = 1; a.ntaps = 1; a.nk = nk_for(1, 1, l.Cin); a.M = B * h * w;
+    a.in_bytes = (unsigned)((size_t)a.M * l.Cin * 4); a.out_bytes = (unsigned)((size_t)a.M * l.coutp_pw * 4);
+    a.w_bytes = (unsigned)((size_t)a.nk * 8 * l.coutp_pw * 16); a.wh3_bytes = a.w_bytes;
+    return a;
+}
+
 }  // namespace dgp
 
 struct dgp_net {
@@ -99,7 +122,7 @@ struct dgp_net {
     // 1 = 16-bit tier (H1 cells: 2-byte activations end to end, fp16 operands, one MFMA per product, fp32 accumulation / epilogues /
     // heads / soft-argmax).  Scales, calibration and the range check are shared; switching tiers re-calibrates.
     int tier = 0;
-    // geometry
+    // geometry at desc.in_h x desc.in_w (set_geometry, with every Unit's grid): conv1's output, the pool's, the feature map (= the last unit's output)
     int h1 = 0, w1 = 0, hp = 0, wp = 0, fh = 0, fw = 0;
     // operand ranges of the fp16-split conv kernels: ABSMAX_SLOTS floats per tensor.  d_wmax[li]: weight panel of
     // layer li (filled at load); d_amax[li]: output of layer li (zeroed and re-tracked every forward);

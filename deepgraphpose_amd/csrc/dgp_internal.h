@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace dgp {
 
@@ -200,9 +201,9 @@ hipError_t launch_unit(const ChainArgs& a, int N, int C, int C1, int CIN2, int r
 // planes: 2 = [hi][lo] pairs; 1 = high fragments only (the 16-bit tier's chunks: f1_pairs + f2_pairs + 1 KiB-fragments per chunk)
 hipError_t launch_chain_pack(const float* src, int n_chunks, int f1_pairs, int f2_pairs, float s1, float s2, void* out, hipStream_t s, int planes = 2);
 
-// Run-time switches of the native code, two classes (README "Switches"):
-//  * dgp_env(): the shipped ones -- the precision tiers (DGP_CONV_MODE, DGP_H2) and the A/B switches between paths that all ship
-//    and that the tests exercise (<= 20 in all); read from the environment once per process;
+// Run-time switches of the native code, two classes (README "Switches"), each read from the environment once per process:
+//  * dgp_env(): the shipped ones -- DGP_H2 and the A/B switches between paths that all ship and that the tests exercise (<= 20 in
+//    all) -- and conv_mode(), the one parse of DGP_CONV_MODE (the precision tiers);
 //  * dgp_tune(): knobs of measured-and-settled choices and the opt-ins that measured SLOWER (the C = 256 chain instance
 //    DGP_CHAIN_WIDE, the trainer's fast pass).  The product binary compiles
 //    the default in; they read the environment only in a tuning build (DGP_BUILD_FLAGS=-DDGP_TUNING python -m deepgraphpose_amd.build),
@@ -218,6 +219,22 @@ inline int dgp_tune(const char* name, int dflt) {
     (void)name;
     return dflt;
 #endif
+}
+// DGP_CONV_MODE, parsed once per process (unset = f16x3; Other = any string that is not listed).  What each value answers:
+//                                                          f16x3  bf16x6  f32  f16  Other
+//   the 16-bit tier is a new net's default (dgp_net_create)   no     no    no   yes   no
+//   fp32 MFMA everywhere: no stem row walk, no fused shortcut no     no    yes  no    no
+//   the cells engine (H2 / H1 activations) may run            yes    no    no   yes   no
+//   pick_tile's rule                                          4      3     2    4     4
+//   the trainer tracks operand ranges (range_pass_begin)      yes    no    no   no    no
+enum class ConvMode { F16x3, BF16x6, F32, F16, Other };
+inline ConvMode conv_mode() {
+    static const ConvMode m = [] {
+        const char* v = getenv("DGP_CONV_MODE");
+        if (!v || !strcmp(v, "f16x3")) return ConvMode::F16x3;
+        return !strcmp(v, "bf16x6") ? ConvMode::BF16x6 : !strcmp(v, "f32") ? ConvMode::F32 : !strcmp(v, "f16") ? ConvMode::F16 : ConvMode::Other;
+    }();
+    return m;
 }
 
 // hipFuncSetAttribute applies to the CURRENT device: the "done once" flags of the launchers are kept per device

@@ -2533,10 +2533,7 @@ int pick_tile(int M, int CoutP, int K, bool have_absmax) {
     // rule 3 (DGP_CONV_MODE=bf16x6): bf16-split kernels (6 bf16 MFMAs per product, no range requirement);
     // rule 2 (DGP_CONV_MODE=f32): fp32 MFMA everywhere (bitwise fmaf chains)
     static const int rule = dgp_tune("DGP_TILE_RULE", 0) ? dgp_tune("DGP_TILE_RULE", 0)
-                            : !getenv("DGP_CONV_MODE") ? 4
-                            : !strcmp(getenv("DGP_CONV_MODE"), "f16") ? 4
-                            : !strcmp(getenv("DGP_CONV_MODE"), "f32") ? 2
-                            : !strcmp(getenv("DGP_CONV_MODE"), "bf16x6") ? 3 : 4;
+                            : conv_mode() == ConvMode::F32 ? 2 : conv_mode() == ConvMode::BF16x6 ? 3 : 4;
     if (rule >= 4 && have_absmax) {
         // fp16 high/low split (3 MFMAs per product; needs the operand ranges).  With the MFMA work cut to a quarter
         // of the fp32 pipe's, the L2 -> L1 operand path sets the pace: the BK = 32 staging (a lane group fetches a

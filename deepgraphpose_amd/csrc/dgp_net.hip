@@ -42,14 +42,6 @@ int pad_before_for(int n, int k, int stride, int rate, bool conv2d_same_explicit
     tf_same(n, k, stride, rate, &out, &pb);
     return pb;
 }
-// The 16-bit tier (dgp_net::tier == 1; DGP_CONV_MODE=f16 makes it the default of every net of the process): H1 cells -- 2-byte
-// activations -- from the pool output to the block4 features, high-only weight cells, one MFMA per product.  Not inside the 1e-3 px gate;
-// bench.py reports what it measures beside the parity tier.
-static bool tier16_env() {
-    static const bool on = getenv("DGP_CONV_MODE") && !strcmp(getenv("DGP_CONV_MODE"), "f16");
-    return on;
-}
-
 static int pow2_exp_for_max(float mx) {        // e with max * 2^e in [2^14, 2^15) -- the weight scale of the fp16 split (pow2_scale_for)
     if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
     int ex; (void)frexpf(mx, &ex);             // mx = f 2^ex, f in [0.5, 1)
@@ -177,6 +169,21 @@ static int add_layer(dgp_net* net, const std::string& scope, int cin, int cout, 
     return (int)net->layers.size() - 1;
 }
 
+// the net's grids at frame size in_h x in_w: root block, then the units' walk (ONE place: the engine, its workspace plan and the trainer read it)
+static void set_geometry(dgp_net* net, int in_h, int in_w) {
+    int pb;
+    net->desc.in_h = in_h; net->desc.in_w = in_w;
+    net->h1 = (in_h + 1) / 2; net->w1 = (in_w + 1) / 2;     // conv2d_same stride 2
+    tf_same(net->h1, 3, 2, 1, &net->hp, &pb); tf_same(net->w1, 3, 2, 1, &net->wp, &pb);
+    int h = net->hp, w = net->wp;
+    for (Unit& u : net->units) {
+        u.h = h; u.w = w; tf_same(h, 3, u.stride, u.rate, &u.ho, &pb); tf_same(w, 3, u.stride, u.rate, &u.wo, &pb);      // (SAME: ceil(n / stride))
+        u.pb_h = pad_before_for(h, 3, u.stride, u.rate, true); u.pb_w = pad_before_for(w, 3, u.stride, u.rate, true);
+        h = u.ho; w = u.wo;
+    }
+    net->fh = h; net->fw = w;
+}
+
 extern "C" {
 
 int dgp_version(void) { return DGP_ABI_VERSION; }
@@ -270,11 +277,10 @@ int dgp_net_create(const dgp_net_desc* d, dgp_net** out) {
             net->head_locref = (int)net->layers.size() - 1;
         }
     }
-    int pb;
-    net->h1 = (d->in_h + 1) / 2; net->w1 = (d->in_w + 1) / 2;     // conv2d_same stride 2
-    tf_same(net->h1, 3, 2, 1, &net->hp, &pb); tf_same(net->w1, 3, 2, 1, &net->wp, &pb);
-    net->fh = (((net->hp + 1) / 2) + 1) / 2; net->fw = (((net->wp + 1) / 2) + 1) / 2;
-    net->tier = tier16_env() ? 1 : 0;
+    set_geometry(net, d->in_h, d->in_w);
+    // The 16-bit tier (tier == 1; DGP_CONV_MODE=f16 makes it the default of every net of the process): H1 cells -- 2-byte activations --
+    // from the pool output to the block4 features, high-only weight cells, one MFMA per product.  Not inside the 1e-3 px gate
+    net->tier = conv_mode() == ConvMode::F16 ? 1 : 0;
     *out = net;
     return DGP_OK;
 }
@@ -292,11 +298,7 @@ int dgp_net_get_tier(const dgp_net* net) { return net ? net->tier : 0; }
 int dgp_net_set_input_size(dgp_net* net, int32_t in_h, int32_t in_w) {
     if (!net) return fail(DGP_ERR_INVALID, "dgp_net_set_input_size: null net");
     if (in_h < 32 || in_w < 32) return fail(DGP_ERR_INVALID, "dgp_net_set_input_size: frames must be at least 32 x 32");
-    net->desc.in_h = in_h; net->desc.in_w = in_w;
-    int pb;
-    net->h1 = (in_h + 1) / 2; net->w1 = (in_w + 1) / 2;
-    tf_same(net->h1, 3, 2, 1, &net->hp, &pb); tf_same(net->w1, 3, 2, 1, &net->wp, &pb);
-    net->fh = (((net->hp + 1) / 2) + 1) / 2; net->fw = (((net->wp + 1) / 2) + 1) / 2;
+    set_geometry(net, in_h, in_w);
     return DGP_OK;
 }
 
@@ -554,14 +556,11 @@ Plan make_plan(const dgp_net* net, int B) {
     size_t p0 = (size_t)B * d.in_h * d.in_w * 4;
     size_t c1 = (size_t)B * net->h1 * net->w1 * 64;
     size_t x = (size_t)B * net->hp * net->wp * 64, sc = 0, r1 = 0, r2 = 0;
-    int h = net->hp, w = net->wp;
     for (const Unit& u : net->units) {
-        const int ho = (h + u.stride - 1) / u.stride, wo = (w + u.stride - 1) / u.stride;
-        r1 = std::max(r1, (size_t)B * h * w * u.depth_bn);
-        r2 = std::max(r2, (size_t)B * ho * wo * u.depth_bn);
-        x = std::max(x, (size_t)B * ho * wo * u.depth);
-        if (u.sc >= 0) sc = std::max(sc, (size_t)B * ho * wo * u.depth);
-        h = ho; w = wo;
+        r1 = std::max(r1, (size_t)B * u.h * u.w * u.depth_bn);
+        r2 = std::max(r2, (size_t)B * u.ho * u.wo * u.depth_bn);
+        x = std::max(x, (size_t)B * u.ho * u.wo * u.depth);
+        if (u.sc >= 0) sc = std::max(sc, (size_t)B * u.ho * u.wo * u.depth);
     }
     r1 = r2 = std::max(r1, r2);       // the unit kernel ping-pongs conv1's output between the two regions
     Plan p{};
@@ -606,62 +605,82 @@ void apply_h2(ConvArgs& a, const H2Spec& h) {
     a.in_scale = ldexpf(1.f, h.in_exp); a.out_scale = ldexpf(1.f, h.out_exp); a.res_inv_scale = ldexpf(1.f, -h.res_exp);
 }
 
-int run_conv(dgp_net* net, const ConvLayer& l, const float* in, int N, int H, int W, int pad_t, int pad_l, int Ho, int Wo,
-             const float* res, int res_s, int res_H, int res_W, bool relu, int out_mode, int dc_nj, float* out,
-             hipStream_t s, float* slabs = nullptr, const float* in_absmax = nullptr, const H2Spec& h2 = H2Spec()) {
+// The geometry of a plain conv launch: shape, derived K walk, ReLU, buffer-descriptor extents (a.res set first: no residual, no extent)
+int fill_conv_geometry(ConvArgs& a, const dgp_conv_desc& d, const char* too_big) {
+    a.N = d.N; a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.log2cin4 = ilog2(d.Cin / 4);
+    a.Ho = d.Ho; a.Wo = d.Wo; a.Cout = d.Cout; a.CoutP = coutp_for(d.Cout);
+    a.KH = d.KH; a.KW = d.KW; a.stride = d.stride; a.dil = d.rate; a.pad_t = d.pad_t; a.pad_l = d.pad_l;
+    a.ntaps = d.KH * d.KW; a.nk = nk_for(d.KH, d.KW, d.Cin); a.M = d.N * d.Ho * d.Wo;
+    a.res_s = d.res_stride; a.res_H = d.res_H; a.res_W = d.res_W; a.relu = d.relu;
+    const double inb = (double)d.N * d.H * d.W * d.Cin * 4, outb = (double)a.M * d.Cout * 4;
+    const double resb = a.res ? (double)d.N * d.res_H * d.res_W * d.Cout * 4 : 0.0;
+    if (!fits_descriptor({inb, outb, resb})) return fail(DGP_ERR_INVALID, too_big);
+    a.in_bytes = (unsigned)inb; a.out_bytes = (unsigned)outb; a.res_bytes = (unsigned)resb;
+    a.w_bytes = (unsigned)((size_t)a.nk * 8 * a.CoutP * 16);
+    return DGP_OK;
+}
+const char* const TOO_BIG = "activation tensor exceeds the 4 GiB buffer-descriptor range; lower the batch";
+
+// One launch of a layer of the net.  conv_call() gives the common case -- the layer on the input's own grid (1x1 convs), no residual,
+// ReLU, plain NHWC output, fp32 tensors without a tracked input range -- and a call site names what differs
+struct ConvCall {
+    const float* in = nullptr;
+    int H = 0, W = 0, Ho = 0, Wo = 0, pad_t = 0, pad_l = 0;
+    const float* res = nullptr;                 // residual [N, res_H, res_W, Cout], read at (ho res_s, wo res_s)
+    int res_s = 0, res_H = 0, res_W = 0;
+    bool relu = true;
+    int out_mode = 0, dc_nj = 0;                // 1: a head's phase scatter with dc_nj channels per phase
+    float *out = nullptr, *slabs = nullptr;     // slabs (out_mode 1): room for the K-split
+    const float* in_absmax = nullptr;
+    H2Spec h2;
+    ConvCall& grid(int ho, int wo, int pt = 0, int pl = 0) { Ho = ho; Wo = wo; pad_t = pt; pad_l = pl; return *this; }
+    ConvCall& residual(const float* r, int s, int rH, int rW) { res = r; res_s = s; res_H = rH; res_W = rW; return *this; }
+    ConvCall& range(const float* in_rng) { in_absmax = in_rng; return *this; }
+    ConvCall& cells(const H2Spec& q) { h2 = q; return *this; }
+    ConvCall& linear() { relu = false; return *this; }
+};
+ConvCall conv_call(const float* in, int H, int W, float* out) {
+    ConvCall c;
+    c.in = in; c.H = c.Ho = H; c.W = c.Wo = W; c.out = out;
+    return c;
+}
+
+int run_conv(dgp_net* net, const ConvLayer& l, int N, const ConvCall& c, hipStream_t s) {
     ConvArgs a{};
     const int li = (int)(&l - net->layers.data());
-    if (!net->wmax_valid) in_absmax = nullptr;
-    apply_h2(a, h2);
-    const bool ranged = in_absmax || h2.in_fmt;
+    const float* in_absmax = net->wmax_valid ? c.in_absmax : nullptr;
+    apply_h2(a, c.h2);
+    const bool ranged = in_absmax || c.h2.in_fmt;
     a.in_absmax = in_absmax; a.w_absmax = ranged ? net->wmax(li) : nullptr;
-    a.out_absmax = out_mode == 0 ? net->amax(li) : nullptr;
+    a.out_absmax = c.out_mode == 0 ? net->amax(li) : nullptr;
     a.slab = net->tail_slab; a.slab_bytes = net->tail_slab_bytes;
-    a.in = in; a.wpk = l.d_w; a.scale = l.has_bn ? l.d_scale : nullptr; a.bias = l.d_bias; a.res = res; a.out = out;
-    a.N = N; a.H = H; a.W = W; a.Cin = l.Cin; a.log2cin4 = ilog2(l.Cin / 4);
-    a.Ho = Ho; a.Wo = Wo; a.Cout = l.Cout; a.CoutP = l.CoutP;
-    a.KH = l.KH; a.KW = l.KW; a.stride = l.stride; a.dil = l.rate; a.pad_t = pad_t; a.pad_l = pad_l;
-    a.ntaps = l.ntaps; a.nk = l.nk; a.M = N * Ho * Wo;
-    a.res_s = res ? res_s : 0; a.res_H = res_H; a.res_W = res_W;
-    a.relu = relu ? 1 : 0; a.out_mode = out_mode; a.dc_nj = dc_nj;
-    {
-        const double lim = 4294967000.0;
-        const double inb = (double)N * H * W * l.Cin * 4, outb = (double)a.M * l.Cout * 4;
-        const double resb = res ? (double)N * res_H * res_W * l.Cout * 4 : 0.0;
-        if (inb > lim || outb > lim || resb > lim)
-            return fail(DGP_ERR_INVALID, "activation tensor exceeds the 4 GiB buffer-descriptor range; lower the batch");
-        if (out_mode == 0 && (l.Cout & 3)) return fail(DGP_ERR_INVALID, "conv: Cout must be a multiple of 4");
-        a.in_bytes = (unsigned)inb; a.out_bytes = (unsigned)outb; a.res_bytes = (unsigned)resb;
-        a.w_bytes = (unsigned)((size_t)l.nk * 8 * l.CoutP * 16);
-    }
+    a.in = c.in; a.wpk = l.d_w; a.scale = l.has_bn ? l.d_scale : nullptr; a.bias = l.d_bias; a.res = c.res; a.out = c.out;
+    dgp_conv_desc d{};
+    d.N = N; d.H = c.H; d.W = c.W; d.Cin = l.Cin; d.Cout = l.Cout; d.KH = l.KH; d.KW = l.KW; d.stride = l.stride; d.rate = l.rate;
+    d.pad_t = c.pad_t; d.pad_l = c.pad_l; d.Ho = c.Ho; d.Wo = c.Wo; d.relu = c.relu; d.res_stride = c.res ? c.res_s : 0; d.res_H = c.res_H; d.res_W = c.res_W;
+    if (int rc = fill_conv_geometry(a, d, TOO_BIG)) return rc;
+    if (c.out_mode == 0 && (l.Cout & 3)) return fail(DGP_ERR_INVALID, "conv: Cout must be a multiple of 4");
+    a.out_mode = c.out_mode; a.dc_nj = c.dc_nj;
     static const bool stem_rows = (dgp_tune("DGP_STEM_ROWS", 1) != 0);        // A/B switch
-    static const bool f32_mode = getenv("DGP_CONV_MODE") && !strcmp(getenv("DGP_CONV_MODE"), "f32");
-    if (li == net->conv1 && l.d_w_rows && net->wmax_valid && stem_rows && !f32_mode && l.CoutP % 64 == 0) {
+    if (li == net->conv1 && l.d_w_rows && net->wmax_valid && stem_rows && conv_mode() != ConvMode::F32 && l.CoutP % 64 == 0) {
         a.stem = 1; a.tap_rows = 8; a.KH = 7; a.KW = 1; a.ntaps = 7; a.nk = 7; a.wpk = l.d_w_rows;
         a.w_bytes = (unsigned)((size_t)7 * 8 * l.CoutP * 16);
     }
     static const bool use_cells = (dgp_tune("DGP_PRESPLIT_WEIGHTS", 1) != 0);   // A/B switch
     if (use_cells && ranged && l.d_wh3 && (li != net->conv1 || a.stem)) { a.wh3 = l.d_wh3; a.wh3_bytes = a.w_bytes; }
-    if (h2.in_fmt == 2) { a.wh3 = l.d_wh1; a.wh3_bytes = a.w_bytes; }       // (null: launch_conv refuses)
+    if (c.h2.in_fmt == 2) { a.wh3 = l.d_wh1; a.wh3_bytes = a.w_bytes; }       // (null: launch_conv refuses)
     const int tile_cfg = pick_tile(a.M, a.CoutP, a.nk * BK, ranged && a.w_absmax);
-    ProfScope ps(net, s, "conv:" + l.scope + "|" + conv_kernel_name(a, tile_cfg), conv_flops_of(l, a.M, out_mode == 1));
-    const long long out_n = (long long)N * 4 * Ho * Wo * dc_nj;
-    if (out_mode == 1 && slabs && (out_n & 3) == 0) {
-        // the heads have a tiny N (4*nj channels) and a huge K (4 x 2048): split K so the grid fills the chip;
-        // slabs are summed in a fixed order (deterministic, unlike float atomics)
-        const int mtiles = (a.M + 127) / 128;
-        int ks = 1;
-        while (ks < HEAD_KSPLIT_MAX && mtiles * ks < 1024 && l.nk % (ks * 2) == 0) ks *= 2;
-        if (ks > 1) {
-            a.ksplit = ks; a.split_stride = out_n; a.out = slabs;
-            hipError_t e = launch_conv(a, tile_cfg, s);
-            if (e == hipSuccess) e = launch_reduce_slabs(slabs, out_n, out_n, ks, out, s);
-            if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("head conv (") + l.scope + "): " + hipGetErrorString(e));
-            return DGP_OK;
-        }
-    }
+    ProfScope ps(net, s, "conv:" + l.scope + "|" + conv_kernel_name(a, tile_cfg), conv_flops_of(l, a.M, c.out_mode == 1));
+    const long long out_n = (long long)N * 4 * c.Ho * c.Wo * c.dc_nj;
+    // the heads have a tiny N (4*nj channels) and a huge K (4 x 2048): split K so the grid fills the chip;
+    // slabs are summed in a fixed order (deterministic, unlike float atomics)
+    int ks = 1;
+    if (c.out_mode == 1 && c.slabs && (out_n & 3) == 0)
+        while (ks < HEAD_KSPLIT_MAX && (a.M + 127) / 128 * ks < 1024 && l.nk % (ks * 2) == 0) ks *= 2;
+    if (ks > 1) { a.ksplit = ks; a.split_stride = out_n; a.out = c.slabs; }
     hipError_t e = launch_conv(a, tile_cfg, s);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("conv launch (") + l.scope + "): " + hipGetErrorString(e));
+    if (ks > 1 && e == hipSuccess) e = launch_reduce_slabs(c.slabs, out_n, out_n, ks, c.out, s);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string(ks > 1 ? "head conv (" : "conv launch (") + l.scope + "): " + hipGetErrorString(e));
     return DGP_OK;
 }
 
@@ -673,16 +692,10 @@ int run_head_pointwise(dgp_net* net, const ConvLayer& l, const float* feat, int 
                        float* T, const float* feat_absmax, const H2Spec& h2 = H2Spec()) {
     const int li = (int)(&l - net->layers.data());
     const int nl = (int)net->layers.size();
-    ConvArgs a{};
+    ConvArgs a = head_pointwise_args(l, feat, B, h, w, T, feat_absmax, net->d_wmax + (size_t)(nl + li) * ABSMAX_SLOTS);
     apply_h2(a, h2);
-    a.in = feat; a.wpk = l.d_w_pw; a.wh3 = h2.in_fmt == 2 ? l.d_wh1_pw : l.d_wh3_pw; a.out = T;
-    a.in_absmax = feat_absmax; a.w_absmax = net->d_wmax + (size_t)(nl + li) * ABSMAX_SLOTS;
+    if (h2.in_fmt == 2) a.wh3 = l.d_wh1_pw;
     a.slab = net->tail_slab; a.slab_bytes = net->tail_slab_bytes;
-    a.N = B; a.H = h; a.W = w; a.Cin = 2048; a.log2cin4 = ilog2(2048 / 4);
-    a.Ho = h; a.Wo = w; a.Cout = l.coutp_pw; a.CoutP = l.coutp_pw;
-    a.KH = 1; a.KW = 1; a.stride = 1; a.dil = 1; a.ntaps = 1; a.nk = nk_for(1, 1, 2048); a.M = B * h * w;
-    a.in_bytes = (unsigned)((size_t)a.M * 2048 * 4); a.out_bytes = (unsigned)((size_t)a.M * l.coutp_pw * 4);
-    a.w_bytes = (unsigned)((size_t)a.nk * 8 * l.coutp_pw * 16); a.wh3_bytes = a.w_bytes;
     const int tile_cfg = pick_tile(a.M, a.CoutP, a.nk * BK, true);
     hipError_t e;
     {
@@ -708,10 +721,8 @@ int run_conv_fused_shortcut(dgp_net* net, const Unit& u, const float* r2, const 
     a.N = N; a.H = H; a.W = W; a.Ho = H; a.Wo = W; a.Cout = l.Cout; a.CoutP = l.CoutP;
     a.KH = 1; a.KW = 1; a.stride = 1; a.dil = 1; a.pad_t = 0; a.pad_l = 0; a.ntaps = 1; a.nk = l.nk_fused; a.M = N * H * W;
     a.relu = 1; a.out_mode = 0;
-    const double lim = 4294967000.0;
     const double inb = (double)a.M * l.Cin * 4, in2b = (double)a.M * l.cin2 * 4, outb = (double)a.M * l.Cout * 4;
-    if (inb > lim || in2b > lim || outb > lim)
-        return fail(DGP_ERR_INVALID, "activation tensor exceeds the 4 GiB buffer-descriptor range; lower the batch");
+    if (!fits_descriptor({inb, in2b, outb})) return fail(DGP_ERR_INVALID, TOO_BIG);
     a.in_bytes = (unsigned)inb; a.in2_bytes = (unsigned)in2b; a.out_bytes = (unsigned)outb;
     a.w_bytes = (unsigned)((size_t)l.nk_fused * 8 * l.CoutP * 16);
     if ((r2_absmax && x_absmax) || h2.in_fmt) {
@@ -728,41 +739,53 @@ int run_conv_fused_shortcut(dgp_net* net, const Unit& u, const float* r2, const 
     return DGP_OK;
 }
 
-// conv3 of unit ui (+ shortcut, ReLU) and conv1 of unit ui + 1 as one launch (dgp_chain.hip).  r2 [M][C]; x: the unit's input (identity
-// shortcut [M][4C], stride-2 unit [N, H, W, 4C], or the K-concatenated source of the shortcut conv [M][CIN2]); all tensors H2
-// r1in != null: the unit kernel -- conv2 of unit ui runs in the same launch, reading R1 (r1in) with its halo; r2 is not used
-int run_chain(dgp_net* net, int ui, const float* r2, const float* x, int N, int Ho, int Wo, int H, int W, float* xout, float* r1out,
-              hipStream_t s, int x_exp, const float* r1in = nullptr) {
+// The tensors of one chain / unit launch with their scale exponents.  All are H2 tensors, or all H1 (h1: 2 bytes per channel
+// instead of 4).  r2 [M][C]; src2: the unit's input -- identity shortcut [M][4C], stride-2 unit [N, H, W, 4C], or the K-concatenated
+// source of the shortcut conv [M][CIN2].  r1in != null: the unit kernel -- conv2 runs in the same launch, reading r1in [N, H, W, C]
+// with its halo (stride 1: Ho x Wo = H x W); r2 is not used
+struct ChainIo {
+    bool h1; int N, Ho, Wo, H, W;
+    const void *r2, *src2, *r1in; void *xout, *r1out;
+    int r1in_exp, r2_exp, src2_exp, xout_exp, r1out_exp;
+    float *r2_absmax, *xout_absmax, *r1_absmax;
+};
+
+// ChainArgs of a plan's launch, ONE place for the engine and the layer-level entry points
+int fill_chain_args(ChainArgs& a, const ChainPlan& cp, const ChainIo& io) {
+    a.h1 = io.h1 ? 1 : 0;                         // the 16-bit tier: the same weight chunks, high fragments only
+    const double EB = io.h1 ? 2.0 : 4.0;          // bytes per channel: H1 cells / H2 cell pairs
+    const bool unit = io.r1in != nullptr;         // (the chain alone skips conv2's chunks at the head of the fragments)
+    const unsigned skip = unit ? 0 : io.h1 ? cp.head_bytes_h1 : cp.head_bytes;
+    a.r2 = io.r2; a.src2 = io.src2; a.xout = io.xout; a.r1out = io.r1out; a.sc1 = cp.d_sc1; a.bi1 = cp.d_bi1;
+    a.wfrag = (const char*)(io.h1 ? cp.d_frags_h1 : cp.d_frags) + skip;
+    a.w_bytes = (io.h1 ? cp.frag_bytes_h1 : cp.frag_bytes) - skip;
+    a.M = io.N * io.Ho * io.Wo; a.HoWo = io.Ho * io.Wo; a.Wo = io.Wo; a.res_H = io.H; a.res_W = io.W;
+    if (unit) {
+        a.r1in = io.r1in; a.H = io.H; a.W = io.W; a.r2_absmax = io.r2_absmax;
+        a.post0 = ldexpf(1.f, -(io.r1in_exp + cp.w2_exp)); a.r2_scale = ldexpf(1.f, io.r2_exp);
+    }
+    a.post1 = ldexpf(1.f, -(io.r2_exp + cp.w3_exp)); a.post2 = ldexpf(1.f, -(io.xout_exp + cp.w1_exp));
+    a.res_inv_scale = ldexpf(1.f, -io.src2_exp); a.xout_scale = ldexpf(1.f, io.xout_exp); a.r1_scale = ldexpf(1.f, io.r1out_exp);
+    a.xout_absmax = io.xout_absmax; a.r1_absmax = io.r1_absmax;
+    const double r2b = (double)a.M * cp.C * EB, xob = (double)a.M * cp.C * 4 * EB, r1b = (double)a.M * cp.C1 * EB;
+    const double s2b = cp.res == 0 ? (double)a.M * cp.CIN2 * EB : (double)io.N * io.H * io.W * cp.C * 4 * EB;
+    const double r1inb = unit ? (double)io.N * io.H * io.W * cp.C * EB : 0.0;
+    if (!fits_descriptor({r2b, xob, r1b, s2b, r1inb})) return fail(DGP_ERR_INVALID, TOO_BIG);
+    a.r2_bytes = (unsigned)r2b; a.xout_bytes = (unsigned)xob; a.r1_bytes = (unsigned)r1b; a.src2_bytes = (unsigned)s2b; a.r1in_bytes = (unsigned)r1inb;
+    return DGP_OK;
+}
+
+// conv3 of unit ui (+ shortcut, ReLU) and conv1 of unit ui + 1 as one launch (dgp_chain.hip); r1in != null: the unit kernel
+int run_chain(dgp_net* net, int ui, const float* r2, const float* x, int N, float* xout, float* r1out, hipStream_t s, int x_exp,
+              const float* r1in = nullptr) {
     const ChainPlan& cp = net->chains[ui];
     const Unit &u = net->units[ui], &un = net->units[ui + 1];
     const ConvLayer &l3 = net->layers[u.c3], &l1 = net->layers[un.c1];
+    const ChainIo io{net->tier != 0, N, u.ho, u.wo, u.h, u.w, r2, x, r1in, xout, r1out,
+                     net->act_exp[u.c1], net->act_exp[u.c2], x_exp, net->act_exp[u.c3], net->act_exp[un.c1],
+                     net->amax(u.c2), net->amax(u.c3), net->amax(un.c1)};
     ChainArgs a{};
-    a.h1 = net->tier ? 1 : 0;                     // the 16-bit tier: H1 tensors, the same weight chunks (high fragments only)
-    const double EB = a.h1 ? 2.0 : 4.0;           // bytes per channel
-    a.r2 = r2; a.src2 = x; a.xout = xout; a.r1out = r1out; a.sc1 = cp.d_sc1; a.bi1 = cp.d_bi1;
-    a.wfrag = a.h1 ? (const char*)cp.d_frags_h1 + (r1in ? 0 : cp.head_bytes_h1) : (const char*)cp.d_frags + (r1in ? 0 : cp.head_bytes);
-    a.M = N * Ho * Wo; a.HoWo = Ho * Wo; a.Wo = Wo; a.res_H = H; a.res_W = W;
-    if (r1in) {                                   // unit kernel: conv2 (stride 1: Ho x Wo = H x W) in front
-        const ConvLayer& l2 = net->layers[u.c2];
-        a.r1in = r1in; a.H = H; a.W = W;
-        a.post0 = ldexpf(1.f, -(net->act_exp[u.c1] + cp.w2_exp));
-        a.r2_scale = ldexpf(1.f, net->act_exp[u.c2]);
-        a.r2_absmax = net->amax(u.c2);
-        a.r1in_bytes = (unsigned)((double)N * H * W * l2.Cin * EB);
-    }
-    a.post1 = ldexpf(1.f, -(net->act_exp[u.c2] + cp.w3_exp));
-    a.post2 = ldexpf(1.f, -(net->act_exp[u.c3] + cp.w1_exp));
-    a.res_inv_scale = ldexpf(1.f, -x_exp);
-    a.xout_scale = ldexpf(1.f, net->act_exp[u.c3]);
-    a.r1_scale = ldexpf(1.f, net->act_exp[un.c1]);
-    a.xout_absmax = net->amax(u.c3); a.r1_absmax = net->amax(un.c1);
-    const double lim = 4294967000.0;
-    const double r2b = (double)a.M * cp.C * EB, xob = (double)a.M * cp.C * 4 * EB, r1b = (double)a.M * cp.C1 * EB;
-    const double s2b = cp.res == 0 ? (double)a.M * cp.CIN2 * EB : (double)N * H * W * cp.C * 4 * EB;
-    if (r2b > lim || xob > lim || r1b > lim || s2b > lim)
-        return fail(DGP_ERR_INVALID, "activation tensor exceeds the 4 GiB buffer-descriptor range; lower the batch");
-    a.r2_bytes = (unsigned)r2b; a.xout_bytes = (unsigned)xob; a.r1_bytes = (unsigned)r1b; a.src2_bytes = (unsigned)s2b;
-    a.w_bytes = a.h1 ? cp.frag_bytes_h1 - (r1in ? 0 : cp.head_bytes_h1) : cp.frag_bytes - (r1in ? 0 : cp.head_bytes);
+    if (int rc = fill_chain_args(a, cp, io)) return rc;
     double flops = conv_flops_of(l3, a.M, false) + conv_flops_of(l1, a.M, false);
     if (u.sc >= 0) flops += conv_flops_of(net->layers[u.sc], a.M, false);
     if (r1in) flops += conv_flops_of(net->layers[u.c2], a.M, false);
@@ -773,6 +796,281 @@ int run_chain(dgp_net* net, int ui, const float* r2, const float* x, int N, int 
     hipError_t e = r1in ? launch_unit(a, N, cp.C, cp.C1, cp.CIN2, cp.res, s) : launch_chain(a, cp.C, cp.C1, cp.CIN2, cp.res, s);
     if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("chain launch (") + l3.scope + "): " + hipGetErrorString(e));
     return DGP_OK;
+}
+
+// ---- dgp_forward in stages: forward_root, forward_unit_f32 | forward_unit_cells per unit, forward_heads, freeze_scales.  FwdCtx is one
+// pass: the call, the workspace regions, the switches resolved against the net's state (fwd_context), the calibration helper and the
+// tensor that travels from stage to stage
+struct FwdCtx {
+    dgp_net* net; hipStream_t s; int B; const uint8_t* frames;
+    float *P0, *C1, *X[2], *SC, *R1, *R2, *scmap_ws, *slabs;
+    // h2 (default): every tensor from the pool output to the block4 features lives in HBM as fp16 cells with a calibrated per-tensor scale
+    // (FMT 1: H2 high / low pairs, the parity tier; 2: H1, the 16-bit tier): K loops of ds_read + MFMA only.  Otherwise fp32 activations,
+    // split in the consumers' K loops (DGP_H2=0, the other DGP_CONV_MODEs, a trainer-owned net)
+    bool h2, calib, stem_fused, f16_mode, head_pw, fuse_on, unit_on;
+    int tier, FMT;
+    // conv3(k) + conv1(k + 1) as one launch (DGP_CHAIN=0: layer by layer).  Calibration runs layer by layer (it needs every tensor's
+    // range before the next layer runs) and is followed by a second, chained pass, so results never depend on which pass produced them
+    bool chain_tier, chain_on;
+    // the running tensor: X[cur] with its tracked range and (cells) scale exponent.  Cells: Ra holds the current unit's conv1 output, Rb its
+    // conv2 output (R1 / R2, trading places); r1_ready: the previous unit's chain launch already wrote Ra
+    int cur, x_exp;
+    const float* x_rng;
+    float *Ra, *Rb;
+    bool r1_ready;
+
+    int exp_for(float mx) const {                 // scale exponent that puts mx into [2^(14 - h2_head), 2^(15 - h2_head))
+        return (mx > 0.f && std::isfinite(mx)) ? pow2_exp_for_max(mx) - net->h2_head : 0;
+    }
+    int read_range(int li, float* mx) const {
+        float host[ABSMAX_SLOTS];
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(host, net->amax(li), sizeof host, hipMemcpyDeviceToHost));
+        *mx = 0.f;
+        for (float v : host) *mx = (v > *mx || v != v) ? v : *mx;
+        return DGP_OK;
+    }
+    // calibration: launch, read the layer's range, fix the exponent, launch again if it changed (first forward only: hidden syncs)
+    template <class Launch>
+    int layer(int li, Launch&& launch, int forced_exp = dgp_net::H2_NONE, bool* forced_ok = nullptr) const {
+        int r = launch();
+        if (r || !calib) return r;
+        float mx = 0.f;
+        if ((r = read_range(li, &mx))) return r;
+        int e = exp_for(mx);
+        if (forced_exp != dgp_net::H2_NONE) {     // must share another tensor's scale (K-concatenated second source)
+            const bool ok = forced_exp <= e + net->h2_head - 1 && forced_exp >= e - 6;
+            if (forced_ok) *forced_ok = ok;
+            if (ok) e = forced_exp;
+        }
+        if (e != net->act_exp[li]) {
+            net->act_exp[li] = e;
+            HIP_TRY(hipMemsetAsync(net->amax(li), 0, ABSMAX_SLOTS * sizeof(float), s));
+            r = launch();
+        }
+        return r;
+    }
+    H2Spec spec(int in_exp, int out_li, bool with_res = false, int res_exp = 0) const {      // cells in, cells out on the layer's scale
+        H2Spec q;
+        q.in_fmt = FMT; q.in_exp = in_exp; q.out_fmt = FMT; q.out_exp = net->act_exp[out_li]; q.res_fmt = with_res ? FMT : 0; q.res_exp = res_exp;
+        return q;
+    }
+    bool can_fuse(int ui) const {                 // conv3 + shortcut conv of unit ui as one K-concatenated GEMM: switches and shape allow it
+        const Unit& u = net->units[ui];
+        return fuse_on && u.sc >= 0 && net->layers[u.c3].d_w_fused && u.stride == 1 && u.ho == u.h && u.wo == u.w && net->layers[u.c3].CoutP % 64 == 0;
+    }
+    int conv(int li, const ConvCall& call) const { return run_conv(net, net->layers[li], B, call, s); }
+};
+
+int fwd_context(FwdCtx& c, dgp_net* net, const uint8_t* frames, int B, char* ws, const Plan& pl, hipStream_t s) {
+    static const bool h2_env = (dgp_env("DGP_H2", 1) != 0);
+    static const bool head_pw = (dgp_tune("DGP_HEAD_PW", 1) != 0);      // A/B switch
+    static const bool fuse_env = (dgp_env("DGP_FUSE_SHORTCUT", 1) != 0);      // A/B switch
+    static const bool cells_env = (dgp_tune("DGP_PRESPLIT_WEIGHTS", 1) != 0);
+    static const bool stem_fused_env = (dgp_tune("DGP_STEM_FUSED", 1) != 0);
+    static const bool chain_env = (dgp_env("DGP_CHAIN", 1) != 0);
+    static const bool chain_h1_env = (dgp_env("DGP_CHAIN_H1", 1) != 0);      // the chain / unit kernels on H1 tensors (the 16-bit tier)
+    static const bool unit_env = (dgp_tune("DGP_UNIT", 1) != 0);      // conv2 inside the chain launch (block1)
+    c = FwdCtx{};
+    c.net = net; c.s = s; c.B = B; c.frames = frames;
+    c.P0 = (float*)(ws + pl.off_p0); c.C1 = (float*)(ws + pl.off_c1); c.X[0] = (float*)(ws + pl.off_x0); c.X[1] = (float*)(ws + pl.off_x1);
+    c.SC = (float*)(ws + pl.off_sc); c.R1 = (float*)(ws + pl.off_r1); c.R2 = (float*)(ws + pl.off_r2);
+    c.scmap_ws = (float*)(ws + pl.off_scmap); c.slabs = (float*)(ws + pl.off_slabs);
+    const ConvLayer& lpart = net->layers[net->head_part];
+    const ConvLayer* lloc = net->head_locref < 0 ? nullptr : &net->layers[net->head_locref];
+    c.f16_mode = conv_mode() == ConvMode::F16x3 || conv_mode() == ConvMode::F16;
+    c.head_pw = head_pw; c.unit_on = unit_env;
+    c.fuse_on = fuse_env && conv_mode() != ConvMode::F32 && net->wmax_valid;
+    c.tier = net->tier; c.FMT = c.tier ? 2 : 1;      // activation cells of this forward: H2 (parity tier) or H1 (16-bit tier)
+    c.h2 = h2_env && cells_env && c.f16_mode && head_pw && net->wmax_valid && net->d_exps && lpart.d_wh3_pw && (!lloc || lloc->d_wh3_pw) &&
+           net->act_exp.size() == net->layers.size();
+    if (c.tier) {            // the 16-bit tier has no fallback: say what is missing instead of silently running another tier
+        bool ok = c.h2 && lpart.d_wh1_pw && (!lloc || lloc->d_wh1_pw);
+        for (const Unit& u : net->units) {
+            ok = ok && net->layers[u.c1].d_wh1 && net->layers[u.c2].d_wh1 && net->layers[u.c3].d_wh1 && (u.sc < 0 || net->layers[u.sc].d_wh1);
+            if (u.sc >= 0 && net->layers[u.c3].d_w_fused && !net->layers[u.c3].d_wh1_fused) ok = false;
+        }
+        if (!ok) return fail(DGP_ERR_STATE, "dgp_forward: the 16-bit tier needs the H2 engine's switches at their defaults (DGP_H2, DGP_PRESPLIT_WEIGHTS, "
+                                            "DGP_HEAD_PW, DGP_CONV_MODE unset or f16) and weights loaded by dgp_net_load_weights");
+    }
+    c.calib = c.h2 && !net->h2_calibrated;
+    const ConvLayer& lstem = net->layers[net->conv1];
+    c.stem_fused = c.h2 && (stem_fused_env || c.tier) && lstem.d_wh3 && lstem.d_w_rows && lstem.CoutP == 64 && lstem.d_scale && lstem.d_bias;
+    if (c.tier && !c.stem_fused) return fail(DGP_ERR_STATE, "dgp_forward: the 16-bit tier needs the fused root block");
+    c.chain_tier = chain_env && (!c.tier || chain_h1_env);
+    c.chain_on = c.h2 && !c.calib && c.chain_tier && net->chains.size() == net->units.size();
+    return DGP_OK;
+}
+
+// Root block.  H2 engine: ONE kernel from the uint8 frame to the pool output's cells (stem_pool_fused_kernel); otherwise
+// preprocess -> conv1 -> max-pool as three launches.  The pool output becomes X[0]
+int forward_root(FwdCtx& c) {
+    dgp_net* net = c.net;
+    const dgp_net_desc& d = net->desc;
+    const ConvLayer& lstem = net->layers[net->conv1];
+    int rc;
+    if (c.stem_fused) {
+        rc = c.layer(net->conv1, [&] {
+            ProfScope ps(net, c.s, "conv:" + lstem.scope + "+pool|stem_pool_fused", conv_flops_of(lstem, c.B * net->h1 * net->w1, false));
+            hipError_t e2 = launch_stem_pool_fused(c.frames, c.B, d.in_h, d.in_w, lstem.d_wh3, net->wmax(net->conv1), lstem.d_scale, lstem.d_bias,
+                                                   d.mean_pixel[0], d.mean_pixel[1], d.mean_pixel[2],
+                                                   ldexpf(1.f, net->act_exp[net->conv1]), c.X[0], net->amax(net->conv1), c.s, c.tier ? 1 : 0);
+            return e2 == hipSuccess ? (int)DGP_OK : fail(DGP_ERR_HIP, std::string("stem + pool: ") + hipGetErrorString(e2));
+        });
+        if (rc) return rc;
+    } else {
+        hipError_t e;
+        {
+            ProfScope ps(net, c.s, "preprocess_u8", 0.0);
+            e = launch_preprocess(c.frames, (long long)c.B * d.in_h * d.in_w, d.mean_pixel[0], d.mean_pixel[1], d.mean_pixel[2], c.P0, c.s);
+        }
+        if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("preprocess: ") + hipGetErrorString(e));
+        // conv1: conv2d_same(7, stride 2): explicit pad 3 before
+        if ((rc = c.conv(net->conv1, conv_call(c.P0, d.in_h, d.in_w, c.C1).grid(net->h1, net->w1, 3, 3).range(net->d_inmax)))) return rc;
+        if (c.calib) {
+            float mx = 0.f;
+            if ((rc = c.read_range(net->conv1, &mx))) return rc;
+            net->act_exp[net->conv1] = c.exp_for(mx);   // (max-pooling cannot raise the maximum of conv1's output)
+        }
+        {
+            ProfScope ps(net, c.s, "maxpool3x3s2", 0.0);
+            e = launch_maxpool(c.C1, c.B, net->h1, net->w1, 64, c.X[0], c.s, c.h2 ? ldexpf(1.f, net->act_exp[net->conv1]) : 0.f);
+        }
+        if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("maxpool: ") + hipGetErrorString(e));
+    }
+    c.cur = 0; c.Ra = c.R1; c.Rb = c.R2; c.r1_ready = false;
+    c.x_rng = net->amax(net->conv1);      // max-pooling cannot raise the maximum of conv1's output
+    c.x_exp = c.h2 ? net->act_exp[net->conv1] : 0;
+    return DGP_OK;
+}
+
+// One bottleneck unit on fp32 activations: (shortcut |) conv1 -> conv2 -> conv3 + residual + ReLU, X[cur] -> X[cur ^ 1]
+int forward_unit_f32(FwdCtx& c, int ui) {
+    dgp_net* net = c.net;
+    const Unit& u = net->units[ui];
+    const float *xin = c.X[c.cur], *r1_rng = net->amax(u.c1), *r2_rng = net->amax(u.c2);
+    float* xout = c.X[c.cur ^ 1];
+    const bool fuse = c.can_fuse(ui);
+    ConvCall c3 = conv_call(c.R2, u.ho, u.wo, xout).range(r2_rng).residual(xin, u.stride, u.h, u.w);
+    int rc = DGP_OK;
+    if (u.sc >= 0 && !fuse) {      // slim.conv2d(1x1, stride, SAME): pad 0, samples x[::s, ::s]
+        rc = c.conv(u.sc, conv_call(xin, u.h, u.w, c.SC).grid(u.ho, u.wo).linear().range(c.x_rng));
+        c3.residual(c.SC, 1, u.ho, u.wo);
+    }
+    if (!rc) rc = c.conv(u.c1, conv_call(xin, u.h, u.w, c.R1).range(c.x_rng));
+    if (!rc) rc = c.conv(u.c2, conv_call(c.R1, u.h, u.w, c.R2).grid(u.ho, u.wo, u.pb_h, u.pb_w).range(r1_rng));
+    if (!rc) rc = fuse ? run_conv_fused_shortcut(net, u, c.R2, xin, c.B, u.h, u.w, xout, c.s, r2_rng, c.x_rng) : c.conv(u.c3, c3);
+    c.x_rng = net->amax(u.c3);
+    c.cur ^= 1;
+    return rc;
+}
+
+// One bottleneck unit on H2 / H1 cells.  conv3 runs, in order of preference, inside the unit kernel (conv2 + conv3 + the next unit's
+// conv1), inside the chain (conv3 + the next conv1), as the fused conv3 + shortcut GEMM, or as a plain conv with a residual.  The chain
+// writes the NEXT unit's conv1 output back into Ra; the unit kernel, which still reads Ra's halos while it writes, into Rb -- the two
+// regions then trade places
+int forward_unit_cells(FwdCtx& c, int ui) {
+    dgp_net* net = c.net;
+    const Unit& u = net->units[ui];
+    const float* xin = c.X[c.cur];
+    float* xout = c.X[c.cur ^ 1];
+    const int x_exp = c.x_exp;
+    const bool can_fuse = c.can_fuse(ui);
+    bool fuse = can_fuse && (c.calib || net->unit_fuse_ok[ui]);
+    int rc;
+    if (!c.r1_ready) {
+        rc = c.layer(u.c1, [&] { return c.conv(u.c1, conv_call(xin, u.h, u.w, c.Ra).cells(c.spec(x_exp, u.c1))); });
+        if (rc) return rc;
+    }
+    const bool chain_ok = c.chain_on && (size_t)ui + 1 < net->units.size() && net->chains[ui].ok;
+    // the K-concatenated shortcut needs R2 on X's scale: known from calibration (unit_fuse_ok) before conv2 runs
+    const bool unit_k = chain_ok && c.unit_on && net->chains[ui].unit && (net->chains[ui].res != 0 || fuse);
+    bool share_ok = true;
+    if (!unit_k) {
+        rc = c.layer(u.c2, [&] { return c.conv(u.c2, conv_call(c.Ra, u.h, u.w, c.Rb).grid(u.ho, u.wo, u.pb_h, u.pb_w).cells(c.spec(net->act_exp[u.c1], u.c2))); },
+                     (fuse && c.calib) ? x_exp : dgp_net::H2_NONE, &share_ok);
+        if (rc) return rc;
+    }
+    if (c.calib && can_fuse) { net->unit_fuse_ok[ui] = share_ok ? 1 : 0; fuse = share_ok; }
+    const bool chain = chain_ok && (net->chains[ui].res != 0 || fuse);
+    ConvCall c3 = conv_call(c.Rb, u.ho, u.wo, xout).residual(xin, u.stride, u.h, u.w);
+    int res_exp = x_exp;
+    if (u.sc >= 0 && !fuse) {
+        rc = c.layer(u.sc, [&] { return c.conv(u.sc, conv_call(xin, u.h, u.w, c.SC).grid(u.ho, u.wo).linear().cells(c.spec(x_exp, u.sc))); });
+        if (rc) return rc;
+        c3.residual(c.SC, 1, u.ho, u.wo);
+        res_exp = net->act_exp[u.sc];
+    }
+    if (unit_k) rc = run_chain(net, ui, nullptr, xin, c.B, xout, c.Rb, c.s, x_exp, c.Ra);
+    else if (chain) rc = run_chain(net, ui, c.Rb, xin, c.B, xout, c.Ra, c.s, x_exp);
+    else if (fuse)           // R2 shares X's scale (calibration)
+        rc = c.layer(u.c3, [&] { return run_conv_fused_shortcut(net, u, c.Rb, xin, c.B, u.h, u.w, xout, c.s, nullptr, nullptr, c.spec(x_exp, u.c3)); });
+    else
+        rc = c.layer(u.c3, [&] { return c.conv(u.c3, c3.cells(c.spec(net->act_exp[u.c2], u.c3, true, res_exp))); });
+    if (unit_k) std::swap(c.Ra, c.Rb);
+    c.r1_ready = unit_k || chain;
+    c.x_exp = net->act_exp[u.c3];
+    c.x_rng = net->amax(u.c3);
+    c.cur ^= 1;
+    return rc;
+}
+
+// the block4 features (optional fp32 copy) and the heads
+int forward_heads(const FwdCtx& c, float* scmap, float* locref, float* features) {
+    dgp_net* net = c.net;
+    const int B = c.B, h = net->fh, w = net->fw, nj = net->desc.num_joints;
+    const float* feat = c.X[c.cur];
+    if (features) {
+        if (c.h2) {
+            const hipError_t e = c.tier ? launch_h1_to_f32(feat, (long long)B * h * w * 2048 / 8, ldexpf(1.f, -c.x_exp), features, c.s)
+                                        : launch_h2_to_f32(feat, (long long)B * h * w * 2048 / 8, ldexpf(1.f, -c.x_exp), features, c.s);
+            if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("features: ") + hipGetErrorString(e));
+        } else
+            HIP_TRY(hipMemcpyAsync(features, feat, (size_t)B * h * w * 2048 * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    }
+    H2Spec hs;
+    if (c.h2) { hs.in_fmt = c.FMT; hs.in_exp = c.x_exp; }
+    const bool pw = c.h2 || (c.head_pw && c.f16_mode && net->wmax_valid && c.x_rng && net->layers[net->head_part].d_wh3_pw);
+    auto head = [&](int li, int njt, float* out) {
+        const ConvLayer& l = net->layers[li];
+        if (pw && l.d_wh3_pw) return run_head_pointwise(net, l, feat, B, h, w, njt, out, c.s, c.R1, c.x_rng, hs);
+        ConvCall hc = conv_call(feat, h, w, out).grid(h, w, 1, 1).linear();      // the 2x2-conv form: phase scatter, K split into slabs
+        hc.out_mode = 1; hc.dc_nj = njt; hc.slabs = c.slabs;
+        return c.conv(li, hc);
+    };
+    if (int rc = head(net->head_part, nj, scmap ? scmap : c.scmap_ws)) return rc;
+    return locref ? head(net->head_locref, 2 * nj, locref) : (int)DGP_OK;
+}
+
+// what a calibrated net's per-forward range check reads: the scale exponent of every cell tensor, per layer
+int upload_scales(dgp_net* net, hipStream_t s) {
+    std::vector<int> ex(net->layers.size(), dgp_net::H2_NONE);
+    ex[net->conv1] = net->act_exp[net->conv1];
+    for (const Unit& u : net->units) {
+        ex[u.c1] = net->act_exp[u.c1]; ex[u.c2] = net->act_exp[u.c2]; ex[u.c3] = net->act_exp[u.c3];
+        if (u.sc >= 0) ex[u.sc] = net->act_exp[u.sc];       // (an unlaunched shortcut conv tracks 0: never flagged)
+    }
+    HIP_TRY(hipStreamSynchronize(s));                        // (a forward still in flight reads the old exponents)
+    HIP_TRY(hipMemcpy(net->d_exps, ex.data(), ex.size() * sizeof(int), hipMemcpyHostToDevice));
+    net->h2_calibrated = true; ++net->h2_calibrations;
+    return DGP_OK;
+}
+
+// end of a pass on cells: a calibration pass freezes its scales (the device copy feeds the range check); every pass checks its ranges
+int freeze_scales(const FwdCtx& c) {
+    if (!c.h2) return DGP_OK;
+    if (c.calib) if (int rc = upload_scales(c.net, c.s)) return rc;
+    const hipError_t e = launch_h2_range_check(c.net->d_amax, c.net->d_exps, (int)c.net->layers.size(), c.net->d_flag, c.s);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("range check: ") + hipGetErrorString(e));
+    return DGP_OK;
+}
+
+// fp32 NHWC <-> H2 / H1 cells at the boundary: n_floats / 8 groups of 8 channels, scale = the power of two the launcher wants
+template <class X, class Y>
+int convert_cells(const std::string& who, hipError_t (*launch)(X, long long, float, Y, hipStream_t), X x, size_t n_floats, float scale, Y out, void* stream) {
+    if (!x || !out || (n_floats & 7)) return fail(DGP_ERR_INVALID, who + ": null argument / length not a multiple of 8");
+    const hipError_t e = launch(x, (long long)(n_floats / 8), scale, out, (hipStream_t)stream);
+    return e == hipSuccess ? (int)DGP_OK : fail(DGP_ERR_HIP, who + ": " + hipGetErrorString(e));
 }
 
 }  // namespace
@@ -799,18 +1097,15 @@ int dgp_net_stats(const dgp_net* net, int32_t batch, int32_t* n_launches, double
     if (!net) return fail(DGP_ERR_INVALID, "dgp_net_stats: null net");
     double macs = (double)net->h1 * net->w1 * 49 * 3 * 64;
     int launches = 3;   // preprocess, conv1, pool
-    int h = net->hp, w = net->wp;
     for (const Unit& u : net->units) {
-        const int ho = (h + u.stride - 1) / u.stride, wo = (w + u.stride - 1) / u.stride;
-        if (u.sc >= 0) { macs += (double)ho * wo * u.depth_in * u.depth; ++launches; }
-        macs += (double)h * w * u.depth_in * u.depth_bn;
-        macs += (double)ho * wo * 9 * u.depth_bn * u.depth_bn;
-        macs += (double)ho * wo * u.depth_bn * u.depth;
+        if (u.sc >= 0) { macs += (double)u.ho * u.wo * u.depth_in * u.depth; ++launches; }
+        macs += (double)u.h * u.w * u.depth_in * u.depth_bn;
+        macs += (double)u.ho * u.wo * 9 * u.depth_bn * u.depth_bn;
+        macs += (double)u.ho * u.wo * u.depth_bn * u.depth;
         launches += 3;
-        h = ho; w = wo;
     }
     const int heads = net->desc.num_joints * (net->desc.with_locref ? 3 : 1);
-    macs += (double)h * w * 9 * 2048 * heads;
+    macs += (double)net->fh * net->fw * 9 * 2048 * heads;
     launches += net->desc.with_locref ? 2 : 1;
     if (n_launches) *n_launches = launches;
     if (conv_flops) *conv_flops = 2.0 * macs * batch;
@@ -828,253 +1123,21 @@ int dgp_forward(dgp_net* net, const uint8_t* frames, int32_t batch, void* worksp
     if (net->owner_sync) { const int rco = net->owner_sync(net->owner, stream); if (rco) return rco; }
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    float* P0 = (float*)(ws + pl.off_p0);
-    float* C1 = (float*)(ws + pl.off_c1);
-    float* X[2] = {(float*)(ws + pl.off_x0), (float*)(ws + pl.off_x1)};
-    float* SC = (float*)(ws + pl.off_sc);
-    float* R1 = (float*)(ws + pl.off_r1);
-    float* R2 = (float*)(ws + pl.off_r2);
-    const dgp_net_desc& d = net->desc;
-    const int B = batch;
-    int rc;
-
-    net->prof_cursor = 0;
-    net->tail_slab = (float*)(ws + pl.off_tail); net->tail_slab_bytes = (unsigned)(TAIL_SLAB_FLOATS * sizeof(float));
-    hipError_t e;
-    if (net->d_amax) HIP_TRY(hipMemsetAsync(net->d_amax, 0, net->layers.size() * ABSMAX_SLOTS * sizeof(float), s));   // ranges are per forward
-    // ---- activation format of this forward.  H2 (default): every tensor from the pool output to the block4 features lives in HBM as
-    // fp16 high / low cells with a calibrated per-tensor scale, so the conv kernels' K loops are ds_read + MFMA only (DGP_H2=0: fp32
-    // activations, split in the consumers' K loops -- also what the other DGP_CONV_MODEs and a trainer-owned net use).
-    static const bool h2_env = (dgp_env("DGP_H2", 1) != 0);
-    static const bool f16_mode = !getenv("DGP_CONV_MODE") || !strcmp(getenv("DGP_CONV_MODE"), "f16x3") || tier16_env();
-    const int tier = net->tier, FMT = tier ? 2 : 1;      // activation cells of this forward: H2 (parity tier) or H1 (16-bit tier)
-    static const bool head_pw = (dgp_tune("DGP_HEAD_PW", 1) != 0);      // A/B switch
-    static const bool fuse_env = (dgp_env("DGP_FUSE_SHORTCUT", 1) != 0);      // A/B switch
-    static const bool f32_mode = getenv("DGP_CONV_MODE") && !strcmp(getenv("DGP_CONV_MODE"), "f32");
-    static const bool cells_env = (dgp_tune("DGP_PRESPLIT_WEIGHTS", 1) != 0);
-    const bool h2 = h2_env && cells_env && f16_mode && head_pw && net->wmax_valid && net->d_exps && net->layers[net->head_part].d_wh3_pw &&
-                    (net->head_locref < 0 || net->layers[net->head_locref].d_wh3_pw) && net->act_exp.size() == net->layers.size();
-    if (tier) {            // the 16-bit tier has no fallback: say what is missing instead of silently running another tier
-        bool ok = h2 && net->layers[net->head_part].d_wh1_pw && (net->head_locref < 0 || net->layers[net->head_locref].d_wh1_pw);
-        for (const Unit& u : net->units) {
-            ok = ok && net->layers[u.c1].d_wh1 && net->layers[u.c2].d_wh1 && net->layers[u.c3].d_wh1 && (u.sc < 0 || net->layers[u.sc].d_wh1);
-            if (u.sc >= 0 && net->layers[u.c3].d_w_fused && !net->layers[u.c3].d_wh1_fused) ok = false;
-        }
-        if (!ok) return fail(DGP_ERR_STATE, "dgp_forward: the 16-bit tier needs the H2 engine's switches at their defaults (DGP_H2, DGP_PRESPLIT_WEIGHTS, "
-                                            "DGP_HEAD_PW, DGP_CONV_MODE unset or f16) and weights loaded by dgp_net_load_weights");
-    }
-    const bool calib = h2 && !net->h2_calibrated;
-    const int H2_HEAD = net->h2_head;             // bits of headroom between a calibrated maximum and the fp16 limit
-    auto exp_for = [H2_HEAD](float mx) {          // scale exponent that puts mx into [2^(14 - H2_HEAD), 2^(15 - H2_HEAD))
-        if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
-        int ex; (void)frexpf(mx, &ex);            // mx = f 2^ex, f in [0.5, 1)
-        return (14 - H2_HEAD) - (ex - 1);
-    };
-    auto read_range = [&](int li, float* mx) -> int {
-        float host[ABSMAX_SLOTS];
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(host, net->amax(li), sizeof host, hipMemcpyDeviceToHost));
-        float m = 0.f;
-        for (float v : host) m = (v > m || v != v) ? v : m;
-        *mx = m;
-        return DGP_OK;
-    };
-    // calibration: launch, read the layer's range, fix the exponent, launch again if it changed (first forward only: hidden syncs)
-    auto layer = [&](int li, auto&& launch, int forced_exp = dgp_net::H2_NONE, bool* forced_ok = nullptr) -> int {
-        int r = launch();
-        if (r || !calib) return r;
-        float mx = 0.f;
-        if ((r = read_range(li, &mx))) return r;
-        int e = exp_for(mx);
-        if (forced_exp != dgp_net::H2_NONE) {     // must share another tensor's scale (K-concatenated second source)
-            const bool ok = forced_exp <= e + H2_HEAD - 1 && forced_exp >= e - 6;
-            if (forced_ok) *forced_ok = ok;
-            if (ok) e = forced_exp;
-        }
-        if (e != net->act_exp[li]) {
-            net->act_exp[li] = e;
-            HIP_TRY(hipMemsetAsync(net->amax(li), 0, ABSMAX_SLOTS * sizeof(float), s));
-            r = launch();
-        }
-        return r;
-    };
-    // ---- root block.  H2 engine: ONE kernel from the uint8 frame to the pool output's cells (stem_pool_fused_kernel);
-    // otherwise preprocess -> conv1 -> max-pool as three launches
-    static const bool stem_fused_env = (dgp_tune("DGP_STEM_FUSED", 1) != 0);
-    const ConvLayer& lstem = net->layers[net->conv1];
-    const bool stem_fused = h2 && (stem_fused_env || tier) && lstem.d_wh3 && lstem.d_w_rows && lstem.CoutP == 64 && lstem.d_scale && lstem.d_bias;
-    if (tier && !stem_fused) return fail(DGP_ERR_STATE, "dgp_forward: the 16-bit tier needs the fused root block");
-    if (stem_fused) {
-        rc = layer(net->conv1, [&] {
-            ProfScope ps(net, s, "conv:" + lstem.scope + "+pool|stem_pool_fused", conv_flops_of(lstem, B * net->h1 * net->w1, false));
-            hipError_t e2 = launch_stem_pool_fused(frames, B, d.in_h, d.in_w, lstem.d_wh3, net->wmax(net->conv1), lstem.d_scale, lstem.d_bias,
-                                                   d.mean_pixel[0], d.mean_pixel[1], d.mean_pixel[2],
-                                                   ldexpf(1.f, net->act_exp[net->conv1]), X[0], net->amax(net->conv1), s, tier ? 1 : 0);
-            return e2 == hipSuccess ? (int)DGP_OK : fail(DGP_ERR_HIP, std::string("stem + pool: ") + hipGetErrorString(e2));
-        });
+    // a net without calibrated scales runs two passes: the calibration pass (layer by layer, with hidden syncs), then the chained pass
+    // that every later forward is
+    for (bool again = true; again;) {
+        net->prof_cursor = 0;
+        net->tail_slab = (float*)(ws + pl.off_tail); net->tail_slab_bytes = (unsigned)(TAIL_SLAB_FLOATS * sizeof(float));
+        if (net->d_amax) HIP_TRY(hipMemsetAsync(net->d_amax, 0, net->layers.size() * ABSMAX_SLOTS * sizeof(float), s));   // ranges are per forward
+        FwdCtx c;
+        int rc = fwd_context(c, net, frames, batch, ws, pl, s);
+        if (!rc) rc = forward_root(c);
+        for (int ui = 0; !rc && ui < (int)net->units.size(); ++ui) rc = c.h2 ? forward_unit_cells(c, ui) : forward_unit_f32(c, ui);
+        if (!rc) rc = forward_heads(c, scmap, locref, features);
+        if (!rc) rc = freeze_scales(c);
         if (rc) return rc;
-    } else {
-        {
-            ProfScope ps(net, s, "preprocess_u8", 0.0);
-            e = launch_preprocess(frames, (long long)B * d.in_h * d.in_w, d.mean_pixel[0], d.mean_pixel[1],
-                                  d.mean_pixel[2], P0, s);
-        }
-        if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("preprocess: ") + hipGetErrorString(e));
-        // conv1: conv2d_same(7, stride 2): explicit pad 3 before
-        rc = run_conv(net, net->layers[net->conv1], P0, B, d.in_h, d.in_w, 3, 3, net->h1, net->w1, nullptr, 0, 0, 0, true, 0,
-                      0, C1, s, nullptr, net->d_inmax);
-        if (rc) return rc;
-        if (calib) {
-            float mx = 0.f;
-            if ((rc = read_range(net->conv1, &mx))) return rc;
-            net->act_exp[net->conv1] = exp_for(mx);   // (max-pooling cannot raise the maximum of conv1's output)
-        }
-        {
-            ProfScope ps(net, s, "maxpool3x3s2", 0.0);
-            e = launch_maxpool(C1, B, net->h1, net->w1, 64, X[0], s, h2 ? ldexpf(1.f, net->act_exp[net->conv1]) : 0.f);
-        }
-        if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("maxpool: ") + hipGetErrorString(e));
-
+        again = c.calib && c.chain_tier;
     }
-    const int pool_exp = h2 ? net->act_exp[net->conv1] : 0;
-    // conv3(k) + conv1(k + 1) as one launch (DGP_CHAIN=0: layer by layer).  Calibration runs layer by layer (it needs every tensor's
-    // range before the next layer runs) and is followed by a second, chained pass, so results never depend on which pass produced them
-    static const bool chain_env = (dgp_env("DGP_CHAIN", 1) != 0);
-    static const bool chain_h1_env = (dgp_env("DGP_CHAIN_H1", 1) != 0);      // the chain / unit kernels on H1 tensors (the 16-bit tier)
-    const bool chain_tier = chain_env && (!tier || chain_h1_env);
-    const bool chain_on = h2 && !calib && chain_tier && net->chains.size() == net->units.size();
-    static const bool unit_env = (dgp_tune("DGP_UNIT", 1) != 0);      // conv2 inside the chain launch (block1)
-    bool r1_ready = false;                            // R1 of this unit came out of the previous unit's chain launch
-    float *Ra = R1, *Rb = R2;
-    int cur = 0, h = net->hp, w = net->wp;
-    const float* x_rng = net->amax(net->conv1);      // max-pooling cannot raise the maximum of conv1's output
-    int x_exp = pool_exp;
-    int ui = 0;
-    for (const Unit& u : net->units) {
-        const int ho = (h + u.stride - 1) / u.stride, wo = (w + u.stride - 1) / u.stride;
-        const float* xin = X[cur];
-        float* xout = X[cur ^ 1];
-        const float* res = xin;
-        int res_s = u.stride, res_H = h, res_W = w;
-        int res_exp = x_exp;
-        const bool can_fuse = fuse_env && !f32_mode && net->wmax_valid && u.sc >= 0 && net->layers[u.c3].d_w_fused && u.stride == 1 && ho == h && wo == w &&
-                              net->layers[u.c3].CoutP % 64 == 0;
-        bool fuse = can_fuse && (!h2 || calib || net->unit_fuse_ok[ui]);
-        const int pb_h = pad_before_for(h, 3, u.stride, u.rate, true);
-        const int pb_w = pad_before_for(w, 3, u.stride, u.rate, true);
-        if (!h2) {
-            if (u.sc >= 0 && !fuse) {
-                // slim.conv2d(1x1, stride, SAME): pad 0, samples x[::s, ::s]
-                rc = run_conv(net, net->layers[u.sc], xin, B, h, w, 0, 0, ho, wo, nullptr, 0, 0, 0, false, 0, 0, SC, s, nullptr, x_rng);
-                if (rc) return rc;
-                res = SC; res_s = 1; res_H = ho; res_W = wo;
-            }
-            rc = run_conv(net, net->layers[u.c1], xin, B, h, w, 0, 0, h, w, nullptr, 0, 0, 0, true, 0, 0, R1, s, nullptr, x_rng);
-            if (rc) return rc;
-            rc = run_conv(net, net->layers[u.c2], R1, B, h, w, pb_h, pb_w, ho, wo, nullptr, 0, 0, 0, true, 0, 0, R2, s, nullptr,
-                          net->amax(u.c1));
-            if (rc) return rc;
-            if (fuse)
-                rc = run_conv_fused_shortcut(net, u, R2, xin, B, h, w, xout, s, net->amax(u.c2), x_rng);
-            else
-                rc = run_conv(net, net->layers[u.c3], R2, B, ho, wo, 0, 0, ho, wo, res, res_s, res_H, res_W, true, 0, 0, xout, s,
-                              nullptr, net->amax(u.c2));
-            if (rc) return rc;
-        } else {
-            auto spec = [&](int in_exp, int out_li, int r_fmt = 0, int r_exp = 0) {
-                H2Spec q; q.in_fmt = FMT; q.in_exp = in_exp; q.out_fmt = FMT; q.out_exp = net->act_exp[out_li]; q.res_fmt = r_fmt ? FMT : 0; q.res_exp = r_exp;
-                return q;
-            };
-            // Ra: this unit's conv1 output; Rb: its conv2 output (the chain writes the NEXT unit's conv1 output back into Ra; the unit
-            // kernel, which still reads Ra's halos while it writes, into Rb -- the two regions then trade places)
-            if (!r1_ready) {
-                rc = layer(u.c1, [&] { return run_conv(net, net->layers[u.c1], xin, B, h, w, 0, 0, h, w, nullptr, 0, 0, 0, true, 0, 0, Ra, s,
-                                                       nullptr, nullptr, spec(x_exp, u.c1)); });
-                if (rc) return rc;
-            }
-            r1_ready = false;
-            const bool chain_ok = chain_on && (size_t)ui + 1 < net->units.size() && net->chains[ui].ok;
-            // the K-concatenated shortcut needs R2 on X's scale: known from calibration (unit_fuse_ok) before conv2 runs
-            const bool unit_k = chain_ok && unit_env && net->chains[ui].unit && (net->chains[ui].res != 0 || fuse);
-            bool share_ok = true;
-            if (!unit_k) {
-                rc = layer(u.c2, [&] { return run_conv(net, net->layers[u.c2], Ra, B, h, w, pb_h, pb_w, ho, wo, nullptr, 0, 0, 0, true, 0, 0, Rb, s,
-                                                       nullptr, nullptr, spec(net->act_exp[u.c1], u.c2)); },
-                           (fuse && calib) ? x_exp : dgp_net::H2_NONE, &share_ok);
-                if (rc) return rc;
-            }
-            if (calib && can_fuse) { net->unit_fuse_ok[ui] = share_ok ? 1 : 0; fuse = share_ok; }
-            const bool chain = chain_ok && (net->chains[ui].res != 0 || fuse);
-            if (u.sc >= 0 && !fuse) {
-                rc = layer(u.sc, [&] { return run_conv(net, net->layers[u.sc], xin, B, h, w, 0, 0, ho, wo, nullptr, 0, 0, 0, false, 0, 0, SC, s,
-                                                       nullptr, nullptr, spec(x_exp, u.sc)); });
-                if (rc) return rc;
-                res = SC; res_s = 1; res_H = ho; res_W = wo; res_exp = net->act_exp[u.sc];
-            }
-            if (unit_k) {
-                rc = run_chain(net, ui, nullptr, xin, B, ho, wo, h, w, xout, Rb, s, x_exp, Ra);
-                std::swap(Ra, Rb);
-                r1_ready = true;
-            } else if (chain) {
-                rc = run_chain(net, ui, Rb, xin, B, ho, wo, h, w, xout, Ra, s, x_exp);
-                r1_ready = true;
-            } else if (fuse)
-                rc = layer(u.c3, [&] { return run_conv_fused_shortcut(net, u, Rb, xin, B, h, w, xout, s, nullptr, nullptr,
-                                                                      spec(x_exp, u.c3)); });      // R2 shares X's scale (calibration)
-            else
-                rc = layer(u.c3, [&] { return run_conv(net, net->layers[u.c3], Rb, B, ho, wo, 0, 0, ho, wo, res, res_s, res_H, res_W, true, 0,
-                                                       0, xout, s, nullptr, nullptr, spec(net->act_exp[u.c2], u.c3, 1, res_exp)); });
-            if (rc) return rc;
-            x_exp = net->act_exp[u.c3];
-        }
-        x_rng = net->amax(u.c3);
-        cur ^= 1; h = ho; w = wo;
-        ++ui;
-    }
-    const float* feat = X[cur];
-    if (features) {
-        if (h2) {
-            e = tier ? launch_h1_to_f32(feat, (long long)B * h * w * 2048 / 8, ldexpf(1.f, -x_exp), features, s)
-                     : launch_h2_to_f32(feat, (long long)B * h * w * 2048 / 8, ldexpf(1.f, -x_exp), features, s);
-            if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("features: ") + hipGetErrorString(e));
-        } else
-            HIP_TRY(hipMemcpyAsync(features, feat, (size_t)B * h * w * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    float* sm = scmap ? scmap : (float*)(ws + pl.off_scmap);
-    float* slabs = (float*)(ws + pl.off_slabs);
-    H2Spec hs;
-    if (h2) { hs.in_fmt = FMT; hs.in_exp = x_exp; }
-    const bool pw = h2 || (head_pw && f16_mode && net->wmax_valid && x_rng && net->layers[net->head_part].d_wh3_pw);
-    if (pw) rc = run_head_pointwise(net, net->layers[net->head_part], feat, B, h, w, d.num_joints, sm, s, R1, x_rng, hs);
-    else rc = run_conv(net, net->layers[net->head_part], feat, B, h, w, 1, 1, h, w, nullptr, 0, 0, 0, false, 1, d.num_joints,
-                       sm, s, slabs);
-    if (rc) return rc;
-    if (locref) {
-        if (pw && net->layers[net->head_locref].d_wh3_pw)
-            rc = run_head_pointwise(net, net->layers[net->head_locref], feat, B, h, w, 2 * d.num_joints, locref, s, R1, x_rng, hs);
-        else rc = run_conv(net, net->layers[net->head_locref], feat, B, h, w, 1, 1, h, w, nullptr, 0, 0, 0, false, 1,
-                           2 * d.num_joints, locref, s, slabs);
-        if (rc) return rc;
-    }
-    if (h2) {
-        if (calib) {                      // freeze the scales: the device copy feeds the per-forward range check
-            std::vector<int> ex(net->layers.size(), dgp_net::H2_NONE);
-            ex[net->conv1] = net->act_exp[net->conv1];
-            int k = 0;
-            for (const Unit& u : net->units) {
-                ex[u.c1] = net->act_exp[u.c1]; ex[u.c2] = net->act_exp[u.c2]; ex[u.c3] = net->act_exp[u.c3];
-                if (u.sc >= 0) ex[u.sc] = net->act_exp[u.sc];       // (an unlaunched shortcut conv tracks 0: never flagged)
-                ++k;
-            }
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipMemcpy(net->d_exps, ex.data(), ex.size() * sizeof(int), hipMemcpyHostToDevice));
-            net->h2_calibrated = true;
-            ++net->h2_calibrations;
-        }
-        e = launch_h2_range_check(net->d_amax, net->d_exps, (int)net->layers.size(), net->d_flag, s);
-        if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("range check: ") + hipGetErrorString(e));
-    }
-    if (calib && chain_tier) return dgp_forward(net, frames, batch, workspace, workspace_bytes, scmap, locref, features, stream);   // the chained pass
     if (net->prof_on && net->prof_used < net->prof_slots && !net->prof_in_infer) ++net->prof_used;
     return DGP_OK;
 }
@@ -1310,22 +1373,10 @@ int dgp_conv2d_ranged(const dgp_conv_desc* d, const float* x, const float* packe
     if (d->Cin < 4 || (d->Cin & 3) || ((d->Cin / 4) & (d->Cin / 4 - 1)))
         return fail(DGP_ERR_INVALID, "dgp_conv2d: Cin must be 4 * 2^k");
     if (d->res_stride > 0 && !residual) return fail(DGP_ERR_INVALID, "dgp_conv2d: residual missing");
-    ConvArgs a{};
-    a.in = x; a.wpk = packed_w; a.scale = scale; a.bias = bias; a.res = d->res_stride > 0 ? residual : nullptr;
-    a.out = y; a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.log2cin4 = ilog2(d->Cin / 4);
-    a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.CoutP = coutp_for(d->Cout);
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.dil = d->rate; a.pad_t = d->pad_t; a.pad_l = d->pad_l;
-    a.ntaps = d->KH * d->KW; a.nk = nk_for(d->KH, d->KW, d->Cin); a.M = d->N * d->Ho * d->Wo;
-    a.res_s = d->res_stride; a.res_H = d->res_H; a.res_W = d->res_W; a.relu = d->relu; a.out_mode = 0; a.dc_nj = 0;
     if (d->Cout & 3) return fail(DGP_ERR_INVALID, "dgp_conv2d: Cout must be a multiple of 4");
-    {
-        const double lim = 4294967000.0;
-        const double inb = (double)d->N * d->H * d->W * d->Cin * 4, outb = (double)a.M * d->Cout * 4;
-        const double resb = a.res ? (double)d->N * d->res_H * d->res_W * d->Cout * 4 : 0.0;
-        if (inb > lim || outb > lim || resb > lim) return fail(DGP_ERR_INVALID, "dgp_conv2d: tensor exceeds 4 GiB");
-        a.in_bytes = (unsigned)inb; a.out_bytes = (unsigned)outb; a.res_bytes = (unsigned)resb;
-        a.w_bytes = (unsigned)((size_t)a.nk * 8 * a.CoutP * 16);
-    }
+    ConvArgs a{};
+    a.in = x; a.wpk = packed_w; a.scale = scale; a.bias = bias; a.res = d->res_stride > 0 ? residual : nullptr; a.out = y;
+    if (int rc = fill_conv_geometry(a, *d, "dgp_conv2d: tensor exceeds 4 GiB")) return rc;
     a.in_absmax = x_absmax; a.w_absmax = w_absmax; a.out_absmax = y_absmax;
     // DGP_CONV2D_CELLS=1 (tests, tuning): split the panel into fp16 cells per call (grow-only scratch, stream-ordered) so that a single
     // layer runs on the engine's compute-side-split / LDS-DMA kernels; the network packs its cells once at load instead
@@ -1350,36 +1401,42 @@ int dgp_conv2d_ranged(const dgp_conv_desc* d, const float* x, const float* packe
 /* ---- H2 activation format at the boundary (tests, PoseNet.extract_features): converters, a single conv layer on H2 tensors, and
  * the engine's range status.  See ConvArgs::in_fmt (csrc/dgp_internal.h) and EXPERIMENTS.md section 3. */
 int dgp_f32_to_h2(const float* x, size_t n_floats, int32_t scale_exp, void* out, void* stream) {
-    if (!x || !out || (n_floats & 7)) return fail(DGP_ERR_INVALID, "dgp_f32_to_h2: null argument / length not a multiple of 8");
-    hipError_t e = launch_f32_to_h2(x, (long long)(n_floats / 8), ldexpf(1.f, scale_exp), out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_f32_to_h2: ") + hipGetErrorString(e));
-    return DGP_OK;
+    return convert_cells("dgp_f32_to_h2", launch_f32_to_h2, x, n_floats, ldexpf(1.f, scale_exp), out, stream);
 }
-
 int dgp_h2_to_f32(const void* x, size_t n_floats, int32_t scale_exp, float* out, void* stream) {
-    if (!x || !out || (n_floats & 7)) return fail(DGP_ERR_INVALID, "dgp_h2_to_f32: null argument / length not a multiple of 8");
-    hipError_t e = launch_h2_to_f32(x, (long long)(n_floats / 8), ldexpf(1.f, -scale_exp), out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_h2_to_f32: ") + hipGetErrorString(e));
-    return DGP_OK;
+    return convert_cells("dgp_h2_to_f32", launch_h2_to_f32, x, n_floats, ldexpf(1.f, -scale_exp), out, stream);
 }
-
 int dgp_f32_to_h1(const float* x, size_t n_floats, int32_t scale_exp, void* out, void* stream) {
-    if (!x || !out || (n_floats & 7)) return fail(DGP_ERR_INVALID, "dgp_f32_to_h1: null argument / length not a multiple of 8");
-    hipError_t e = launch_f32_to_h1(x, (long long)(n_floats / 8), ldexpf(1.f, scale_exp), out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_f32_to_h1: ") + hipGetErrorString(e));
-    return DGP_OK;
+    return convert_cells("dgp_f32_to_h1", launch_f32_to_h1, x, n_floats, ldexpf(1.f, scale_exp), out, stream);
 }
-
 int dgp_h1_to_f32(const void* x, size_t n_floats, int32_t scale_exp, float* out, void* stream) {
-    if (!x || !out || (n_floats & 7)) return fail(DGP_ERR_INVALID, "dgp_h1_to_f32: null argument / length not a multiple of 8");
-    hipError_t e = launch_h1_to_f32(x, (long long)(n_floats / 8), ldexpf(1.f, -scale_exp), out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_h1_to_f32: ") + hipGetErrorString(e));
-    return DGP_OK;
+    return convert_cells("dgp_h1_to_f32", launch_h1_to_f32, x, n_floats, ldexpf(1.f, -scale_exp), out, stream);
 }
 
 static int conv2d_cells(int fmt, const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
                         const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
-                        int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, void* stream);
+                        int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, void* stream) {
+    if (!d || !x_h2 || !packed_w || !w_absmax || !y || !cells_scratch) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: null argument");
+    if (d->Cin < 32 || (d->Cin & 7) || ((d->Cin / 4) & (d->Cin / 4 - 1)) || (d->Cout & 7))
+        return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: Cin must be 4 * 2^k >= 32, Cout a multiple of 8");
+    if (d->res_stride > 0 && !residual) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: residual missing");
+    if (d->res_stride > 0 && res_is_h2 && !y_is_h2)
+        return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: an H2 residual needs an H2 output (the fp32-output epilogue adds fp32 residuals only)");
+    ConvArgs a{};
+    a.in = (const float*)x_h2; a.wpk = packed_w; a.scale = scale; a.bias = bias; a.res = d->res_stride > 0 ? (const float*)residual : nullptr;
+    a.out = (float*)y;
+    if (int rc = fill_conv_geometry(a, *d, "dgp_conv2d_h2: tensor exceeds 4 GiB")) return rc;
+    H2Spec h; h.in_fmt = fmt; h.in_exp = x_exp; h.out_fmt = y_is_h2 ? fmt : 0; h.out_exp = y_exp; h.res_fmt = (a.res && res_is_h2) ? fmt : 0; h.res_exp = res_exp;
+    apply_h2(a, h);
+    a.w_absmax = w_absmax; a.out_absmax = y_absmax;
+    hipError_t pe = fmt == 2 ? launch_pack_h1(packed_w, a.nk, a.CoutP, w_absmax, cells_scratch, (hipStream_t)stream)
+                             : launch_pack_h3(packed_w, a.nk, a.CoutP, w_absmax, cells_scratch, (hipStream_t)stream);
+    if (pe != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_h2: pack cells: ") + hipGetErrorString(pe));
+    a.wh3 = cells_scratch; a.wh3_bytes = a.w_bytes;
+    hipError_t e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_h2: ") + hipGetErrorString(e));
+    return DGP_OK;
+}
 
 int dgp_conv2d_h2(const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
                   const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
@@ -1396,128 +1453,58 @@ int dgp_conv2d_h1(const dgp_conv_desc* d, const void* x_h1, int32_t x_exp, const
                         cells_scratch, stream);
 }
 
-static int conv2d_cells(int fmt, const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
-                        const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
-                        int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, void* stream) {
-    if (!d || !x_h2 || !packed_w || !w_absmax || !y || !cells_scratch) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: null argument");
-    if (d->Cin < 32 || (d->Cin & 7) || ((d->Cin / 4) & (d->Cin / 4 - 1)) || (d->Cout & 7))
-        return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: Cin must be 4 * 2^k >= 32, Cout a multiple of 8");
-    if (d->res_stride > 0 && !residual) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: residual missing");
-    if (d->res_stride > 0 && res_is_h2 && !y_is_h2)
-        return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: an H2 residual needs an H2 output (the fp32-output epilogue adds fp32 residuals only)");
-    ConvArgs a{};
-    a.in = (const float*)x_h2; a.wpk = packed_w; a.scale = scale; a.bias = bias; a.res = d->res_stride > 0 ? (const float*)residual : nullptr;
-    a.out = (float*)y; a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.log2cin4 = ilog2(d->Cin / 4);
-    a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.CoutP = coutp_for(d->Cout);
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.dil = d->rate; a.pad_t = d->pad_t; a.pad_l = d->pad_l;
-    a.ntaps = d->KH * d->KW; a.nk = nk_for(d->KH, d->KW, d->Cin); a.M = d->N * d->Ho * d->Wo;
-    a.res_s = d->res_stride; a.res_H = d->res_H; a.res_W = d->res_W; a.relu = d->relu;
-    const double lim = 4294967000.0;
-    const double inb = (double)d->N * d->H * d->W * d->Cin * 4, outb = (double)a.M * d->Cout * 4;
-    const double resb = a.res ? (double)d->N * d->res_H * d->res_W * d->Cout * 4 : 0.0;
-    if (inb > lim || outb > lim || resb > lim) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: tensor exceeds 4 GiB");
-    a.in_bytes = (unsigned)inb; a.out_bytes = (unsigned)outb; a.res_bytes = (unsigned)resb;
-    a.w_bytes = (unsigned)((size_t)a.nk * 8 * a.CoutP * 16);
-    H2Spec h; h.in_fmt = fmt; h.in_exp = x_exp; h.out_fmt = y_is_h2 ? fmt : 0; h.out_exp = y_exp; h.res_fmt = (a.res && res_is_h2) ? fmt : 0; h.res_exp = res_exp;
-    apply_h2(a, h);
-    a.w_absmax = w_absmax; a.out_absmax = y_absmax;
-    hipError_t pe = fmt == 2 ? launch_pack_h1(packed_w, a.nk, a.CoutP, w_absmax, cells_scratch, (hipStream_t)stream)
-                             : launch_pack_h3(packed_w, a.nk, a.CoutP, w_absmax, cells_scratch, (hipStream_t)stream);
-    if (pe != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_h2: pack cells: ") + hipGetErrorString(pe));
-    a.wh3 = cells_scratch; a.wh3_bytes = a.w_bytes;
-    hipError_t e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_h2: ") + hipGetErrorString(e));
-    return DGP_OK;
+// The chain / unit kernels at layer level (tests): weights and BN affines are HOST arrays, packed per call.  w2 != null: the unit kernel
+struct LayerWeights { const float *w2, *scale2, *bias2, *w3cat, *scale3, *bias3, *w1, *scale1, *bias1; };
+static int launch_layer(const std::string& who, const ChainIo& io, int C, int C1, int CIN2, int res_mode, const LayerWeights& w, hipStream_t s) {
+    const bool unit = w.w2 != nullptr;
+    if (!(unit ? io.r1in : io.r2) || !io.src2 || !w.w3cat || !w.w1 || !io.xout || !io.r1out) return fail(DGP_ERR_INVALID, who + ": null argument");
+    if (!(unit ? unit_supported(C, C1, CIN2, res_mode) : chain_supported(C, C1, CIN2, res_mode)))
+        return fail(DGP_ERR_INVALID, who + ": no kernel instance for this (C, C1, CIN2, res_mode)");
+    if (res_mode == 0 && io.src2_exp != io.r2_exp) return fail(DGP_ERR_INVALID, who + ": the K-concatenated source must share R2's scale");
+    if (unit && io.r1in == io.r1out) return fail(DGP_ERR_INVALID, who + ": r1out must not alias r1 (halo reads)");
+    ChainPlan cp;
+    int rc = build_chain_plan(cp, C, C1, CIN2, res_mode, w.w3cat, w.scale3, w.bias3, w.w1, w.scale1, w.bias1, w.w2, w.scale2, w.bias2);
+    if (rc) return rc;
+    ChainArgs a{};
+    rc = fill_chain_args(a, cp, io);
+    hipError_t e = hipSuccess;
+    if (!rc) e = unit ? launch_unit(a, io.N, C, C1, CIN2, res_mode, s) : launch_chain(a, C, C1, CIN2, res_mode, s);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);       // (the fragments are freed below)
+    free_chain_plan(cp);
+    return e != hipSuccess ? fail(DGP_ERR_HIP, who + ": " + hipGetErrorString(e)) : rc;
 }
 
 /* conv3 (+ shortcut, ReLU) of a bottleneck unit and conv1 of the next unit as ONE launch on H2 tensors (the engine's chain kernel,
- * csrc/dgp_chain.hip) -- layer-level entry for tests: weights and BN affines are HOST arrays, packed per call. */
-static int chain_layer(bool h1, int32_t N, int32_t Ho, int32_t Wo, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode, int32_t res_H, int32_t res_W,
-                 const void* r2_h2, int32_t r2_exp, const void* src2_h2, int32_t src2_exp,
-                 const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
-                 void* xout_h2, int32_t xout_exp, void* r1_h2, int32_t r1_exp, float* xout_absmax, float* r1_absmax, void* stream) {
-    const size_t EB = h1 ? 2 : 4;                  // bytes per channel: H1 cells / H2 cell pairs
-    if (!r2_h2 || !src2_h2 || !w3cat || !w1 || !xout_h2 || !r1_h2) return fail(DGP_ERR_INVALID, h1 ? "dgp_chain_h1: null argument" : "dgp_chain_h2: null argument");
-    if (!chain_supported(C, C1, CIN2, res_mode))
-        return fail(DGP_ERR_INVALID, "dgp_chain_h2 / _h1: no kernel instance for this (C, C1, CIN2, res_mode)");
-    if (res_mode == 0 && src2_exp != r2_exp) return fail(DGP_ERR_INVALID, "dgp_chain_h2 / _h1: the K-concatenated source must share R2's scale");
-    ChainPlan cp;
-    int rc = build_chain_plan(cp, C, C1, CIN2, res_mode, w3cat, scale3, bias3, w1, scale1, bias1);
-    if (rc) return rc;
-    ChainArgs a{};
-    a.h1 = h1 ? 1 : 0;
-    a.r2 = r2_h2; a.src2 = src2_h2; a.xout = xout_h2; a.r1out = r1_h2; a.wfrag = h1 ? cp.d_frags_h1 : cp.d_frags; a.sc1 = cp.d_sc1; a.bi1 = cp.d_bi1;
-    a.M = N * Ho * Wo; a.HoWo = Ho * Wo; a.Wo = Wo; a.res_H = res_H; a.res_W = res_W;
-    a.post1 = ldexpf(1.f, -(r2_exp + cp.w3_exp)); a.post2 = ldexpf(1.f, -(xout_exp + cp.w1_exp));
-    a.res_inv_scale = ldexpf(1.f, -src2_exp); a.xout_scale = ldexpf(1.f, xout_exp); a.r1_scale = ldexpf(1.f, r1_exp);
-    a.xout_absmax = xout_absmax; a.r1_absmax = r1_absmax;
-    a.r2_bytes = (unsigned)((size_t)a.M * C * EB); a.xout_bytes = (unsigned)((size_t)a.M * C * 4 * EB); a.r1_bytes = (unsigned)((size_t)a.M * C1 * EB);
-    a.src2_bytes = (unsigned)(res_mode == 0 ? (size_t)a.M * CIN2 * EB : (size_t)N * res_H * res_W * C * 4 * EB);
-    a.w_bytes = h1 ? cp.frag_bytes_h1 : cp.frag_bytes;
-    hipError_t e = launch_chain(a, C, C1, CIN2, res_mode, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);       // (the fragments are freed below)
-    free_chain_plan(cp);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string(h1 ? "dgp_chain_h1: " : "dgp_chain_h2: ") + hipGetErrorString(e));
-    return DGP_OK;
-}
-
-/* The unit kernel at layer level (tests): conv2 (3x3, stride 1, SAME) + BN + ReLU of a bottleneck unit, its conv3 + shortcut + ReLU and
- * conv1 of the next unit in one launch; R2 never leaves the registers. */
-static int unit_layer(bool h1, int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode,
-                const void* r1_h2, int32_t r1_exp, const void* src2_h2, int32_t src2_exp,
-                const float* w2, const float* scale2, const float* bias2, int32_t r2_exp,
-                const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
-                void* xout_h2, int32_t xout_exp, void* r1out_h2, int32_t r1out_exp, float* r2_absmax, float* xout_absmax, float* r1_absmax,
-                void* stream) {
-    const size_t EB = h1 ? 2 : 4;
-    if (!r1_h2 || !src2_h2 || !w2 || !w3cat || !w1 || !xout_h2 || !r1out_h2) return fail(DGP_ERR_INVALID, h1 ? "dgp_unit_h1: null argument" : "dgp_unit_h2: null argument");
-    if (!unit_supported(C, C1, CIN2, res_mode))
-        return fail(DGP_ERR_INVALID, "dgp_unit_h2 / _h1: no kernel instance for this (C, C1, CIN2, res_mode)");
-    if (res_mode == 0 && src2_exp != r2_exp) return fail(DGP_ERR_INVALID, "dgp_unit_h2 / _h1: the K-concatenated source must share R2's scale");
-    if (r1_h2 == r1out_h2) return fail(DGP_ERR_INVALID, "dgp_unit_h2 / _h1: r1out must not alias r1 (halo reads)");
-    ChainPlan cp;
-    int rc = build_chain_plan(cp, C, C1, CIN2, res_mode, w3cat, scale3, bias3, w1, scale1, bias1, w2, scale2, bias2);
-    if (rc) return rc;
-    ChainArgs a{};
-    a.h1 = h1 ? 1 : 0;
-    a.r1in = r1_h2; a.src2 = src2_h2; a.xout = xout_h2; a.r1out = r1out_h2; a.wfrag = h1 ? cp.d_frags_h1 : cp.d_frags; a.sc1 = cp.d_sc1; a.bi1 = cp.d_bi1;
-    a.M = N * H * W; a.HoWo = H * W; a.Wo = W; a.res_H = H; a.res_W = W; a.H = H; a.W = W;
-    a.post0 = ldexpf(1.f, -(r1_exp + cp.w2_exp)); a.r2_scale = ldexpf(1.f, r2_exp);
-    a.post1 = ldexpf(1.f, -(r2_exp + cp.w3_exp)); a.post2 = ldexpf(1.f, -(xout_exp + cp.w1_exp));
-    a.res_inv_scale = ldexpf(1.f, -src2_exp); a.xout_scale = ldexpf(1.f, xout_exp); a.r1_scale = ldexpf(1.f, r1out_exp);
-    a.r2_absmax = r2_absmax; a.xout_absmax = xout_absmax; a.r1_absmax = r1_absmax;
-    a.r1in_bytes = (unsigned)((size_t)a.M * C * EB); a.xout_bytes = (unsigned)((size_t)a.M * C * 4 * EB); a.r1_bytes = (unsigned)((size_t)a.M * C1 * EB);
-    a.src2_bytes = (unsigned)(res_mode == 0 ? (size_t)a.M * CIN2 * 4 : (size_t)a.M * C * 4 * EB);
-    a.w_bytes = h1 ? cp.frag_bytes_h1 : cp.frag_bytes;
-    hipError_t e = launch_unit(a, N, C, C1, CIN2, res_mode, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    free_chain_plan(cp);
-    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string(h1 ? "dgp_unit_h1: " : "dgp_unit_h2: ") + hipGetErrorString(e));
-    return DGP_OK;
-}
+ * csrc/dgp_chain.hip) */
 int dgp_chain_h2(int32_t N, int32_t Ho, int32_t Wo, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode, int32_t res_H, int32_t res_W,
                  const void* r2_h2, int32_t r2_exp, const void* src2_h2, int32_t src2_exp,
                  const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
                  void* xout_h2, int32_t xout_exp, void* r1_h2, int32_t r1_exp, float* xout_absmax, float* r1_absmax, void* stream) {
-    return chain_layer(false, N, Ho, Wo, C, C1, CIN2, res_mode, res_H, res_W, r2_h2, r2_exp, src2_h2, src2_exp, w3cat, scale3, bias3, w1, scale1, bias1,
-                       xout_h2, xout_exp, r1_h2, r1_exp, xout_absmax, r1_absmax, stream);
+    const ChainIo io{false, N, Ho, Wo, res_H, res_W, r2_h2, src2_h2, nullptr, xout_h2, r1_h2, 0, r2_exp, src2_exp, xout_exp, r1_exp,
+                     nullptr, xout_absmax, r1_absmax};
+    return launch_layer("dgp_chain_h2", io, C, C1, CIN2, res_mode, {nullptr, nullptr, nullptr, w3cat, scale3, bias3, w1, scale1, bias1}, (hipStream_t)stream);
 }
-/* the same launches on H1 tensors (the 16-bit tier: 2 bytes per channel, high weight fragments only, one MFMA per product) */
+/* the same launch on H1 tensors (the 16-bit tier: 2 bytes per channel, high weight fragments only, one MFMA per product) */
 int dgp_chain_h1(int32_t N, int32_t Ho, int32_t Wo, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode, int32_t res_H, int32_t res_W,
                  const void* r2_h1, int32_t r2_exp, const void* src2_h1, int32_t src2_exp,
                  const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
                  void* xout_h1, int32_t xout_exp, void* r1_h1, int32_t r1_exp, float* xout_absmax, float* r1_absmax, void* stream) {
-    return chain_layer(true, N, Ho, Wo, C, C1, CIN2, res_mode, res_H, res_W, r2_h1, r2_exp, src2_h1, src2_exp, w3cat, scale3, bias3, w1, scale1, bias1,
-                       xout_h1, xout_exp, r1_h1, r1_exp, xout_absmax, r1_absmax, stream);
+    const ChainIo io{true, N, Ho, Wo, res_H, res_W, r2_h1, src2_h1, nullptr, xout_h1, r1_h1, 0, r2_exp, src2_exp, xout_exp, r1_exp,
+                     nullptr, xout_absmax, r1_absmax};
+    return launch_layer("dgp_chain_h1", io, C, C1, CIN2, res_mode, {nullptr, nullptr, nullptr, w3cat, scale3, bias3, w1, scale1, bias1}, (hipStream_t)stream);
 }
+/* The unit kernel: conv2 (3x3, stride 1, SAME) + BN + ReLU of a bottleneck unit, its conv3 + shortcut + ReLU and conv1 of the next unit in
+ * one launch; R2 never leaves the registers. */
 int dgp_unit_h2(int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode,
                 const void* r1_h2, int32_t r1_exp, const void* src2_h2, int32_t src2_exp,
                 const float* w2, const float* scale2, const float* bias2, int32_t r2_exp,
                 const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
                 void* xout_h2, int32_t xout_exp, void* r1out_h2, int32_t r1out_exp, float* r2_absmax, float* xout_absmax, float* r1_absmax,
                 void* stream) {
-    return unit_layer(false, N, H, W, C, C1, CIN2, res_mode, r1_h2, r1_exp, src2_h2, src2_exp, w2, scale2, bias2, r2_exp, w3cat, scale3, bias3, w1, scale1, bias1,
-                      xout_h2, xout_exp, r1out_h2, r1out_exp, r2_absmax, xout_absmax, r1_absmax, stream);
+    if (!w2) return fail(DGP_ERR_INVALID, "dgp_unit_h2: null argument");
+    const ChainIo io{false, N, H, W, H, W, nullptr, src2_h2, r1_h2, xout_h2, r1out_h2, r1_exp, r2_exp, src2_exp, xout_exp, r1out_exp,
+                     r2_absmax, xout_absmax, r1_absmax};
+    return launch_layer("dgp_unit_h2", io, C, C1, CIN2, res_mode, {w2, scale2, bias2, w3cat, scale3, bias3, w1, scale1, bias1}, (hipStream_t)stream);
 }
 int dgp_unit_h1(int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode,
                 const void* r1_h1, int32_t r1_exp, const void* src2_h1, int32_t src2_exp,
@@ -1525,8 +1512,10 @@ int dgp_unit_h1(int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t 
                 const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
                 void* xout_h1, int32_t xout_exp, void* r1out_h1, int32_t r1out_exp, float* r2_absmax, float* xout_absmax, float* r1_absmax,
                 void* stream) {
-    return unit_layer(true, N, H, W, C, C1, CIN2, res_mode, r1_h1, r1_exp, src2_h1, src2_exp, w2, scale2, bias2, r2_exp, w3cat, scale3, bias3, w1, scale1, bias1,
-                      xout_h1, xout_exp, r1out_h1, r1out_exp, r2_absmax, xout_absmax, r1_absmax, stream);
+    if (!w2) return fail(DGP_ERR_INVALID, "dgp_unit_h1: null argument");
+    const ChainIo io{true, N, H, W, H, W, nullptr, src2_h1, r1_h1, xout_h1, r1out_h1, r1_exp, r2_exp, src2_exp, xout_exp, r1out_exp,
+                     r2_absmax, xout_absmax, r1_absmax};
+    return launch_layer("dgp_unit_h1", io, C, C1, CIN2, res_mode, {w2, scale2, bias2, w3cat, scale3, bias3, w1, scale1, bias1}, (hipStream_t)stream);
 }
 
 int dgp_net_range_status(dgp_net* net, int32_t* overflow, int32_t* calibrations, void* stream) {
@@ -1568,18 +1557,7 @@ int dgp_net_copy_scales(dgp_net* dst, const dgp_net* src, void* stream) {
     dst->act_exp = src->act_exp;
     dst->unit_fuse_ok = src->unit_fuse_ok;
     dst->h2_head = src->h2_head;
-    std::vector<int> ex(dst->layers.size(), dgp_net::H2_NONE);          // (what the calibration pass uploads for the per-forward range check)
-    ex[dst->conv1] = dst->act_exp[dst->conv1];
-    for (const Unit& u : dst->units) {
-        ex[u.c1] = dst->act_exp[u.c1]; ex[u.c2] = dst->act_exp[u.c2]; ex[u.c3] = dst->act_exp[u.c3];
-        if (u.sc >= 0) ex[u.sc] = dst->act_exp[u.sc];
-    }
-    hipError_t e;
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));                  // (a forward of `dst` still in flight reads the old exponents)
-    HIP_TRY(hipMemcpy(dst->d_exps, ex.data(), ex.size() * sizeof(int), hipMemcpyHostToDevice));
-    dst->h2_calibrated = true;
-    ++dst->h2_calibrations;
-    return DGP_OK;
+    return upload_scales(dst, (hipStream_t)stream);      // (what the calibration pass uploads for the per-forward range check)
 }
 
 int dgp_net_reset_scales(dgp_net* net) {

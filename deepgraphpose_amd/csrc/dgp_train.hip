@@ -1696,7 +1696,7 @@ TPlan make_tplan(const dgp_trainer* tr, int B) {
     int h = net->hp, w = net->wp;
     size_t xmax = (size_t)B * h * w * 64, r1max = 0, r2max = 0;
     for (const Unit& u : net->units) {
-        const int ho = (h + u.stride - 1) / u.stride, wo = (w + u.stride - 1) / u.stride;
+        const int ho = u.ho, wo = u.wo;
         p.sc.push_back(u.sc >= 0 ? take((size_t)B * ho * wo * u.depth) : 0);
         p.r1.push_back(take((size_t)B * h * w * u.depth_bn));
         p.r2.push_back(take((size_t)B * ho * wo * u.depth_bn));
@@ -1740,7 +1740,7 @@ TPlan make_tplan(const dgp_trainer* tr, int B) {
         int hh = net->hp, ww = net->wp;
         for (size_t ui = 0; ui < net->units.size(); ++ui) {
             const Unit& u = net->units[ui];
-            const int ho = (hh + u.stride - 1) / u.stride, wo = (ww + u.stride - 1) / u.stride;
+            const int ho = u.ho, wo = u.wo;
             // a copy pays where a 128 x 128 tile reads it: r1 feeds conv2 (K = 9 C1, Cdy = C1), r2 feeds conv3, xo the next unit's conv1 / shortcut
             if (u.depth_bn >= 128) p.sh_r1[ui] = take((size_t)B * hh * ww * u.depth_bn);
             if (u.depth_bn >= 128) p.sh_r2[ui] = take((size_t)B * ho * wo * u.depth_bn);
@@ -1806,8 +1806,7 @@ static void range_set(const void* p, const float* slot) {
 // Start of a forward or a backward pass.  Forward: everything fresh (first half of the pool).  Backward: the forward tensors'
 // ranges stay (weight gradients read the retained activations), gradient tensors take slots from the second half.
 static void range_pass_begin(dgp_trainer* tr, hipStream_t s, bool backward, int* flag_to_clear = nullptr) {
-    static const bool enabled = (dgp_tune("DGP_TRAIN_F16", 1) != 0) &&
-                                !(getenv("DGP_CONV_MODE") && strcmp(getenv("DGP_CONV_MODE"), "f16x3") != 0);
+    static const bool enabled = (dgp_tune("DGP_TRAIN_F16", 1) != 0) && conv_mode() == ConvMode::F16x3;
     g_ctx->rng.on = enabled && tr->d_rng_pool && tr->d_wrng;
     g_ctx->rng.pool = tr->d_rng_pool;
     const size_t fwd_bytes = (size_t)(2 * RANGE_FWD) * ABSMAX_SLOTS * sizeof(float);
@@ -2461,7 +2460,7 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
         hipStream_t cs = c.cs;
         auto at = [&](size_t off, size_t per_frame) { return F(off) + (size_t)n0 * per_frame; };
         const Unit& u = net->units[ui];
-        const int ho = (hh + u.stride - 1) / u.stride, wo = (ww + u.stride - 1) / u.stride;
+        const int ho = u.ho, wo = u.wo;
         const size_t pin = (size_t)hh * ww, pout = (size_t)ho * wo;
         const bool h2u = fast && ui >= ub;             // this unit's tensors are H2
         // (the first H2 unit reads the fp16 copy of its fp32 input; ranges and scales go by the tensor's own name, F(c.x_off))
@@ -2494,7 +2493,7 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
                             l1.d_bias, nullptr, 0, 0, 0, nullptr, true, 0, 0, atf(pl.r1[ui], pin * u.depth_bn, h1u), cs, F(c.x_off),
                             F(pl.r1[ui])));
         const ConvLayer& l2 = net->layers[u.c2];
-        const int pb_h = pad_before_for(hh, 3, u.stride, u.rate, true), pb_w = pad_before_for(ww, 3, u.stride, u.rate, true);
+        const int pb_h = u.pb_h, pb_w = u.pb_w;
         h2_next(false);
         TRY_HIP(conv_launch(l2, l2.d_w, l2.nk, l2.CoutP, atf(pl.r1[ui], pin * u.depth_bn, h1u), nB, hh, ww, l2.Cin, pb_h, pb_w, ho, wo,
                             l2.Cout, u.stride, 0, l2.d_scale, l2.d_bias, nullptr, 0, 0, 0, nullptr, true, 0, 0,
@@ -2527,11 +2526,8 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
             }
         }
     }
-    for (size_t ui = 0; ui < net->units.size(); ++ui) {
-        const Unit& u = net->units[ui];
-        h = (h + u.stride - 1) / u.stride; w = (w + u.stride - 1) / u.stride;
-        xin = F(pl.xo[ui]);
-    }
+    h = net->fh; w = net->fw;
+    xin = F(pl.xo[net->units.size() - 1]);
     // heads: pointwise GEMM on the cell kernels + gather of the four taps (as the inference engine) when the feature map's range
     // and the pointwise cells exist, else the 2x2-conv form on the fp32 kernel
     static const bool head_pw = (dgp_tune("DGP_HEAD_PW", 1) != 0);
@@ -2543,19 +2539,13 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
             return conv_launch(hd, hd.d_w, hd.nk, hd.CoutP, xin, B, h, w, hd.Cin, 1, 1, h, w, hd.Cout, 1, 0, nullptr, hd.d_bias,
                                nullptr, 0, 0, 0, nullptr, false, 1, njt, out, s);
         float* T = F(pl.g0);                       // gradient scratch: free during the forward pass
-        ConvArgs a{};
-        a.in = xin; a.wpk = hd.d_w_pw; a.wh3 = hd.d_wh3_pw; a.out = T; a.in_absmax = rin; a.w_absmax = rw;
+        ConvArgs a = head_pointwise_args(hd, xin, B, h, w, T, rin, rw);
         if (fast) {
             a.in_fmt = FMT; a.in_scale_dev = range_prev_of(rin);
             if (!a.in_scale_dev) return hipErrorInvalidValue;
             if (FMT == 2) a.wh3 = hd.d_wh1_pw;
         }
         a.slab = g_ctx->tail_slab; a.slab_bytes = g_ctx->tail_slab ? (unsigned)(TAIL_SLAB_FLOATS * sizeof(float)) : 0u;
-        a.N = B; a.H = h; a.W = w; a.Cin = hd.Cin; a.log2cin4 = ilog2(hd.Cin / 4);
-        a.Ho = h; a.Wo = w; a.Cout = hd.coutp_pw; a.CoutP = hd.coutp_pw;
-        a.KH = 1; a.KW = 1; a.stride = 1; a.dil = 1; a.ntaps = 1; a.nk = nk_for(1, 1, hd.Cin); a.M = B * h * w;
-        a.in_bytes = (unsigned)((size_t)a.M * hd.Cin * 4); a.out_bytes = (unsigned)((size_t)a.M * hd.coutp_pw * 4);
-        a.w_bytes = (unsigned)((size_t)a.nk * 8 * hd.coutp_pw * 16); a.wh3_bytes = a.w_bytes;
         hipError_t e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), s);
         if (e != hipSuccess) return e;
         return launch_head_gather(T, hd.d_bias, B, h, w, njt, hd.coutp_pw, out, s);
@@ -2695,15 +2685,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
         ctx->readers.erase(range.first, range.second);
         return hipSuccess;
     };
-    // geometry per unit input
-    std::vector<int> hs(nu + 1), wsz(nu + 1);
-    hs[0] = net->hp; wsz[0] = net->wp;
-    for (int ui = 0; ui < nu; ++ui) {
-        const Unit& u = net->units[ui];
-        hs[ui + 1] = (hs[ui] + u.stride - 1) / u.stride;
-        wsz[ui + 1] = (wsz[ui] + u.stride - 1) / u.stride;
-    }
-    const int fh = hs[nu], fw = wsz[nu];
+    const int fh = net->fh, fw = net->fw;
     float* dwraw = F(pl.dwraw);
     float* colsum = F(pl.colsum);
     float* G[2] = {F(pl.g0), F(pl.g1)};
@@ -2953,7 +2935,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
         if (stop_after >= 0 && (nu - 1 - ui) >= stop_after) {
             if (const char* e2 = getenv("DGP_BWD_DUMP")) {
                 (void)hipStreamSynchronize(s);
-                const size_t n = (size_t)B * hs[ui + 1] * wsz[ui + 1] * net->units[ui].depth;
+                const size_t n = (size_t)B * net->units[ui].ho * net->units[ui].wo * net->units[ui].depth;
                 std::vector<float> hbuf(n);
                 (void)hipMemcpy(hbuf.data(), G[cur], n * sizeof(float), hipMemcpyDeviceToHost);
                 FILE* f = fopen(e2, "wb");
@@ -2965,7 +2947,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             return DGP_OK;
         }
         const Unit& u = net->units[ui];
-        const int h = hs[ui], w = wsz[ui], ho = hs[ui + 1], wo = wsz[ui + 1];
+        const int h = u.h, w = u.w, ho = u.ho, wo = u.wo;
         const float* xin = ui == 0 ? F(pl.pool) : F(pl.xo[ui - 1]);
         if (h1p && ui >= ub) {
             // ---- 16-bit tier: every tensor of this unit is an H1 tensor with a predicted scale; data gradients are H1 -> H1 launches of the
@@ -2989,7 +2971,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             fmt(true, nullptr);
             TRY_HIP(conv_launch(l3, t3.d_wT, t3.nkT, t3.cinP, GoutH, B, ho, wo, l3.Cout, 0, 0, ho, wo, l3.Cin, 1, 0, nullptr, nullptr,
                                 nullptr, 0, 0, 0, F(pl.r2[ui]), false, 0, 0, DR2H, s));
-            const int pb_h = pad_before_for(h, 3, u.stride, u.rate, true), pb_w = pad_before_for(w, 3, u.stride, u.rate, true);
+            const int pb_h = u.pb_h, pb_w = u.pb_w;
             rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2H, ho, wo, u.stride, pb_h, pb_w, s);
             if (rc) return rc;
             const int keff = 2 * u.rate + 1;
@@ -3071,7 +3053,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
         TRY_HIP(conv_launch(l3, t3.d_wT, t3.nkT, t3.cinP, Gout, B, ho, wo, l3.Cout, 0, 0, ho, wo, l3.Cin, 1, 0, nullptr, nullptr,
                             nullptr, 0, 0, 0, F(pl.r2[ui]), false, 0, 0, DR2, s));
         // conv2: params, then dR1 = convT(dR2) gated by R1 > 0
-        const int pb_h = pad_before_for(h, 3, u.stride, u.rate, true), pb_w = pad_before_for(w, 3, u.stride, u.rate, true);
+        const int pb_h = u.pb_h, pb_w = u.pb_w;
         rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2, ho, wo, u.stride, pb_h, pb_w, s);
         if (rc) return rc;
         const int keff = 2 * u.rate + 1;
