@@ -123,8 +123,13 @@ constexpr size_t SOFT_ARGMAX_LDS_LIMIT = 150 * 1024;      // bytes of one joint'
 hipError_t launch_soft_argmax(const float* scmap, int B, int H, int W, int C, float gamma,
                               int gauss_len, float* mu, float* conf, int* idx, float* pmap,
                               hipStream_t s, int record_stride = 0);
+// the locref instance: offs [.,2] = E[(dx, dy)] of locref [B,H,W,2C] under the normalised blurred softmax; record_stride 0 or 7
+hipError_t launch_soft_argmax_locref(const float* scmap, const float* locref, int B, int H, int W, int C, float gamma,
+                                     int gauss_len, float* mu, float* conf, int* idx, float* offs, float* pmap,
+                                     hipStream_t s, int record_stride = 0);
+// rec != nullptr: idx / prob / offs are lanes 3, 2 and 5 of packed records of record_stride (7) floats that start at rec
 hipError_t launch_hard_argmax(const float* scmap, const float* locref, int B, int H, int W, int C,
-                              int* idx, float* prob, float* offs, hipStream_t s);
+                              int* idx, float* prob, float* offs, hipStream_t s, float* rec = nullptr, int record_stride = 0);
 hipError_t launch_pmap_threshold(float* pmap, int B, int H, int W, int C, float th, float* mu, hipStream_t s);
 
 // Arguments of the DGP loss forward+backward kernels (dgp_loss.hip).

@@ -1154,6 +1154,20 @@ int dgp_soft_argmax(const float* scmap, int32_t B, int32_t H, int32_t W, int32_t
     return DGP_OK;
 }
 
+int dgp_soft_argmax_locref(const float* scmap, const float* locref, int32_t B, int32_t H, int32_t W, int32_t C, float gamma,
+                           int32_t gauss_len, float* mu, float* conf, int32_t* idx, float* offs, float* pmap, void* stream) {
+    if (!scmap || !locref || !mu || !conf || !idx || !offs) return fail(DGP_ERR_INVALID, "dgp_soft_argmax_locref: null argument");
+    if (B < 0 || H < 1 || W < 1 || C < 1) return fail(DGP_ERR_INVALID, "dgp_soft_argmax_locref: bad shape");
+    if (gauss_len < 1 || gauss_len > 7)             // (as dgp_soft_argmax)
+        return fail(DGP_ERR_INVALID, "dgp_soft_argmax_locref: gauss_len must be 1..7");
+    if (reinterpret_cast<uintptr_t>(locref) & 7u)   // the kernel reads a joint's (dx, dy) pair as one 8-byte load
+        return fail(DGP_ERR_INVALID, "dgp_soft_argmax_locref: locref must be 8-byte aligned");
+    if (B == 0) return DGP_OK;
+    hipError_t e = launch_soft_argmax_locref(scmap, locref, B, H, W, C, gamma, gauss_len, mu, conf, idx, offs, pmap, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("soft_argmax_locref: ") + hipGetErrorString(e));
+    return DGP_OK;
+}
+
 int dgp_pmap_threshold(float* pmap, int32_t B, int32_t H, int32_t W, int32_t C, float th, float* mu, void* stream) {
     if (!pmap || !mu) return fail(DGP_ERR_INVALID, "dgp_pmap_threshold: null argument");
     if (B < 0 || H < 1 || W < 1 || C < 1 || C > 65535 || B > 65535) return fail(DGP_ERR_INVALID, "dgp_pmap_threshold: bad shape");
@@ -1174,22 +1188,33 @@ int dgp_hard_argmax(const float* scmap, const float* locref, int32_t B, int32_t 
     return DGP_OK;
 }
 
+// mode 0: the plain read-out (soft-argmax, record_stride 0 or 5).  mode 1 / 2: the refined read-out -- the forward also runs the locref
+// head (into locref_out or the workspace's locref slot) and ONE launch writes 7-lane records at mu: soft-argmax + expected offset (1,
+// "dgp") or hard arg-max + the offset there (2, "dlc").  The heads write fp32 and read block4's calibrated tensor: they own no scale, so
+// a net calibrated through either entry is calibrated for the other, and the range check covers both alike.
 static int infer_impl(dgp_net* net, const uint8_t* frames, int32_t batch, void* workspace, size_t workspace_bytes, float gamma,
-                      int32_t gauss_len, float* mu, float* conf, int32_t* idx, float* scmap_out, int record_stride, void* stream) {
+                      int32_t gauss_len, float* mu, float* conf, int32_t* idx, float* scmap_out, int record_stride, void* stream,
+                      int mode = 0, float* locref_out = nullptr) {
     if (!net) return fail(DGP_ERR_INVALID, "dgp_infer: null net");
     if (!mu || !conf || !idx) return fail(DGP_ERR_INVALID, "dgp_infer: null output");
     if (gauss_len < 1 || gauss_len > 7) return fail(DGP_ERR_INVALID, "dgp_infer: gauss_len must be 1..7");      // (as dgp_soft_argmax)
     // (the soft-argmax keeps one joint's map in LDS up to 38 400 cells -- frames up to ~1920 x 1280 -- and streams larger ones: launch_soft_argmax)
+    if (mode && net->head_locref < 0) return fail(DGP_ERR_INVALID, "dgp_forward: net built without locref head");
+    if (mode && (!workspace || batch < 1 || batch > net->desc.max_batch)) return fail(DGP_ERR_INVALID, "dgp_infer_packed_locref: null workspace / batch out of range");
+    float* lr = !mode ? nullptr : locref_out ? locref_out : (float*)((char*)workspace + make_plan(net, batch).off_locref);
     net->prof_in_infer = true;
-    int rc = dgp_forward(net, frames, batch, workspace, workspace_bytes, scmap_out, nullptr, nullptr, stream);
+    int rc = dgp_forward(net, frames, batch, workspace, workspace_bytes, scmap_out, lr, nullptr, stream);
     net->prof_in_infer = false;
     if (rc) return rc;
     const float* sm = scmap_out ? scmap_out : (const float*)((char*)workspace + make_plan(net, batch).off_scmap);
     if (batch > 0) {
-        ProfScope ps(net, (hipStream_t)stream, "soft_argmax", 0.0);
-        hipError_t e = launch_soft_argmax(sm, batch, 2 * net->fh, 2 * net->fw, net->desc.num_joints, gamma, gauss_len, mu, conf, idx,
-                                          nullptr, (hipStream_t)stream, record_stride);
-        if (e != hipSuccess) rc = fail(DGP_ERR_HIP, std::string("soft_argmax: ") + hipGetErrorString(e));
+        const int H = 2 * net->fh, W = 2 * net->fw, nj = net->desc.num_joints;
+        ProfScope ps(net, (hipStream_t)stream, mode == 2 ? "hard_argmax_locref" : mode ? "soft_argmax_locref" : "soft_argmax", 0.0);
+        hipError_t e;
+        if (mode == 2) e = launch_hard_argmax(sm, lr, batch, H, W, nj, idx, conf, mu + 5, (hipStream_t)stream, mu, record_stride);
+        else if (mode) e = launch_soft_argmax_locref(sm, lr, batch, H, W, nj, gamma, gauss_len, mu, conf, idx, mu + 5, nullptr, (hipStream_t)stream, record_stride);
+        else e = launch_soft_argmax(sm, batch, H, W, nj, gamma, gauss_len, mu, conf, idx, nullptr, (hipStream_t)stream, record_stride);
+        if (e != hipSuccess) rc = fail(DGP_ERR_HIP, std::string(mode == 2 ? "hard_argmax: " : "soft_argmax: ") + hipGetErrorString(e));
     }
     if (net->prof_on && net->prof_used < net->prof_slots) ++net->prof_used;
     return rc;
@@ -1207,11 +1232,20 @@ int dgp_infer_packed(dgp_net* net, const uint8_t* frames, int32_t batch, void* w
                       reinterpret_cast<int32_t*>(traj) + 3, scmap_out, 5, stream);
 }
 
+int dgp_infer_packed_locref(dgp_net* net, const uint8_t* frames, int32_t batch, void* workspace, size_t workspace_bytes, float gamma,
+                            int32_t gauss_len, int32_t mode, float* traj, float* scmap_out, float* locref_out, void* stream) {
+    if (!traj) return fail(DGP_ERR_INVALID, "dgp_infer_packed_locref: null trajectory");
+    if (mode != 1 && mode != 2) return fail(DGP_ERR_INVALID, "dgp_infer_packed_locref: mode must be 1 (dgp) or 2 (dlc)");
+    if (locref_out && (reinterpret_cast<uintptr_t>(locref_out) & 7u)) return fail(DGP_ERR_INVALID, "dgp_infer_packed_locref: locref_out must be 8-byte aligned");
+    return infer_impl(net, frames, batch, workspace, workspace_bytes, gamma, gauss_len, traj, traj + 2,
+                      reinterpret_cast<int32_t*>(traj) + 3, scmap_out, 7, stream, mode, locref_out);
+}
+
 int dgp_net_profile_begin(dgp_net* net, int32_t max_steps) {
     if (!net || max_steps < 1) return fail(DGP_ERR_INVALID, "dgp_net_profile_begin: bad argument");
     int nl = 0;
     dgp_net_stats(net, 1, &nl, nullptr);
-    nl += 1;   // soft-argmax
+    nl += 1;   // the read-out (dgp_net_stats counts the locref head's launch when the net has one: the refined entries fit)
     net->prof_free();
     net->prof_launches = nl; net->prof_slots = max_steps; net->prof_used = 0; net->prof_cursor = 0;
     net->prof_names.assign(nl, ""); net->prof_flops.assign(nl, 0.0);

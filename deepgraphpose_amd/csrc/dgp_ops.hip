@@ -774,17 +774,23 @@ hipError_t launch_stem_pool_fused(const unsigned char* frames, int B, int H, int
 // expressions on the same inputs, so every output is bit-identical to what the LDS variant would give; (2 r + 1)^2 exps per cell
 // instead of one, a fallback for frames beyond ~1920 x 1280, not a fast path.
 constexpr int SOFT_ARGMAX_THREADS = 1024;      // (256 until round 6: one workgroup per map is a latency chain -- 19 iterations per thread and pass on a 60 x 80 map)
-template <bool LARGE>
+// LOCREF (location refinement in the streaming path): the blur / moments loop also reads the joint's pair of the locref field
+// [B,H,W,2C] at its cell and carries two more fp64 sums, offs = E[(dx, dy)] under the normalised blurred softmax, in units of
+// locref_stdev (the weights of DGP/models/eval.py:757-786; the pair layout of PET/nnet/predict.py:62-77).  The sums are ADDED to the
+// plain instance's arithmetic, nothing of it is reordered: mu, conf, idx and pmap keep the plain instance's bits.
+template <bool LARGE, bool LOCREF>
 __global__ __launch_bounds__(SOFT_ARGMAX_THREADS) void soft_argmax_kernel(const float* __restrict__ scmap, int H, int W, int C,
                                                           float gamma, int glen, float* __restrict__ mu,
                                                           float* __restrict__ conf, int* __restrict__ idx,
-                                                          float* __restrict__ pmap, int rs) {
-    // rs = elements per (frame, joint) record: 0 -> three dense arrays mu [.,2], conf [.], idx [.,2]; 5 -> mu / conf / idx point
-    // into ONE packed [.,5] record (row, col, conf, iy, ix) -- the trajectory layout the RCCL all-gather moves
+                                                          float* __restrict__ pmap, int rs,
+                                                          const float* __restrict__ locref, float* __restrict__ offs) {
+    // rs = elements per (frame, joint) record: 0 -> dense arrays mu [.,2], conf [.], idx [.,2] (, offs [.,2]); 5 -> mu / conf / idx point
+    // into ONE packed [.,5] record (row, col, conf, iy, ix) -- the trajectory layout the RCCL all-gather moves; 7 (LOCREF) -> offs
+    // points into it as well: (row, col, conf, iy, ix, dx, dy)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sp = reinterpret_cast<float*>(smem);       // H*W
     constexpr int NT = SOFT_ARGMAX_THREADS, NW = NT / 64;
-    __shared__ double red[3][NW];
+    __shared__ double red[LOCREF ? 5 : 3][NW];
     __shared__ float redf[NW];
     __shared__ float gk[16];
 
@@ -844,7 +850,7 @@ __global__ __launch_bounds__(SOFT_ARGMAX_THREADS) void soft_argmax_kernel(const 
     auto P = [&](int i) -> float { return LARGE ? expf(scaled(i) - mx) / denom : sp[i]; };
 
     // blur (zero padded) + moments
-    double s0 = 0.0, sh = 0.0, sw = 0.0;
+    double s0 = 0.0, sh = 0.0, sw = 0.0, sdx = 0.0, sdy = 0.0;
     for (int i = t; i < HW; i += NT) {
         const int h = i / W, w = i - h * W;
         float acc = 0.f;
@@ -861,10 +867,19 @@ __global__ __launch_bounds__(SOFT_ARGMAX_THREADS) void soft_argmax_kernel(const 
         s0 += (double)acc;
         sh += (double)acc * (double)h;
         sw += (double)acc * (double)w;
+        if constexpr (LOCREF) {      // the joint's (dx, dy) at this cell: one 8-byte load (the pair index 2 cj is even)
+            const float2 l = *reinterpret_cast<const float2*>(locref + ((long long)b * HW + i) * (2 * C) + 2 * cj);
+            sdx += (double)acc * (double)l.x;
+            sdy += (double)acc * (double)l.y;
+        }
         if (pmap) pmap[((long long)b * HW + i) * C + cj] = acc;   // un-normalised; fixed below
     }
     s0 = wave_sum(s0); sh = wave_sum(sh); sw = wave_sum(sw);
-    if (lane == 0) { red[0][wave] = s0; red[1][wave] = sh; red[2][wave] = sw; }
+    if constexpr (LOCREF) { sdx = wave_sum(sdx); sdy = wave_sum(sdy); }
+    if (lane == 0) {
+        red[0][wave] = s0; red[1][wave] = sh; red[2][wave] = sw;
+        if constexpr (LOCREF) { red[3][wave] = sdx; red[4][wave] = sdy; }
+    }
     __syncthreads();
     double t0 = red[0][0], th = red[1][0], tw = red[2][0];
 #pragma unroll
@@ -883,6 +898,13 @@ __global__ __launch_bounds__(SOFT_ARGMAX_THREADS) void soft_argmax_kernel(const 
         const long long om = rs ? o * rs : o * 2, oc = rs ? o * rs : o;
         mu[om + 0] = mh;
         mu[om + 1] = mw;
+        if constexpr (LOCREF) {
+            double tdx = red[3][0], tdy = red[4][0];
+#pragma unroll
+            for (int k = 1; k < NW; ++k) { tdx += red[3][k]; tdy += red[4][k]; }
+            offs[om + 0] = (float)(tdx / t0);
+            offs[om + 1] = (float)(tdy / t0);
+        }
         // likelihood window on raw logits
         // (a NaN mu -- a +inf or NaN logit in the map -- has no window: cell (0, 0), never an index outside the map)
         const bool mok = mh == mh && mw == mw;
@@ -908,26 +930,37 @@ __global__ __launch_bounds__(SOFT_ARGMAX_THREADS) void soft_argmax_kernel(const 
     }
 }
 
-hipError_t launch_soft_argmax(const float* scmap, int B, int H, int W, int C, float gamma, int gauss_len,
-                              float* mu, float* conf, int* idx, float* pmap, hipStream_t s, int record_stride) {
+template <bool LOCREF>
+static hipError_t launch_soft_argmax_t(const float* scmap, const float* locref, int B, int H, int W, int C, float gamma, int gauss_len,
+                                       float* mu, float* conf, int* idx, float* offs, float* pmap, hipStream_t s, int record_stride) {
     const size_t smem = (size_t)H * W * sizeof(float);
     const char* force = getenv("DGP_SOFTARGMAX_STREAM");      // tests: the streaming variant on a map the LDS variant also takes (read per call)
     if (smem > SOFT_ARGMAX_LDS_LIMIT || (force && atoi(force) != 0)) {      // the map does not fit the LDS: streaming variant (same arithmetic, bit-identical)
-        hipLaunchKernelGGL(soft_argmax_kernel<true>, dim3((unsigned)(B * C)), dim3(SOFT_ARGMAX_THREADS), 0, s, scmap, H, W, C, gamma, gauss_len, mu, conf, idx,
-                           pmap, record_stride);
+        hipLaunchKernelGGL((soft_argmax_kernel<true, LOCREF>), dim3((unsigned)(B * C)), dim3(SOFT_ARGMAX_THREADS), 0, s, scmap, H, W, C, gamma, gauss_len,
+                           mu, conf, idx, pmap, record_stride, locref, offs);
         return hipGetLastError();
     }
-    static size_t attr_set_dev[16] = {};
+    static size_t attr_set_dev[16] = {};      // (per instance: the attribute belongs to the kernel function)
     size_t& attr_set = attr_set_dev[dgp_device_slot()];
     if (smem > 64 * 1024 && smem > attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(soft_argmax_kernel<false>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(soft_argmax_kernel<false, LOCREF>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
         attr_set = smem;
     }
-    hipLaunchKernelGGL(soft_argmax_kernel<false>, dim3((unsigned)(B * C)), dim3(SOFT_ARGMAX_THREADS), smem, s, scmap, H, W, C, gamma,
-                       gauss_len, mu, conf, idx, pmap, record_stride);
+    hipLaunchKernelGGL((soft_argmax_kernel<false, LOCREF>), dim3((unsigned)(B * C)), dim3(SOFT_ARGMAX_THREADS), smem, s, scmap, H, W, C, gamma,
+                       gauss_len, mu, conf, idx, pmap, record_stride, locref, offs);
     return hipGetLastError();
+}
+
+hipError_t launch_soft_argmax(const float* scmap, int B, int H, int W, int C, float gamma, int gauss_len,
+                              float* mu, float* conf, int* idx, float* pmap, hipStream_t s, int record_stride) {
+    return launch_soft_argmax_t<false>(scmap, nullptr, B, H, W, C, gamma, gauss_len, mu, conf, idx, nullptr, pmap, s, record_stride);
+}
+
+hipError_t launch_soft_argmax_locref(const float* scmap, const float* locref, int B, int H, int W, int C, float gamma, int gauss_len,
+                                     float* mu, float* conf, int* idx, float* offs, float* pmap, hipStream_t s, int record_stride) {
+    return launch_soft_argmax_t<true>(scmap, locref, B, H, W, C, gamma, gauss_len, mu, conf, idx, offs, pmap, s, record_stride);
 }
 
 // ------------------------------------------------------------------------------------
@@ -945,7 +978,9 @@ __device__ __forceinline__ bool argmax_takes(float v, int i, float bv, int bi) {
 __global__ __launch_bounds__(256) void hard_argmax_kernel(const float* __restrict__ scmap,
                                                           const float* __restrict__ locref, int H, int W, int C,
                                                           int* __restrict__ idx, float* __restrict__ prob,
-                                                          float* __restrict__ offs) {
+                                                          float* __restrict__ offs, float* __restrict__ rec, int rs) {
+    // rs = 0: dense idx [.,2], prob [.], offs [.,2].  rs = 7: idx / prob / offs point into ONE packed [.,7] record that starts at rec,
+    // (iy as float, ix as float, prob, iy, ix, dx, dy) -- the refined trajectory layout of the soft-argmax kernel
     __shared__ float rv[4];
     __shared__ int ri[4];
     const int b = blockIdx.x / C;
@@ -973,24 +1008,26 @@ __global__ __launch_bounds__(256) void hard_argmax_kernel(const float* __restric
             if (argmax_takes(rv[k], ri[k], bv, bi)) { bv = rv[k]; bi = ri[k]; }
         const long long o = (long long)b * C + cj;
         const int h = bi / W, w = bi - h * W;
-        idx[o * 2 + 0] = h;
-        idx[o * 2 + 1] = w;
-        prob[o] = bv;
+        const long long om = rs ? o * rs : o * 2, oc = rs ? o * rs : o;
+        if (rs) { rec[om + 0] = (float)h; rec[om + 1] = (float)w; }
+        idx[om + 0] = h;
+        idx[om + 1] = w;
+        prob[oc] = bv;
         float dx = 0.f, dy = 0.f;
         if (locref) {
             const float* l = locref + ((long long)b * HW + bi) * (2 * C) + 2 * cj;
             dx = l[0];
             dy = l[1];
         }
-        offs[o * 2 + 0] = dx;
-        offs[o * 2 + 1] = dy;
+        offs[om + 0] = dx;
+        offs[om + 1] = dy;
     }
 }
 
 hipError_t launch_hard_argmax(const float* scmap, const float* locref, int B, int H, int W, int C, int* idx,
-                              float* prob, float* offs, hipStream_t s) {
+                              float* prob, float* offs, hipStream_t s, float* rec, int record_stride) {
     hipLaunchKernelGGL(hard_argmax_kernel, dim3((unsigned)(B * C)), dim3(256), 0, s, scmap, locref, H, W, C, idx,
-                       prob, offs);
+                       prob, offs, rec, rec ? record_stride : 0);
     return hipGetLastError();
 }
 

@@ -35,6 +35,14 @@ def unpack_keypoints(buf: torch.Tensor):
     return mu, conf, idx
 
 
+def unpack_offsets(buf: torch.Tensor) -> torch.Tensor:
+    """lanes 5..6 of a 7-lane record [..., 7] (engine.DGPNet.infer_packed with loc_ref): the raw location-refinement offset (dx, dy),
+    in units of locref_stdev"""
+    if buf.shape[-1] != 7:
+        raise ValueError("unpack_offsets: records have %d lanes, not 7 (no location refinement in them)" % buf.shape[-1])
+    return buf[..., 5:7].contiguous()
+
+
 def gather_trajectory(local: torch.Tensor, n_frames: int, group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
     """All-gather per-rank packed keypoints [T_r, nj, 5] into the frame-ordered [T, nj, 5]
     on every rank.  Shards are padded to ceil(T/W) so one fixed-size all-gather suffices."""

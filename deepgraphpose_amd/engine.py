@@ -244,21 +244,46 @@ class DGPNet:
         self.scale_epoch += 1
 
     def infer_packed(self, frames: torch.Tensor, traj: torch.Tensor, gamma: float = 1.0, gauss_len: int = 1,
-                     scmap_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     scmap_out: Optional[torch.Tensor] = None, loc_ref: Optional[str] = None,
+                     locref_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Fused frames -> traj [B,nj,5] fp32 lanes (row, col, likelihood, iy, ix; indices as int32 bit patterns): the record
         layout of the per-video trajectory (dist.unpack_keypoints splits it).  `traj` is a caller-owned contiguous slice of the
-        trajectory buffer, written in place by the soft-argmax kernel."""
+        trajectory buffer, written in place by the soft-argmax kernel.
+
+        loc_ref (LOC_REF_MODES): location refinement -- the forward also runs the locref head and the read-out writes 7-lane records
+        traj [B,nj,7] whose lanes 5..6 are the raw (dx, dy) offset (dist.unpack_offsets).  "dgp": lanes 0..4 as above, the offset is the
+        expectation of the locref field under the soft-argmax's map; "dlc": the hard arg-max cell (as floats), its sigmoid, the cell
+        again and the offset at that cell.  The net must have been created with_locref."""
         _need_cuda(frames, torch.uint8, "frames")
         _need_cuda(traj, torch.float32, "traj")
         B = frames.shape[0]
         if tuple(frames.shape[1:]) != (self.in_h, self.in_w, 3):
             raise _lib.DgpError("frames must be [B,%d,%d,3], got %s" % (self.in_h, self.in_w, tuple(frames.shape)))
-        if tuple(traj.shape) != (B, self.nj, 5):
-            raise _lib.DgpError("traj must be [%d,%d,5], got %s" % (B, self.nj, tuple(traj.shape)))
+        lanes = record_lanes(loc_ref)
+        if tuple(traj.shape) != (B, self.nj, lanes):
+            raise _lib.DgpError("traj must be [%d,%d,%d], got %s" % (B, self.nj, lanes, tuple(traj.shape)))
         ws = self.workspace(B)
-        _lib.check(self.lib.dgp_infer_packed(self._h, _ptr(frames), B, _ptr(ws), ws.numel(), float(gamma), int(gauss_len),
-                                             _ptr(traj), _ptr(scmap_out), _stream(self.device)), "dgp_infer_packed")
+        if loc_ref is None:
+            _lib.check(self.lib.dgp_infer_packed(self._h, _ptr(frames), B, _ptr(ws), ws.numel(), float(gamma), int(gauss_len),
+                                                 _ptr(traj), _ptr(scmap_out), _stream(self.device)), "dgp_infer_packed")
+        else:
+            _lib.check(self.lib.dgp_infer_packed_locref(self._h, _ptr(frames), B, _ptr(ws), ws.numel(), float(gamma), int(gauss_len),
+                                                        LOC_REF_MODES[loc_ref], _ptr(traj), _ptr(scmap_out), _ptr(locref_out),
+                                                        _stream(self.device)), "dgp_infer_packed_locref")
         return traj
+
+
+# location refinement in the streaming read-out (dgp_infer_packed_locref's mode): None = off, 5-lane records
+LOC_REF_MODES = {"dgp": 1, "dlc": 2}
+
+
+def record_lanes(loc_ref: Optional[str]) -> int:
+    """fp32 lanes of one (frame, joint) record of infer_packed: 5, or 7 with location refinement"""
+    if loc_ref is None:
+        return 5
+    if loc_ref not in LOC_REF_MODES:
+        raise ValueError("loc_ref must be None, 'dgp' or 'dlc', not %r" % (loc_ref,))
+    return 7
 
 
 class DGPPipeline:
@@ -306,16 +331,16 @@ class DGPPipeline:
         n0 = self.nets[0]
         self.in_h, self.in_w, self.out_h, self.out_w = n0.in_h, n0.in_w, n0.out_h, n0.out_w
 
-    def calibrate(self, frames: torch.Tensor, gamma: float = 1.0, gauss_len: int = 1):
+    def calibrate(self, frames: torch.Tensor, gamma: float = 1.0, gauss_len: int = 1, loc_ref: Optional[str] = None):
         """Engine 0 runs `frames` (it calibrates on them after load_weights / recalibrate / an overflow) and the other engines take its
         scales (dgp_net_copy_scales: the calibration is deterministic, so that is what each would have found on the same batch -- round 6,
-        one layer-by-layer pass per video instead of one per engine); synchronises."""
-        scratch = torch.empty((frames.shape[0], self.nj, 5), dtype=torch.float32, device=self.device)
+        one layer-by-layer pass per video instead of one per engine); synchronises.  loc_ref: the variant the submits will run."""
+        scratch = torch.empty((frames.shape[0], self.nj, record_lanes(loc_ref)), dtype=torch.float32, device=self.device)
         cur = torch.cuda.current_stream(self.device)
         n0, st0 = self.nets[0], self.streams[0]
         st0.wait_stream(cur)
         with torch.cuda.stream(st0):
-            n0.infer_packed(frames, scratch, gamma, gauss_len)
+            n0.infer_packed(frames, scratch, gamma, gauss_len, loc_ref=loc_ref)
         st0.synchronize()
         for n, st in zip(self.nets[1:], self.streams[1:]):
             with torch.cuda.stream(st):
@@ -323,20 +348,21 @@ class DGPPipeline:
         self._calibrated = True
         self._epochs = [n.scale_epoch for n in self.nets]
 
-    def submit(self, frames: torch.Tensor, traj: torch.Tensor, gamma: float = 1.0, gauss_len: int = 1) -> "torch.cuda.Event":
-        """infer_packed(frames -> traj) on the next engine's stream, ordered after the work already on the caller's current stream.
+    def submit(self, frames: torch.Tensor, traj: torch.Tensor, gamma: float = 1.0, gauss_len: int = 1,
+               loc_ref: Optional[str] = None) -> "torch.cuda.Event":
+        """infer_packed(frames -> traj, loc_ref) on the next engine's stream, ordered after the work already on the caller's current stream.
         Returns the event recorded behind it (frames / traj may be reused once it has completed).  The first batch after
         load_weights / recalibrate / an overflow goes through EVERY engine first (calibrate), so all engines share its scales."""
         if self._calibrated and [n.scale_epoch for n in self.nets] != self._epochs:
             self._resync()                  # an engine was re-calibrated behind the pipeline's back (EvalSession shares engine 0)
         if not self._calibrated:
-            self.calibrate(frames, gamma, gauss_len)
+            self.calibrate(frames, gamma, gauss_len, loc_ref)
         i = self._next
         self._next = (i + 1) % len(self.nets)
         st = self.streams[i]
         st.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(st):
-            self.nets[i].infer_packed(frames, traj, gamma, gauss_len)
+            self.nets[i].infer_packed(frames, traj, gamma, gauss_len, loc_ref=loc_ref)
             ev = torch.cuda.Event()
             ev.record(st)
         return ev
@@ -408,6 +434,31 @@ def soft_argmax(scmap: torch.Tensor, gamma: float = 1.0, gauss_len: int = 2, wan
     _lib.check(lib.dgp_soft_argmax(_ptr(scmap), B, H, W, Cn, float(gamma), int(gauss_len), _ptr(mu), _ptr(conf),
                                    _ptr(idx), _ptr(pmap), _stream(dev)), "dgp_soft_argmax")
     return (mu, conf, idx, pmap) if want_pmap else (mu, conf, idx)
+
+
+def soft_argmax_locref(scmap: torch.Tensor, locref: torch.Tensor, gamma: float = 1.0, gauss_len: int = 2, want_pmap: bool = False):
+    """soft_argmax plus the location-refinement read-out in the same launch (dgp_soft_argmax_locref): locref fp32 [B,H,W,2C] on device
+    -> (mu, conf, idx, offs[, pmap]); offs [B,C,2] = (dx, dy), the expectation of the raw locref field under the normalised blurred
+    softmax (multiply by locref_stdev for pixels).  mu, conf, idx, pmap are soft_argmax's, bit for bit."""
+    lib = _lib.load()
+    _need_cuda(scmap, torch.float32, "scmap")
+    if scmap.dim() != 4:
+        raise _lib.DgpError("scmap must be rank 4 [B,H,W,C]")
+    B, H, W, Cn = scmap.shape
+    if locref is not None:
+        _need_cuda(locref, torch.float32, "locref")
+        if tuple(locref.shape) != (B, H, W, 2 * Cn):
+            raise _lib.DgpError("locref must be [B,H,W,2*C]")
+    dev = scmap.device
+    mu = torch.empty((B, Cn, 2), dtype=torch.float32, device=dev)
+    conf = torch.empty((B, Cn), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, Cn, 2), dtype=torch.int32, device=dev)
+    offs = torch.empty((B, Cn, 2), dtype=torch.float32, device=dev)
+    pmap = torch.empty_like(scmap) if want_pmap else None
+    if not (B * Cn == 0 and H > 0 and W > 0 and locref is not None):      # no frames or no joints: empty outputs
+        _lib.check(lib.dgp_soft_argmax_locref(_ptr(scmap), _ptr(locref), B, H, W, Cn, float(gamma), int(gauss_len), _ptr(mu), _ptr(conf),
+                                              _ptr(idx), _ptr(offs), _ptr(pmap), _stream(dev)), "dgp_soft_argmax_locref")
+    return (mu, conf, idx, offs, pmap) if want_pmap else (mu, conf, idx, offs)
 
 
 def pmap_threshold(pmap: torch.Tensor, th: float) -> torch.Tensor:

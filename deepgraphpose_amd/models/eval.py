@@ -192,7 +192,31 @@ def clear_session_cache():
 
 # counters of the last estimate_pose call (tests, soak runs): chunks processed and chunks re-run after a range overflow
 RUN_STATS = {"chunks": 0, "chunk_reruns": 0, "strict_passes": 0, "stage_s": 0.0, "wait_frames_s": 0.0, "wait_h2d_s": 0.0, "drain_s": 0.0,
-             "setup_s": 0.0, "alloc_s": 0.0, "calibrate_s": 0.0, "finish_s": 0.0, "prep_backend": "none"}
+             "setup_s": 0.0, "alloc_s": 0.0, "calibrate_s": 0.0, "finish_s": 0.0, "prep_backend": "none", "loc_ref": None}
+
+# location refinement of estimate_pose / plot_dgp (engine.LOC_REF_MODES): None = the reference's video path (soft-argmax only), "dgp" =
+# soft-argmax + the softmax-weighted locref offset, "dlc" = DLC's hard arg-max + the offset at that cell
+LOC_REF_CHOICES = (None, "dgp", "dlc")
+LOCREF_VARIABLE = "pose/locref_pred/block4/weights"
+
+
+def refined_pose(records, stride, locref_stdev, scale_x=1.0, scale_y=1.0):
+    """Pixel coordinates from 7-lane read-out records [..., 7] = (row, col, likelihood, iy, ix, dx, dy) (engine.DGPNet.infer_packed with
+    loc_ref; "dlc" records carry the arg-max cell in lanes 0..1): -> (x, y, likelihood), float64,
+
+        x = (col * stride + stride / 2 + dx * locref_stdev) * scale_x
+        y = (row * stride + stride / 2 + dy * locref_stdev) * scale_y.
+
+    This is DLC's geometry (PET/nnet/predict.py:62-77) and the one the locref targets are built in: channel 2j of the head is joint j's x
+    offset, 2j + 1 its y offset (compute_target_part_scoremap).  The reference's experimental loc_ref_calc='dgp' branch of evaluate_dgp
+    (DGP/models/eval.py:769-780; soft_argmax_locref_pose here) adds channel 2j to the ROW instead; evaluate_dgp keeps that branch as it
+    is, the video path does not copy it."""
+    r = np.asarray(records, dtype=np.float64)
+    if r.shape[-1] != 7:
+        raise ValueError("refined_pose: records have %d lanes, not 7" % r.shape[-1])
+    x = (r[..., 1] * stride + 0.5 * stride + r[..., 5] * locref_stdev) * scale_x
+    y = (r[..., 0] * stride + 0.5 * stride + r[..., 6] * locref_stdev) * scale_y
+    return x, y, r[..., 2].copy()
 
 # who resizes / crops the frames of estimate_pose(new_size=, crop_size=): "hip" = engine.resize_frames on the copy stream (source-size
 # frames cross PCIe), "pil" = Pillow per frame on the host (the reference's code), "auto" = "hip" unless the kernel refuses the shape
@@ -225,8 +249,10 @@ class _PoseRun:
     batch k+1 to the GPU while batch k runs through dgp_infer on the compute stream, and the keypoints of the whole video come back in
     ONE device-to-host copy at the end (the reference fetched the full scoremap every frame)."""
 
-    def __init__(self, sess, clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend):
-        self.sess, self.clip, self.video_file = sess, clip, video_file
+    def __init__(self, sess, clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend, loc_ref=None):
+        self.sess, self.clip, self.video_file, self.loc_ref = sess, clip, video_file, loc_ref
+        self.lanes = 5 if loc_ref is None else 7          # fp32 lanes of a (frame, joint) record (engine.record_lanes)
+        self.records = None                               # loc_ref: the whole video's 7-lane records, float32 [n_frames, nj, 7]
         self.lo, self.hi, self.world, self.n_frames, self.batch_size = lo, hi, world, int(clip.n_frames), batch_size
         self.new_size, self.crop_size, self.resize_backend = new_size, crop_size, resize_backend
         resizing = new_size is not None or crop_size is not None
@@ -285,7 +311,7 @@ class _PoseRun:
         RUN_STATS["alloc_s"] += time.perf_counter() - t_        # pinned ring (kept between calls) + the chunk's device buffer
         self.copy_streams = [torch.cuda.Stream(device=dev) for _ in range(COPY_STREAMS)]
         self.compute = torch.cuda.current_stream(dev)
-        self.traj = torch.zeros((max(self.hi - self.lo, 1), self.sess.nj, 5), dtype=torch.float32, device=dev)      # packed (row, col, likelihood, iy, ix)
+        self.traj = torch.zeros((max(self.hi - self.lo, 1), self.sess.nj, self.lanes), dtype=torch.float32, device=dev)      # packed (row, col, likelihood, iy, ix[, dx, dy])
 
     def calibrate_on_first_batch(self):
         """Calibration: every engine of every rank calibrates its activation scales on the video's FIRST batch (not on its own shard's),
@@ -300,7 +326,7 @@ class _PoseRun:
         self.cal_batch = self.pinned[0][:nb0].to(self.dev)
         if self.on_gpu:
             self.cal_batch = engine.resize_frames(self.cal_batch, self.new_size, self.crop_size)
-        self.net.calibrate(self.cal_batch, self.sess.gamma, self.sess.gauss_len)
+        self.net.calibrate(self.cal_batch, self.sess.gamma, self.sess.gauss_len, self.loc_ref)
         torch.cuda.synchronize(self.dev)
 
     def start_staging(self, f0, rest):
@@ -362,9 +388,9 @@ class _PoseRun:
         if self.cal_batch is None:
             self.cal_batch = dst.clone()
             t_ = time.perf_counter()
-            net.calibrate(self.cal_batch, sess.gamma, sess.gauss_len)      # (what the first submit would do: timed apart)
+            net.calibrate(self.cal_batch, sess.gamma, sess.gauss_len, self.loc_ref)      # (what the first submit would do: timed apart)
             RUN_STATS["calibrate_s"] += time.perf_counter() - t_
-        net.submit(dst, self.traj[start:start + nb], sess.gamma, sess.gauss_len)      # written in place by the soft-argmax kernel, on the next engine's stream
+        net.submit(dst, self.traj[start:start + nb], sess.gamma, sess.gauss_len, self.loc_ref)      # written in place by the soft-argmax kernel, on the next engine's stream
         # the consumer blocks on its oldest pending copy once it holds all slots but one
         self.release(len(self.pending) >= len(self.pinned) - 1)
 
@@ -391,14 +417,14 @@ class _PoseRun:
                 raise RuntimeError("activation scales did not settle after 4 re-calibrations in %s" % self.video_file)
             if not overflow:
                 net.widen()
-            net.calibrate(self.cal_batch, sess.gamma, sess.gauss_len)
+            net.calibrate(self.cal_batch, sess.gamma, sess.gauss_len, self.loc_ref)
             widened = True
             if overflow or strict:
                 print("activation ranges outgrew the calibrated scales: re-calibrated, re-running frames %d-%d of %s"
                       % (self.lo + entries[0][2] if entries else self.lo, self.lo + end, self.video_file), flush=True)
                 RUN_STATS["chunk_reruns"] += 1
                 for k, nb, off in entries:
-                    net.submit(self.dchunk[k][:nb], self.traj[off:off + nb], sess.gamma, sess.gauss_len)
+                    net.submit(self.dchunk[k][:nb], self.traj[off:off + nb], sess.gamma, sess.gauss_len, self.loc_ref)
         return widened
 
     def gather(self, n_done):
@@ -406,12 +432,16 @@ class _PoseRun:
         from .. import dist as ddist
         t_ = time.perf_counter()
         if self.world > 1:
-            mu_t, lik_t, _ = ddist.unpack_keypoints(ddist.gather_trajectory(self.traj[:self.hi - self.lo], self.n_frames))
+            rec = ddist.gather_trajectory(self.traj[:self.hi - self.lo], self.n_frames)
             n_done = self.n_frames
         else:
-            mu_t, lik_t, _ = ddist.unpack_keypoints(self.traj[:n_done])
+            rec = self.traj[:n_done]
+        mu_t, lik_t, _ = ddist.unpack_keypoints(rec)
         self.markers[:n_done] = mu_t.cpu().numpy()
         self.likelihoods[:n_done] = lik_t.cpu().numpy()
+        if self.loc_ref is not None:                 # refined_pose composes the coordinates from the whole records
+            self.records = np.zeros((self.n_frames, self.sess.nj, 7), dtype=np.float32)
+            self.records[:n_done] = rec.cpu().numpy()
         RUN_STATS["finish_s"] += time.perf_counter() - t_
 
     def run_pass(self, first_pass):
@@ -469,7 +499,8 @@ class _PoseRun:
 
 
 def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle=1, save_pose=True, save_str="",
-                  new_size=None, crop_size=None, batch_size: int = 32, tier: Optional[str] = None, resize_backend: str = "auto"):
+                  new_size=None, crop_size=None, batch_size: int = 32, tier: Optional[str] = None, resize_backend: str = "auto",
+                  loc_ref: Optional[str] = None):
     """Estimate pose on an arbitrary video (eval.py:217-372).  Returns {'x','y','likelihoods'} [T,nj] float64,
     or the csv path if labels already exist (:247-249).  `batch_size` is new: frames go through the GPU in
     batches instead of one sess.run per frame.  `tier` is new (resolve_tier): None = DGP_EVAL_TIER or the parity tier; "f16" = the
@@ -477,6 +508,11 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     PIL resize / crop of eval.py:307-326 when `new_size` / `crop_size` are given -- "hip": engine.resize_frames (Pillow's bytes, computed on
     the GPU behind the upload of the source-size frames), "pil": Pillow on the host, "auto": "hip", and "pil" (with one printed line) only
     for a shape the kernel refuses or frames that are not uint8 RGB.  RUN_STATS["prep_backend"] names the one that ran ("none": no resize).
+    `loc_ref` is new (LOC_REF_CHOICES): location refinement with the snapshot's trained pose/locref_pred head, which the reference's
+    video path never applied (DLC's own always does).  None: as the reference.  "dgp": soft-argmax position + the softmax-weighted
+    offset, likelihood = the window sigmoid; "dlc": hard arg-max cell + the offset at that cell, likelihood = the arg-max probability
+    (PET/nnet/predict.py:62-77).  Coordinates are composed by refined_pose (DLC's axis convention).  A snapshot without the head raises
+    KeyError naming the variable.  RUN_STATS["loc_ref"] names the mode that ran.
 
     Multi-GPU: under torchrun (one process per GPU; RANK / WORLD_SIZE / LOCAL_RANK in the environment, or an
     already initialised torch.distributed group) rank r decodes and infers only the contiguous frame block
@@ -489,8 +525,10 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     t_entry = time.perf_counter()
     if resize_backend not in RESIZE_BACKENDS:
         raise ValueError("estimate_pose: resize_backend must be one of %s, not %r" % ("|".join(RESIZE_BACKENDS), resize_backend))
+    if loc_ref not in LOC_REF_CHOICES:
+        raise ValueError("estimate_pose: loc_ref must be None, 'dgp' or 'dlc', not %r" % (loc_ref,))
     RUN_STATS.update(chunks=0, chunk_reruns=0, strict_passes=0, stage_s=0.0, wait_frames_s=0.0, wait_h2d_s=0.0, drain_s=0.0, setup_s=0.0,
-                     alloc_s=0.0, calibrate_s=0.0, finish_s=0.0)
+                     alloc_s=0.0, calibrate_s=0.0, finish_s=0.0, loc_ref=loc_ref)
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not tdist.is_initialized():
         ddist.init_from_env()                      # before anything touches the GPU
@@ -511,16 +549,22 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         proj_config = yaml.safe_load(stream)
     proj_config["video_path"] = None
     dlc_cfg = get_train_config(proj_config, shuffle=shuffle)
+    with_head = loc_ref is not None
     try:
         dlc_cfg.net_type = "resnet_50"
-        sess = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, tier=tier)[0]
+        sess = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, loc_ref=with_head, tier=tier)[0]
     except KeyError:
         dlc_cfg.net_type = "resnet_101"
-        sess = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, tier=tier)[0]
+        sess = setup_dgp_eval_graph(dlc_cfg, dgp_model_file, loc_ref=with_head, tier=tier)[0]
+    if with_head and LOCREF_VARIABLE not in sess.weights:      # (checked after the depth is settled: not a reason to try ResNet-101)
+        sess.close()
+        video_clip.close()
+        raise KeyError("snapshot %s holds no %s: estimate_pose(loc_ref=%r) needs a model trained with location refinement"
+                       % (dgp_model_file, LOCREF_VARIABLE, loc_ref))
     sess.max_batch = int(batch_size)
     sess.device = local_rank
     lo, hi = ddist.shard_range(int(video_clip.n_frames), rank, world)        # this rank's frames
-    run = _PoseRun(sess, video_clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend)
+    run = _PoseRun(sess, video_clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend, loc_ref)
 
     # Bit-identity of a sharded run with a single-process run holds as long as no chunk overflows (or only the first one does).  After an
     # overflow in a LATER chunk the earlier chunks keep the (valid) results of the narrower scales, which a run that started with the
@@ -541,6 +585,9 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     xr *= run.scale_x
     yr *= run.scale_y
     labels = {"x": xr, "y": yr, "likelihoods": run.likelihoods}
+    if loc_ref is not None:
+        xr, yr, lik = refined_pose(run.records, dlc_cfg.stride, dlc_cfg.locref_stdev, run.scale_x, run.scale_y)
+        labels = {"x": xr, "y": yr, "likelihoods": lik}
     if save_pose and rank == 0:
         if not Path(save_file).parent.exists():
             os.makedirs(os.path.dirname(save_file))
@@ -577,8 +624,8 @@ def load_pose_from_dlc_to_dict(filename):
 
 
 def plot_dgp(video_file, output_dir="", label_dir=None, proj_cfg_file=None, dgp_model_file=None, shuffle=1, dotsize=3,
-             colormap="jet", save_str="", mask_threshold=0.1, new_size=None, tier=None):
-    """eval.py:816-874 (`tier` is new: estimate_pose's).  Exports the labels when missing, then hands (clip, x, y, mask) to the movie
+             colormap="jet", save_str="", mask_threshold=0.1, new_size=None, tier=None, loc_ref=None):
+    """eval.py:816-874 (`tier` and `loc_ref` are new: estimate_pose's).  Exports the labels when missing, then hands (clip, x, y, mask) to the movie
     renderer.  Drawing the annotated movie is moviepy / matplotlib work outside this package's scope: when
     those are absent the labels are still produced and the csv path is returned."""
     f = os.path.basename(str(video_file)).rsplit(".", 1)
@@ -591,7 +638,7 @@ def plot_dgp(video_file, output_dir="", label_dir=None, proj_cfg_file=None, dgp_
     labels = None
     if not ddist.from_rank0(os.path.exists(label_file)):
         labels = estimate_pose(proj_cfg_file, dgp_model_file, video_file, label_dir, shuffle=shuffle, save_str=save_str,
-                               new_size=new_size, tier=tier)
+                               new_size=new_size, tier=tier, loc_ref=loc_ref)
     if not isinstance(labels, dict):                       # labels were there already (estimate_pose returns the csv path then)
         labels = load_pose_from_dlc_to_dict(label_file)
     mask_array = labels["likelihoods"].T > mask_threshold

@@ -15,6 +15,9 @@
  *                      + likelihood read-out                        DGP/models/eval.py:331-343
  *   dgp_hard_argmax    argmax_pose_predict                          PET/nnet/predict.py:62-77
  *   dgp_infer          sess.run([mu_n, scmap]) + read-out           DGP/models/eval.py:306-345
+ *   dgp_soft_argmax_locref   softmax-weighted locref offset         DGP/models/eval.py:757-786
+ *   dgp_infer_packed_locref  the same loop with location refinement: DLC's own video analysis always applies the offsets
+ *                      (PET/nnet/predict.py:62-77); the soft form is evaluate_dgp's loc_ref_calc='dgp' (DGP/models/eval.py:752-786)
  *   dgp_net_create /   setup_dgp_eval_graph (graph build + Saver.restore)
  *   dgp_net_load_weights                                            DGP/models/eval.py:147-214
  *
@@ -107,6 +110,15 @@ int  dgp_soft_argmax(const float* scmap, int32_t B, int32_t H, int32_t W, int32_
                      float gamma, int32_t gauss_len, float* mu, float* conf, int32_t* idx,
                      float* pmap, void* stream);
 
+/* dgp_soft_argmax plus the location-refinement read-out in the same launch: locref [B,H,W,2C] fp32 (pose/locref_pred, channel 2c = dx,
+ * 2c + 1 = dy of joint c: PET/nnet/predict.py:62-77, targets built by compute_target_part_scoremap), 8-byte aligned ->
+ * offs [B,C,2] = sum(p * locref) / sum(p) over the normalised blurred softmax p that mu is the expectation under: the softmax-weighted
+ * offset of DGP/models/eval.py:757-786, NOT yet scaled by locref_stdev.  mu, conf, idx and pmap are bit-identical to dgp_soft_argmax's
+ * on the same scmap; the same argument checks apply (gauss_len 1..7).  A map with a +inf or NaN logit gives NaN offs. */
+int  dgp_soft_argmax_locref(const float* scmap, const float* locref, int32_t B, int32_t H, int32_t W, int32_t C,
+                            float gamma, int32_t gauss_len, float* mu, float* conf, int32_t* idx, float* offs,
+                            float* pmap, void* stream);
+
 /* argmax_2d_from_cm's `th` branch (DGP/models/fitdgp_util.py:377-388; unused by the reference's drivers): on the pmap that
  * dgp_soft_argmax wrote, per (frame, joint) map: values below th * max become 0, the map is renormalised IN PLACE and
  * mu [B,C,2] (row, col) is its expectation. */
@@ -133,6 +145,19 @@ int  dgp_infer(dgp_net* net, const uint8_t* frames, int32_t batch, void* workspa
 int  dgp_infer_packed(dgp_net* net, const uint8_t* frames, int32_t batch, void* workspace,
                       size_t workspace_bytes, float gamma, int32_t gauss_len, float* traj,
                       float* scmap_out, void* stream);
+
+/* dgp_infer_packed with location refinement: the forward also runs the locref head (into locref_out, or the workspace when NULL) and
+ * ONE read-out launch writes traj [batch, nj, 7] fp32 lanes.
+ *   mode 1 ("dgp"): (row, col, likelihood, iy, ix, dx, dy) = dgp_soft_argmax_locref's mu, conf, idx, offs
+ *                   (DGP/models/eval.py:752-786: soft-argmax + softmax-weighted offset);
+ *   mode 2 ("dlc"): (iy as float, ix as float, prob, iy, ix, dx, dy) = dgp_hard_argmax's idx, prob, offs
+ *                   (PET/nnet/predict.py:62-77: arg-max of the sigmoid + the offset at that cell; gamma / gauss_len are only checked).
+ * Lanes 0..4 of mode 1 are dgp_infer_packed's record, bit for bit; dx, dy are raw head outputs (multiply by locref_stdev).
+ * A net created without with_locref: DGP_ERR_INVALID.  The heads own no activation scale: a net calibrated by dgp_infer_packed stays
+ * calibrated for this entry and the other way round. */
+int  dgp_infer_packed_locref(dgp_net* net, const uint8_t* frames, int32_t batch, void* workspace,
+                             size_t workspace_bytes, float gamma, int32_t gauss_len, int32_t mode, float* traj,
+                             float* scmap_out, float* locref_out, void* stream);
 
 /* ---- measurement: hipEvent pairs around every launch of dgp_forward / dgp_infer, recorded on
  * the caller's stream (no syncs until dgp_net_profile_launch reads them).  Used by bench.py for
