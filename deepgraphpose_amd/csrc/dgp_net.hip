@@ -605,22 +605,6 @@ void apply_h2(ConvArgs& a, const H2Spec& h) {
     a.in_scale = ldexpf(1.f, h.in_exp); a.out_scale = ldexpf(1.f, h.out_exp); a.res_inv_scale = ldexpf(1.f, -h.res_exp);
 }
 
-// The geometry of a plain conv launch: shape, derived K walk, ReLU, buffer-descriptor extents (a.res set first: no residual, no extent)
-int fill_conv_geometry(ConvArgs& a, const dgp_conv_desc& d, const char* too_big) {
-    a.N = d.N; a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.log2cin4 = ilog2(d.Cin / 4);
-    a.Ho = d.Ho; a.Wo = d.Wo; a.Cout = d.Cout; a.CoutP = coutp_for(d.Cout);
-    a.KH = d.KH; a.KW = d.KW; a.stride = d.stride; a.dil = d.rate; a.pad_t = d.pad_t; a.pad_l = d.pad_l;
-    a.ntaps = d.KH * d.KW; a.nk = nk_for(d.KH, d.KW, d.Cin); a.M = d.N * d.Ho * d.Wo;
-    a.res_s = d.res_stride; a.res_H = d.res_H; a.res_W = d.res_W; a.relu = d.relu;
-    const double inb = (double)d.N * d.H * d.W * d.Cin * 4, outb = (double)a.M * d.Cout * 4;
-    const double resb = a.res ? (double)d.N * d.res_H * d.res_W * d.Cout * 4 : 0.0;
-    if (!fits_descriptor({inb, outb, resb})) return fail(DGP_ERR_INVALID, too_big);
-    a.in_bytes = (unsigned)inb; a.out_bytes = (unsigned)outb; a.res_bytes = (unsigned)resb;
-    a.w_bytes = (unsigned)((size_t)a.nk * 8 * a.CoutP * 16);
-    return DGP_OK;
-}
-const char* const TOO_BIG = "activation tensor exceeds the 4 GiB buffer-descriptor range; lower the batch";
-
 // One launch of a layer of the net.  conv_call() gives the common case -- the layer on the input's own grid (1x1 convs), no residual,
 // ReLU, plain NHWC output, fp32 tensors without a tracked input range -- and a call site names what differs
 struct ConvCall {

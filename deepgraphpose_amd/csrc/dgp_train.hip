@@ -1536,38 +1536,70 @@ struct TLayer {
     int nkT = 0, cinP = 0, cpad = 0;                  // cpad: padded phase-major channel count (heads)
 };
 
-// Per-trainer launch context (was process-global state: two trainers, or a trainer created after another was destroyed, must not
-// see each other's range maps, fp16 cell tables or workspace pointers).  Bound to the calling thread for the duration of an entry point.
-struct TPlanFwd;
+// Operand ranges for the fp16-split conv kernels inside the training step.  Every conv launched through conv_launch takes a
+// fresh slot array from a pool for max |out| and records it under its output pointer; a later conv whose input pointer (and
+// weight panel) has a recorded range runs the fp16 kernels, anything else (tensors written by other kernels: pooling, loss
+// gradients, head gathers) falls back to the range-free bf16 split.  The pool is zeroed at the start of each pass.
+constexpr int RANGE_POOL = 768;             // forward chain 1 [0, 256) | forward chain 2 [256, 512) | backward [512, 768)
+constexpr int RANGE_FWD = 256;
+
 struct RangeCtx {
     float* pool = nullptr;            // RANGE_POOL slot arrays of ABSMAX_SLOTS floats
     float* prev = nullptr;            // the pool as the previous pass of the same kind (forward / backward) left it: scales of the fp16 copies
     int next = 0, limit = 0;
-    std::map<const void*, const float*> of;     // tensor / panel pointer -> its slot array
+    std::map<const void*, const float*> slots;  // tensor / panel pointer -> its slot array
     // second forward chain (frames [n1, B)): its own slot arrays, CHAIN2_OFF arrays above the first chain's and taken in the same
     // order, so that each chain's scales depend on its own frames only (deterministic) and one elementwise max after the join
     // gives the backward pass the ranges of the whole tensors
-    std::map<const void*, const float*> of2;
+    std::map<const void*, const float*> slots2;
     int next2 = 0;
     bool chain2 = false;
     bool on = false;
+    // the next slot array of the running pass (of the running chain); the ORDER of these calls pairs a tensor with its slots of one step ago
+    float* take() {
+        if (!on || !pool) return nullptr;
+        if (chain2) {
+            if (next2 >= RANGE_FWD) return nullptr;
+            return pool + (size_t)(RANGE_FWD + next2++) * dgp::ABSMAX_SLOTS;
+        }
+        if (next >= limit) return nullptr;
+        return pool + (size_t)(next++) * dgp::ABSMAX_SLOTS;
+    }
+    const float* of(const void* p) const {
+        if (!on) return nullptr;
+        if (chain2) {                     // the chain's own tensors first; weight panels are shared
+            auto it2 = slots2.find(p);
+            if (it2 != slots2.end()) return it2->second;
+        }
+        auto it = slots.find(p);
+        return it == slots.end() ? nullptr : it->second;
+    }
+    void set(const void* p, const float* slot) {
+        auto& m = chain2 ? slots2 : slots;
+        if (slot) m[p] = slot; else m.erase(p);
+    }
+    // previous-step slots of the tensor that takes `slot` in this pass (the passes take their slots in the same order every step)
+    const float* prev_of(const float* slot) const {
+        if (!slot || !pool || !prev) return nullptr;
+        long long idx = (slot - pool) / dgp::ABSMAX_SLOTS;
+        if (idx < 0 || idx >= RANGE_POOL) return nullptr;
+        if (idx >= RANGE_FWD && idx < 2 * RANGE_FWD) idx -= RANGE_FWD;      // chain 2 writes its frames of the same copy with the same scale
+        return prev + idx * dgp::ABSMAX_SLOTS;
+    }
 };
+
+// Per-trainer launch state that outlives a pass (two trainers, or a trainer created after another was destroyed, must not see each
+// other's range maps, fp16 cell tables or copies).  A pass reaches it through its TrainPass; nothing here is bound to a thread.
 struct TrainCtx {
-    float* tail_slab = nullptr;                  // K-split slab of the running forward / backward pass (a region of the caller's workspace)
     RangeCtx rng;
     std::unordered_map<const float*, const float*> cells;      // weight panel -> the same panel pre-split into fp16 cells
     std::unordered_map<const float*, const void*> cells1;      // ... -> its high-only H1 cells (16-bit tier, launch_pack_h1)
-    const void* defer_plan = nullptr;            // TPlan of the running backward pass: every layer's dWraw / colsum region (layer_param_grads)
-    char* defer_ws = nullptr;
     // Weight gradients on a second stream (EXPERIMENTS.md section 6a (8)): the data-gradient chain is the critical path of the backward pass
     // and its 11-frame grids leave CUs idle; a layer's weight gradient only needs (x, dY) and is not needed before the finalisation
-    // launches, so it runs on `s2` behind an event and the chain goes on.  readers: events recorded on s2 behind the launches that
-    // READ a gradient buffer -- the chain waits for them before it overwrites that buffer.
+    // launches, so it runs on `s2` behind an event and the chain goes on (WgradSide).  The forward pass runs its second chain of frames there.
     hipStream_t s2 = nullptr;
     std::vector<hipEvent_t> ev_pool;
     size_t ev_next = 0;
-    std::multimap<const void*, hipEvent_t> readers;
-    bool overlap = false;                        // set for the duration of a backward pass
     // fp16 high / low copies of retained activations and gradient buffers (ConvArgs::shadow), operands of wgrad_dma:
     // tensor base -> copy base (from the plan, per pass); tensor base -> previous-step range slots of the launch that WROTE the copy
     // in this pass (absent: no copy of the current contents exists)
@@ -1585,6 +1617,14 @@ struct TrainCtx {
             ev_pool.push_back(e);
         }
         return ev_pool[ev_next++];
+    }
+    // `t` exists only as fp16 cells (an H2 / H1 tensor) scaled by the previous-step slots `pv`: weight gradients read it in place, and the
+    // pass checks this step's range against the prediction at its end
+    void note_cells(const void* t, const float* pv) {
+        shadow_base[t] = const_cast<float*>(static_cast<const float*>(t));
+        shadow_prev[t] = pv;
+        const int idx = (int)((pv - rng.prev) / dgp::ABSMAX_SLOTS);
+        if (std::find(h2_slots.begin(), h2_slots.end(), idx) == h2_slots.end()) h2_slots.push_back(idx);
     }
 };
 
@@ -1684,8 +1724,7 @@ size_t al(size_t x) { return (x + 255) / 256 * 256; }
 int heads_ct(int nj) { return (next_pow2(4 * nj) + next_pow2(8 * nj) + 63) / 64 * 64; }
 
 TPlan make_tplan(const dgp_trainer* tr, int B) {
-    const dgp_net* net = tr->net;
-    const dgp_net_desc& d = net->desc;
+    const dgp_net* net = tr->net; const dgp_net_desc& d = net->desc;
     TPlan p;
     size_t o = 0;
     auto take = [&](size_t nfl) { size_t r = o; o += al(nfl * sizeof(float)); return r; };
@@ -1756,16 +1795,6 @@ TPlan make_tplan(const dgp_trainer* tr, int B) {
     return p;
 }
 
-// K-split slab of the running forward / backward pass (a region of the caller's workspace)
-static thread_local TrainCtx* g_ctx = nullptr;      // the trainer whose entry point is running on this thread
-
-// Operand ranges for the fp16-split conv kernels inside the training step.  Every conv launched through conv_launch takes a
-// fresh slot array from a pool for max |out| and records it under its output pointer; a later conv whose input pointer (and
-// weight panel) has a recorded range runs the fp16 kernels, anything else (tensors written by other kernels: pooling, loss
-// gradients, head gathers) falls back to the range-free bf16 split.  The pool is zeroed at the start of each pass.
-constexpr int RANGE_POOL = 768;             // forward chain 1 [0, 256) | forward chain 2 [256, 512) | backward [512, 768)
-constexpr int RANGE_FWD = 256;
-
 __global__ __launch_bounds__(256) void range_merge_kernel(float* __restrict__ a, const float* __restrict__ b, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) { const float x = a[i], y = b[i]; a[i] = (y > x || y != y) ? y : x; }      // non-negative maxima; a NaN stays
@@ -1780,43 +1809,27 @@ __global__ __launch_bounds__(256) void range_roll_kernel(float* __restrict__ poo
     if (i == 0 && flag) *flag = 0;
 }
 
-static float* range_take() {
-    if (!g_ctx || !g_ctx->rng.on || !g_ctx->rng.pool) return nullptr;
-    if (g_ctx->rng.chain2) {
-        if (g_ctx->rng.next2 >= RANGE_FWD) return nullptr;
-        return g_ctx->rng.pool + (size_t)(RANGE_FWD + g_ctx->rng.next2++) * ABSMAX_SLOTS;
-    }
-    if (g_ctx->rng.next >= g_ctx->rng.limit) return nullptr;
-    return g_ctx->rng.pool + (size_t)(g_ctx->rng.next++) * ABSMAX_SLOTS;
-}
-static const float* range_of(const void* p) {
-    if (!g_ctx || !g_ctx->rng.on) return nullptr;
-    if (g_ctx->rng.chain2) {                     // the chain's own tensors first; weight panels are shared
-        auto it2 = g_ctx->rng.of2.find(p);
-        if (it2 != g_ctx->rng.of2.end()) return it2->second;
-    }
-    auto it = g_ctx->rng.of.find(p);
-    return it == g_ctx->rng.of.end() ? nullptr : it->second;
-}
-static void range_set(const void* p, const float* slot) {
-    auto& m = g_ctx->rng.chain2 ? g_ctx->rng.of2 : g_ctx->rng.of;
-    if (slot) m[p] = slot; else m.erase(p);
-}
+#define TRY_HIP(expr)                                                                               \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) return fail(DGP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
 
 // Start of a forward or a backward pass.  Forward: everything fresh (first half of the pool).  Backward: the forward tensors'
 // ranges stay (weight gradients read the retained activations), gradient tensors take slots from the second half.
 static void range_pass_begin(dgp_trainer* tr, hipStream_t s, bool backward, int* flag_to_clear = nullptr) {
     static const bool enabled = (dgp_tune("DGP_TRAIN_F16", 1) != 0) && conv_mode() == ConvMode::F16x3;
-    g_ctx->rng.on = enabled && tr->d_rng_pool && tr->d_wrng;
-    g_ctx->rng.pool = tr->d_rng_pool;
+    RangeCtx& rng = tr->ctx.rng;
+    rng.on = enabled && tr->d_rng_pool && tr->d_wrng;
+    rng.pool = tr->d_rng_pool;
     const size_t fwd_bytes = (size_t)(2 * RANGE_FWD) * ABSMAX_SLOTS * sizeof(float);
     const size_t bwd_bytes = (size_t)(RANGE_POOL - 2 * RANGE_FWD) * ABSMAX_SLOTS * sizeof(float);
-    g_ctx->rng.chain2 = false;
-    if (!backward) { g_ctx->rng.of.clear(); g_ctx->rng.of2.clear(); g_ctx->rng.next = 0; g_ctx->rng.next2 = 0; g_ctx->rng.limit = RANGE_FWD; }
-    else { g_ctx->rng.next = 2 * RANGE_FWD; g_ctx->rng.limit = RANGE_POOL; }
-    g_ctx->rng.prev = tr->d_rng_prev;
-    if (!backward) g_ctx->shadow_prev.clear();
-    if (!g_ctx->rng.on) return;
+    rng.chain2 = false;
+    if (!backward) { rng.slots.clear(); rng.slots2.clear(); rng.next = 0; rng.next2 = 0; rng.limit = RANGE_FWD; }
+    else { rng.next = 2 * RANGE_FWD; rng.limit = RANGE_POOL; }
+    rng.prev = tr->d_rng_prev;
+    if (!backward) tr->ctx.shadow_prev.clear();
+    if (!rng.on) return;
     // what this kind of pass measured one step ago predicts the scales of this pass's fp16 copies (chain 2's own slots are not needed:
     // after the merge chain 1's hold the maxima of the whole tensors)
     {
@@ -1829,27 +1842,11 @@ static void range_pass_begin(dgp_trainer* tr, hipStream_t s, bool backward, int*
     if (backward) return;
     const size_t nl = tr->net->layers.size();
     for (size_t li = 0; li < nl; ++li) {
-        if (tr->net->layers[li].d_w) g_ctx->rng.of[tr->net->layers[li].d_w] = tr->d_wrng + li * ABSMAX_SLOTS;
-        if (tr->tl[li].d_wT) g_ctx->rng.of[tr->tl[li].d_wT] = tr->d_wrng + (nl + li) * ABSMAX_SLOTS;
+        if (tr->net->layers[li].d_w) rng.slots[tr->net->layers[li].d_w] = tr->d_wrng + li * ABSMAX_SLOTS;
+        if (tr->tl[li].d_wT) rng.slots[tr->tl[li].d_wT] = tr->d_wrng + (nl + li) * ABSMAX_SLOTS;
     }
-    if (tr->d_hmT && tr->d_hm_rng) g_ctx->rng.of[tr->d_hmT] = tr->d_hm_rng;
+    if (tr->d_hmT && tr->d_hm_rng) rng.slots[tr->d_hmT] = tr->d_hm_rng;
 }
-
-
-// previous-step slots of the tensor that takes `slot` in this pass (the passes take their slots in the same order every step)
-static const float* range_prev_of(const float* slot) {
-    if (!slot || !g_ctx || !g_ctx->rng.pool || !g_ctx->rng.prev) return nullptr;
-    long long idx = (slot - g_ctx->rng.pool) / ABSMAX_SLOTS;
-    if (idx < 0 || idx >= RANGE_POOL) return nullptr;
-    if (idx >= RANGE_FWD && idx < 2 * RANGE_FWD) idx -= RANGE_FWD;      // chain 2 writes its frames of the same copy with the same scale
-    return g_ctx->rng.prev + idx * ABSMAX_SLOTS;
-}
-static thread_local bool g_shadow_want = true;      // backward pass: only gradients that a 128 x 128 weight-gradient tile will read
-// fast pass: formats of the NEXT conv_launch (consumed by it).  An H2 tensor's scale is the one predicted from the previous step's slots
-// of the tensor named by the launch's in_key / out_key / res_key.
-struct H2Launch { int in_fmt = 0, out_fmt = 0, res_fmt = 0, mask_fmt = 0; const void* res_key = nullptr; };
-static thread_local H2Launch g_h2;
-static thread_local int g_shadow_fmt = 1;            // format of the fp16 copies written in this pass: 1 H2 (high / low), 2 H1 (tier 1: high only)
 
 // weight panel -> the same panel pre-split into fp16 cells (filled by dgp_trainer_sync_weights): with the cells and both ranges the
 // conv runs on the compute-side-split / LDS-DMA kernels of the inference engine
@@ -1858,100 +1855,237 @@ static thread_local int g_shadow_fmt = 1;            // format of the fp16 copie
 // 16x16x32 kernels: 17.0 -> 16.2 ms per step.  (With one pack launch per layer and panel the packing cost what the kernels saved.)
 static const bool g_train_cells = (dgp_tune("DGP_TRAIN_CELLS", 1) != 0);
 
-hipError_t conv_launch(const ConvLayer& l, const float* wpk, int nk, int coutP, const float* in, int N, int H, int W,
-                       int Cin, int pad_t, int pad_l, int Ho, int Wo, int Cout, int stride, int up, const float* scale,
-                       const float* bias, const float* res, int res_s, int res_H, int res_W, const float* mask,
-                       bool relu, int out_mode, int dc_nj, float* out, hipStream_t s, const void* in_key = nullptr,
-                       const void* out_key = nullptr) {
+// first unit whose tensors a fast pass keeps as cells: the first one with a 128-channel bottleneck (block2; its input is the fp16 copy --
+// ConvArgs::shadow -- of block1's output), or EVERY unit for an H1 pass (16-bit tier: the first one reads the H1 copy of the pool output)
+size_t first_cell_unit(const dgp_net* net, const TPlan& pl, bool h1) {
+    if (h1 && pl.sh_pool) return 0;
+    for (size_t ui = 1; ui < net->units.size(); ++ui)
+        if (net->units[ui].depth_bn >= 128 && pl.sh_xo[ui - 1]) return ui;
+    return net->units.size();
+}
+
+// Weight gradients beside the data-gradient chain of a backward pass (TrainCtx::s2).  readers: events recorded on s2 behind the launches
+// that READ a gradient buffer -- the chain waits for them before it overwrites that buffer.
+struct WgradSide {
+    TrainCtx* c = nullptr;
+    hipStream_t s = nullptr;                     // the chain's stream
+    bool on = false;
+    std::multimap<const void*, hipEvent_t> readers;
+    void begin(TrainCtx* ctx, hipStream_t chain) { c = ctx; s = chain; on = true; c->ev_next = 0; }
+    // st <- the stream for a launch that may run beside the chain: s2 behind everything enqueued on the chain's stream so far, or the chain's
+    int fork(hipStream_t& st) {
+        st = s;
+        if (!on) return DGP_OK;
+        hipEvent_t ready = c->take_event();
+        if (!ready) return fail(DGP_ERR_HIP, "weight-gradient stream: hipEventCreate failed");
+        TRY_HIP(hipEventRecord(ready, s));
+        TRY_HIP(hipStreamWaitEvent(c->s2, ready, 0));
+        st = c->s2;
+        return DGP_OK;
+    }
+    // everything enqueued on s2 so far reads `buf`
+    int reads(const void* buf) {
+        hipEvent_t done = c->take_event();
+        if (!done) return fail(DGP_ERR_HIP, "weight-gradient stream: hipEventCreate failed");
+        TRY_HIP(hipEventRecord(done, c->s2));
+        readers.emplace(buf, done);
+        return DGP_OK;
+    }
+    // the chain is about to overwrite `buf`: wait for the weight-gradient launches that still read it
+    hipError_t before_write(const void* buf) {
+        if (!on) return hipSuccess;
+        auto range = readers.equal_range(buf);
+        for (auto it = range.first; it != range.second; ++it) {
+            hipError_t e2 = hipStreamWaitEvent(s, it->second, 0);
+            if (e2 != hipSuccess) return e2;
+        }
+        readers.erase(range.first, range.second);
+        return hipSuccess;
+    }
+    // the chain's stream waits for every weight gradient (before the finalisation launches, and on every exit path)
+    void join() {
+        if (!on) return;
+        on = false;
+        readers.clear();
+        hipEvent_t e = c->take_event();
+        if (e && hipEventRecord(e, c->s2) == hipSuccess) (void)hipStreamWaitEvent(s, e, 0);
+        else (void)hipStreamSynchronize(c->s2);
+    }
+    ~WgradSide() { join(); }
+};
+
+// One pass of the training step: a stack object of dgp_train_forward / dgp_train_backward, handed to everything that launches.
+struct TrainPass {
+    dgp_trainer* tr; TrainCtx& ctx; const dgp_net* net; const TPlan& pl;
+    hipStream_t s;                  // the caller's stream
+    char* ws;                       // workspace base
+    int B;
+    bool fast = false;              // units >= ub keep their tensors as cells with predicted scales (dgp_trainer_fast_mode)
+    int fmt = 1;                    // cell format of the pass: 1 H2 (high / low), 2 H1 (tier 1: high only)
+    size_t ub = 0;
+    float* slab = nullptr;          // K-split slab for the launches of the running chain (null: forward chain 2)
+    bool stem_fused = false;        // forward: the root block as the inference engine's one kernel
+    // backward
+    WgradSide side;
+    struct { const FinDesc* tab = nullptr; int max_cout = 0, max_krows = 0; } fin;      // grids of the deferred finalisation's table launches
+    float *G[2] = {nullptr, nullptr}, *GH[2] = {nullptr, nullptr};      // d loss / d (unit output), ping-pong: fp32 | as H1 tensors (tier 1)
+    int cur = 0;
+    bool heads_h1 = false, stem_wgrad_h1 = false;
+    const float *stem_g = nullptr, *stem_g_prev = nullptr;              // unit 0's data gradient left as an H1 tensor for stem_wgrad_h1_kernel
+    size_t grp_next = 0;            // next gradient group to complete
+    TrainPass(dgp_trainer* t, hipStream_t st, void* workspace, const TPlan& p, int nt)
+        : tr(t), ctx(t->ctx), net(t->net), pl(p), s(st), ws((char*)workspace), B(nt) { slab = F(p.tail); }
+    float* F(size_t off) const { return (float*)(ws + off); }
+    bool h1p() const { return fast && fmt == 2; }              // every tensor of units >= ub is H1-only
+    int copy_fmt() const { return h1p() ? 2 : 1; }             // format of the fp16 copies (ConvArgs::shadow) written in this pass
+    int nu() const { return (int)net->units.size(); }
+};
+
+// One conv launch of the training step: a panel, the geometry as the kernels see it (a data gradient: the transposed conv), range keys, cell
+// formats, the fp16 copy.  conv_call() / dgrad_call() give the common cases, a call site names what differs (as ConvCall in dgp_net.hip).
+struct ConvCall {
+    dgp_conv_desc d{};                          // N, grids, channels, taps, padding, ReLU, residual mode and extent
+    const float* wpk = nullptr;                 // the panel as packed: nk K-steps x coutP columns
+    int nk = 0, coutP = 0;
+    const float *scale = nullptr, *bias = nullptr;
+    const float *in = nullptr, *res = nullptr, *mask = nullptr;
+    float* out = nullptr;
+    int up = 0;                                 // > 1: the input is read on the zero-stuffed grid (data gradient of a strided conv)
+    int out_mode = 0, dc_nj = 0;                // 1: a head's phase scatter with dc_nj channels per phase
     // in_key / out_key: the tensors under whose names this launch looks up / registers range slots when `in` / `out` are frame ranges
     // inside them (the forward pass as two chains of frames; each chain keeps its own slots, merged after the join)
+    const void *in_key = nullptr, *out_key = nullptr;
+    // fast pass: cell formats of the launch's tensors (0: fp32).  An H2 / H1 tensor's scale is the one predicted from the previous step's
+    // slots of the tensor named by in_key / out_key / res_key.
+    int in_fmt = 0, out_fmt = 0, res_fmt = 0, mask_fmt = 0;
+    const void* res_key = nullptr;
+    bool copy = true;                           // the output gets an fp16 copy where it has a region for one (backward: only gradients that a 128 x 128 weight-gradient tile will read)
+    ConvCall& grid(int ho, int wo, int pt = 0, int pl = 0) { d.Ho = ho; d.Wo = wo; d.pad_t = pt; d.pad_l = pl; return *this; }
+    ConvCall& strided(int s) { d.stride = s; return *this; }
+    ConvCall& upsampled(int u) { up = u; return *this; }
+    // residual [N, rH, rW, Cout]; mode s >= 1: read at (ho s, wo s), -2: the subsample shortcut's gradient on the 2x coarser grid
+    ConvCall& residual(const float* r, int s, int rH, int rW) { res = r; d.res_stride = r ? s : 0; d.res_H = rH; d.res_W = rW; return *this; }
+    ConvCall& gate(const float* m, int fmt = 0) { mask = m; mask_fmt = fmt; return *this; }      // out = 0 where m <= 0 (m as fp32 or as cells)
+    ConvCall& linear() { d.relu = 0; return *this; }
+    ConvCall& head_scatter(int nj) { out_mode = 1; dc_nj = nj; return *this; }
+    ConvCall& keys(const void* ik, const void* ok) { in_key = ik; out_key = ok; return *this; }
+    ConvCall& cells(int fmt, const void* rkey = nullptr) { in_fmt = out_fmt = fmt; res_fmt = rkey ? fmt : 0; res_key = rkey; return *this; }
+    // the heads' data gradient: the 2x2-conv form, dy padded to cdy phase columns; optionally both heads' merged panel of nkT K-steps
+    ConvCall& head_taps(int cdy) { d.KH = d.KW = 2; d.rate = 1; d.Cin = cdy; return *this; }
+    ConvCall& panel(const float* w, int nkT) { wpk = w; nk = nkT; return *this; }
+    ConvCall& no_copy(bool none = true) { copy = !none; return *this; }
+};
+// forward conv of layer l on the input's own grid: its panel, BN affine, ReLU
+ConvCall conv_call(const ConvLayer& l, const float* in, int N, int H, int W, float* out) {
+    ConvCall c;
+    c.d.N = N; c.d.H = c.d.Ho = H; c.d.W = c.d.Wo = W; c.d.Cin = l.Cin; c.d.Cout = l.Cout;
+    c.d.KH = l.KH; c.d.KW = l.KW; c.d.stride = 1; c.d.rate = l.rate; c.d.relu = 1;
+    c.wpk = l.d_w; c.nk = l.nk; c.coutP = l.CoutP; c.scale = l.has_bn ? l.d_scale : nullptr; c.bias = l.d_bias;
+    c.in = in; c.out = out;
+    return c;
+}
+// data gradient of layer l: dy [N, H, W, l.Cout] through the transposed panel -> dx [N, H, W, l.Cin] on the same grid, no affine, linear
+ConvCall dgrad_call(const ConvLayer& l, const TLayer& t, const float* dy, int N, int H, int W, float* dx) {
+    ConvCall c;
+    c.d.N = N; c.d.H = c.d.Ho = H; c.d.W = c.d.Wo = W; c.d.Cin = l.Cout; c.d.Cout = l.Cin;
+    c.d.KH = l.KH; c.d.KW = l.KW; c.d.stride = 1; c.d.rate = l.rate;
+    c.wpk = t.d_wT; c.nk = t.nkT; c.coutP = t.cinP;
+    c.in = dy; c.out = dx;
+    return c;
+}
+
+hipError_t conv_launch(TrainPass& p, const ConvCall& c, hipStream_t s) {
+    TrainCtx& ctx = p.ctx; RangeCtx& rng = ctx.rng;
     ConvArgs a{};
-    a.in = in; a.wpk = wpk; a.scale = scale; a.bias = bias; a.res = res; a.mask = mask; a.out = out;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.log2cin4 = ilog2(Cin / 4);
-    a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.CoutP = coutP;
-    a.KH = l.KH; a.KW = l.KW; a.stride = stride; a.dil = l.rate; a.pad_t = pad_t; a.pad_l = pad_l;
-    a.ntaps = l.KH * l.KW; a.nk = nk; a.M = N * Ho * Wo;
-    a.res_s = res ? res_s : 0; a.res_H = res_H; a.res_W = res_W; a.up = up;
-    a.relu = relu ? 1 : 0; a.out_mode = out_mode; a.dc_nj = dc_nj;
-    if ((double)N * H * W * Cin * 4 > 4294967000.0 || (double)a.M * Cout * 4 > 4294967000.0 ||
-        (res && (double)N * res_H * res_W * Cout * 4 > 4294967000.0))
-        return hipErrorInvalidValue;              // 32-bit buffer descriptors: every tensor stays below 4 GiB (lower the batch)
-    a.in_bytes = (unsigned)((size_t)N * H * W * Cin * 4);
-    a.out_bytes = (unsigned)((size_t)a.M * Cout * 4);
-    a.res_bytes = res ? (unsigned)((size_t)N * res_H * res_W * Cout * 4) : 0u;
-    a.w_bytes = (unsigned)((size_t)nk * 8 * coutP * 16);
-    a.slab = g_ctx->tail_slab; a.slab_bytes = g_ctx->tail_slab ? (unsigned)(TAIL_SLAB_FLOATS * sizeof(float)) : 0u;
-    const H2Launch h2 = g_h2;
-    g_h2 = H2Launch();
-    const float* rin = range_of(in_key ? in_key : in);
-    const float* rw = range_of(wpk);
-    a.mask_fmt = h2.mask_fmt;
-    if (h2.in_fmt || h2.out_fmt || h2.res_fmt) {
-        if (!(rin && rw && out_mode == 0 && h2.in_fmt && h2.out_fmt == h2.in_fmt && (!h2.res_fmt || h2.res_fmt == h2.in_fmt))) return hipErrorInvalidValue;
-        a.in_fmt = h2.in_fmt; a.out_fmt = h2.out_fmt; a.res_fmt = h2.res_fmt;
-        a.in_scale_dev = range_prev_of(rin);
-        if (h2.res_fmt) a.res_scale_dev = range_prev_of(range_of(h2.res_key));
-        if (!a.in_scale_dev || (h2.res_fmt && !a.res_scale_dev)) return hipErrorInvalidValue;
+    a.in = c.in; a.wpk = c.wpk; a.scale = c.scale; a.bias = c.bias; a.res = c.res; a.mask = c.mask; a.out = c.out;
+    if (fill_conv_geometry(a, c.d, TOO_BIG)) return hipErrorInvalidValue;       // 32-bit buffer descriptors: every tensor stays below 4 GiB (lower the batch)
+    a.CoutP = c.coutP; a.nk = c.nk; a.w_bytes = (unsigned)((size_t)c.nk * 8 * c.coutP * 16);      // (the panel as the trainer packed it)
+    a.up = c.up; a.out_mode = c.out_mode; a.dc_nj = c.dc_nj;
+    a.slab = p.slab; a.slab_bytes = p.slab ? (unsigned)(TAIL_SLAB_FLOATS * sizeof(float)) : 0u;
+    const int out_mode = c.out_mode;
+    const float* rin = rng.of(c.in_key ? c.in_key : c.in);
+    const float* rw = rng.of(c.wpk);
+    a.mask_fmt = c.mask_fmt;
+    if (c.in_fmt || c.out_fmt || c.res_fmt) {
+        if (!(rin && rw && out_mode == 0 && c.in_fmt && c.out_fmt == c.in_fmt && (!c.res_fmt || c.res_fmt == c.in_fmt))) return hipErrorInvalidValue;
+        a.in_fmt = c.in_fmt; a.out_fmt = c.out_fmt; a.res_fmt = c.res_fmt;
+        a.in_scale_dev = rng.prev_of(rin);
+        if (c.res_fmt) a.res_scale_dev = rng.prev_of(rng.of(c.res_key));
+        if (!a.in_scale_dev || (c.res_fmt && !a.res_scale_dev)) return hipErrorInvalidValue;
     }
     if (rin && rw && out_mode == 0) {
         a.in_absmax = rin; a.w_absmax = rw;
-        const auto c = g_ctx->cells.find(wpk);
-        if (g_train_cells && c != g_ctx->cells.end()) { a.wh3 = c->second; a.wh3_bytes = a.w_bytes; }
+        const auto cl = ctx.cells.find(c.wpk);
+        if (g_train_cells && cl != ctx.cells.end()) { a.wh3 = cl->second; a.wh3_bytes = a.w_bytes; }
         if (a.in_fmt == 2) {                       // H1 operands: the panel's high-only cells (none: launch_conv refuses)
-            const auto c1 = g_ctx->cells1.find(wpk);
-            a.wh3 = c1 != g_ctx->cells1.end() ? c1->second : nullptr;
+            const auto c1 = ctx.cells1.find(c.wpk);
+            a.wh3 = c1 != ctx.cells1.end() ? c1->second : nullptr;
             a.wh3_bytes = a.w_bytes;               // (fp32-panel bytes: launch_conv halves both for H1 cells)
         }
     }
+    const void* key = c.out_key ? c.out_key : (const void*)c.out;
     if (out_mode == 0) {
-        a.out_absmax = range_take();
-        range_set(out_key ? out_key : out, a.out_absmax);
+        a.out_absmax = rng.take();
+        rng.set(key, a.out_absmax);
     }
-    const int tile = pick_tile(a.M, coutP, nk * BK, a.in_absmax && a.w_absmax);
+    const int tile = pick_tile(a.M, a.CoutP, a.nk * BK, a.in_absmax && a.w_absmax);
     if (a.out_fmt) {
         // the output IS the fp16 high / low tensor: later weight-gradient launches read it in place
-        const void* key = out_key ? out_key : (const void*)out;
-        a.out_scale_dev = range_prev_of(a.out_absmax);
+        a.out_scale_dev = rng.prev_of(a.out_absmax);
         if (!a.out_scale_dev || !a.wh3) return hipErrorInvalidValue;
-        g_ctx->shadow_base[key] = const_cast<float*>(static_cast<const float*>(key));
-        g_ctx->shadow_prev[key] = a.out_scale_dev;
-        const int idx = (int)((a.out_scale_dev - g_ctx->rng.prev) / ABSMAX_SLOTS);
-        if (std::find(g_ctx->h2_slots.begin(), g_ctx->h2_slots.end(), idx) == g_ctx->h2_slots.end()) g_ctx->h2_slots.push_back(idx);
-    } else if (g_ctx && out_mode == 0) {
+        ctx.note_cells(key, a.out_scale_dev);
+    } else if (out_mode == 0) {
         // fp16 copy of the output for wgrad_dma: kernels that end in ls_epilogue / tail_fixup_kernel write it
-        const void* key = out_key ? out_key : (const void*)out;
-        const auto sb = g_ctx->shadow_base.find(key);
-        const float* prev = range_prev_of(a.out_absmax);
-        if (sb != g_ctx->shadow_base.end() && g_shadow_want && prev && (tile == TILE_128x128_H3K32 || tile == TILE_128x64_H3) &&
-            a.in_absmax && a.w_absmax && Cin >= 32 && Cout % 8 == 0) {
-            a.shadow_fmt = g_shadow_fmt;
-            a.shadow = g_shadow_fmt == 2 ? reinterpret_cast<float*>(reinterpret_cast<char*>(sb->second) + (out - static_cast<const float*>(key)) * 2)
-                                         : sb->second + (out - static_cast<const float*>(key));
+        const auto sb = ctx.shadow_base.find(key);
+        const float* prev = rng.prev_of(a.out_absmax);
+        if (sb != ctx.shadow_base.end() && c.copy && prev && (tile == TILE_128x128_H3K32 || tile == TILE_128x64_H3) &&
+            a.in_absmax && a.w_absmax && a.Cin >= 32 && a.Cout % 8 == 0) {
+            const ptrdiff_t off = c.out - static_cast<const float*>(key);
+            a.shadow_fmt = p.copy_fmt();
+            a.shadow = a.shadow_fmt == 2 ? reinterpret_cast<float*>(reinterpret_cast<char*>(sb->second) + off * 2) : sb->second + off;
             a.shadow_prev = prev;
-            g_ctx->shadow_prev[key] = prev;
+            ctx.shadow_prev[key] = prev;
         } else {
-            g_ctx->shadow_prev.erase(key);
+            ctx.shadow_prev.erase(key);
         }
     }
     return launch_conv(a, tile, s);
 }
 
-hipError_t wgrad_launch(const float* x, int N, int H, int W, int Cin, const float* dy, int Ho, int Wo, int Cdy, int KH,
-                        int KW, int stride, int dil, int pad_t, int pad_l, float* dwraw, float* colsum, hipStream_t s,
-                        bool zeroed = false, const float* rx_given = nullptr, const float* rdy_given = nullptr,
-                        const void* xs = nullptr, const float* x_prev = nullptr, const void* dys = nullptr, const float* dy_prev = nullptr,
-                        int* x_h2_only_flag = nullptr, bool h1 = false) {
-    // x_h2_only_flag: x exists only as H2 cells (xs; fast pass) -- the LDS-DMA tile is the only kernel that can read it, and copies that
-    // left their predicted range raise the flag instead of falling back
+// One operand of a weight gradient: the fp32 tensor, this step's range slots (null: unknown) and, where the operand also exists as fp16
+// cells -- a copy its producer wrote, or the tensor itself in a fast pass -- the cells and the previous-step slots that scaled them
+struct WgradOperand {
+    const float* p = nullptr;
+    const float* rng = nullptr;
+    const void* cells = nullptr;
+    const float* prev = nullptr;
+};
+// dWraw[(tap, ci)][co] = sum over pixels of x[m + tap][ci] * dy[m][co], colsum[co] = sum of dy[m][co]
+struct WgradCall {
+    dgp_conv_desc d{};                          // the forward conv: x [N, H, W, Cin] -> dy [N, Ho, Wo, Cout]
+    WgradOperand x, dy;
+    float *dwraw = nullptr, *colsum = nullptr;  // output scratch
+    bool zeroed = false;                        // the scratch was zeroed for the whole pass
+    // x exists only as cells (fast pass): the LDS-DMA tile is the only kernel that can read it, and copies that left their predicted range
+    // raise the flag instead of falling back
+    int* fail_flag = nullptr;
+    bool h1 = false;                            // 16-bit tier: both operands are H1 tensors (in place or the H1 copy of a boundary tensor)
+};
+
+hipError_t wgrad_launch(const WgradCall& c, hipStream_t s) {
+    const dgp_conv_desc& d = c.d;
+    const int N = d.N, Cin = d.Cin, Cdy = d.Cout;
+    float* const dwraw = c.dwraw; float* const colsum = c.colsum;
     WgradArgs a{};
-    a.x = x; a.dy = dy; a.dw = dwraw; a.colsum = colsum; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.log2cin4 = ilog2(Cin / 4);
-    a.Ho = Ho; a.Wo = Wo; a.Cdy = Cdy; a.KW = KW; a.stride = stride; a.dil = dil; a.pad_t = pad_t; a.pad_l = pad_l;
-    a.ntaps = KH * KW; a.kchunks = KH * KW * (Cin / 4); a.M = N * Ho * Wo;
-    if ((double)N * H * W * Cin * 4 > 4294967000.0 || (double)a.M * Cdy * 4 > 4294967000.0) return hipErrorInvalidValue;
-    a.x_bytes = (unsigned)((size_t)N * H * W * Cin * 4);
-    a.dy_bytes = (unsigned)((size_t)a.M * Cdy * 4);
+    a.x = c.x.p; a.dy = c.dy.p; a.dw = dwraw; a.colsum = colsum; a.N = N; a.H = d.H; a.W = d.W; a.Cin = Cin; a.log2cin4 = ilog2(Cin / 4);
+    a.Ho = d.Ho; a.Wo = d.Wo; a.Cdy = Cdy; a.KW = d.KW; a.stride = d.stride; a.dil = d.rate; a.pad_t = d.pad_t; a.pad_l = d.pad_l;
+    a.ntaps = d.KH * d.KW; a.kchunks = d.KH * d.KW * (Cin / 4); a.M = N * a.Ho * a.Wo;
+    const double xb = (double)N * a.H * a.W * Cin * 4, dyb = (double)a.M * Cdy * 4;
+    if (!fits_descriptor({xb, dyb})) return hipErrorInvalidValue;
+    a.x_bytes = (unsigned)xb;
+    a.dy_bytes = (unsigned)dyb;
     hipError_t e = hipSuccess;
-    if (zeroed) {
+    if (c.zeroed) {
         // per-layer scratch, zeroed once for the whole pass (dgp_train_backward)
     } else if (colsum && colsum + 2 * 4096 == dwraw) {      // the plan's layout: [colsum | dot][dwraw] -> one fill
         e = hipMemsetAsync(colsum, 0, ((size_t)2 * 4096 + (size_t)a.kchunks * 4 * Cdy) * sizeof(float), s);
@@ -1964,6 +2098,7 @@ hipError_t wgrad_launch(const float* x, int N, int H, int W, int Cin, const floa
             if (e != hipSuccess) return e;
         }
     }
+    const bool h1 = c.h1;
     const bool big = h1 || (a.kchunks * 4 >= 128 && Cdy >= 128);       // (H1 operands: the LDS-DMA tile, partly filled for the 64-channel layers)
     const int BR = big ? 128 : 64;
     const int kt = (a.kchunks * 4 + BR - 1) / BR, nt = (Cdy + BR - 1) / BR;
@@ -1982,34 +2117,33 @@ hipError_t wgrad_launch(const float* x, int N, int H, int W, int Cin, const floa
     static bool attr_dev[16][3] = {};
     auto& attr = attr_dev[dgp_device_slot()];
     static const bool h3_env = (dgp_tune("DGP_WGRAD_F16", 1) != 0);       // A/B switch
-    const float* rx = rx_given ? rx_given : range_of(x);
-    const float* rdy = rdy_given ? rdy_given : range_of(dy);
+    const float *rx = c.x.rng, *rdy = c.dy.rng;
     // both operands also exist as fp16 high / low copies written by their producers: LDS-DMA tile (falls back per workgroup to the
     // fp32-MFMA tile when this step's ranges left the copies' predicted scales)
     // (guards: the kernel's offset walkers run up to 15 (row0) + 63 (sub-steps rounded up to four) + 64 (four prefetched steps) = 142
     //  pixel rows past the tensor's end, and its channel masks need Cin / 8 to be a power of two)
-    if (h1) {       // 16-bit tier: both operands are H1 tensors (xs, dys: in place or the H1 copy of a boundary tensor); no other kernel reads them
-        if (!(big && g_wgrad_dma && rx && rdy && xs && dys && x_prev && dy_prev && x_h2_only_flag && Cin % 16 == 0 && ((Cin / 8) & (Cin / 8 - 1)) == 0 &&
-              Cdy % 8 == 0 && (double)a.x_bytes + 160.0 * Cin * 4 < 4294967000.0 && (double)a.dy_bytes + 160.0 * Cdy * 4 < 4294967000.0))
-            return hipErrorInvalidValue;
-        a.xs = xs; a.dys = dys; a.x_prev = x_prev; a.x_cur = rx; a.dy_prev = dy_prev; a.dy_cur = rdy;
-        a.x = nullptr; a.dy = nullptr; a.fail_flag = x_h2_only_flag;
+    const bool dma_ok = big && g_wgrad_dma && rx && rdy && c.x.cells && c.dy.cells && c.x.prev && c.dy.prev && Cin % 16 == 0 &&
+                        ((Cin / 8) & (Cin / 8 - 1)) == 0 && Cdy % 8 == 0 && fits_descriptor({xb + 160.0 * Cin * 4, dyb + 160.0 * Cdy * 4});
+    auto read_cells = [&] { a.xs = c.x.cells; a.dys = c.dy.cells; a.x_prev = c.x.prev; a.x_cur = rx; a.dy_prev = c.dy.prev; a.dy_cur = rdy; };
+    if (h1) {       // 16-bit tier: both operands are H1 tensors; no other kernel reads them
+        if (!(dma_ok && c.fail_flag)) return hipErrorInvalidValue;
+        read_cells();
+        a.x = nullptr; a.dy = nullptr; a.fail_flag = c.fail_flag;
         hipLaunchKernelGGL(wgrad_dma_h1, dim3(kt, nt, split), dim3(256), 32 * 1024, s, a);
         return hipGetLastError();
     }
-    if (big && h3_env && g_wgrad_dma && rx && rdy && xs && dys && x_prev && dy_prev && Cin % 16 == 0 && ((Cin / 8) & (Cin / 8 - 1)) == 0 && Cdy % 8 == 0 &&
-        (double)a.x_bytes + 160.0 * Cin * 4 < 4294967000.0 && (double)a.dy_bytes + 160.0 * Cdy * 4 < 4294967000.0) {
+    if (dma_ok && h3_env) {
         if (!attr[2]) {
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
             if (e != hipSuccess) return e;
             attr[2] = true;
         }
-        a.xs = xs; a.dys = dys; a.x_prev = x_prev; a.x_cur = rx; a.dy_prev = dy_prev; a.dy_cur = rdy;
-        if (x_h2_only_flag) { a.x = nullptr; a.fail_flag = x_h2_only_flag; }
+        read_cells();
+        if (c.fail_flag) { a.x = nullptr; a.fail_flag = c.fail_flag; }
         hipLaunchKernelGGL(wgrad_dma, dim3(kt, nt, split), dim3(256), 64 * 1024, s, a);
         return hipGetLastError();
     }
-    if (x_h2_only_flag) return hipErrorInvalidValue;       // (no other kernel reads H2 cells)
+    if (c.fail_flag) return hipErrorInvalidValue;          // (no other kernel reads H2 cells)
     if (big && h3_env && rx && rdy && Cin % 4 == 0) {      // both operand ranges known: 16-bit matrix pipe
         if (!attr[0]) {
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_h3p), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
@@ -2031,12 +2165,6 @@ hipError_t wgrad_launch(const float* x, int N, int H, int W, int Cin, const floa
     }
     return hipGetLastError();
 }
-
-#define TRY_HIP(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return fail(DGP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 }  // namespace
 
@@ -2176,7 +2304,6 @@ static int refresh_parity_panels(dgp_trainer* tr, hipStream_t s) {
 static int trainer_owner_sync(void* owner, void* stream) {
     dgp_trainer* tr = static_cast<dgp_trainer*>(owner);
     if (!tr || !tr->parity_stale) return DGP_OK;
-    g_ctx = &tr->ctx;
     return refresh_parity_panels(tr, (hipStream_t)stream);
 }
 
@@ -2184,7 +2311,6 @@ extern "C" {
 
 // master parameters -> forward panels / folded BN / data-gradient panels of the engine
 int dgp_trainer_sync_weights(dgp_trainer* tr, void* stream) {
-    if (tr) g_ctx = &tr->ctx;
     if (!tr) return fail(DGP_ERR_INVALID, "dgp_trainer_sync_weights: null");
     dgp_net* net = tr->net;
     hipStream_t s = (hipStream_t)stream;
@@ -2279,13 +2405,13 @@ int dgp_trainer_sync_weights(dgp_trainer* tr, void* stream) {
         int rc;
         if (!tr->d_h3_table &&
             (rc = cell_table(16, [](int K, int, int) { return K >= 32; }, &ConvLayer::d_wh3, &TLayer::d_wTh3, &ConvLayer::d_wh3_pw,
-                             [&](const float* panel, void* c) { g_ctx->cells[panel] = static_cast<const float*>(c); }, &tr->d_h3_table, &tr->n_h3)))
+                             [&](const float* panel, void* c) { tr->ctx.cells[panel] = static_cast<const float*>(c); }, &tr->d_h3_table, &tr->n_h3)))
             return rc;
         if (!lazy) TRY_HIP(launch_pack_h3_all(reinterpret_cast<const PackH3Desc*>(tr->d_h3_table), tr->n_h3, s));
         if (tr->tier == 1) {              // 16-bit tier: the same panels as high-only H1 cells (K-steps of 64 channels: K % 64 == 0)
             if (!tr->d_h1_table &&
                 (rc = cell_table(8, [](int K, int nk, int NP) { return K >= 64 && K % 64 == 0 && nk % 2 == 0 && NP % 64 == 0; }, &ConvLayer::d_wh1,
-                                 &TLayer::d_wTh1, &ConvLayer::d_wh1_pw, [&](const float* panel, void* c) { g_ctx->cells1[panel] = c; },
+                                 &TLayer::d_wTh1, &ConvLayer::d_wh1_pw, [&](const float* panel, void* c) { tr->ctx.cells1[panel] = c; },
                                  &tr->d_h1_table, &tr->n_h1)))
                 return rc;
             TRY_HIP(launch_pack_h1_all(reinterpret_cast<const PackH3Desc*>(tr->d_h1_table), tr->n_h1, s));
@@ -2306,7 +2432,7 @@ int dgp_trainer_sync_weights(dgp_trainer* tr, void* stream) {
                     hipLaunchKernelGGL(pack_heads_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, tr->params + t0.w_off, l0.Cout / 4, t0.cpad,
                                        tr->params + t1.w_off, l1.Cout / 4, t1.cpad, l0.Cin, CT, t0.cinP, nkT * 8, tr->d_hmT, tr->d_hm_rng);
                     TRY_HIP(launch_pack_h1(tr->d_hmT, nkT, t0.cinP, tr->d_hm_rng, tr->d_hmT_h1, s));
-                    g_ctx->cells1[tr->d_hmT] = tr->d_hmT_h1;
+                    tr->ctx.cells1[tr->d_hmT] = tr->d_hmT_h1;
                 }
             }
             // the fused root block's weight cells (stem_pool_fused_kernel): row panel of conv1 from the panel pack_all_kernel just wrote
@@ -2330,48 +2456,209 @@ int dgp_trainer_sync_weights(dgp_trainer* tr, void* stream) {
     return DGP_OK;
 }
 
-int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* workspace, size_t workspace_bytes,
-                      float** scmap, float** locref, void* stream) {
-    if (tr) g_ctx = &tr->ctx;
+}  // extern "C"
+
+// the trainer's second stream (least urgent priority), created on first use
+static int ensure_side_stream(TrainCtx& ctx) {
+    if (ctx.s2) return DGP_OK;
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);         // lo: numerically greatest = least urgent
+    TRY_HIP(hipStreamCreateWithPriority(&ctx.s2, hipStreamNonBlocking, lo));
+    return DGP_OK;
+}
+
+// ---- the forward pass in stages: root block and bottleneck units per chain of frames, heads, the fast pass's check ----
+// One chain of frames [n0, n0 + nB) on stream cs; (hh, ww, x_off, x_c): the grid, workspace offset and channels of the next unit's input
+struct Chain { int n0, nB; hipStream_t cs; bool second; int hh, ww; size_t x_off; int x_c; };
+
+// the launches that follow belong to chain c: its range slots, and the K-split slab for the first chain only
+static void enter_chain(TrainPass& p, const Chain& c) {
+    p.slab = c.second ? nullptr : p.F(p.pl.tail);
+    p.ctx.rng.chain2 = c.second;
+}
+
+static int forward_root(TrainPass& p, const Chain& c, const uint8_t* frames) {
+    enter_chain(p, c);
+    dgp_trainer* tr = p.tr; const dgp_net* net = p.net; const TPlan& pl = p.pl; TrainCtx& ctx = p.ctx; RangeCtx& rng = ctx.rng;
+    const dgp_net_desc& d = net->desc;
+    const ConvLayer& c1 = net->layers[net->conv1];
+    const int n0 = c.n0, nB = c.nB;
+    hipStream_t cs = c.cs;
+    auto at = [&](size_t off, size_t per_frame) { return p.F(off) + (size_t)n0 * per_frame; };
+    const size_t px_in = (size_t)d.in_h * d.in_w, px1 = (size_t)net->h1 * net->w1, pxp = (size_t)net->hp * net->wp;
+    TRY_HIP(launch_preprocess(frames + (size_t)n0 * px_in * 3, (long long)nB * d.in_h * d.in_w, d.mean_pixel[0], d.mean_pixel[1],
+                              d.mean_pixel[2], at(pl.p0, px_in * 4), cs));
+    if (p.stem_fused) {
+        // 16-bit tier: the root block as the inference engine's ONE kernel (uint8 frame -> conv1 + BN + ReLU -> max-pool -> H1 cells of the
+        // pool output, scale predicted from conv1's range one step ago) that also records each window's first maximum.  No conv1 map, no
+        // fp32 pool output: the first unit reads the H1 tensor, the pool's backward needs only the record.  (The centred frame above
+        // stays: the stem's weight gradient reads it.)  The launch takes conv1's range slot, in conv1's place in the order of slots.
+        float* slot = rng.take();
+        const float* yprev = rng.prev_of(slot);
+        if (!slot || !yprev) return fail(DGP_ERR_STATE, "16-bit tier: the root block's output has no predicted range");
+        rng.set(p.F(pl.c1), slot);
+        rng.set(p.F(pl.pool), slot);
+        ctx.shadow_base[p.F(pl.pool)] = p.F(pl.sh_pool);
+        ctx.shadow_prev[p.F(pl.pool)] = yprev;
+        TRY_HIP(launch_stem_pool_fused(frames + (size_t)n0 * px_in * 3, nB, d.in_h, d.in_w, tr->d_stem_cells,
+                                       tr->d_wrng + (size_t)net->conv1 * ABSMAX_SLOTS, c1.d_scale, c1.d_bias, d.mean_pixel[0], d.mean_pixel[1],
+                                       d.mean_pixel[2], 0.f, reinterpret_cast<float*>(reinterpret_cast<char*>(p.F(pl.sh_pool)) + (size_t)n0 * pxp * 64 * 2),
+                                       slot, cs, 1, yprev, reinterpret_cast<unsigned char*>(p.ws + pl.pidx) + (size_t)n0 * pxp * 64));
+        return DGP_OK;
+    }
+    TRY_HIP(conv_launch(p, conv_call(c1, at(pl.p0, px_in * 4), nB, d.in_h, d.in_w, at(pl.c1, px1 * 64)).grid(net->h1, net->w1, 3, 3).strided(2)
+                               .keys(p.F(pl.p0), p.F(pl.c1)), cs));
+    int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
+    int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
+    const long long totp = (long long)nB * net->hp * net->wp * 16;
+    uint2* yh1 = nullptr;
+    const float* yprev = nullptr;
+    if (p.h1p() && p.ub == 0) {        // H1 copy of the pool output for the first unit (scale: conv1's range one step ago)
+        yprev = rng.prev_of(rng.of(p.F(pl.c1)));
+        if (!yprev) return fail(DGP_ERR_STATE, "16-bit tier: the root block's output has no predicted range");
+        yh1 = reinterpret_cast<uint2*>(reinterpret_cast<char*>(p.F(pl.sh_pool)) + (size_t)n0 * pxp * 64 * 2);
+        ctx.shadow_base[p.F(pl.pool)] = p.F(pl.sh_pool);
+        ctx.shadow_prev[p.F(pl.pool)] = yprev;
+    }
+    hipLaunchKernelGGL(maxpool_fwd_idx_kernel, dim3(grid_for(totp)), dim3(256), 0, cs, at(pl.c1, px1 * 64), nB, net->h1, net->w1, 16,
+                       net->hp, net->wp, pth / 2, ptw / 2, at(pl.pool, pxp * 64),
+                       reinterpret_cast<uchar4*>(p.ws + pl.pidx) + (size_t)n0 * pxp * 16, yh1, yprev);
+    rng.set(p.F(pl.pool), rng.of(p.F(pl.c1)));      // max-pooling cannot raise the maximum
+    return DGP_OK;
+}
+
+static int forward_unit(TrainPass& p, Chain& c, size_t ui) {
+    enter_chain(p, c);
+    const dgp_net* net = p.net; const TPlan& pl = p.pl;
+    const int n0 = c.n0, nB = c.nB, hh = c.hh, ww = c.ww;
+    hipStream_t cs = c.cs;
+    const Unit& u = net->units[ui];
+    const int ho = u.ho, wo = u.wo;
+    const size_t pin = (size_t)hh * ww, pout = (size_t)ho * wo;
+    const bool h2u = p.fast && ui >= p.ub;         // this unit's tensors are H2 / H1 cells
+    const bool h1u = h2u && p.fmt == 2;
+    // (the first H2 unit reads the fp16 copy of its fp32 input; ranges and scales go by the tensor's own name, F(c.x_off))
+    // (frame offsets inside H1 tensors are half the fp32 ones: atf)
+    auto atf = [&](size_t off, size_t per_frame, bool cells1) {
+        return cells1 ? reinterpret_cast<float*>(reinterpret_cast<char*>(p.F(off)) + (size_t)n0 * per_frame * 2) : p.F(off) + (size_t)n0 * per_frame;
+    };
+    // a launch of this unit: range keys, and on a fast pass the cell format of its tensors (rkey: the residual's tensor)
+    auto launch = [&](ConvCall call, const void* in_key, const void* out_key, const void* rkey = nullptr) {
+        call.keys(in_key, out_key);
+        if (h2u) call.cells(p.fmt, rkey);
+        return conv_launch(p, call, cs);
+    };
+    const float* x = (h2u && ui == p.ub) ? atf(ui == 0 ? pl.sh_pool : pl.sh_xo[ui - 1], pin * c.x_c, h1u) : atf(c.x_off, pin * c.x_c, h1u && ui > p.ub);
+    float* const r1 = atf(pl.r1[ui], pin * u.depth_bn, h1u);
+    float* const r2 = atf(pl.r2[ui], pout * u.depth_bn, h1u);
+    const float* res = x;
+    const void* res_key = p.F(c.x_off);
+    int res_s = u.stride, res_H = hh, res_W = ww;
+    if (u.sc >= 0) {
+        float* const sc = atf(pl.sc[ui], pout * u.depth, h1u);
+        TRY_HIP(launch(conv_call(net->layers[u.sc], x, nB, hh, ww, sc).grid(ho, wo).strided(u.stride).linear(), p.F(c.x_off), p.F(pl.sc[ui])));
+        res = sc; res_s = 1; res_H = ho; res_W = wo;
+        res_key = p.F(pl.sc[ui]);
+    }
+    TRY_HIP(launch(conv_call(net->layers[u.c1], x, nB, hh, ww, r1), p.F(c.x_off), p.F(pl.r1[ui])));
+    TRY_HIP(launch(conv_call(net->layers[u.c2], r1, nB, hh, ww, r2).grid(ho, wo, u.pb_h, u.pb_w).strided(u.stride), p.F(pl.r1[ui]), p.F(pl.r2[ui])));
+    TRY_HIP(launch(conv_call(net->layers[u.c3], r2, nB, ho, wo, atf(pl.xo[ui], pout * u.depth, h1u)).residual(res, res_s, res_H, res_W),
+                   p.F(pl.r2[ui]), p.F(pl.xo[ui]), res_key));
+    c.x_off = pl.xo[ui]; c.x_c = u.depth; c.hh = ho; c.ww = wo;
+    return DGP_OK;
+}
+
+// one head on the features xin [B, h, w, Cin]: pointwise GEMM on the cell kernels + gather of the four taps (as the inference engine) when the
+// feature map's range and the pointwise cells exist, else the 2x2-conv form on the fp32 kernel
+static hipError_t forward_head(TrainPass& p, int li, int njt, const float* xin, int h, int w, float* out) {
+    static const bool head_pw = (dgp_tune("DGP_HEAD_PW", 1) != 0);
+    const dgp_trainer* tr = p.tr;
+    const ConvLayer& hd = p.net->layers[li];
+    const RangeCtx& rng = p.ctx.rng;
+    const float* rin = rng.of(xin);
+    const float* rw = tr->d_wrng ? tr->d_wrng + (size_t)li * ABSMAX_SLOTS : nullptr;
+    if (p.fast && !(head_pw && rin && rw && hd.d_wh3_pw && tr->d_h3_table && (p.fmt == 1 || hd.d_wh1_pw))) return hipErrorInvalidValue;       // (H2 / H1 features: cell kernels only)
+    if (!(head_pw && rng.on && rin && rw && hd.d_wh3_pw && tr->d_h3_table))
+        return conv_launch(p, conv_call(hd, xin, p.B, h, w, out).grid(h, w, 1, 1).linear().head_scatter(njt), p.s);
+    float* T = p.F(p.pl.g0);                       // gradient scratch: free during the forward pass
+    ConvArgs a = head_pointwise_args(hd, xin, p.B, h, w, T, rin, rw);
+    if (p.fast) {
+        a.in_fmt = p.fmt; a.in_scale_dev = rng.prev_of(rin);
+        if (!a.in_scale_dev) return hipErrorInvalidValue;
+        if (p.fmt == 2) a.wh3 = hd.d_wh1_pw;
+    }
+    a.slab = p.slab; a.slab_bytes = p.slab ? (unsigned)(TAIL_SLAB_FLOATS * sizeof(float)) : 0u;
+    hipError_t e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), p.s);
+    if (e != hipSuccess) return e;
+    return launch_head_gather(T, hd.d_bias, p.B, h, w, njt, hd.coutp_pw, out, p.s);
+}
+
+// every tensor of `ctx.h2_slots` against its predicted scale: raises the trainer's flag (the host repeats the step)
+static int check_predictions(TrainPass& p, const char* too_many) {
+    H2CheckList cl{};
+    const std::vector<int>& slots = p.ctx.h2_slots;
+    if (slots.size() > sizeof(cl.idx) / sizeof(cl.idx[0])) return fail(DGP_ERR_STATE, too_many);
+    cl.n = (int)slots.size();
+    for (int k = 0; k < cl.n; ++k) cl.idx[k] = (short)slots[k];
+    if (cl.n) hipLaunchKernelGGL(h2_pred_check_kernel, dim3(cl.n), dim3(64), 0, p.s, cl, p.ctx.rng.pool, p.ctx.rng.prev, p.tr->d_fast_flag);
+    return DGP_OK;
+}
+
+// end of a fast forward pass: the check of its predicted scales, and the fp32 copy of the features for the heads' backward
+static int forward_fast_tail(TrainPass& p, const float* xin, int h, int w) {
+    dgp_trainer* tr = p.tr; TrainCtx& ctx = p.ctx; const TPlan& pl = p.pl;
+    {   // every H2 tensor of this pass is checked against its predicted scale, and the fp16 copy of block1's output that the first H2 unit read
+        const float* pv = ctx.rng.prev_of(ctx.rng.of(p.ub == 0 ? p.F(pl.pool) : p.F(pl.xo[p.ub - 1])));
+        if (!pv) return fail(DGP_ERR_STATE, "fast pass: the first H2 unit's input has no range");
+        ctx.h2_slots.push_back((int)((pv - ctx.rng.prev) / ABSMAX_SLOTS));
+    }
+    if (int rc = check_predictions(p, "fast pass: too many H2 tensors")) return rc;
+    // fp32 copy of the features for the heads' backward (not when it reads the H1 features in place: merged heads of the 16-bit tier)
+    const float* rfeat = ctx.rng.of(xin);
+    const long long n8 = (long long)p.B * h * w * p.net->units.back().depth / 8;
+    tr->fwd_feat32 = !(p.fmt == 2 && tr->d_hmT && tr->d_hmT_h1);
+    if (!tr->fwd_feat32) {
+    } else if (p.fmt == 2)
+        hipLaunchKernelGGL(h1_to_f32_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, p.s, reinterpret_cast<const uint4*>(xin), n8,
+                           ctx.rng.prev_of(rfeat), reinterpret_cast<float4*>(p.F(pl.feat32)), (const uint4*)nullptr);
+    else
+        hipLaunchKernelGGL(h2_to_f32_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, p.s, reinterpret_cast<const uint4*>(xin), n8,
+                           ctx.rng.prev_of(rfeat), reinterpret_cast<float4*>(p.F(pl.feat32)));
+    TRY_HIP(hipGetLastError());
+    return DGP_OK;
+}
+
+extern "C" int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* workspace, size_t workspace_bytes,
+                                 float** scmap, float** locref, void* stream) {
     if (!tr || !frames || !workspace) return fail(DGP_ERR_INVALID, "dgp_train_forward: null argument");
     dgp_net* net = tr->net;
     if (!net->loaded) return fail(DGP_ERR_STATE, "dgp_train_forward: call dgp_trainer_sync_weights first");
     const TPlan pl = make_tplan(tr, nt);
     if (workspace_bytes < pl.total) return fail(DGP_ERR_INVALID, "dgp_train_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    auto F = [&](size_t off) { return (float*)(ws + off); };
-    g_ctx->tail_slab = F(pl.tail);
+    TrainPass p(tr, s, workspace, pl, nt);
+    TrainCtx& ctx = p.ctx;
     range_pass_begin(tr, s, false, tr->d_fast_flag);      // (also clears the range flag of a fast pass: fast needs the ranges on)
-    g_ctx->shadow_base.clear();
-    g_ctx->h2_slots.clear();
-    g_shadow_want = true;
-    g_h2 = H2Launch();
-    // Fast pass (dgp_trainer_fast_mode; the host asks for it once a pass of the same shapes has left its ranges behind): from the first
-    // unit with a 128-channel bottleneck on (block2) every retained activation is an H2 tensor -- fp16 high / low cells with a scale
-    // predicted from the previous step's range, no fp32 twin -- so these convs run the inference engine's cell kernels (no split in the
-    // K loop, no second copy written) and the weight gradients read them in place.  ub: first such unit; its input is the fp16 copy
-    // (ConvArgs::shadow) of block1's output.
-    size_t ub = net->units.size();
-    for (size_t ui = 1; ui < net->units.size(); ++ui)
-        if (net->units[ui].depth_bn >= 128 && pl.sh_xo[ui - 1]) { ub = ui; break; }
-    // (16-bit tier: EVERY unit -- block1 included -- keeps H1 tensors; the first one reads the H1 copy of the pool output)
-    if (tr->tier == 1 && pl.sh_pool) ub = 0;
-    const bool fast = tr->fast_next && g_wgrad_dma && g_train_cells && g_ctx->rng.on && ub < net->units.size() && pl.feat32 &&
-                      (tr->tier != 1 || tr->d_h1_table);
-    const int FMT = tr->tier == 1 ? 2 : 1;       // cell format of this pass's H2 / H1 tensors
-    tr->fwd_fast = fast;
-    tr->fwd_fmt = fast ? FMT : 0;
-    if (!fast && tr->parity_stale) {             // a plain pass after lazy syncs: its panels first
+    ctx.shadow_base.clear();
+    ctx.h2_slots.clear();
+    // Fast pass (dgp_trainer_fast_mode; the host asks for it once a pass of the same shapes has left its ranges behind): from unit ub on every
+    // retained activation is an H2 tensor -- fp16 high / low cells with a scale predicted from the previous step's range, no fp32 twin -- so
+    // these convs run the inference engine's cell kernels (no split in the K loop, no second copy) and the weight gradients read them in place
+    const size_t nu = net->units.size();
+    p.ub = first_cell_unit(net, pl, tr->tier == 1);
+    p.fmt = tr->tier == 1 ? 2 : 1;
+    p.fast = tr->fast_next && g_wgrad_dma && g_train_cells && ctx.rng.on && p.ub < nu && pl.feat32 && (tr->tier != 1 || tr->d_h1_table);
+    tr->fwd_fast = p.fast;
+    tr->fwd_fmt = p.fast ? p.fmt : 0;
+    if (!p.fast && tr->parity_stale) {           // a plain pass after lazy syncs: its panels first
         const int rcp = refresh_parity_panels(tr, s);
         if (rcp) return rcp;
     }
-    g_shadow_fmt = (fast && FMT == 2) ? 2 : 1;   // (the one copy a tier-1 forward pass writes: block1's output, read by the first H1 unit)
-    for (size_t ui = 0; ui < net->units.size(); ++ui) {
-        if (fast && ui >= ub) continue;              // (H2 tensors register themselves as they are written)
-        if (pl.sh_r1[ui]) g_ctx->shadow_base[F(pl.r1[ui])] = F(pl.sh_r1[ui]);
-        if (pl.sh_r2[ui]) g_ctx->shadow_base[F(pl.r2[ui])] = F(pl.sh_r2[ui]);
-        if (pl.sh_xo[ui]) g_ctx->shadow_base[F(pl.xo[ui])] = F(pl.sh_xo[ui]);
+    for (size_t ui = 0; ui < nu; ++ui) {
+        if (p.fast && ui >= p.ub) continue;          // (H2 tensors register themselves as they are written)
+        if (pl.sh_r1[ui]) ctx.shadow_base[p.F(pl.r1[ui])] = p.F(pl.sh_r1[ui]);
+        if (pl.sh_r2[ui]) ctx.shadow_base[p.F(pl.r2[ui])] = p.F(pl.sh_r2[ui]);
+        if (pl.sh_xo[ui]) ctx.shadow_base[p.F(pl.xo[ui])] = p.F(pl.sh_xo[ui]);
     }
     const dgp_net_desc& d = net->desc;
     const int B = nt;
@@ -2381,456 +2668,117 @@ int dgp_train_forward(dgp_trainer* tr, const uint8_t* frames, int32_t nt, void* 
     // (the backward pass sees one batch) and max into the same range slots.
     static const bool side_env = (dgp_tune("DGP_WGRAD_OVERLAP", 1) != 0);
     static const int chains_env = dgp_tune("DGP_FWD_CHAINS", 2);
-    if (side_env && !g_ctx->s2) {
-        int lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        TRY_HIP(hipStreamCreateWithPriority(&g_ctx->s2, hipStreamNonBlocking, lo));
-    }
-    g_ctx->ev_next = 0;                          // (the previous backward pass has joined: its events are free again)
-    const bool two = side_env && g_ctx->s2 && chains_env >= 2 && B >= 4;
+    if (side_env)
+        if (int rc = ensure_side_stream(ctx)) return rc;
+    ctx.ev_next = 0;                             // (the previous backward pass has joined: its events are free again)
+    const bool two = side_env && ctx.s2 && chains_env >= 2 && B >= 4;
     const int n1 = two ? (B + 1) / 2 : B;
     const ConvLayer& c1 = net->layers[net->conv1];
-    const bool stem_fused = fast && FMT == 2 && ub == 0 && tr->d_stem_cells && tr->d_wrng && c1.d_scale && c1.d_bias;
-    tr->fwd_stem_fused = stem_fused;
+    p.stem_fused = p.h1p() && p.ub == 0 && tr->d_stem_cells && tr->d_wrng && c1.d_scale && c1.d_bias;
+    tr->fwd_stem_fused = p.stem_fused;
     if (two) {
-        hipEvent_t ready = g_ctx->take_event();
+        hipEvent_t ready = ctx.take_event();
         if (!ready) return fail(DGP_ERR_HIP, "forward chains: hipEventCreate failed");
         TRY_HIP(hipEventRecord(ready, s));       // frames, weights and the zeroed range slots are in place
-        TRY_HIP(hipStreamWaitEvent(g_ctx->s2, ready, 0));
+        TRY_HIP(hipStreamWaitEvent(ctx.s2, ready, 0));
     }
-    int h = net->hp, w = net->wp;
-    const float* xin = F(pl.pool);
     // host enqueue order: stage by stage, chain 0 then chain 1 (a chain enqueued whole before the other would start a millisecond late)
-    struct Chain { int n0, nB; hipStream_t cs; bool second; int hh, ww; size_t x_off; int x_c; };
-    Chain chains[2] = {{0, n1, s, false, net->hp, net->wp, pl.pool, 64}, {n1, B - n1, g_ctx->s2, true, net->hp, net->wp, pl.pool, 64}};
+    Chain chains[2] = {{0, n1, s, false, net->hp, net->wp, pl.pool, 64}, {n1, B - n1, ctx.s2, true, net->hp, net->wp, pl.pool, 64}};
     const int nchains = two ? 2 : 1;
-    float* const slab_keep = g_ctx->tail_slab;
-    struct Restore { float*& ref; float* v; ~Restore() { ref = v; } } restore{g_ctx->tail_slab, slab_keep};
-    auto root = [&](Chain& c) -> int {
-        g_ctx->tail_slab = c.second ? nullptr : slab_keep;      // the K-split slab belongs to the first chain's launches
-        g_ctx->rng.chain2 = c.second;
-        const int n0 = c.n0, nB = c.nB;
-        hipStream_t cs = c.cs;
-        auto at = [&](size_t off, size_t per_frame) { return F(off) + (size_t)n0 * per_frame; };
-        const size_t px_in = (size_t)d.in_h * d.in_w, px1 = (size_t)net->h1 * net->w1, pxp = (size_t)net->hp * net->wp;
-        TRY_HIP(launch_preprocess(frames + (size_t)n0 * px_in * 3, (long long)nB * d.in_h * d.in_w, d.mean_pixel[0], d.mean_pixel[1],
-                                  d.mean_pixel[2], at(pl.p0, px_in * 4), cs));
-        if (stem_fused) {
-            // 16-bit tier: the root block as the inference engine's ONE kernel (uint8 frame -> conv1 + BN + ReLU -> max-pool -> H1 cells of the
-            // pool output, scale predicted from conv1's range one step ago) that also records each window's first maximum.  No conv1 map, no
-            // fp32 pool output: the first unit reads the H1 tensor, the pool's backward needs only the record.  (The centred frame above
-            // stays: the stem's weight gradient reads it.)  The launch takes conv1's range slot, in conv1's place in the order of slots.
-            float* slot = range_take();
-            const float* yprev = range_prev_of(slot);
-            if (!slot || !yprev) return fail(DGP_ERR_STATE, "16-bit tier: the root block's output has no predicted range");
-            range_set(F(pl.c1), slot);
-            range_set(F(pl.pool), slot);
-            g_ctx->shadow_base[F(pl.pool)] = F(pl.sh_pool);
-            g_ctx->shadow_prev[F(pl.pool)] = yprev;
-            TRY_HIP(launch_stem_pool_fused(frames + (size_t)n0 * px_in * 3, nB, d.in_h, d.in_w, tr->d_stem_cells,
-                                           tr->d_wrng + (size_t)net->conv1 * ABSMAX_SLOTS, c1.d_scale, c1.d_bias, d.mean_pixel[0], d.mean_pixel[1],
-                                           d.mean_pixel[2], 0.f, reinterpret_cast<float*>(reinterpret_cast<char*>(F(pl.sh_pool)) + (size_t)n0 * pxp * 64 * 2),
-                                           slot, cs, 1, yprev, reinterpret_cast<unsigned char*>(ws + pl.pidx) + (size_t)n0 * pxp * 64));
-            return DGP_OK;
-        }
-        TRY_HIP(conv_launch(c1, c1.d_w, c1.nk, c1.CoutP, at(pl.p0, px_in * 4), nB, d.in_h, d.in_w, 4, 3, 3, net->h1, net->w1, 64, 2, 0,
-                            c1.d_scale, c1.d_bias, nullptr, 0, 0, 0, nullptr, true, 0, 0, at(pl.c1, px1 * 64), cs, F(pl.p0), F(pl.c1)));
-        int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
-        int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
-        const long long totp = (long long)nB * net->hp * net->wp * 16;
-        uint2* yh1 = nullptr;
-        const float* yprev = nullptr;
-        if (fast && FMT == 2 && ub == 0) {        // H1 copy of the pool output for the first unit (scale: conv1's range one step ago)
-            yprev = range_prev_of(range_of(F(pl.c1)));
-            if (!yprev) return fail(DGP_ERR_STATE, "16-bit tier: the root block's output has no predicted range");
-            yh1 = reinterpret_cast<uint2*>(reinterpret_cast<char*>(F(pl.sh_pool)) + (size_t)n0 * pxp * 64 * 2);
-            g_ctx->shadow_base[F(pl.pool)] = F(pl.sh_pool);
-            g_ctx->shadow_prev[F(pl.pool)] = yprev;
-        }
-        hipLaunchKernelGGL(maxpool_fwd_idx_kernel, dim3(grid_for(totp)), dim3(256), 0, cs, at(pl.c1, px1 * 64), nB, net->h1, net->w1, 16,
-                           net->hp, net->wp, pth / 2, ptw / 2, at(pl.pool, pxp * 64),
-                           reinterpret_cast<uchar4*>(ws + pl.pidx) + (size_t)n0 * pxp * 16, yh1, yprev);
-        range_set(F(pl.pool), range_of(F(pl.c1)));      // max-pooling cannot raise the maximum
-        return DGP_OK;
-    };
-    auto unit = [&](Chain& c, size_t ui) -> int {
-        g_ctx->tail_slab = c.second ? nullptr : slab_keep;
-        g_ctx->rng.chain2 = c.second;
-        const int n0 = c.n0, nB = c.nB, hh = c.hh, ww = c.ww;
-        hipStream_t cs = c.cs;
-        auto at = [&](size_t off, size_t per_frame) { return F(off) + (size_t)n0 * per_frame; };
-        const Unit& u = net->units[ui];
-        const int ho = u.ho, wo = u.wo;
-        const size_t pin = (size_t)hh * ww, pout = (size_t)ho * wo;
-        const bool h2u = fast && ui >= ub;             // this unit's tensors are H2
-        // (the first H2 unit reads the fp16 copy of its fp32 input; ranges and scales go by the tensor's own name, F(c.x_off))
-        // (frame offsets inside H1 tensors are half the fp32 ones: atf)
-        auto atf = [&](size_t off, size_t per_frame, bool cells1) {
-            return cells1 ? reinterpret_cast<float*>(reinterpret_cast<char*>(F(off)) + (size_t)n0 * per_frame * 2) : F(off) + (size_t)n0 * per_frame;
-        };
-        const bool h1u = h2u && FMT == 2;
-        const float* x = (h2u && ui == ub) ? atf(ui == 0 ? pl.sh_pool : pl.sh_xo[ui - 1], pin * c.x_c, h1u) : atf(c.x_off, pin * c.x_c, h1u && ui > ub);
-        const float* res = x;
-        const void* res_key = F(c.x_off);
-        int res_s = u.stride, res_H = hh, res_W = ww;
-        auto h2_next = [&](bool with_res) {
-            if (!h2u) return;
-            g_h2.in_fmt = FMT; g_h2.out_fmt = FMT;
-            if (with_res) { g_h2.res_fmt = FMT; g_h2.res_key = res_key; }
-        };
-        if (u.sc >= 0) {
-            const ConvLayer& l = net->layers[u.sc];
-            h2_next(false);
-            TRY_HIP(conv_launch(l, l.d_w, l.nk, l.CoutP, x, nB, hh, ww, l.Cin, 0, 0, ho, wo, l.Cout, u.stride, 0, l.d_scale,
-                                l.d_bias, nullptr, 0, 0, 0, nullptr, false, 0, 0, atf(pl.sc[ui], pout * u.depth, h1u), cs, F(c.x_off),
-                                F(pl.sc[ui])));
-            res = atf(pl.sc[ui], pout * u.depth, h1u); res_s = 1; res_H = ho; res_W = wo;
-            res_key = F(pl.sc[ui]);
-        }
-        const ConvLayer& l1 = net->layers[u.c1];
-        h2_next(false);
-        TRY_HIP(conv_launch(l1, l1.d_w, l1.nk, l1.CoutP, x, nB, hh, ww, l1.Cin, 0, 0, hh, ww, l1.Cout, 1, 0, l1.d_scale,
-                            l1.d_bias, nullptr, 0, 0, 0, nullptr, true, 0, 0, atf(pl.r1[ui], pin * u.depth_bn, h1u), cs, F(c.x_off),
-                            F(pl.r1[ui])));
-        const ConvLayer& l2 = net->layers[u.c2];
-        const int pb_h = u.pb_h, pb_w = u.pb_w;
-        h2_next(false);
-        TRY_HIP(conv_launch(l2, l2.d_w, l2.nk, l2.CoutP, atf(pl.r1[ui], pin * u.depth_bn, h1u), nB, hh, ww, l2.Cin, pb_h, pb_w, ho, wo,
-                            l2.Cout, u.stride, 0, l2.d_scale, l2.d_bias, nullptr, 0, 0, 0, nullptr, true, 0, 0,
-                            atf(pl.r2[ui], pout * u.depth_bn, h1u), cs, F(pl.r1[ui]), F(pl.r2[ui])));
-        const ConvLayer& l3 = net->layers[u.c3];
-        h2_next(true);
-        TRY_HIP(conv_launch(l3, l3.d_w, l3.nk, l3.CoutP, atf(pl.r2[ui], pout * u.depth_bn, h1u), nB, ho, wo, l3.Cin, 0, 0, ho, wo, l3.Cout,
-                            1, 0, l3.d_scale, l3.d_bias, res, res_s, res_H, res_W, nullptr, true, 0, 0,
-                            atf(pl.xo[ui], pout * u.depth, h1u), cs, F(pl.r2[ui]), F(pl.xo[ui])));
-        c.x_off = pl.xo[ui]; c.x_c = u.depth; c.hh = ho; c.ww = wo;
-        return DGP_OK;
-    };
-    {
-        int rc0;
-        for (int ci = 0; ci < nchains; ++ci) if ((rc0 = root(chains[ci]))) return rc0;
-        for (size_t ui = 0; ui < net->units.size(); ++ui)
-            for (int ci = 0; ci < nchains; ++ci) if ((rc0 = unit(chains[ci], ui))) return rc0;
-        g_ctx->tail_slab = slab_keep;
-        g_ctx->rng.chain2 = false;
-        if (two) {
-            hipEvent_t done = g_ctx->take_event();
-            if (!done) return fail(DGP_ERR_HIP, "forward chains: hipEventCreate failed");
-            TRY_HIP(hipEventRecord(done, g_ctx->s2));
-            TRY_HIP(hipStreamWaitEvent(s, done, 0));
-            if (g_ctx->rng.on && g_ctx->rng.next2 > 0) {      // ranges of the whole tensors = max of the chains' (same slot order)
-                if (g_ctx->rng.next2 != g_ctx->rng.next) return fail(DGP_ERR_STATE, "forward chains took different numbers of range slots");
-                const int nfl = g_ctx->rng.next2 * ABSMAX_SLOTS;
-                hipLaunchKernelGGL(range_merge_kernel, dim3((nfl + 255) / 256), dim3(256), 0, s, g_ctx->rng.pool,
-                                   g_ctx->rng.pool + (size_t)RANGE_FWD * ABSMAX_SLOTS, nfl);
-            }
+    int rc;
+    for (int ci = 0; ci < nchains; ++ci) if ((rc = forward_root(p, chains[ci], frames))) return rc;
+    for (size_t ui = 0; ui < nu; ++ui)
+        for (int ci = 0; ci < nchains; ++ci) if ((rc = forward_unit(p, chains[ci], ui))) return rc;
+    enter_chain(p, chains[0]);
+    if (two) {
+        hipEvent_t done = ctx.take_event();
+        if (!done) return fail(DGP_ERR_HIP, "forward chains: hipEventCreate failed");
+        TRY_HIP(hipEventRecord(done, ctx.s2));
+        TRY_HIP(hipStreamWaitEvent(s, done, 0));
+        if (ctx.rng.on && ctx.rng.next2 > 0) {      // ranges of the whole tensors = max of the chains' (same slot order)
+            if (ctx.rng.next2 != ctx.rng.next) return fail(DGP_ERR_STATE, "forward chains took different numbers of range slots");
+            const int nfl = ctx.rng.next2 * ABSMAX_SLOTS;
+            hipLaunchKernelGGL(range_merge_kernel, dim3((nfl + 255) / 256), dim3(256), 0, s, ctx.rng.pool,
+                               ctx.rng.pool + (size_t)RANGE_FWD * ABSMAX_SLOTS, nfl);
         }
     }
-    h = net->fh; w = net->fw;
-    xin = F(pl.xo[net->units.size() - 1]);
-    // heads: pointwise GEMM on the cell kernels + gather of the four taps (as the inference engine) when the feature map's range
-    // and the pointwise cells exist, else the 2x2-conv form on the fp32 kernel
-    static const bool head_pw = (dgp_tune("DGP_HEAD_PW", 1) != 0);
-    auto head_forward = [&](const ConvLayer& hd, int li, int njt, float* out) -> hipError_t {
-        const float* rin = range_of(xin);
-        const float* rw = tr->d_wrng ? tr->d_wrng + (size_t)li * ABSMAX_SLOTS : nullptr;
-        if (fast && !(head_pw && rin && rw && hd.d_wh3_pw && tr->d_h3_table && (FMT == 1 || hd.d_wh1_pw))) return hipErrorInvalidValue;       // (H2 / H1 features: cell kernels only)
-        if (!(head_pw && g_ctx->rng.on && rin && rw && hd.d_wh3_pw && tr->d_h3_table))
-            return conv_launch(hd, hd.d_w, hd.nk, hd.CoutP, xin, B, h, w, hd.Cin, 1, 1, h, w, hd.Cout, 1, 0, nullptr, hd.d_bias,
-                               nullptr, 0, 0, 0, nullptr, false, 1, njt, out, s);
-        float* T = F(pl.g0);                       // gradient scratch: free during the forward pass
-        ConvArgs a = head_pointwise_args(hd, xin, B, h, w, T, rin, rw);
-        if (fast) {
-            a.in_fmt = FMT; a.in_scale_dev = range_prev_of(rin);
-            if (!a.in_scale_dev) return hipErrorInvalidValue;
-            if (FMT == 2) a.wh3 = hd.d_wh1_pw;
-        }
-        a.slab = g_ctx->tail_slab; a.slab_bytes = g_ctx->tail_slab ? (unsigned)(TAIL_SLAB_FLOATS * sizeof(float)) : 0u;
-        hipError_t e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), s);
-        if (e != hipSuccess) return e;
-        return launch_head_gather(T, hd.d_bias, B, h, w, njt, hd.coutp_pw, out, s);
-    };
-    TRY_HIP(head_forward(net->layers[net->head_part], net->head_part, d.num_joints, F(pl.scmap)));
-    TRY_HIP(head_forward(net->layers[net->head_locref], net->head_locref, 2 * d.num_joints, F(pl.locref)));
-    if (fast) {
-        // every H2 tensor of this pass against its predicted scale (the scoremaps are garbage when one failed: the host repeats the step)
-        H2CheckList cl{};
-        if (g_ctx->h2_slots.size() > sizeof(cl.idx) / sizeof(cl.idx[0])) return fail(DGP_ERR_STATE, "fast pass: too many H2 tensors");
-        {   // ... and the fp16 copy of block1's output that the first H2 unit read
-            const float* pv = range_prev_of(range_of(ub == 0 ? F(pl.pool) : F(pl.xo[ub - 1])));
-            if (!pv) return fail(DGP_ERR_STATE, "fast pass: the first H2 unit's input has no range");
-            g_ctx->h2_slots.push_back((int)((pv - g_ctx->rng.prev) / ABSMAX_SLOTS));
-        }
-        cl.n = (int)g_ctx->h2_slots.size();
-        for (int k = 0; k < cl.n; ++k) cl.idx[k] = (short)g_ctx->h2_slots[k];
-        hipLaunchKernelGGL(h2_pred_check_kernel, dim3(cl.n), dim3(64), 0, s, cl, g_ctx->rng.pool, g_ctx->rng.prev, tr->d_fast_flag);
-        // fp32 copy of the features for the heads' backward (not when it reads the H1 features in place: merged heads of the 16-bit tier)
-        const float* rfeat = range_of(xin);
-        const long long n8 = (long long)B * h * w * net->units.back().depth / 8;
-        tr->fwd_feat32 = !(FMT == 2 && tr->d_hmT && tr->d_hmT_h1);
-        if (!tr->fwd_feat32) {
-        } else if (FMT == 2)
-            hipLaunchKernelGGL(h1_to_f32_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, s, reinterpret_cast<const uint4*>(xin), n8,
-                               range_prev_of(rfeat), reinterpret_cast<float4*>(F(pl.feat32)), (const uint4*)nullptr);
-        else
-        hipLaunchKernelGGL(h2_to_f32_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, s, reinterpret_cast<const uint4*>(xin), n8,
-                           range_prev_of(rfeat), reinterpret_cast<float4*>(F(pl.feat32)));
-        TRY_HIP(hipGetLastError());
-    }
-    if (scmap) *scmap = F(pl.scmap);
-    if (locref) *locref = F(pl.locref);
+    const int h = net->fh, w = net->fw;
+    const float* xin = p.F(pl.xo[nu - 1]);
+    TRY_HIP(forward_head(p, net->head_part, d.num_joints, xin, h, w, p.F(pl.scmap)));
+    TRY_HIP(forward_head(p, net->head_locref, 2 * d.num_joints, xin, h, w, p.F(pl.locref)));
+    if (p.fast && (rc = forward_fast_tail(p, xin, h, w))) return rc;
+    if (scmap) *scmap = p.F(pl.scmap);
+    if (locref) *locref = p.F(pl.locref);
     return DGP_OK;
 }
+
+// ---- the backward pass in stages ----
+struct MapRef { const float* p; int H, W; };        // an NHWC tensor of the batch on its grid
 
 // One conv layer's parameter gradients: dWraw = A^T dY, d beta = colsum(dY), then the BN-affine algebra.
-// Every non-head layer accumulates dWraw / colsum in its own region of the workspace (zeroed once per pass; g_ctx->defer_plan holds the
-// running pass's plan) and two table launches of dgp_train_backward turn them into dW, d gamma, d beta for all layers -- ~150
-// dispatches fewer per step than fill + fill + wgrad + scale + bn per layer.
-
-static int layer_param_grads(dgp_trainer* tr, size_t li, const float* x, int N, int H, int W, const float* dy, int Ho,
-                             int Wo, int stride, int pad_t, int pad_l, hipStream_t s) {
-    const ConvLayer& l = tr->net->layers[li];
-    hipStream_t ws_ = s;
-    hipEvent_t done = nullptr;
-    if (g_ctx->overlap) {                    // behind everything enqueued on the chain's stream so far (dY's producer included)
-        hipEvent_t ready = g_ctx->take_event();
-        done = g_ctx->take_event();
-        if (!ready || !done) return fail(DGP_ERR_HIP, "weight-gradient stream: hipEventCreate failed");
-        TRY_HIP(hipEventRecord(ready, s));
-        TRY_HIP(hipStreamWaitEvent(g_ctx->s2, ready, 0));
-        ws_ = g_ctx->s2;
-    }
-    const void *xs = nullptr, *dys = nullptr;
-    const float *xp = nullptr, *dyp = nullptr;
+// Every non-head layer accumulates dWraw / colsum in its own region of the workspace (zeroed once per pass; TPlan::dw_l / cs_l) and two
+// table launches at the end of the pass turn them into dW, d gamma, d beta for all layers -- ~150 dispatches fewer per step than
+// fill + fill + wgrad + scale + bn per layer.  side: beside the chain (WgradSide) where the pass overlaps.
+static int layer_param_grads(TrainPass& p, size_t li, MapRef x, MapRef dy, int stride = 1, int pad_t = 0, int pad_l = 0, bool side = true) {
+    dgp_trainer* tr = p.tr; TrainCtx& ctx = p.ctx;
+    const ConvLayer& l = p.net->layers[li];
+    hipStream_t st = p.s;
+    const bool beside = side && p.side.on;
+    if (beside)
+        if (int rc = p.side.fork(st)) return rc;
+    WgradCall c;
+    c.d.N = p.B; c.d.H = x.H; c.d.W = x.W; c.d.Cin = l.Cin; c.d.Ho = dy.H; c.d.Wo = dy.W; c.d.Cout = l.Cout;
+    c.d.KH = l.KH; c.d.KW = l.KW; c.d.stride = stride; c.d.rate = l.rate; c.d.pad_t = pad_t; c.d.pad_l = pad_l;
+    c.x = {x.p, ctx.rng.of(x.p)};
+    c.dy = {dy.p, ctx.rng.of(dy.p)};
+    c.dwraw = reinterpret_cast<float*>(p.ws + p.pl.dw_l[li]);
+    c.colsum = reinterpret_cast<float*>(p.ws + p.pl.cs_l[li]);
+    c.zeroed = true;
     {
-        const auto px = g_ctx->shadow_prev.find(x), py = g_ctx->shadow_prev.find(dy);
-        const auto bx = g_ctx->shadow_base.find(x), by = g_ctx->shadow_base.find(dy);
-        if (px != g_ctx->shadow_prev.end() && py != g_ctx->shadow_prev.end() && bx != g_ctx->shadow_base.end() && by != g_ctx->shadow_base.end()) {
-            xs = bx->second; xp = px->second; dys = by->second; dyp = py->second;
+        const auto px = ctx.shadow_prev.find(x.p), py = ctx.shadow_prev.find(dy.p);
+        const auto bx = ctx.shadow_base.find(x.p), by = ctx.shadow_base.find(dy.p);
+        if (px != ctx.shadow_prev.end() && py != ctx.shadow_prev.end() && bx != ctx.shadow_base.end() && by != ctx.shadow_base.end()) {
+            c.x.cells = bx->second; c.x.prev = px->second;
+            c.dy.cells = by->second; c.dy.prev = py->second;
         }
     }
-    int* h2_only = (xs && xs == (const void*)x) ? tr->d_fast_flag : nullptr;       // fast pass: the activation has no fp32 twin
-    const bool h1 = tr->fwd_fast && tr->fwd_fmt == 2 && xs && dys;                 // 16-bit tier: both operands are H1 tensors
-    if (h1) h2_only = tr->d_fast_flag;
-    if (!h2_only && tr->fwd_fast && g_ctx->shadow_base.count(x) && g_ctx->shadow_base[x] == x)
+    if (c.x.cells && c.x.cells == (const void*)x.p) c.fail_flag = tr->d_fast_flag;      // fast pass: the activation has no fp32 twin
+    c.h1 = p.h1p() && c.x.cells && c.dy.cells;                                          // 16-bit tier: both operands are H1 tensors
+    if (c.h1) c.fail_flag = tr->d_fast_flag;
+    if (!c.fail_flag && p.fast && ctx.shadow_base.count(x.p) && ctx.shadow_base[x.p] == x.p)
         return fail(DGP_ERR_STATE, "weight gradient of an H2-only activation without a usable gradient copy");
-    TRY_HIP(wgrad_launch(x, N, H, W, l.Cin, dy, Ho, Wo, l.Cout, l.KH, l.KW, stride, l.rate, pad_t, pad_l,
-                         reinterpret_cast<float*>(g_ctx->defer_ws + ((const TPlan*)g_ctx->defer_plan)->dw_l[li]),
-                         reinterpret_cast<float*>(g_ctx->defer_ws + ((const TPlan*)g_ctx->defer_plan)->cs_l[li]), ws_, true,
-                         nullptr, nullptr, xs, xp, dys, dyp, h2_only, h1));
-    if (done) {
-        TRY_HIP(hipEventRecord(done, g_ctx->s2));
-        g_ctx->readers.emplace((const void*)dy, done);
-    }
+    TRY_HIP(wgrad_launch(c, st));
+    if (beside) return p.side.reads(dy.p);
     return DGP_OK;
 }
 
-int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t workspace_bytes, const float* dscmap,
-                       const float* dlocref, void* stream) {
-    if (tr) g_ctx = &tr->ctx;
-    if (!tr || !workspace || !dscmap || !dlocref) return fail(DGP_ERR_INVALID, "dgp_train_backward: null argument");
-    dgp_net* net = tr->net;
-    const TPlan pl = make_tplan(tr, nt);
-    if (workspace_bytes < pl.total) return fail(DGP_ERR_INVALID, "dgp_train_backward: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    auto F = [&](size_t off) { return (float*)(ws + off); };
-    g_ctx->tail_slab = F(pl.tail);
-    range_pass_begin(tr, s, true);
-    if (pl.sh_g0) {
-        const size_t gb[6][2] = {{pl.g0, pl.sh_g0}, {pl.g1, pl.sh_g1}, {pl.dr1, pl.sh_dr1}, {pl.dr2, pl.sh_dr2}, {pl.dr1_b, pl.sh_dr1_b}, {pl.dr2_b, pl.sh_dr2_b}};
-        for (const auto& q : gb) { g_ctx->shadow_base[F(q[0])] = F(q[1]); g_ctx->shadow_prev.erase(F(q[0])); }
-    }
-    struct WantReset { ~WantReset() { g_shadow_want = true; } } want_reset;
-    const dgp_net_desc& d = net->desc;
-    const int B = nt, nj = d.num_joints;
-    const int nu = (int)net->units.size();
-    g_ctx->defer_plan = &pl;
-    g_ctx->defer_ws = ws;
-    TRY_HIP(hipMemsetAsync(ws + pl.dwall, 0, pl.dwall_bytes, s));
-    // weight gradients on their own stream beside the data-gradient chain (DGP_WGRAD_OVERLAP=0: one stream, A/B)
-    static const bool overlap_env = (dgp_tune("DGP_WGRAD_OVERLAP", 1) != 0);
-    TrainCtx* const ctx = g_ctx;
-    if (overlap_env) {
-        if (!ctx->s2) {
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);         // lo: numerically greatest = least urgent
-            TRY_HIP(hipStreamCreateWithPriority(&ctx->s2, hipStreamNonBlocking, lo));
-        }
-        ctx->overlap = true;
-        ctx->ev_next = 0;
-        ctx->readers.clear();
-    }
-    // join: the chain's stream waits for every weight gradient (before the finalisation launches, and on every exit path)
-    struct Join {
-        TrainCtx* c; hipStream_t s;
-        void operator()() {
-            if (!c->overlap) return;
-            c->overlap = false;
-            c->readers.clear();
-            hipEvent_t e = c->take_event();
-            if (e && hipEventRecord(e, c->s2) == hipSuccess) (void)hipStreamWaitEvent(s, e, 0);
-            else (void)hipStreamSynchronize(c->s2);
-        }
-        ~Join() { (*this)(); }
-    } join{ctx, s};
-    // the chain is about to overwrite `buf`: wait for the weight-gradient launches that still read it
-    auto before_write = [&](const void* buf) -> hipError_t {
-        if (!ctx->overlap) return hipSuccess;
-        auto range = ctx->readers.equal_range(buf);
-        for (auto it = range.first; it != range.second; ++it) {
-            hipError_t e2 = hipStreamWaitEvent(s, it->second, 0);
-            if (e2 != hipSuccess) return e2;
-        }
-        ctx->readers.erase(range.first, range.second);
-        return hipSuccess;
-    };
-    const int fh = net->fh, fw = net->fw;
-    float* dwraw = F(pl.dwraw);
-    float* colsum = F(pl.colsum);
-    float* G[2] = {F(pl.g0), F(pl.g1)};
-    int cur = 0;
-    int rc;
+// a head's weight gradient (the 2x2-conv form on the feature grid) through the shared dwraw / colsum scratch of the plan
+static WgradCall head_wgrad_call(TrainPass& p, int cin, int cdy) {
+    WgradCall c;
+    c.d.N = p.B; c.d.H = c.d.Ho = p.net->fh; c.d.W = c.d.Wo = p.net->fw; c.d.Cin = cin; c.d.Cout = cdy;
+    c.d.KH = c.d.KW = 2; c.d.stride = c.d.rate = 1; c.d.pad_t = c.d.pad_l = 1;
+    c.dwraw = p.F(p.pl.dwraw); c.colsum = p.F(p.pl.colsum);
+    return c;
+}
 
-    // fast pass (dgp_train_forward): the activations of units >= ub are H2 tensors -- gates read them as such, weight gradients read
-    // them in place, and the heads use the fp32 copy of the features the forward pass left in feat32
-    const bool fast = tr->fwd_fast;
-    const bool h1p = fast && tr->fwd_fmt == 2;          // 16-bit tier: the gradient tensors of units >= ub are H1-only as well
-    int ub = nu;
-    for (int ui = 1; ui < nu; ++ui)
-        if (net->units[ui].depth_bn >= 128 && pl.sh_xo[ui - 1]) { ub = ui; break; }
-    if (h1p && pl.sh_pool) ub = 0;      // (as dgp_train_forward decided)
-    g_h2 = H2Launch();
-    g_shadow_fmt = h1p ? 2 : 1;
-    if (h1p) g_ctx->h2_slots.clear();                   // this pass's H1 gradient tensors, checked against their predicted scales at its end
-    float* GH[2] = {F(pl.sh_g0), F(pl.sh_g1)};           // tier 1: G of the H1 units (the fp16-copy regions of the parity pass hold the tensors themselves)
-    // H1 tensor `t` takes the range slot / predicted scale of the launch that wrote `src` (a converted copy of it)
-    auto adopt_h1 = [&](const void* t, const void* src) -> int {
-        const float* slot = range_of(src);
-        const float* pv = range_prev_of(slot);
-        if (!slot || !pv) return fail(DGP_ERR_STATE, "16-bit tier: a gradient tensor has no predicted range");
-        range_set(t, slot);
-        g_ctx->shadow_base[t] = const_cast<float*>(static_cast<const float*>(t));
-        g_ctx->shadow_prev[t] = pv;
-        const int idx = (int)((pv - g_ctx->rng.prev) / ABSMAX_SLOTS);
-        if (std::find(g_ctx->h2_slots.begin(), g_ctx->h2_slots.end(), idx) == g_ctx->h2_slots.end()) g_ctx->h2_slots.push_back(idx);
-        return DGP_OK;
-    };
-    // ---- heads: gather phases, parameter grads, data grad into G[cur] (gated by the last unit's ReLU)
-    const float* feat = fast ? F(pl.feat32) : F(pl.xo[nu - 1]);
-    // range of the gathered loss gradients (both heads): the first slot of every backward pass -- it predicts the scale of the merged
-    // H1 tensor of the next 16-bit pass
-    float* const slot_dph = range_take();
-    const bool heads_h1 = h1p && tr->d_hmT && tr->d_hmT_h1 && slot_dph && range_prev_of(slot_dph) && !tr->fwd_feat32;
-    if (fast && !heads_h1 && !tr->fwd_feat32) return fail(DGP_ERR_STATE, "backward: the forward pass left no fp32 features for the heads");
-    if (heads_h1) {
-        // ---- 16-bit tier: both heads at once.  Their loss gradients are gathered into ONE H1 tensor (scale predicted from its range one
-        // step ago); ONE weight-gradient launch reads it and the H1 features in place (second stream), ONE H1 -> H1 data-gradient launch
-        // with the merged panel writes d features, gated by the features' ReLU, as the H1 tensor the last unit's backward reads.
-        const ConvLayer &l0 = net->layers[net->head_part], &l1 = net->layers[net->head_locref];
-        const TLayer &t0 = tr->tl[net->head_part], &t1 = tr->tl[net->head_locref];
-        const int CT = tr->hm_ct, njt0 = l0.Cout / 4, njt1 = l1.Cout / 4;
-        float* const DPH = F(pl.dphh);
-        const float* dprev = range_prev_of(slot_dph);
-        const float* featH = F(pl.xo[nu - 1]);
-        const auto fp = g_ctx->shadow_prev.find(featH);
-        if (fp == g_ctx->shadow_prev.end()) return fail(DGP_ERR_STATE, "16-bit tier: the features have no predicted range");
-        hipLaunchKernelGGL(head_gather_h1_kernel, dim3(grid_for((long long)B * fh * fw * (CT / 8))), dim3(256), 0, s, dscmap, dlocref, B, fh, fw,
-                           njt0, t0.cpad, njt1, t1.cpad, CT, dprev, reinterpret_cast<uint4*>(DPH), slot_dph);
-        range_set(DPH, slot_dph);
-        g_ctx->shadow_base[DPH] = DPH;
-        g_ctx->shadow_prev[DPH] = dprev;
-        g_ctx->h2_slots.push_back((int)((dprev - g_ctx->rng.prev) / ABSMAX_SLOTS));
-        hipStream_t hs_ = s;
-        if (ctx->overlap) {
-            hipEvent_t ready = ctx->take_event();
-            if (!ready) return fail(DGP_ERR_HIP, "weight-gradient stream: hipEventCreate failed");
-            TRY_HIP(hipEventRecord(ready, s));
-            TRY_HIP(hipStreamWaitEvent(ctx->s2, ready, 0));
-            hs_ = ctx->s2;
-        }
-        TRY_HIP(wgrad_launch(featH, B, fh, fw, l0.Cin, DPH, fh, fw, CT, 2, 2, 1, 1, 1, 1, dwraw, colsum, hs_, false, nullptr, nullptr, featH,
-                             fp->second, DPH, dprev, tr->d_fast_flag, true));
-        hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt0 * l0.Cin)), dim3(256), 0, hs_, dwraw, colsum, njt0, l0.Cin, CT, 0,
-                           tr->grads + t0.w_off, tr->grads + t0.b_off);
-        hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt1 * l1.Cin)), dim3(256), 0, hs_, dwraw, colsum, njt1, l1.Cin, CT, t0.cpad,
-                           tr->grads + t1.w_off, tr->grads + t1.b_off);
-        (void)range_take();                      // (the slot the first head's launch takes in a plain pass: every pass takes its slots in one order)
-        ConvLayer lt = l0;
-        lt.KH = lt.KW = 2; lt.rate = 1;
-        g_h2 = H2Launch();
-        g_h2.in_fmt = 2; g_h2.out_fmt = 2; g_h2.mask_fmt = 2;
-        TRY_HIP(conv_launch(lt, tr->d_hmT, tr->hm_nk, t0.cinP, DPH, B, fh, fw, CT, 0, 0, fh, fw, l0.Cin, 1, 0, nullptr, nullptr, nullptr, 0, 0, 0,
-                            featH, false, 0, 0, GH[cur], s));
-    } else {
-        // the per-head data-gradient panels (t.d_wT) are parity-only panels: a 16-bit pass that cannot merge its heads (DGP_TRAIN_HEADS_H1=0,
-        // head widths the merged panel does not take) lands here after lazy syncs and must not read last step's weights
-        if (tr->parity_stale && (rc = refresh_parity_panels(tr, s))) return rc;
-        const size_t heads[2] = {(size_t)net->head_part, (size_t)net->head_locref};
-        const float* dsrc[2] = {dscmap, dlocref};
-        float* dph[2] = {F(pl.dph0), F(pl.dph1)};
-        for (int k = 0; k < 2; ++k) {
-            const ConvLayer& l = net->layers[heads[k]];
-            const TLayer& t = tr->tl[heads[k]];
-            const int njt = l.Cout / 4;
-            const long long tot = (long long)B * fh * fw * t.cpad;
-            hipLaunchKernelGGL(head_gather_kernel, dim3(grid_for(tot)), dim3(256), 0, s, dsrc[k], B, fh, fw, njt, t.cpad, dph[k], slot_dph);
-            // the head's parameter gradients (fill + wgrad + finalise through the shared dwraw / colsum scratch, in stream order) go to the
-            // second stream when the pass overlaps: the chain only needs dph[k] for the data gradient below
-            hipStream_t hs_ = s;
-            if (ctx->overlap) {
-                hipEvent_t ready = ctx->take_event();
-                if (!ready) return fail(DGP_ERR_HIP, "weight-gradient stream: hipEventCreate failed");
-                TRY_HIP(hipEventRecord(ready, s));
-                TRY_HIP(hipStreamWaitEvent(ctx->s2, ready, 0));
-                hs_ = ctx->s2;
-            }
-            TRY_HIP(wgrad_launch(feat, B, fh, fw, l.Cin, dph[k], fh, fw, t.cpad, 2, 2, 1, 1, 1, 1, dwraw, colsum, hs_));
-            hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt * l.Cin)), dim3(256), 0, hs_, dwraw, colsum, njt,
-                               l.Cin, t.cpad, 0, tr->grads + t.w_off, tr->grads + t.b_off);
-            // dfeat (+)= convT: 2x2 taps flipped, pad' = 0; second head accumulates onto the first; gate on the last
-            ConvLayer lt = l;
-            lt.KH = lt.KW = 2; lt.rate = 1;
-            TRY_HIP(conv_launch(lt, t.d_wT, t.nkT, t.cinP, dph[k], B, fh, fw, t.cpad, 0, 0, fh, fw, l.Cin, 1, 0, nullptr, nullptr,
-                                k == 1 ? G[cur] : nullptr, 1, fh, fw, k == 1 ? feat : nullptr, false, 0, 0, G[cur], s));
-        }
-    }
+// the deferred finalisation of `count` rows of the table from `first` on stream st: dW from dWraw, then d gamma / d beta
+static void finalise(TrainPass& p, int first, int count, hipStream_t st) {
+    if (count <= 0) return;
+    const int rpb = 128;
+    hipLaunchKernelGGL(scale_dw_dot_all_kernel, dim3((p.fin.max_cout + 63) / 64, (p.fin.max_krows + rpb - 1) / rpb, (unsigned)count), dim3(256), 0, st,
+                       p.fin.tab + first, (const char*)p.ws, p.tr->params, p.tr->grads, rpb);
+}
+static void bn_grads(TrainPass& p, int first, int count, hipStream_t st) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(bn_param_grads_all_kernel, dim3((p.fin.max_cout + 127) / 128, (unsigned)count), dim3(128), 0, st, p.fin.tab + first,
+                       (const char*)p.ws, p.tr->stats, p.net->desc.bn_eps, p.tr->grads);
+}
 
-    if (heads_h1) {
-        // (the merged launch wrote the H1 tensor itself)
-    } else if (h1p) {
-        // the heads' data gradient (fp32, from the kernels of the parity path) enters the H1 units as an H1 tensor
-        if ((rc = adopt_h1(GH[cur], G[cur]))) return rc;
-        const long long n8 = (long long)B * fh * fw * net->units[nu - 1].depth / 8;
-        hipLaunchKernelGGL(f32_to_h1_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, s, reinterpret_cast<const float4*>(G[cur]), n8,
-                           g_ctx->shadow_prev[GH[cur]], reinterpret_cast<uint4*>(GH[cur]));
-    } else if (fast) {
-        // the heads' data gradient came from a kernel that writes no fp16 copy, and the last unit's conv3 weight gradient can only read
-        // its H2 activation through the LDS-DMA tile: make the copy here
-        const float* pv = range_prev_of(range_of(G[cur]));
-        const auto sb = g_ctx->shadow_base.find(G[cur]);
-        if (!pv || sb == g_ctx->shadow_base.end()) return fail(DGP_ERR_STATE, "fast pass: no range for the heads' data gradient");
-        const long long n8 = (long long)B * fh * fw * net->units[nu - 1].depth / 8;
-        hipLaunchKernelGGL(f32_to_shadow_kernel, dim3(grid_for(n8)), dim3(256), 0, s, reinterpret_cast<const float4*>(G[cur]), n8, pv,
-                           reinterpret_cast<uint4*>(sb->second));
-        g_ctx->shadow_prev[G[cur]] = pv;
-    }
-    // ---- bottleneck units, last to first.  G[cur] = d loss / d (unit output), already gated by its ReLU.
-    int stop_after = -1;
-#ifdef DGP_TUNING
-    if (const char* e = getenv("DGP_BWD_STOP")) stop_after = atoi(e);      // debugging aid (tuning builds): leave G of an inner unit in place
-#endif
-    // 16-bit tier with the fused root block: the stem's weight gradient reads d pool as the H1 tensor unit 0 leaves (stem_wgrad_h1_kernel:
-    // pool backward fused, no d conv1 map); A/B switch DGP_TRAIN_STEM_WGRAD_H1=0
-    static const bool stem_wgrad_env = (dgp_tune("DGP_TRAIN_STEM_WGRAD_H1", 1) != 0);
-    const bool stem_wgrad_h1 = stem_wgrad_env && h1p && ub == 0 && tr->fwd_stem_fused &&
-                               net->layers[net->conv1].Cout == 64 && net->layers[net->conv1].KH == 7 && net->layers[net->conv1].Cin == 4;
-    const float* stem_g = nullptr;
-    const float* stem_g_prev = nullptr;
-    // finalisation: table of every non-head layer, conv1 LAST (its weight gradient is the last launch of the pass: the other
-    // layers are finalised beside it)
-    int max_cout = 0, max_krows = 0;
-    if (!tr->d_fin_table || tr->fin_B != B || tr->fin_h != d.in_h || tr->fin_w != d.in_w) {      // offsets follow the plan
+// Finalisation table of every non-head layer, conv1 LAST (its weight gradient is the last launch of the pass: the other layers are
+// finalised beside it); rebuilt (behind a stream synchronisation) when the plan's offsets change with the batch or the frame size
+static int plan_finalisation(TrainPass& p) {
+    dgp_trainer* tr = p.tr; const dgp_net* net = p.net; const dgp_net_desc& d = net->desc;
+    if (!tr->d_fin_table || tr->fin_B != p.B || tr->fin_h != d.in_h || tr->fin_w != d.in_w) {      // offsets follow the plan
         std::vector<FinDesc> tab;
         tr->fin_of_layer.assign(net->layers.size(), -1);
         auto entry = [&](size_t li) {
@@ -2838,7 +2786,7 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             const ConvLayer& l = net->layers[li];
             const TLayer& t = tr->tl[li];
             FinDesc f{};
-            f.dw_off = (long long)pl.dw_l[li]; f.cs_off = (long long)pl.cs_l[li];
+            f.dw_off = (long long)p.pl.dw_l[li]; f.cs_off = (long long)p.pl.cs_l[li];
             f.w_off = t.w_off; f.g_off = t.g_off; f.b_off = t.b_off; f.mean_off = t.mean_off; f.var_off = t.var_off;
             f.taps = l.KH * l.KW; f.cin = l.Cin; f.cin_real = t.cin_real; f.cout = l.Cout; f.d_scale = l.d_scale;
             tab.push_back(f);
@@ -2847,310 +2795,437 @@ int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t work
             if ((int)li != net->head_part && (int)li != net->head_locref && (int)li != net->conv1) entry(li);
         entry((size_t)net->conv1);
         if (!tr->d_fin_table) TRY_HIP(hipMalloc(&tr->d_fin_table, tab.size() * sizeof(FinDesc)));
-        TRY_HIP(hipStreamSynchronize(s));        // (a previous pass may still read the old table)
+        TRY_HIP(hipStreamSynchronize(p.s));        // (a previous pass may still read the old table)
         TRY_HIP(hipMemcpy(tr->d_fin_table, tab.data(), tab.size() * sizeof(FinDesc), hipMemcpyHostToDevice));
-        tr->n_fin = (int)tab.size(); tr->fin_B = B; tr->fin_h = d.in_h; tr->fin_w = d.in_w;
+        tr->n_fin = (int)tab.size(); tr->fin_B = p.B; tr->fin_h = d.in_h; tr->fin_w = d.in_w;
     }
+    p.fin.tab = reinterpret_cast<const FinDesc*>(tr->d_fin_table);
     for (size_t li = 0; li < net->layers.size(); ++li) {
         if ((int)li == net->head_part || (int)li == net->head_locref) continue;
-        max_cout = std::max(max_cout, net->layers[li].Cout);
-        max_krows = std::max(max_krows, net->layers[li].KH * net->layers[li].KW * tr->tl[li].cin_real);
+        p.fin.max_cout = std::max(p.fin.max_cout, net->layers[li].Cout);
+        p.fin.max_krows = std::max(p.fin.max_krows, net->layers[li].KH * net->layers[li].KW * tr->tl[li].cin_real);
     }
-    const int rpb = 128;
-    const FinDesc* fin_tab = reinterpret_cast<const FinDesc*>(tr->d_fin_table);
-    auto finalise = [&](int first, int count, hipStream_t st) {
-        if (count <= 0) return;
-        hipLaunchKernelGGL(scale_dw_dot_all_kernel, dim3((max_cout + 63) / 64, (max_krows + rpb - 1) / rpb, (unsigned)count), dim3(256), 0, st,
-                           fin_tab + first, (const char*)ws, tr->params, tr->grads, rpb);
+    return DGP_OK;
+}
+
+// Gradient groups (see dgp_trainer::GradGroup), built once per trainer after the finalisation table: cut the units, back to front, into
+// runs of >= a quarter of the parameters each
+static int plan_grad_groups(dgp_trainer* tr) {
+    if (!tr->groups.empty()) return DGP_OK;
+    const dgp_net* net = tr->net;
+    const int nu = (int)net->units.size();
+    auto layer_range = [&](int li, long long& lo, long long& hi) {
+        if (li < 0) return;
+        const ConvLayer& l = net->layers[li];
+        const TLayer& t = tr->tl[li];
+        const bool head = (li == net->head_part || li == net->head_locref);
+        const long long wsz_ = head ? 9ll * (l.Cout / 4) * l.Cin : (long long)l.KH * l.KW * t.cin_real * l.Cout;
+        const long long bsz_ = head ? l.Cout / 4 : l.Cout;
+        auto acc = [&](long long off, long long n) { lo = std::min(lo, off); hi = std::max(hi, off + (n + 3) / 4 * 4); };
+        acc(t.w_off, wsz_);
+        if (!head) acc(t.g_off, bsz_);
+        acc(t.b_off, bsz_);
     };
-    auto bn_grads = [&](int first, int count, hipStream_t st) {
-        if (count <= 0) return;
-        hipLaunchKernelGGL(bn_param_grads_all_kernel, dim3((max_cout + 127) / 128, (unsigned)count), dim3(128), 0, st, fin_tab + first,
-                           (const char*)ws, tr->stats, d.bn_eps, tr->grads);
-    };
-    // ---- gradient groups (see dgp_trainer::GradGroup): cut the units, back to front, into runs of >= a quarter of the parameters each
-    if (tr->groups.empty()) {
-        auto layer_range = [&](int li, long long& lo, long long& hi) {
-            if (li < 0) return;
-            const ConvLayer& l = net->layers[li];
-            const TLayer& t = tr->tl[li];
-            const bool head = (li == net->head_part || li == net->head_locref);
-            const long long wsz_ = head ? 9ll * (l.Cout / 4) * l.Cin : (long long)l.KH * l.KW * t.cin_real * l.Cout;
-            const long long bsz_ = head ? l.Cout / 4 : l.Cout;
-            auto acc = [&](long long off, long long n) { lo = std::min(lo, off); hi = std::max(hi, off + (n + 3) / 4 * 4); };
-            acc(t.w_off, wsz_);
-            if (!head) acc(t.g_off, bsz_);
-            acc(t.b_off, bsz_);
-        };
-        std::vector<dgp_trainer::GradGroup> gs;
-        dgp_trainer::GradGroup cur_g;
-        long long lo = tr->n_train, hi = 0;
-        int f_lo = tr->n_fin, f_n = 0;
-        layer_range(net->head_part, lo, hi);
-        layer_range(net->head_locref, lo, hi);
-        for (int ui = nu - 1; ui >= 1; --ui) {
-            const Unit& u = net->units[ui];
-            for (int li : {u.sc, u.c1, u.c2, u.c3}) {
-                if (li < 0) continue;
-                layer_range(li, lo, hi);
-                f_lo = std::min(f_lo, tr->fin_of_layer[li]); ++f_n;
-            }
-            if (hi - lo >= tr->n_train / 4 && gs.size() < 6) {
-                cur_g.cut_ui = ui; cur_g.fin_first = f_lo; cur_g.fin_count = f_n; cur_g.lo = lo; cur_g.hi = hi;
-                gs.push_back(cur_g);
-                lo = tr->n_train; hi = 0; f_lo = tr->n_fin; f_n = 0;
-            }
-        }
-        // the last group: everything in front of the last cut (its table rows are [0, first cut row) + the stem's row, finalised at the end)
-        dgp_trainer::GradGroup last;
-        last.cut_ui = -1; last.lo = 0; last.hi = gs.empty() ? tr->n_train : gs.back().lo;
-        last.fin_first = 0; last.fin_count = gs.empty() ? tr->n_fin - 1 : gs.back().fin_first;
-        bool ok = true;                              // the groups must tile the flat buffer and the table, back to front
-        long long expect_hi = tr->n_train;
-        int expect_f = tr->n_fin - 1;
-        for (const auto& g : gs) {
-            ok = ok && g.hi == expect_hi && g.fin_first + g.fin_count == expect_f && g.lo < g.hi;
-            expect_hi = g.lo; expect_f = g.fin_first;
-        }
-        if (!ok) gs.clear(), last.hi = tr->n_train, last.fin_count = tr->n_fin - 1;
-        gs.push_back(last);
-        for (auto& g : gs)
-            if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) return fail(DGP_ERR_HIP, "gradient groups: hipEventCreate failed");
-        tr->groups = gs;
-    }
-    size_t grp_next = 0;                                 // next group to complete
-    // a group is complete behind the weight gradients of its layers: finalise it on their stream and record its event
-    auto close_groups_at = [&](int ui) -> hipError_t {
-        while (grp_next + 1 < tr->groups.size() && tr->groups[grp_next].cut_ui == ui) {
-            auto& g = tr->groups[grp_next++];
-            hipStream_t st = ctx->overlap ? ctx->s2 : s;
-            finalise(g.fin_first, g.fin_count, st);
-            bn_grads(g.fin_first, g.fin_count, st);
-            hipError_t e2 = hipEventRecord(g.ev, st);
-            if (e2 != hipSuccess) return e2;
-        }
-        return hipSuccess;
-    };
-    for (int ui = nu - 1; ui >= 0; --ui) {
-        if (stop_after >= 0 && (nu - 1 - ui) >= stop_after) {
-            if (const char* e2 = getenv("DGP_BWD_DUMP")) {
-                (void)hipStreamSynchronize(s);
-                const size_t n = (size_t)B * net->units[ui].ho * net->units[ui].wo * net->units[ui].depth;
-                std::vector<float> hbuf(n);
-                (void)hipMemcpy(hbuf.data(), G[cur], n * sizeof(float), hipMemcpyDeviceToHost);
-                FILE* f = fopen(e2, "wb");
-                if (f) { fwrite(hbuf.data(), sizeof(float), n, f); fclose(f); }
-                (void)hipMemcpy(hbuf.data(), F(pl.xo[ui]), n * sizeof(float), hipMemcpyDeviceToHost);
-                f = fopen((std::string(e2) + ".x").c_str(), "wb");
-                if (f) { fwrite(hbuf.data(), sizeof(float), n, f); fclose(f); }
-            }
-            return DGP_OK;
-        }
+    std::vector<dgp_trainer::GradGroup> gs;
+    dgp_trainer::GradGroup cur_g;
+    long long lo = tr->n_train, hi = 0;
+    int f_lo = tr->n_fin, f_n = 0;
+    layer_range(net->head_part, lo, hi);
+    layer_range(net->head_locref, lo, hi);
+    for (int ui = nu - 1; ui >= 1; --ui) {
         const Unit& u = net->units[ui];
-        const int h = u.h, w = u.w, ho = u.ho, wo = u.wo;
-        const float* xin = ui == 0 ? F(pl.pool) : F(pl.xo[ui - 1]);
-        if (h1p && ui >= ub) {
-            // ---- 16-bit tier: every tensor of this unit is an H1 tensor with a predicted scale; data gradients are H1 -> H1 launches of the
-            // cell kernels (gate and residual read as H1), weight gradients read both operands in place (wgrad_dma_h1)
-            const ConvLayer &l1 = net->layers[u.c1], &l2 = net->layers[u.c2], &l3 = net->layers[u.c3];
-            const TLayer &t1 = tr->tl[u.c1], &t2 = tr->tl[u.c2], &t3 = tr->tl[u.c3];
-            float* const GoutH = GH[cur];
-            float* const GinH = GH[cur ^ 1];
-            float* const DR2H = F((ui & 1) ? pl.sh_dr2_b : pl.sh_dr2);
-            float* const DR1H = F((ui & 1) ? pl.sh_dr1_b : pl.sh_dr1);
-            float* const DXAH = F((ui & 1) ? pl.dxa_b : pl.dxa);
-            const float* xinH = ui > ub ? xin : F(ui == 0 ? pl.sh_pool : pl.sh_xo[ui - 1]);       // (unit ub reads the H1 copy of its fp32 input)
-            auto fmt = [&](bool gate, const void* res_key) {
-                g_h2 = H2Launch();
-                g_h2.in_fmt = 2; g_h2.out_fmt = 2; g_h2.mask_fmt = gate ? 2 : 0;
-                if (res_key) { g_h2.res_fmt = 2; g_h2.res_key = res_key; }
-            };
-            rc = layer_param_grads(tr, u.c3, F(pl.r2[ui]), B, ho, wo, GoutH, ho, wo, 1, 0, 0, s);
-            if (rc) return rc;
-            TRY_HIP(before_write(DR2H));
-            fmt(true, nullptr);
-            TRY_HIP(conv_launch(l3, t3.d_wT, t3.nkT, t3.cinP, GoutH, B, ho, wo, l3.Cout, 0, 0, ho, wo, l3.Cin, 1, 0, nullptr, nullptr,
-                                nullptr, 0, 0, 0, F(pl.r2[ui]), false, 0, 0, DR2H, s));
-            const int pb_h = u.pb_h, pb_w = u.pb_w;
-            rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2H, ho, wo, u.stride, pb_h, pb_w, s);
-            if (rc) return rc;
-            const int keff = 2 * u.rate + 1;
-            TRY_HIP(before_write(DR1H));
-            if (u.stride > 1) {
-                // stride-2 conv2: its data gradient reads dR2 on the zero-stuffed grid; materialised (a few MB) so that it is a plain stride-1 launch
-                if (u.stride != 2) return fail(DGP_ERR_STATE, "16-bit tier: stride > 2");
-                float* const ZS = F(pl.dr1);             // (the fp32 dR1 region is free while the H1 units run)
-                const size_t zbytes = (size_t)B * 2 * ho * 2 * wo * l2.Cout * 2;
-                if (zbytes > (size_t)B * h * w * u.depth_bn * 4 + 0) { if (zbytes > (size_t)4 * ((size_t)B * h * w * u.depth_bn)) return fail(DGP_ERR_STATE, "16-bit tier: zero-stuffed gradient does not fit"); }
-                TRY_HIP(before_write(ZS));
-                TRY_HIP(hipMemsetAsync(ZS, 0, zbytes, s));
-                const long long tot = (long long)B * ho * wo * (l2.Cout / 8);
-                hipLaunchKernelGGL(h1_zero_stuff_kernel, dim3(grid_for(tot)), dim3(256), 0, s, reinterpret_cast<const uint4*>(DR2H), B, ho, wo,
-                                   l2.Cout / 8, reinterpret_cast<uint4*>(ZS));
-                fmt(true, nullptr);
-                TRY_HIP(conv_launch(l2, t2.d_wT, t2.nkT, t2.cinP, ZS, B, 2 * ho, 2 * wo, l2.Cout, keff - 1 - pb_h, keff - 1 - pb_w, h, w,
-                                    l2.Cin, 1, 0, nullptr, nullptr, nullptr, 0, 0, 0, F(pl.r1[ui]), false, 0, 0, DR1H, s, DR2H));
-            } else {
-                fmt(true, nullptr);
-                TRY_HIP(conv_launch(l2, t2.d_wT, t2.nkT, t2.cinP, DR2H, B, ho, wo, l2.Cout, keff - 1 - pb_h, keff - 1 - pb_w, h, w,
-                                    l2.Cin, 1, 0, nullptr, nullptr, nullptr, 0, 0, 0, F(pl.r1[ui]), false, 0, 0, DR1H, s));
-            }
-            const float* dxa = GoutH;
-            int dxa_mode = 1, dxa_h = ho, dxa_w = wo;
-            if (u.sc >= 0) {
-                const ConvLayer& ls = net->layers[u.sc];
-                const TLayer& ts = tr->tl[u.sc];
-                if (u.stride != 1) return fail(DGP_ERR_STATE, "16-bit tier: strided shortcut conv");
-                rc = layer_param_grads(tr, u.sc, xin, B, h, w, GoutH, ho, wo, 1, 0, 0, s);
-                if (rc) return rc;
-                TRY_HIP(before_write(DXAH));
-                fmt(false, nullptr);
-                TRY_HIP(conv_launch(ls, ts.d_wT, ts.nkT, ts.cinP, GoutH, B, ho, wo, ls.Cout, 0, 0, h, w, ls.Cin, 1, 0, nullptr, nullptr,
-                                    nullptr, 0, 0, 0, nullptr, false, 0, 0, DXAH, s));
-                dxa = DXAH; dxa_h = h; dxa_w = w;
-            } else if (u.stride > 1) {
-                dxa_mode = -2;
-            }
-            rc = layer_param_grads(tr, u.c1, xin, B, h, w, DR1H, h, w, 1, 0, 0, s);
-            if (rc) return rc;
-            TRY_HIP(before_write(GinH));
-            fmt(true, dxa);
-            TRY_HIP(conv_launch(l1, t1.d_wT, t1.nkT, t1.cinP, DR1H, B, h, w, l1.Cout, 0, 0, h, w, l1.Cin, 1, 0, nullptr, nullptr,
-                                dxa, dxa_mode, dxa_h, dxa_w, xinH, false, 0, 0, GinH, s));
-            if (ui == ub && ub == 0 && stem_wgrad_h1) {
-                // (unit 0's data gradient stays H1: the fused stem weight-gradient kernel below reads it in place)
-                stem_g = GinH;
-                stem_g_prev = g_ctx->shadow_prev[GinH];
-            } else if (ui == ub) {
-                // the data gradient leaves the H1 units: fp32 copy for block1's kernels (same range slot: the epilogue tracked max |G| before rounding)
-                float* Gf = G[cur ^ 1];
-                TRY_HIP(before_write(Gf));
-                const long long n8 = (long long)B * h * w * l1.Cin / 8;
-                hipLaunchKernelGGL(h1_to_f32_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, s, reinterpret_cast<const uint4*>(GinH), n8,
-                                   g_ctx->shadow_prev[GinH], reinterpret_cast<float4*>(Gf), (const uint4*)nullptr);
-                range_set(Gf, range_of(GinH));
-                g_ctx->shadow_prev.erase(Gf);
-            }
-            cur ^= 1;
-            TRY_HIP(close_groups_at(ui));
-            continue;
+        for (int li : {u.sc, u.c1, u.c2, u.c3}) {
+            if (li < 0) continue;
+            layer_range(li, lo, hi);
+            f_lo = std::min(f_lo, tr->fin_of_layer[li]); ++f_n;
         }
-        float* Gout = G[cur];
-        float* Gin = G[cur ^ 1];
-        const ConvLayer &l1 = net->layers[u.c1], &l2 = net->layers[u.c2], &l3 = net->layers[u.c3];
-        const TLayer &t1 = tr->tl[u.c1], &t2 = tr->tl[u.c2], &t3 = tr->tl[u.c3];
-        // gradient buffers of this unit (units alternate between two sets: a weight gradient still reading unit ui + 1's dR1 / dR2 on
-        // the second stream does not hold this unit's chain back)
-        float* const DR2 = F((ui & 1) ? pl.dr2_b : pl.dr2);
-        float* const DR1 = F((ui & 1) ? pl.dr1_b : pl.dr1);
-        float* const DXA = F((ui & 1) ? pl.dxa_b : pl.dxa);
-        // conv3: params, then dR2 = convT(G) gated by R2 > 0
-        rc = layer_param_grads(tr, u.c3, F(pl.r2[ui]), B, ho, wo, Gout, ho, wo, 1, 0, 0, s);
-        if (rc) return rc;
-        TRY_HIP(before_write(DR2));
-        g_shadow_want = u.depth_bn >= 128;       // dR2 -> conv2's weight gradient (9 C1 x C1)
-        g_h2.mask_fmt = (fast && ui >= ub) ? 1 : 0;
-        TRY_HIP(conv_launch(l3, t3.d_wT, t3.nkT, t3.cinP, Gout, B, ho, wo, l3.Cout, 0, 0, ho, wo, l3.Cin, 1, 0, nullptr, nullptr,
-                            nullptr, 0, 0, 0, F(pl.r2[ui]), false, 0, 0, DR2, s));
-        // conv2: params, then dR1 = convT(dR2) gated by R1 > 0
-        const int pb_h = u.pb_h, pb_w = u.pb_w;
-        rc = layer_param_grads(tr, u.c2, F(pl.r1[ui]), B, h, w, DR2, ho, wo, u.stride, pb_h, pb_w, s);
-        if (rc) return rc;
-        const int keff = 2 * u.rate + 1;
-        TRY_HIP(before_write(DR1));
-        g_shadow_want = u.depth_bn >= 128 && u.depth_in >= 128;      // dR1 -> conv1's weight gradient (Cin x C1)
-        g_h2.mask_fmt = (fast && ui >= ub) ? 1 : 0;
-        TRY_HIP(conv_launch(l2, t2.d_wT, t2.nkT, t2.cinP, DR2, B, ho, wo, l2.Cout, keff - 1 - pb_h, keff - 1 - pb_w, h, w,
-                            l2.Cin, 1, u.stride > 1 ? u.stride : 0, nullptr, nullptr, nullptr, 0, 0, 0, F(pl.r1[ui]), false, 0, 0,
-                            DR1, s));
-        // shortcut branch
-        const float* dxa = Gout;
-        int dxa_mode = 1;                       // same grid
-        int dxa_h = ho, dxa_w = wo;
-        if (u.sc >= 0) {
-            const ConvLayer& ls = net->layers[u.sc];
-            const TLayer& ts = tr->tl[u.sc];
-            rc = layer_param_grads(tr, u.sc, xin, B, h, w, Gout, ho, wo, u.stride, 0, 0, s);
-            if (rc) return rc;
-            TRY_HIP(before_write(DXA));
-            g_shadow_want = false;                // (dXa is only added to the next data gradient)
-            TRY_HIP(conv_launch(ls, ts.d_wT, ts.nkT, ts.cinP, Gout, B, ho, wo, ls.Cout, 0, 0, h, w, ls.Cin, 1,
-                                u.stride > 1 ? u.stride : 0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, false, 0, 0, DXA, s));
-            dxa = DXA; dxa_h = h; dxa_w = w;
-        } else if (u.stride > 1) {
-            dxa_mode = -2;                      // subsample shortcut: gradient lives on the coarser grid
+        if (hi - lo >= tr->n_train / 4 && gs.size() < 6) {
+            cur_g.cut_ui = ui; cur_g.fin_first = f_lo; cur_g.fin_count = f_n; cur_g.lo = lo; cur_g.hi = hi;
+            gs.push_back(cur_g);
+            lo = tr->n_train; hi = 0; f_lo = tr->n_fin; f_n = 0;
         }
-        // conv1: params, then dX = (convT(dR1) + dXa) gated by X_in > 0  -> G for the previous unit
-        rc = layer_param_grads(tr, u.c1, xin, B, h, w, DR1, h, w, 1, 0, 0, s);
-        if (rc) return rc;
-        TRY_HIP(before_write(Gin));              // (the G of two units ago: its conv3 / shortcut weight gradients)
-        g_shadow_want = ui > 0 && net->units[ui - 1].depth_bn >= 128;      // G of unit ui - 1 -> its conv3 / shortcut weight gradients
-        g_h2.mask_fmt = (fast && ui > ub) ? 1 : 0;                           // (unit ub's input is block1's fp32 output)
-        TRY_HIP(conv_launch(l1, t1.d_wT, t1.nkT, t1.cinP, DR1, B, h, w, l1.Cout, 0, 0, h, w, l1.Cin, 1, 0, nullptr, nullptr,
-                            dxa, dxa_mode, dxa_h, dxa_w, xin, false, 0, 0, Gin, s));
-        cur ^= 1;
-        TRY_HIP(close_groups_at(ui));
     }
-    // ---- root block: max-pool backward (+ stem ReLU gate), stem weight gradient
-    const bool fin_split = ctx->overlap && tr->n_fin > 1;
-    {
-        int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
-        int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
-        const long long tot = (long long)B * net->h1 * net->w1 * 16;
-        if (stem_g) {
-            if (fin_split) finalise(0, tr->groups.back().fin_count, ctx->s2);      // (what the gradient groups have not finalised yet)
-            StemWgradArgs sa{};
-            sa.x = F(pl.p0); sa.g = reinterpret_cast<const uint4*>(stem_g); sa.idx = reinterpret_cast<const unsigned char*>(ws + pl.pidx);
-            sa.g_prev = stem_g_prev;
-            sa.dw = reinterpret_cast<float*>(ws + pl.dw_l[net->conv1]); sa.colsum = reinterpret_cast<float*>(ws + pl.cs_l[net->conv1]);
-            sa.B = B; sa.H = d.in_h; sa.W = d.in_w; sa.H1 = net->h1; sa.W1 = net->w1; sa.HP = net->hp; sa.WP = net->wp; sa.pt = pth / 2; sa.pl = ptw / 2;
-            sa.bands = (net->h1 + 3) / 4; sa.chunks = (net->w1 + 31) / 32; sa.nitems = B * sa.bands * sa.chunks;
-            static int n_cu_s = 0;
-            if (!n_cu_s) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu_s, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu_s <= 0) n_cu_s = 256; }
-            static const int wgs_per_cu = dgp_tune("DGP_STEM_WGRAD_WGS", 2);      // (1: 6.77, 2: 6.72, 3: 6.72, 4: 6.84 ms per step)
-            const int grid = sa.nitems < wgs_per_cu * n_cu_s ? sa.nitems : wgs_per_cu * n_cu_s;
-            sa.slab = F(pl.dc1);                  // (the d conv1 map's region: unused on this path; grid x 50 KB)
-            hipLaunchKernelGGL(stem_wgrad_h1_kernel, dim3((unsigned)grid), dim3(256), 0, s, sa);
-            hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((STEM_SLAB_ROW + 255) / 256, (grid + 31) / 32), dim3(256), 0, s, sa, grid);
-        } else          // (fused root block in the forward pass: no conv1 map -- unit 0's data gradient is already gated by pool > 0)
-            hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_for(tot)), dim3(256), 0, s, (h1p && tr->fwd_stem_fused) ? (const float*)nullptr : F(pl.c1), G[cur],
-                               reinterpret_cast<const uchar4*>(ws + pl.pidx), B, net->h1, net->w1, 64, net->hp, net->wp, pth / 2, ptw / 2,
-                               F(pl.dc1));
-        if (stem_g) {
-            rc = DGP_OK;
-        } else if (fin_split) {
-            // the stem's weight gradient (0.3 ms at 11 frames, fp32 MFMA on a 216 MB gradient) is the pass's last launch and nothing else
-            // is left to run beside it -- except the finalisation of all OTHER layers: that goes to the second stream behind the last of
-            // their weight gradients, the stem's weight gradient to this stream
-            finalise(0, tr->groups.back().fin_count, ctx->s2);
-            ctx->overlap = false;
-            rc = layer_param_grads(tr, net->conv1, F(pl.p0), B, d.in_h, d.in_w, F(pl.dc1), net->h1, net->w1, 2, 3, 3, s);
-            ctx->overlap = true;
-        } else {
-            rc = layer_param_grads(tr, net->conv1, F(pl.p0), B, d.in_h, d.in_w, F(pl.dc1), net->h1, net->w1, 2, 3, 3, s);
-        }
-        if (rc) return rc;
+    // the last group: everything in front of the last cut (its table rows are [0, first cut row) + the stem's row, finalised at the end)
+    dgp_trainer::GradGroup last;
+    last.cut_ui = -1; last.lo = 0; last.hi = gs.empty() ? tr->n_train : gs.back().lo;
+    last.fin_first = 0; last.fin_count = gs.empty() ? tr->n_fin - 1 : gs.back().fin_first;
+    bool ok = true;                              // the groups must tile the flat buffer and the table, back to front
+    long long expect_hi = tr->n_train;
+    int expect_f = tr->n_fin - 1;
+    for (const auto& g : gs) {
+        ok = ok && g.hi == expect_hi && g.fin_first + g.fin_count == expect_f && g.lo < g.hi;
+        expect_hi = g.lo; expect_f = g.fin_first;
     }
-    (void)nj;
-    if (h1p) {            // every H1 gradient tensor of this pass against its predicted scale (wgrad_dma_h1 raised the same flag for its operands)
-        H2CheckList cl{};
-        if (g_ctx->h2_slots.size() > sizeof(cl.idx) / sizeof(cl.idx[0])) return fail(DGP_ERR_STATE, "16-bit tier: too many H1 gradient tensors");
-        cl.n = (int)g_ctx->h2_slots.size();
-        for (int k = 0; k < cl.n; ++k) cl.idx[k] = (short)g_ctx->h2_slots[k];
-        if (cl.n) hipLaunchKernelGGL(h2_pred_check_kernel, dim3(cl.n), dim3(64), 0, s, cl, g_ctx->rng.pool, g_ctx->rng.prev, tr->d_fast_flag);
+    if (!ok) gs.clear(), last.hi = tr->n_train, last.fin_count = tr->n_fin - 1;
+    gs.push_back(last);
+    for (auto& g : gs)
+        if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) return fail(DGP_ERR_HIP, "gradient groups: hipEventCreate failed");
+    tr->groups = gs;
+    return DGP_OK;
+}
+
+// a group is complete behind the weight gradients of its layers: finalise it on their stream and record its event
+static hipError_t close_groups_at(TrainPass& p, int ui) {
+    dgp_trainer* tr = p.tr;
+    while (p.grp_next + 1 < tr->groups.size() && tr->groups[p.grp_next].cut_ui == ui) {
+        auto& g = tr->groups[p.grp_next++];
+        hipStream_t st = p.side.on ? p.ctx.s2 : p.s;
+        finalise(p, g.fin_first, g.fin_count, st);
+        bn_grads(p, g.fin_first, g.fin_count, st);
+        hipError_t e2 = hipEventRecord(g.ev, st);
+        if (e2 != hipSuccess) return e2;
     }
-    join();                                      // every weight gradient has landed before the finalisation reads them
-    g_ctx->defer_plan = nullptr;
+    return hipSuccess;
+}
+
+// H1 tensor `t` takes the range slot / predicted scale of the launch that wrote `src` (a converted copy of it)
+static int adopt_h1(TrainPass& p, const void* t, const void* src) {
+    RangeCtx& rng = p.ctx.rng;
+    const float* slot = rng.of(src);
+    const float* pv = rng.prev_of(slot);
+    if (!slot || !pv) return fail(DGP_ERR_STATE, "16-bit tier: a gradient tensor has no predicted range");
+    rng.set(t, slot);
+    p.ctx.note_cells(t, pv);
+    return DGP_OK;
+}
+
+// Heads of the 16-bit tier, both at once.  Their loss gradients are gathered into ONE H1 tensor (scale predicted from its range one
+// step ago, slot_dph); ONE weight-gradient launch reads it and the H1 features in place (second stream), ONE H1 -> H1 data-gradient launch
+// with the merged panel writes d features, gated by the features' ReLU, as the H1 tensor the last unit's backward reads.
+static int backward_heads_h1(TrainPass& p, const float* dscmap, const float* dlocref, float* slot_dph) {
+    dgp_trainer* tr = p.tr; const dgp_net* net = p.net; TrainCtx& ctx = p.ctx;
+    const int B = p.B, fh = net->fh, fw = net->fw;
+    const ConvLayer &l0 = net->layers[net->head_part], &l1 = net->layers[net->head_locref];
+    const TLayer &t0 = tr->tl[net->head_part], &t1 = tr->tl[net->head_locref];
+    const int CT = tr->hm_ct, njt0 = l0.Cout / 4, njt1 = l1.Cout / 4;
+    float* const dwraw = p.F(p.pl.dwraw); float* const colsum = p.F(p.pl.colsum);
+    float* const DPH = p.F(p.pl.dphh);
+    const float* dprev = ctx.rng.prev_of(slot_dph);
+    const float* featH = p.F(p.pl.xo[p.nu() - 1]);
+    const auto fp = ctx.shadow_prev.find(featH);
+    if (fp == ctx.shadow_prev.end()) return fail(DGP_ERR_STATE, "16-bit tier: the features have no predicted range");
+    hipLaunchKernelGGL(head_gather_h1_kernel, dim3(grid_for((long long)B * fh * fw * (CT / 8))), dim3(256), 0, p.s, dscmap, dlocref, B, fh, fw,
+                       njt0, t0.cpad, njt1, t1.cpad, CT, dprev, reinterpret_cast<uint4*>(DPH), slot_dph);
+    ctx.rng.set(DPH, slot_dph);
+    ctx.note_cells(DPH, dprev);
+    hipStream_t hs;
+    if (int rc = p.side.fork(hs)) return rc;
+    WgradCall wc = head_wgrad_call(p, l0.Cin, CT);
+    wc.x = {featH, ctx.rng.of(featH), featH, fp->second};
+    wc.dy = {DPH, ctx.rng.of(DPH), DPH, dprev};
+    wc.fail_flag = tr->d_fast_flag; wc.h1 = true;
+    TRY_HIP(wgrad_launch(wc, hs));
+    hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt0 * l0.Cin)), dim3(256), 0, hs, dwraw, colsum, njt0, l0.Cin, CT, 0,
+                       tr->grads + t0.w_off, tr->grads + t0.b_off);
+    hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt1 * l1.Cin)), dim3(256), 0, hs, dwraw, colsum, njt1, l1.Cin, CT, t0.cpad,
+                       tr->grads + t1.w_off, tr->grads + t1.b_off);
+    (void)ctx.rng.take();                    // (the slot the first head's launch takes in a plain pass: every pass takes its slots in one order)
+    TRY_HIP(conv_launch(p, dgrad_call(l0, t0, DPH, B, fh, fw, p.GH[p.cur]).head_taps(CT).panel(tr->d_hmT, tr->hm_nk).cells(2).gate(featH, 2), p.s));
+    return DGP_OK;
+}
+
+// Heads on the parity path's kernels: per head gather the phases, parameter gradients, data gradient into G[cur] (the second head accumulates
+// onto the first and gates by the last unit's ReLU).  feat: the fp32 features (a fast pass: the copy it left in feat32).
+static int backward_heads_f32(TrainPass& p, const float* dscmap, const float* dlocref, float* slot_dph) {
+    dgp_trainer* tr = p.tr; const dgp_net* net = p.net; const RangeCtx& rng = p.ctx.rng;
+    const int B = p.B, fh = net->fh, fw = net->fw;
+    float* const dwraw = p.F(p.pl.dwraw); float* const colsum = p.F(p.pl.colsum);
+    float* const Gc = p.G[p.cur];
+    const float* feat = p.fast ? p.F(p.pl.feat32) : p.F(p.pl.xo[p.nu() - 1]);
+    // the per-head data-gradient panels (t.d_wT) are parity-only panels: a 16-bit pass that cannot merge its heads (DGP_TRAIN_HEADS_H1=0,
+    // head widths the merged panel does not take) lands here after lazy syncs and must not read last step's weights
+    if (tr->parity_stale)
+        if (int rc = refresh_parity_panels(tr, p.s)) return rc;
+    const size_t heads[2] = {(size_t)net->head_part, (size_t)net->head_locref};
+    const float* dsrc[2] = {dscmap, dlocref};
+    float* dph[2] = {p.F(p.pl.dph0), p.F(p.pl.dph1)};
+    for (int k = 0; k < 2; ++k) {
+        const ConvLayer& l = net->layers[heads[k]];
+        const TLayer& t = tr->tl[heads[k]];
+        const int njt = l.Cout / 4;
+        const long long tot = (long long)B * fh * fw * t.cpad;
+        hipLaunchKernelGGL(head_gather_kernel, dim3(grid_for(tot)), dim3(256), 0, p.s, dsrc[k], B, fh, fw, njt, t.cpad, dph[k], slot_dph);
+        // the head's parameter gradients (fill + wgrad + finalise through the shared dwraw / colsum scratch, in stream order) go to the
+        // second stream when the pass overlaps: the chain only needs dph[k] for the data gradient below
+        hipStream_t hs;
+        if (int rc = p.side.fork(hs)) return rc;
+        WgradCall wc = head_wgrad_call(p, l.Cin, t.cpad);
+        wc.x = {feat, rng.of(feat)};
+        wc.dy = {dph[k], rng.of(dph[k])};
+        TRY_HIP(wgrad_launch(wc, hs));
+        hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt * l.Cin)), dim3(256), 0, hs, dwraw, colsum, njt,
+                           l.Cin, t.cpad, 0, tr->grads + t.w_off, tr->grads + t.b_off);
+        // dfeat (+)= convT: 2x2 taps flipped, pad' = 0; second head accumulates onto the first; gate on the last
+        TRY_HIP(conv_launch(p, dgrad_call(l, t, dph[k], B, fh, fw, Gc).head_taps(t.cpad).residual(k == 1 ? Gc : nullptr, 1, fh, fw)
+                                   .gate(k == 1 ? feat : nullptr), p.s));
+    }
+    return DGP_OK;
+}
+
+// the heads' data gradient in the form the last unit's backward reads
+static int backward_heads_handover(TrainPass& p) {
+    TrainCtx& ctx = p.ctx; const dgp_net* net = p.net;
+    float* const Gc = p.G[p.cur];
+    const long long n8 = (long long)p.B * net->fh * net->fw * net->units[p.nu() - 1].depth / 8;
+    if (p.heads_h1) {
+        // (the merged launch wrote the H1 tensor itself)
+    } else if (p.h1p()) {
+        // the heads' data gradient (fp32, from the kernels of the parity path) enters the H1 units as an H1 tensor
+        float* const GHc = p.GH[p.cur];
+        if (int rc = adopt_h1(p, GHc, Gc)) return rc;
+        hipLaunchKernelGGL(f32_to_h1_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, p.s, reinterpret_cast<const float4*>(Gc), n8,
+                           ctx.shadow_prev[GHc], reinterpret_cast<uint4*>(GHc));
+    } else if (p.fast) {
+        // the heads' data gradient came from a kernel that writes no fp16 copy, and the last unit's conv3 weight gradient can only read
+        // its H2 activation through the LDS-DMA tile: make the copy here
+        const float* pv = ctx.rng.prev_of(ctx.rng.of(Gc));
+        const auto sb = ctx.shadow_base.find(Gc);
+        if (!pv || sb == ctx.shadow_base.end()) return fail(DGP_ERR_STATE, "fast pass: no range for the heads' data gradient");
+        hipLaunchKernelGGL(f32_to_shadow_kernel, dim3(grid_for(n8)), dim3(256), 0, p.s, reinterpret_cast<const float4*>(Gc), n8, pv,
+                           reinterpret_cast<uint4*>(sb->second));
+        ctx.shadow_prev[Gc] = pv;
+    }
+    return DGP_OK;
+}
+
+// One bottleneck unit of the 16-bit tier: every tensor of this unit is an H1 tensor with a predicted scale; data gradients are H1 -> H1
+// launches of the cell kernels (gate and residual read as H1), weight gradients read both operands in place (wgrad_dma_h1).
+// GH[cur] = d loss / d (unit output), already gated by its ReLU.
+static int backward_unit_h1(TrainPass& p, int ui) {
+    dgp_trainer* tr = p.tr; const dgp_net* net = p.net; const TPlan& pl = p.pl; TrainCtx& ctx = p.ctx; hipStream_t s = p.s;
+    const int B = p.B, ub = (int)p.ub;
+    const Unit& u = net->units[ui];
+    const int h = u.h, w = u.w, ho = u.ho, wo = u.wo;
+    const float* xin = ui == 0 ? p.F(pl.pool) : p.F(pl.xo[ui - 1]);
+    const ConvLayer &l1 = net->layers[u.c1], &l2 = net->layers[u.c2], &l3 = net->layers[u.c3];
+    const TLayer &t1 = tr->tl[u.c1], &t2 = tr->tl[u.c2], &t3 = tr->tl[u.c3];
+    float* const GoutH = p.GH[p.cur];
+    float* const GinH = p.GH[p.cur ^ 1];
+    float* const DR2H = p.F((ui & 1) ? pl.sh_dr2_b : pl.sh_dr2);
+    float* const DR1H = p.F((ui & 1) ? pl.sh_dr1_b : pl.sh_dr1);
+    float* const DXAH = p.F((ui & 1) ? pl.dxa_b : pl.dxa);
+    const float* const R1 = p.F(pl.r1[ui]);
+    const float* const R2 = p.F(pl.r2[ui]);
+    const float* xinH = ui > ub ? xin : p.F(ui == 0 ? pl.sh_pool : pl.sh_xo[ui - 1]);       // (unit ub reads the H1 copy of its fp32 input)
+    int rc;
+    if ((rc = layer_param_grads(p, u.c3, {R2, ho, wo}, {GoutH, ho, wo}))) return rc;
+    TRY_HIP(p.side.before_write(DR2H));
+    TRY_HIP(conv_launch(p, dgrad_call(l3, t3, GoutH, B, ho, wo, DR2H).cells(2).gate(R2, 2), s));
+    const int pb_h = u.pb_h, pb_w = u.pb_w;
+    if ((rc = layer_param_grads(p, u.c2, {R1, h, w}, {DR2H, ho, wo}, u.stride, pb_h, pb_w))) return rc;
+    const int keff = 2 * u.rate + 1;
+    TRY_HIP(p.side.before_write(DR1H));
+    if (u.stride > 1) {
+        // stride-2 conv2: its data gradient reads dR2 on the zero-stuffed grid; materialised (a few MB) so that it is a plain stride-1 launch
+        if (u.stride != 2) return fail(DGP_ERR_STATE, "16-bit tier: stride > 2");
+        float* const ZS = p.F(pl.dr1);             // (the fp32 dR1 region is free while the H1 units run)
+        const size_t zbytes = (size_t)B * 2 * ho * 2 * wo * l2.Cout * 2;
+        if (zbytes > (size_t)4 * ((size_t)B * h * w * u.depth_bn)) return fail(DGP_ERR_STATE, "16-bit tier: zero-stuffed gradient does not fit");
+        TRY_HIP(p.side.before_write(ZS));
+        TRY_HIP(hipMemsetAsync(ZS, 0, zbytes, s));
+        const long long tot = (long long)B * ho * wo * (l2.Cout / 8);
+        hipLaunchKernelGGL(h1_zero_stuff_kernel, dim3(grid_for(tot)), dim3(256), 0, s, reinterpret_cast<const uint4*>(DR2H), B, ho, wo,
+                           l2.Cout / 8, reinterpret_cast<uint4*>(ZS));
+        TRY_HIP(conv_launch(p, dgrad_call(l2, t2, ZS, B, 2 * ho, 2 * wo, DR1H).grid(h, w, keff - 1 - pb_h, keff - 1 - pb_w).cells(2).gate(R1, 2)
+                                   .keys(DR2H, nullptr), s));
+    } else {
+        TRY_HIP(conv_launch(p, dgrad_call(l2, t2, DR2H, B, ho, wo, DR1H).grid(h, w, keff - 1 - pb_h, keff - 1 - pb_w).cells(2).gate(R1, 2), s));
+    }
+    const float* dxa = GoutH;
+    int dxa_mode = 1, dxa_h = ho, dxa_w = wo;
+    if (u.sc >= 0) {
+        if (u.stride != 1) return fail(DGP_ERR_STATE, "16-bit tier: strided shortcut conv");
+        if ((rc = layer_param_grads(p, u.sc, {xin, h, w}, {GoutH, ho, wo}))) return rc;
+        TRY_HIP(p.side.before_write(DXAH));
+        TRY_HIP(conv_launch(p, dgrad_call(net->layers[u.sc], tr->tl[u.sc], GoutH, B, ho, wo, DXAH).grid(h, w).cells(2), s));
+        dxa = DXAH; dxa_h = h; dxa_w = w;
+    } else if (u.stride > 1) {
+        dxa_mode = -2;
+    }
+    if ((rc = layer_param_grads(p, u.c1, {xin, h, w}, {DR1H, h, w}))) return rc;
+    TRY_HIP(p.side.before_write(GinH));
+    TRY_HIP(conv_launch(p, dgrad_call(l1, t1, DR1H, B, h, w, GinH).residual(dxa, dxa_mode, dxa_h, dxa_w).cells(2, dxa).gate(xinH, 2), s));
+    if (ui == ub && ub == 0 && p.stem_wgrad_h1) {
+        // (unit 0's data gradient stays H1: the fused stem weight-gradient kernel reads it in place)
+        p.stem_g = GinH;
+        p.stem_g_prev = ctx.shadow_prev[GinH];
+    } else if (ui == ub) {
+        // the data gradient leaves the H1 units: fp32 copy for block1's kernels (same range slot: the epilogue tracked max |G| before rounding)
+        float* Gf = p.G[p.cur ^ 1];
+        TRY_HIP(p.side.before_write(Gf));
+        const long long n8 = (long long)B * h * w * l1.Cin / 8;
+        hipLaunchKernelGGL(h1_to_f32_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, s, reinterpret_cast<const uint4*>(GinH), n8,
+                           ctx.shadow_prev[GinH], reinterpret_cast<float4*>(Gf), (const uint4*)nullptr);
+        ctx.rng.set(Gf, ctx.rng.of(GinH));
+        ctx.shadow_prev.erase(Gf);
+    }
+    return DGP_OK;
+}
+
+// One bottleneck unit on the parity path's kernels (a fast H2 pass: the gates of units >= ub read the activations as H2 cells).
+// G[cur] = d loss / d (unit output), already gated by its ReLU.
+static int backward_unit_f32(TrainPass& p, int ui) {
+    dgp_trainer* tr = p.tr; const dgp_net* net = p.net; const TPlan& pl = p.pl; hipStream_t s = p.s;
+    const int B = p.B, ub = (int)p.ub;
+    const Unit& u = net->units[ui];
+    const int h = u.h, w = u.w, ho = u.ho, wo = u.wo;
+    const float* xin = ui == 0 ? p.F(pl.pool) : p.F(pl.xo[ui - 1]);
+    float* Gout = p.G[p.cur];
+    float* Gin = p.G[p.cur ^ 1];
+    const ConvLayer &l1 = net->layers[u.c1], &l2 = net->layers[u.c2], &l3 = net->layers[u.c3];
+    const TLayer &t1 = tr->tl[u.c1], &t2 = tr->tl[u.c2], &t3 = tr->tl[u.c3];
+    // gradient buffers of this unit (units alternate between two sets: a weight gradient still reading unit ui + 1's dR1 / dR2 on
+    // the second stream does not hold this unit's chain back)
+    float* const DR2 = p.F((ui & 1) ? pl.dr2_b : pl.dr2);
+    float* const DR1 = p.F((ui & 1) ? pl.dr1_b : pl.dr1);
+    float* const DXA = p.F((ui & 1) ? pl.dxa_b : pl.dxa);
+    const float* const R1 = p.F(pl.r1[ui]);
+    const float* const R2 = p.F(pl.r2[ui]);
+    const int gate_fmt = (p.fast && ui >= ub) ? 1 : 0;     // this unit's activations are H2 tensors
+    const int up = u.stride > 1 ? u.stride : 0;
+    int rc;
+    // conv3: params, then dR2 = convT(G) gated by R2 > 0; its copy feeds conv2's weight gradient (9 C1 x C1)
+    if ((rc = layer_param_grads(p, u.c3, {R2, ho, wo}, {Gout, ho, wo}))) return rc;
+    TRY_HIP(p.side.before_write(DR2));
+    TRY_HIP(conv_launch(p, dgrad_call(l3, t3, Gout, B, ho, wo, DR2).gate(R2, gate_fmt).no_copy(u.depth_bn < 128), s));
+    // conv2: params, then dR1 = convT(dR2) gated by R1 > 0; its copy feeds conv1's weight gradient (Cin x C1)
+    const int pb_h = u.pb_h, pb_w = u.pb_w;
+    if ((rc = layer_param_grads(p, u.c2, {R1, h, w}, {DR2, ho, wo}, u.stride, pb_h, pb_w))) return rc;
+    const int keff = 2 * u.rate + 1;
+    TRY_HIP(p.side.before_write(DR1));
+    TRY_HIP(conv_launch(p, dgrad_call(l2, t2, DR2, B, ho, wo, DR1).grid(h, w, keff - 1 - pb_h, keff - 1 - pb_w).upsampled(up).gate(R1, gate_fmt)
+                               .no_copy(!(u.depth_bn >= 128 && u.depth_in >= 128)), s));
+    // shortcut branch
+    const float* dxa = Gout;
+    int dxa_mode = 1;                       // same grid
+    int dxa_h = ho, dxa_w = wo;
+    if (u.sc >= 0) {
+        if ((rc = layer_param_grads(p, u.sc, {xin, h, w}, {Gout, ho, wo}, u.stride))) return rc;
+        TRY_HIP(p.side.before_write(DXA));
+        // (dXa is only added to the next data gradient: no copy)
+        TRY_HIP(conv_launch(p, dgrad_call(net->layers[u.sc], tr->tl[u.sc], Gout, B, ho, wo, DXA).grid(h, w).upsampled(up).no_copy(), s));
+        dxa = DXA; dxa_h = h; dxa_w = w;
+    } else if (u.stride > 1) {
+        dxa_mode = -2;                      // subsample shortcut: gradient lives on the coarser grid
+    }
+    // conv1: params, then dX = (convT(dR1) + dXa) gated by X_in > 0  -> G for the previous unit (its copy feeds that unit's conv3 /
+    // shortcut weight gradients; unit ub's input is block1's fp32 output)
+    if ((rc = layer_param_grads(p, u.c1, {xin, h, w}, {DR1, h, w}))) return rc;
+    TRY_HIP(p.side.before_write(Gin));       // (the G of two units ago: its conv3 / shortcut weight gradients)
+    TRY_HIP(conv_launch(p, dgrad_call(l1, t1, DR1, B, h, w, Gin).residual(dxa, dxa_mode, dxa_h, dxa_w).gate(xin, (p.fast && ui > ub) ? 1 : 0)
+                               .no_copy(!(ui > 0 && net->units[ui - 1].depth_bn >= 128)), s));
+    return DGP_OK;
+}
+
+// Root block: max-pool backward (+ stem ReLU gate) and the stem's weight gradient -- or, 16-bit tier with the fused root block, both in
+// stem_wgrad_h1_kernel reading unit 0's H1 data gradient.  The stem's weight gradient is the pass's last launch and nothing else is left to
+// run beside it except the finalisation of all OTHER layers: that goes to the second stream behind the last of their weight gradients.
+static int backward_root(TrainPass& p, bool fin_split) {
+    dgp_trainer* tr = p.tr; const dgp_net* net = p.net; const TPlan& pl = p.pl; const dgp_net_desc& d = net->desc;
+    const int B = p.B;
+    hipStream_t s = p.s;
+    int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
+    int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
+    if (p.stem_g) {
+        if (fin_split) finalise(p, 0, tr->groups.back().fin_count, p.ctx.s2);      // (what the gradient groups have not finalised yet)
+        StemWgradArgs sa{};
+        sa.x = p.F(pl.p0); sa.g = reinterpret_cast<const uint4*>(p.stem_g); sa.idx = reinterpret_cast<const unsigned char*>(p.ws + pl.pidx);
+        sa.g_prev = p.stem_g_prev;
+        sa.dw = reinterpret_cast<float*>(p.ws + pl.dw_l[net->conv1]); sa.colsum = reinterpret_cast<float*>(p.ws + pl.cs_l[net->conv1]);
+        sa.B = B; sa.H = d.in_h; sa.W = d.in_w; sa.H1 = net->h1; sa.W1 = net->w1; sa.HP = net->hp; sa.WP = net->wp; sa.pt = pth / 2; sa.pl = ptw / 2;
+        sa.bands = (net->h1 + 3) / 4; sa.chunks = (net->w1 + 31) / 32; sa.nitems = B * sa.bands * sa.chunks;
+        static int n_cu_s = 0;
+        if (!n_cu_s) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu_s, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu_s <= 0) n_cu_s = 256; }
+        static const int wgs_per_cu = dgp_tune("DGP_STEM_WGRAD_WGS", 2);      // (1: 6.77, 2: 6.72, 3: 6.72, 4: 6.84 ms per step)
+        const int grid = sa.nitems < wgs_per_cu * n_cu_s ? sa.nitems : wgs_per_cu * n_cu_s;
+        sa.slab = p.F(pl.dc1);                // (the d conv1 map's region: unused on this path; grid x 50 KB)
+        hipLaunchKernelGGL(stem_wgrad_h1_kernel, dim3((unsigned)grid), dim3(256), 0, s, sa);
+        hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((STEM_SLAB_ROW + 255) / 256, (grid + 31) / 32), dim3(256), 0, s, sa, grid);
+        return DGP_OK;
+    }
+    // (fused root block in the forward pass: no conv1 map -- unit 0's data gradient is already gated by pool > 0)
+    const long long tot = (long long)B * net->h1 * net->w1 * 16;
+    hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_for(tot)), dim3(256), 0, s, (p.h1p() && tr->fwd_stem_fused) ? (const float*)nullptr : p.F(pl.c1), p.G[p.cur],
+                       reinterpret_cast<const uchar4*>(p.ws + pl.pidx), B, net->h1, net->w1, 64, net->hp, net->wp, pth / 2, ptw / 2,
+                       p.F(pl.dc1));
+    if (fin_split) finalise(p, 0, tr->groups.back().fin_count, p.ctx.s2);
+    // (0.3 ms at 11 frames, fp32 MFMA on a 216 MB gradient; with the finalisation beside it: on the chain's stream)
+    return layer_param_grads(p, net->conv1, {p.F(pl.p0), d.in_h, d.in_w}, {p.F(pl.dc1), net->h1, net->w1}, 2, 3, 3, !fin_split);
+}
+
+// End of the pass: the check of the 16-bit tier's predicted scales, the join, the last gradient group's finalisation
+static int backward_finish(TrainPass& p, bool fin_split) {
+    dgp_trainer* tr = p.tr; hipStream_t s = p.s;
+    // every H1 gradient tensor of this pass against its predicted scale (wgrad_dma_h1 raised the same flag for its operands)
+    if (p.h1p())
+        if (int rc = check_predictions(p, "16-bit tier: too many H1 gradient tensors")) return rc;
+    p.side.join();                               // every weight gradient has landed before the finalisation reads them
     const int rest = tr->groups.back().fin_count;      // rows [0, rest) + the stem's row: the last gradient group
-    if (!fin_split) finalise(0, rest, s);
-    finalise(tr->n_fin - 1, 1, s);
-    bn_grads(0, rest, s);
-    bn_grads(tr->n_fin - 1, 1, s);
-    if (grp_next + 1 != tr->groups.size()) return fail(DGP_ERR_STATE, "backward: a gradient group was not closed");
+    if (!fin_split) finalise(p, 0, rest, s);
+    finalise(p, tr->n_fin - 1, 1, s);
+    bn_grads(p, 0, rest, s);
+    bn_grads(p, tr->n_fin - 1, 1, s);
+    if (p.grp_next + 1 != tr->groups.size()) return fail(DGP_ERR_STATE, "backward: a gradient group was not closed");
     TRY_HIP(hipEventRecord(tr->groups.back().ev, s));
     TRY_HIP(hipGetLastError());
     return DGP_OK;
 }
+
+extern "C" int dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t workspace_bytes, const float* dscmap,
+                                  const float* dlocref, void* stream) {
+    if (!tr || !workspace || !dscmap || !dlocref) return fail(DGP_ERR_INVALID, "dgp_train_backward: null argument");
+    dgp_net* net = tr->net;
+    const TPlan pl = make_tplan(tr, nt);
+    if (workspace_bytes < pl.total) return fail(DGP_ERR_INVALID, "dgp_train_backward: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    TrainPass p(tr, s, workspace, pl, nt);
+    TrainCtx& ctx = p.ctx;
+    range_pass_begin(tr, s, true);
+    if (pl.sh_g0) {
+        const size_t gb[6][2] = {{pl.g0, pl.sh_g0}, {pl.g1, pl.sh_g1}, {pl.dr1, pl.sh_dr1}, {pl.dr2, pl.sh_dr2}, {pl.dr1_b, pl.sh_dr1_b}, {pl.dr2_b, pl.sh_dr2_b}};
+        for (const auto& q : gb) { ctx.shadow_base[p.F(q[0])] = p.F(q[1]); ctx.shadow_prev.erase(p.F(q[0])); }
+    }
+    TRY_HIP(hipMemsetAsync(p.ws + pl.dwall, 0, pl.dwall_bytes, s));
+    // weight gradients on their own stream beside the data-gradient chain (DGP_WGRAD_OVERLAP=0: one stream, A/B)
+    static const bool overlap_env = (dgp_tune("DGP_WGRAD_OVERLAP", 1) != 0);
+    if (overlap_env) {
+        if (int rc = ensure_side_stream(ctx)) return rc;
+        p.side.begin(&ctx, s);
+    }
+    // what dgp_train_forward did: a fast pass left the activations of units >= ub as H2 tensors -- gates read them as such, weight gradients
+    // read them in place, the heads use the fp32 copy in feat32; in the 16-bit tier the gradient tensors of those units are H1-only as well
+    p.fast = tr->fwd_fast;
+    p.fmt = p.fast ? tr->fwd_fmt : 1;
+    p.ub = first_cell_unit(net, pl, p.h1p());
+    if (p.h1p()) ctx.h2_slots.clear();                  // this pass's H1 gradient tensors, checked against their predicted scales at its end
+    p.G[0] = p.F(pl.g0); p.G[1] = p.F(pl.g1);
+    p.GH[0] = p.F(pl.sh_g0); p.GH[1] = p.F(pl.sh_g1);   // tier 1: G of the H1 units (the fp16-copy regions of the parity pass hold the tensors themselves)
+    // range of the gathered loss gradients (both heads): the first slot of every backward pass -- it predicts the scale of the merged
+    // H1 tensor of the next 16-bit pass
+    float* const slot_dph = ctx.rng.take();
+    p.heads_h1 = p.h1p() && tr->d_hmT && tr->d_hmT_h1 && slot_dph && ctx.rng.prev_of(slot_dph) && !tr->fwd_feat32;
+    if (p.fast && !p.heads_h1 && !tr->fwd_feat32) return fail(DGP_ERR_STATE, "backward: the forward pass left no fp32 features for the heads");
+    int rc = p.heads_h1 ? backward_heads_h1(p, dscmap, dlocref, slot_dph) : backward_heads_f32(p, dscmap, dlocref, slot_dph);
+    if (rc || (rc = backward_heads_handover(p))) return rc;
+    // 16-bit tier with the fused root block: the stem's weight gradient reads d pool as the H1 tensor unit 0 leaves (stem_wgrad_h1_kernel:
+    // pool backward fused, no d conv1 map); A/B switch DGP_TRAIN_STEM_WGRAD_H1=0
+    static const bool stem_wgrad_env = (dgp_tune("DGP_TRAIN_STEM_WGRAD_H1", 1) != 0);
+    const ConvLayer& c1 = net->layers[net->conv1];
+    p.stem_wgrad_h1 = stem_wgrad_env && p.h1p() && p.ub == 0 && tr->fwd_stem_fused && c1.Cout == 64 && c1.KH == 7 && c1.Cin == 4;
+    if ((rc = plan_finalisation(p)) || (rc = plan_grad_groups(tr))) return rc;
+    for (int ui = p.nu() - 1; ui >= 0; --ui) {
+        rc = (p.h1p() && ui >= (int)p.ub) ? backward_unit_h1(p, ui) : backward_unit_f32(p, ui);
+        if (rc) return rc;
+        p.cur ^= 1;
+        TRY_HIP(close_groups_at(p, ui));
+    }
+    const bool fin_split = p.side.on && tr->n_fin > 1;
+    if ((rc = backward_root(p, fin_split))) return rc;
+    return backward_finish(p, fin_split);
+}
+
+extern "C" {
+
 
 /* Fast pass of the training step.  enable != 0: the NEXT dgp_train_forward keeps the retained activations of blocks 2-4 as H2 tensors
  * whose scales are predicted from the ranges the previous pass left behind (call it only after a pass of the same frame count and
@@ -3184,7 +3259,6 @@ int dgp_trainer_grad_groups(dgp_trainer* tr, int32_t max_groups, int32_t* n_grou
  * on the host).  A communication stream that waits for group k can all-reduce it while the pass is still computing the later groups. */
 int dgp_trainer_grad_group_wait(dgp_trainer* tr, int32_t k, void* stream) {
     if (!tr || k < 0 || k >= (int)tr->groups.size() || !tr->groups[k].ev) return fail(DGP_ERR_INVALID, "dgp_trainer_grad_group_wait: no such group");
-    g_ctx = &tr->ctx;
     TRY_HIP(hipStreamWaitEvent((hipStream_t)stream, tr->groups[k].ev, 0));
     return DGP_OK;
 }
@@ -3236,14 +3310,15 @@ int dgp_trainer_fast_status(dgp_trainer* tr, int32_t* was_fast, int32_t* failed)
  * With both ranges (DGP_ABSMAX_SLOTS floats each) the fp16-split kernel wgrad_h3p runs where the tile is 128 x 128, else wgrad_f32. */
 int dgp_conv2d_wgrad(const dgp_conv_desc* d, const float* x, const float* dy, const float* x_absmax, const float* dy_absmax,
                      float* dw_raw, float* colsum, void* stream) {
-    g_ctx = nullptr;              // layer-level call: explicit ranges only
     if (!d || !x || !dy || !dw_raw) return fail(DGP_ERR_INVALID, "dgp_conv2d_wgrad: null argument");
     if (d->Cin < 4 || (d->Cin & 3) || ((d->Cin / 4) & (d->Cin / 4 - 1)) || (d->Cout & 3))
         return fail(DGP_ERR_INVALID, "dgp_conv2d_wgrad: Cin must be 4 * 2^k, Cout a multiple of 4");
-    if ((double)d->N * d->H * d->W * d->Cin * 4 > 4294967000.0 || (double)d->N * d->Ho * d->Wo * d->Cout * 4 > 4294967000.0)
+    if (!fits_descriptor({(double)d->N * d->H * d->W * d->Cin * 4, (double)d->N * d->Ho * d->Wo * d->Cout * 4}))
         return fail(DGP_ERR_INVALID, "dgp_conv2d_wgrad: tensor exceeds 4 GiB");
-    hipError_t e = wgrad_launch(x, d->N, d->H, d->W, d->Cin, dy, d->Ho, d->Wo, d->Cout, d->KH, d->KW, d->stride, d->rate, d->pad_t,
-                                d->pad_l, dw_raw, colsum, (hipStream_t)stream, false, x_absmax, dy_absmax);
+    // (layer-level call: no pass, the caller's ranges only)
+    WgradCall c;
+    c.d = *d; c.x = {x, x_absmax}; c.dy = {dy, dy_absmax}; c.dwraw = dw_raw; c.colsum = colsum;
+    hipError_t e = wgrad_launch(c, (hipStream_t)stream);
     if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_wgrad: ") + hipGetErrorString(e));
     return DGP_OK;
 }
@@ -3254,7 +3329,6 @@ int dgp_conv2d_wgrad(const dgp_conv_desc* d, const float* x, const float* dy, co
  * scratch: 4 * (numel(x) + numel(dy)) device bytes. */
 int dgp_conv2d_wgrad_shadow(const dgp_conv_desc* d, const float* x, const float* dy, const float* x_absmax, const float* dy_absmax,
                             const float* x_prev, const float* dy_prev, void* scratch, float* dw_raw, float* colsum, void* stream) {
-    g_ctx = nullptr;
     if (!d || !x || !dy || !dw_raw || !scratch || !x_absmax || !dy_absmax || !x_prev || !dy_prev)
         return fail(DGP_ERR_INVALID, "dgp_conv2d_wgrad_shadow: null argument");
     if (d->Cin < 16 || (d->Cin & 15) || ((d->Cin / 4) & (d->Cin / 4 - 1)) || (d->Cout & 7) || d->Cout < 128 || d->KH * d->KW * d->Cin < 128)
@@ -3269,8 +3343,9 @@ int dgp_conv2d_wgrad_shadow(const dgp_conv_desc* d, const float* x, const float*
                        reinterpret_cast<uint4*>(xs));
     hipLaunchKernelGGL(f32_to_shadow_kernel, dim3(grid_for(ny / 8)), dim3(256), 0, s, reinterpret_cast<const float4*>(dy), ny / 8, dy_prev,
                        reinterpret_cast<uint4*>(dys));
-    hipError_t e = wgrad_launch(x, d->N, d->H, d->W, d->Cin, dy, d->Ho, d->Wo, d->Cout, d->KH, d->KW, d->stride, d->rate, d->pad_t,
-                                d->pad_l, dw_raw, colsum, s, false, x_absmax, dy_absmax, xs, x_prev, dys, dy_prev);
+    WgradCall c;
+    c.d = *d; c.x = {x, x_absmax, xs, x_prev}; c.dy = {dy, dy_absmax, dys, dy_prev}; c.dwraw = dw_raw; c.colsum = colsum;
+    hipError_t e = wgrad_launch(c, s);
     if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_wgrad_shadow: ") + hipGetErrorString(e));
     return DGP_OK;
 }
@@ -3289,7 +3364,6 @@ size_t dgp_conv2d_dgrad_scratch_bytes(const dgp_conv_desc* d) {
 
 int dgp_conv2d_dgrad(const dgp_conv_desc* d, const float* dy, const float* w_hwio, const float* scale, const float* mask,
                      const float* dx_add, int32_t add_mode, float* dx, void* scratch, int32_t ranged, void* stream) {
-    g_ctx = nullptr;
     if (!d || !dy || !w_hwio || !dx || !scratch) return fail(DGP_ERR_INVALID, "dgp_conv2d_dgrad: null argument");
     // (Cin < 64: dx goes through the 32-column fp32 tile, which reads the gate as fp32 -- garbage with H2 cells; found by scripts/fuzz_backward_layers.py)
     if ((ranged & 2) && (!(ranged & 1) || !mask || (d->Cin & 7) || d->Cin < 64))
@@ -3313,20 +3387,17 @@ int dgp_conv2d_dgrad(const dgp_conv_desc* d, const float* dy, const float* w_hwi
     const long long totT = (long long)nkT * 8 * cinP;
     hipLaunchKernelGGL(pack_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, w_hwio, scale, taps, d->Cin, d->Cout, cinP, nkT * 8,
                        panel, rng + ABSMAX_SLOTS);
-    ConvArgs a{};
+    // the launch as the kernels see it: the transposed conv, dy [N, Ho, Wo, Cout] -> dx [N, H, W, Cin] on the (zero-stuffed) grid of dy
     const int keff_h = (d->KH - 1) * d->rate + 1, keff_w = (d->KW - 1) * d->rate + 1;
+    dgp_conv_desc t{};
+    t.N = d->N; t.H = d->Ho; t.W = d->Wo; t.Cin = d->Cout; t.Cout = d->Cin; t.KH = d->KH; t.KW = d->KW; t.stride = 1; t.rate = d->rate;
+    t.pad_t = keff_h - 1 - d->pad_t; t.pad_l = keff_w - 1 - d->pad_l; t.Ho = d->H; t.Wo = d->W;
+    t.res_stride = dx_add ? add_mode : 0;
+    t.res_H = add_mode == -2 ? (d->H + 1) / 2 : d->H; t.res_W = add_mode == -2 ? (d->W + 1) / 2 : d->W;
+    ConvArgs a{};
     a.in = dy; a.wpk = panel; a.out = dx; a.mask = mask; a.res = dx_add;
-    a.N = d->N; a.H = d->Ho; a.W = d->Wo; a.Cin = d->Cout; a.log2cin4 = ilog2(d->Cout / 4);
-    a.Ho = d->H; a.Wo = d->W; a.Cout = d->Cin; a.CoutP = cinP;
-    a.KH = d->KH; a.KW = d->KW; a.stride = 1; a.dil = d->rate; a.pad_t = keff_h - 1 - d->pad_t; a.pad_l = keff_w - 1 - d->pad_l;
-    a.ntaps = taps; a.nk = nkT; a.M = d->N * d->H * d->W;
+    if (int rc = fill_conv_geometry(a, t, "dgp_conv2d_dgrad: tensor exceeds 4 GiB")) return rc;      // (CoutP = cinP, nk = nkT, w_bytes = panel_bytes)
     a.up = d->stride > 1 ? d->stride : 0;
-    a.res_s = dx_add ? add_mode : 0;
-    a.res_H = add_mode == -2 ? (d->H + 1) / 2 : d->H; a.res_W = add_mode == -2 ? (d->W + 1) / 2 : d->W;
-    a.in_bytes = (unsigned)((size_t)d->N * d->Ho * d->Wo * d->Cout * 4);
-    a.out_bytes = (unsigned)((size_t)a.M * d->Cin * 4);
-    a.res_bytes = dx_add ? (unsigned)((size_t)d->N * a.res_H * a.res_W * d->Cin * 4) : 0u;
-    a.w_bytes = (unsigned)panel_bytes;
     a.mask_fmt = (ranged & 2) ? 1 : 0;          // the gate tensor is H2 (fast pass of the training step): gate = stored value > 0
     if (ranged & 1) {
         TRY_HIP(launch_absmax(dy, (long long)d->N * d->Ho * d->Wo * d->Cout, rng, s));

@@ -846,6 +846,44 @@ def test_trainer_tier_f16_recovers_from_a_failed_prediction(lib_built):
     assert cos >= 0.999 and rel <= 0.05
 
 
+def test_two_trainers_interleaved_on_one_thread_match_their_solo_runs(lib_built):
+    """A pass's launch state (formats, range slots, fp16 copies, the weight-gradient stream) belongs to that pass of that trainer: a parity
+    trainer and a 16-bit trainer whose calls alternate P, F, P, F, F on one thread give what each gives alone -- losses to 1e-6 relative
+    (run-to-run equality of the atomically summed loss terms), every gradient tensor to the fp32 round-off bound 2e-5 in relative L2 (weight
+    gradients are accumulated with float atomics), and the 16-bit trainer's last pass is a 16-bit pass that kept its predictions."""
+    import ctypes
+    from deepgraphpose_amd.train import Trainer
+    from deepgraphpose_amd.loss import DGPHyper
+    batch, S0, wts, frames, ws, ws_max = _train_case(3)
+    hy = DGPHyper(gm2=1, gm3=3)
+    ft = torch.from_numpy(frames).cuda()
+
+    def trainer(tier):
+        tr = Trainer(50, 3, 64, 96, max_frames=3, tier=tier)
+        tr.load_weights(wts)
+        return tr
+
+    def run(order):
+        trs = {k: trainer({"P": "parity", "F": "f16"}[k]) for k in sorted(set(order))}
+        losses = {}
+        for k in order:
+            losses[k] = trs[k].forward_backward(ft, batch, hy, S0, ws, ws_max, 300.0, 25.0)
+        was, failed = ctypes.c_int32(-1), ctypes.c_int32(-1)
+        if "F" in trs:
+            trs["F"].lib.dgp_trainer_fast_status(trs["F"]._t, was, failed)
+        return losses, {k: t.get_grads() for k, t in trs.items()}, (was.value, failed.value)
+
+    (solo_l, solo_g, _), (l2, g2, solo_st) = run("PP"), run("FFF")
+    solo_l.update(l2); solo_g.update(g2)
+    both_l, both_g, both_st = run("PFPFF")
+    assert solo_st == (1, 0) and both_st == (1, 0)
+    for k in "PF":
+        for name, v in solo_l[k].items():
+            assert abs(both_l[k][name] - v) <= 1e-6 * max(1.0, abs(v)), (k, name, both_l[k][name], v)
+        rel = {n: np.linalg.norm((both_g[k][n] - g).ravel()) / (np.linalg.norm(g.ravel()) + 1e-30) for n, g in solo_g[k].items()}
+        assert max(rel.values()) < 2e-5, (k, sorted(rel.items(), key=lambda kv: -kv[1])[:4])
+
+
 def test_fifty_steps_of_both_trainer_tiers_stay_in_one_band(lib_built):
     """50 optimiser steps (clip-by-global-norm + momentum, lr 0.005) from the same weights on the same batch, parity tier and 16-bit tier:
     both losses fall, and the 16-bit trajectory stays within 3 % (+ 2e-3) of the parity trajectory at every step -- the stated band of
