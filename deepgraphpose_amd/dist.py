@@ -15,6 +15,11 @@ import torch
 import torch.distributed as dist
 
 
+def data_parallel(group: Optional[dist.ProcessGroup] = None) -> bool:
+    """The one test for "this is a data-parallel run": torch.distributed is available and initialised and the group has more than one rank."""
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+
+
 def shard_range(n_frames: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous block of frame indices owned by `rank` (last shards may be short or empty)."""
     per = -(-n_frames // world) if n_frames > 0 else 0
@@ -66,7 +71,7 @@ def gather_trajectory(local: torch.Tensor, n_frames: int, group: Optional[dist.P
 
 def any_rank(flag: bool, device=None, group: Optional[dist.ProcessGroup] = None) -> bool:
     """True on every rank when `flag` is true on at least one (one all-reduce(MAX) of a single int)."""
-    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+    if not data_parallel(group):
         return bool(flag)
     on_host = dist.get_backend(group) == "gloo" or device is None
     t = torch.tensor([int(bool(flag))], dtype=torch.int32, device="cpu" if on_host else device)
@@ -76,7 +81,7 @@ def any_rank(flag: bool, device=None, group: Optional[dist.ProcessGroup] = None)
 
 def from_rank0(flag: bool, group: Optional[dist.ProcessGroup] = None) -> bool:
     """Rank 0's value of `flag` on every rank (a decision all ranks must take together, e.g. "the labels already exist")."""
-    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+    if not data_parallel(group):
         return bool(flag)
     box = [bool(flag)]
     dist.broadcast_object_list(box, src=0, group=group)
@@ -92,7 +97,7 @@ def average_gradients(flat_grads: torch.Tensor, group: Optional[dist.ProcessGrou
     small enough that the tail of bucket k overlaps the reduction of bucket k+1) instead of ~160 per-tensor calls.
     Each rank then applies the same clip + momentum update, so the replicas stay bit-identical.  The reference
     trains on a single GPU; with W ranks each step consumes W windows of frames (one per rank)."""
-    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+    if not data_parallel(group):
         return flat_grads
     world = dist.get_world_size(group)
     flat = flat_grads.view(-1)

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from .engine import _ptr, _stream, _need_cuda
+from .staged import Staged, _on_current_stream
 
 LOSS_NAMES = ("visible_loss_pred", "hidden_loss_pred", "visible_loss_locref", "ws_loss", "total_loss",
               "total_loss_visible", "wt_loss")
@@ -127,15 +128,11 @@ def dgp_loss_prepare(nt: int, H: int, W: int, nj: int, batch: dict, hyper: DGPHy
     vf_dev = None
     if use_wt:          # temporal clique: flow magnitude [nt-1,Hin,Win] (learn_wt) and wt * batch_mask (fitdgp.py:774,905)
         vf = batch["vector_field"]
-        if isinstance(vf, torch.Tensor) and vf.is_cuda:       # computed on the device (engine.optical_flow): used in place
+        if isinstance(vf, Staged) or (isinstance(vf, torch.Tensor) and vf.is_cuda):   # computed on the device (engine.optical_flow): used in place
+            vf = _on_current_stream(vf)         # (the trainer calls this under its upload stream: the wait for the flow lands there)
             _need_cuda(vf, torch.float32, "vector_field")
             if vf.dim() != 3 or vf.shape[0] != nt - 1:
                 raise ValueError("vector_field %s must be [nt-1, Hin, Win] with nt = %d" % (tuple(vf.shape), nt))
-            cur = torch.cuda.current_stream(vf.device)
-            ev = getattr(vf, "_dgp_ready", None)
-            if ev is not None:
-                cur.wait_event(ev)
-            vf.record_stream(cur)
             vf_dev = vf
             hin, win = int(vf.shape[1]), int(vf.shape[2])
         else:

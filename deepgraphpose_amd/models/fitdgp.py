@@ -5,7 +5,10 @@
   dgp_loss(data_batcher, dgp_cfg)               DGP/models/fitdgp.py:848-1144  (loss pre-computation + closure)
   fit_dlc(snapshot, dlcpath, ...)               DGP/models/fitdgp.py:53-254    (step 0: DLC baseline trainer)
 
-One iteration = `Trainer.step` (deepgraphpose_amd/train.py) = the reference's sess.run([loss, train_op]).
+One iteration = `TrainSession.run([loss, train_op], feed_dict)` (models/session.py) = the reference's sess.run([loss, train_op]): it calls
+`Trainer.forward_backward` and then `Trainer.apply_gradients`, each with a read-back of its own (the losses, the gradient norm).
+`Trainer.step` (deepgraphpose_amd/train.py) is the same step with a single synchronisation; the training benchmark times that one,
+the drivers here do not use it.
 Snapshots are what the reference's tf.train.Saver leaves in the train folder (fitdgp.py:239-245, 535-540, 832-839):
 TensorFlow V2 bundles `snapshot-step{k}--{it}.{index,data-00000-of-00001}`, `snapshot-step{k}--0.*` and
 `snapshot-step{k}-final--0.*` plus the `checkpoint` state file, written without TensorFlow (weights_io.Saver,
@@ -25,10 +28,13 @@ from pathlib import Path
 from random import randint
 
 import numpy as np
+import torch.distributed as dist
 
 from .. import config as dcfg
+from .. import dist as ddist
 from ..dataset import MultiDataset, coord2map
 from ..loss import DGPHyper
+from ..staged import _FrameUploader, _device_flow
 from .fitdgp_util import gen_batch
 
 PREFETCH_DEPTH = 2          # iterations of host batches built ahead on a background thread (0: inline); a measured setting, not a switch
@@ -123,10 +129,9 @@ def _setup(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources):
 
 def _dp_index(it, n):
     """Data-parallel runs (torch.distributed initialised, world W > 1): the schedule is identical on every
-    rank (same seeds), iteration `it` of rank r consumes entry it*W + r, and Trainer.step averages the gradients over the
+    rank (same seeds), iteration `it` of rank r consumes entry it*W + r, and TrainSession.run averages the gradients over the
     ranks -- W windows per optimiser step.  Single process: the reference's schedule, unchanged."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if ddist.data_parallel():
         return (it * dist.get_world_size() + dist.get_rank()) % n
     return it
 
@@ -148,78 +153,9 @@ def _make_trainer(data_batcher, init_weights, max_frames, device=0):
     return tr
 
 
-class _FrameUploader:
-    """Uploads a batch's frames from the prefetch thread: numpy -> one of a few pinned staging buffers -> device, asynchronously on its
-    own HIP stream, so that the frames of iteration it + 1 are already resident when the GPU finishes iteration it (a 10 MB pageable
-    copy at the start of every step is 0.4 ms of idle GPU).  The device tensor carries the copy's event; _frames_to_device waits on it."""
-
-    def __init__(self, device, slots: int = 4):
-        import torch
-        self.device = torch.device("cuda", device) if isinstance(device, int) else device
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.slots, self.pinned, self.turn = slots, [None] * slots, 0
-        self.copied = [None] * slots              # event behind the last H2D copy issued from each staging buffer
-
-    def __call__(self, images):
-        import torch
-        img = np.ascontiguousarray(images)
-        if img.dtype != np.uint8:
-            img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
-        k = self.turn
-        self.turn = (k + 1) % self.slots
-        if self.copied[k] is not None:
-            self.copied[k].synchronize()          # the copy queued from this buffer `slots` items ago must have read it (any prefetch depth)
-        if self.pinned[k] is None or self.pinned[k].numel() < img.size:
-            self.pinned[k] = torch.empty(img.size, dtype=torch.uint8).pin_memory()
-        stage = self.pinned[k][:img.size].view(img.shape)
-        stage.numpy()[...] = img
-        with torch.cuda.stream(self.stream):
-            dev = stage.to(self.device, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(self.stream)
-        dev._dgp_ready = ev
-        self.copied[k] = ev
-        return dev
-
-
-def _device_flow(uploader, device, images):
-    """fit_dgp's temporal clique on the device: the batch's frames are uploaded (by the uploader, on its stream, when prefetching) and
-    learn_wt's flow magnitude [nt-1, H, W] is computed from them on the same stream (engine.optical_flow, the reference's parameters).
-    -> (device frames, device magnitude); the magnitude carries the event dgp_loss_prepare waits on."""
-    import torch
-    from .. import engine
-    if uploader is None:
-        dev = torch.from_numpy(np.ascontiguousarray(np.asarray(images).astype(np.uint8))).to(device)
-        return dev, engine.optical_flow(dev)
-    dev = uploader(images)
-    with torch.cuda.stream(uploader.stream):
-        mag = engine.optical_flow(dev)
-        ev = torch.cuda.Event()
-        ev.record(uploader.stream)
-    mag._dgp_ready = ev
-    dev._dgp_ready = ev                 # (the frames are ready no later than the flow that read them)
-    return dev, mag
-
-
-def _frames_to_device(trainer, images):
-    """Batch images -> uint8 device frames; the net follows the batch's resolution (videos of one project may differ in size:
-    the reference's placeholders are [None, None, None, 3]).  A device tensor from _FrameUploader passes through (after its copy)."""
-    import torch
-    if isinstance(images, torch.Tensor) and images.is_cuda:
-        ev = getattr(images, "_dgp_ready", None)
-        cur = torch.cuda.current_stream(images.device)
-        if ev is not None:
-            cur.wait_event(ev)
-        images.record_stream(cur)
-        if (trainer.net.in_h, trainer.net.in_w) != tuple(images.shape[1:3]):
-            trainer.set_input_size(int(images.shape[1]), int(images.shape[2]))
-        return images
-    img = np.ascontiguousarray(images)
-    if img.dtype != np.uint8:
-        img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
-    if (trainer.net.in_h, trainer.net.in_w) != tuple(img.shape[1:3]):
-        trainer.set_input_size(int(img.shape[1]), int(img.shape[2]))
-    return torch.from_numpy(img).to(trainer.device)
+def _make_uploader(trainer):
+    """The prefetch thread's frame uploader (staged.py), or None when batches are built inline (PREFETCH_DEPTH = 0, read at call time)."""
+    return _FrameUploader(trainer.device) if PREFETCH_DEPTH > 0 else None
 
 
 def _locref_targets(joint_loc, nt, vis_within, nx_out, ny_out, nj, dgp_cfg):
@@ -235,10 +171,8 @@ def _locref_targets(joint_loc, nt, vis_within, nx_out, ny_out, nj, dgp_cfg):
 def _save(saver, trainer, prefix, step, it, final, debug=""):
     """The reference's three Saver.save calls (fitdgp.py:535-540, 832-839): `<prefix>-step{k}-` at global_step it and 0, and
     `<prefix>-step{k}-final-` at 0 after the last iteration."""
-    if _is_dp():
-        import torch.distributed as dist
-        if dist.get_rank() != 0:                 # every rank holds the same weights: one writer
-            return
+    if ddist.data_parallel() and dist.get_rank() != 0:      # every rank holds the same weights: one writer
+        return
     w = trainer.get_weights()
     model_name = prefix + "-step" + str(step) + debug + "-"
     saver.save(w, model_name, global_step=it)
@@ -255,11 +189,6 @@ def _augment(dgp_cfg):
     return build_aug(apply_prob=0.8)
 
 
-def _is_dp():
-    import torch.distributed as dist
-    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-
-
 def _dp_setup():
     """Data-parallel runs (torchrun: RANK / WORLD_SIZE in the environment): join the process group BEFORE any GPU use and
     return (rank, world, local_rank).  The batch schedule must be identical on every rank, so rank 0's RNG seeds are broadcast."""
@@ -267,8 +196,6 @@ def _dp_setup():
         return 0, 1, 0
     import random
     import torch
-    import torch.distributed as dist
-    from .. import dist as ddist
     rank, local, world = ddist.init_from_env()
     seed = torch.tensor([np.random.randint(0, 2 ** 31 - 1)], dtype=torch.int64)
     if dist.get_backend() == "nccl":
@@ -342,7 +269,7 @@ def _pretrained_checkpoint(net_type: str, dlc_cfg) -> str:
                             "snapshot via the `snapshot` argument" % (name, ", ".join(str(c) for c in cands)))
 
 
-def _fresh_heads(wts, depth, nj, location_refinement, seed=None):
+def _fresh_heads(wts, depth, nj, seed=None):
     """Head variables absent from an ImageNet checkpoint, initialised like slim.conv2d_transpose does
     (pose_net.py:37-44: xavier/glorot-uniform weights over (fan_in + fan_out)/2, zero biases)."""
     rng = np.random.RandomState(seed)
@@ -412,7 +339,7 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
     else:
         print("Loading ImageNet-pretrained", dlc_cfg.net_type, flush=True)
         wts = {k: v for k, v in wts.items() if k.startswith("resnet_v1")}
-    wts = _fresh_heads(wts, depth, nj, dlc_cfg.location_refinement)
+    wts = _fresh_heads(wts, depth, nj)
     trainer = Trainer(depth, nj, 64, 64, max_frames=1, device=local_rank)
     trainer.load_weights(wts)
 
@@ -476,36 +403,42 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
     return None
 
 
-def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, displayiters=5, maxiters=50000, ns=10,
-                        nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None):
-    """Run DGP with labeled frames only (fitdgp.py:257-546): batch = one labeled frame, loss =
-    total_loss_visible.  `frame_sources` (new, optional) injects already-open frame sources per video."""
+def _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, hyper, final, done, ns, nc, n_max_frames):
+    """What a DGP driver does before it builds anything: join the process group, read the project, put its hyper-parameters on the
+    config singleton, stop when `<snapshot_prefix><final>` already exists, select the frames.
+    -> (data_batcher, init_weights, world, local_rank), or None when this step has been run before."""
+    from .. import weights_io
     rank, world, local_rank = _dp_setup()
     data_batcher, init_weights = _setup(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources)
     dgp_cfg = data_batcher.dlc_config
-    dgp_cfg.update(ws=0, ws_max=1.2, wt=0, wt_max=0, wn_visible=1, wn_hidden=0, gamma=1, gauss_len=1, lengthscale=1,
-                   max_to_keep=5, batch_size=1, n_times_all_frames=100, lr=0.005, gm2=0, gm3=0, aug=aug)
-    from .. import weights_io
-    final = dgp_cfg.snapshot_prefix + "-step1-final--0"
+    dgp_cfg.update(**hyper)
+    final = dgp_cfg.snapshot_prefix + final
     if weights_io.exists(final):
-        print(final, "  exists! DGP with labeled frames has already been run.", flush=True)
+        print(final, done, flush=True)
         return None
     data_batcher.create_batches_from_resnet_output(0, ns_jump=None, step=1, ns=ns, nc=nc, n_max_frames=n_max_frames)
-    nj = data_batcher.nj
-    visible_frame_total = [d.idxs["pv"] for d in data_batcher.datasets]
+    return data_batcher, init_weights, world, local_rank
+
+
+def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_frames, schedule, entry, progress, finished, step,
+           save_every, displayiters, debug="", flow_backend=None):
+    """The loop of both DGP drivers.  schedule() draws the run's entries, entry(data_batcher, e) -> (dataset_i, visible frames, hidden
+    frames) of one of them, progress(...) prints a displayed iteration's lines, `finished` is the closing line.  Iteration `it` trains on
+    entry _dp_index(it) and rank 0 saves every `save_every` iterations and after the last.  labeled_only: the objective is
+    total_loss_visible and the batch is the general one without hidden frames, frame pairs or flow."""
+    from .. import weights_io
     from .session import Placeholder, TrainSession
+    dgp_cfg, nj = data_batcher.dlc_config, data_batcher.nj
     loss, total_loss, total_loss_visible, placeholders = dgp_loss(data_batcher, dgp_cfg)
     pipeline = _augment(dgp_cfg)                 # before the expensive setup: a broken augmentation stack fails here
-    trainer = _make_trainer(data_batcher, init_weights, max_frames=1, device=local_rank)
+    trainer = _make_trainer(data_batcher, init_weights, max_frames=max_frames, device=local_rank)
     learning_rate = Placeholder("learning_rate")
-    train_op = loss.graph.minimize(total_loss_visible, learning_rate)          # fitdgp.py:412-418
+    train_op = loss.graph.minimize(total_loss_visible if labeled_only else total_loss, learning_rate)     # fitdgp.py:412-418, 708-713
     sess = TrainSession(trainer, loss.graph)
     saver = weights_io.Saver(max_to_keep=dgp_cfg.max_to_keep)     # fitdgp.py:401, 696
-    uploader = _FrameUploader(trainer.device) if PREFETCH_DEPTH > 0 else None
-    nepoch = int(np.min([int(data_batcher.n_visible_frames_total * dgp_cfg.n_times_all_frames), maxiters]))
-    table = np.array([(i, vv) for i, v in enumerate(visible_frame_total) for vv in v]).reshape(-1, 2)
-    batch_ind_all = np.random.randint(0, table.shape[0], size=nepoch)
-    n_sched = batch_ind_all.shape[0]
+    uploader = _make_uploader(trainer)
+    entries = schedule()
+    n_sched = len(entries)
     maxiters = max(1, n_sched // world)          # data-parallel: W windows per optimiser step
     data_batcher.reset()
     print("Begin Training for {} iterations".format(maxiters))
@@ -513,34 +446,94 @@ def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, di
     it = -1
 
     def make_batch(it):                          # host side of one iteration (runs one iteration ahead on the prefetch thread)
-        dataset_i, frame_i = table[batch_ind_all[_dp_index(it, n_sched)]]
+        dataset_i, vis_b, hid_b = entry(data_batcher, entries[_dp_index(it, n_sched)])
         d = data_batcher.datasets[dataset_i]
-        (vis, hid, _, images, joint_loc, _, _, addn), _ = data_batcher.next_batch(0, dataset_i, np.array([frame_i]),
-                                                                                  np.array([], dtype=int))
+        (vis, hid, _, images, joint_loc, wt_mask, _, addn), _ = data_batcher.next_batch(0, dataset_i, vis_b, hid_b)
         all_frame = np.sort(list(vis) + list(hid))
         vis_within = [int(np.where(all_frame == i)[0][0]) for i in vis]
-        if pipeline is not None and dgp_cfg.wt == 0 and len(vis_within) > 0:      # fitdgp.py:481-482
+        if pipeline is not None and dgp_cfg.wt == 0 and len(vis_within) > 0:      # fitdgp.py:481-482, 778-779
             from ..augment import data_aug
             images, joint_loc = data_aug(images, vis_within, joint_loc, pipeline, dgp_cfg)
         lmap, lmask = _locref_targets(joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
-        feed_dict = _feed(placeholders, images, joint_loc, lmap, lmask, addn, None, None, 0, d.nx_out, d.ny_out, learning_rate,
-                          dgp_cfg.lr)
-        if uploader is not None:
-            feed_dict[placeholders["inputs"]] = uploader(images)
-        return dataset_i, frame_i, feed_dict
+        vector_field, frames = None, None
+        if dgp_cfg.wt > 0 and flow_backend == "hip":                  # temporal clique: flow magnitude on the device
+            frames, vector_field = _device_flow(uploader, trainer.device, images)
+        elif dgp_cfg.wt > 0:                                          # temporal clique: flow field from the host hook
+            from .fitdgp_util import learn_wt
+            vector_field = learn_wt(images, backend=flow_backend)
+        feed_dict = _feed(placeholders, images, joint_loc, lmap, lmask, addn, None if labeled_only else wt_mask, vector_field,
+                          dgp_cfg.wt, d.nx_out, d.ny_out, learning_rate, dgp_cfg.lr)
+        if frames is None and uploader is not None:
+            frames = uploader(images)
+        if frames is not None:
+            feed_dict[placeholders["inputs"]] = frames
+        return dataset_i, vis_b, hid_b, feed_dict
 
-    for it, (dataset_i, frame_i, feed_dict) in enumerate(_prefetched(make_batch, maxiters)):
+    for it, (dataset_i, vis_b, hid_b, feed_dict) in enumerate(_prefetched(make_batch, maxiters)):
         t0 = time.time()
         loss_eval, _ = sess.run([loss, train_op], feed_dict)
         if it % displayiters == 0 and it > 0:
             print("\nIteration {}/{}".format(it, maxiters))
-            print("dataset_i: ", dataset_i, " visible_frame_batch_i: ", [frame_i], flush=True)
-            print(" running time: ", time.time() - t0, "\n loss: ", loss_eval, flush=True)
-        if (it % saveiters == 0) or (it + 1) == maxiters:
-            _save(saver, trainer, dgp_cfg.snapshot_prefix, step, it, (it + 1) == maxiters)
-    print("Finished training {} iterations\n".format(it), flush=True)
+            progress(dataset_i, vis_b, hid_b, t0, loss_eval)
+        if (it % save_every == 0) or (it + 1) == maxiters:
+            _save(saver, trainer, dgp_cfg.snapshot_prefix, step, it, (it + 1) == maxiters, debug)
+    print(finished.format(it), flush=True)
     print("\n\n TOTAL TIME ELAPSED: ", time.time() - t_start)
+
+
+def _labeled_entry(data_batcher, row):
+    """(dataset, labeled frame) -> that frame alone"""
+    dataset_i, frame_i = row
+    return dataset_i, np.array([frame_i]), np.array([], dtype=int)
+
+
+def _labeled_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
+    print("dataset_i: ", dataset_i, " visible_frame_batch_i: ", [vis_b[0]], flush=True)
+    print(" running time: ", time.time() - t0, "\n loss: ", loss_eval, flush=True)
+
+
+def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, displayiters=5, maxiters=50000, ns=10,
+                        nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None):
+    """Run DGP with labeled frames only (fitdgp.py:257-546): batch = one labeled frame, loss =
+    total_loss_visible.  `frame_sources` (new, optional) injects already-open frame sources per video."""
+    hyper = dict(ws=0, ws_max=1.2, wt=0, wt_max=0, wn_visible=1, wn_hidden=0, gamma=1, gauss_len=1, lengthscale=1,
+                 max_to_keep=5, batch_size=1, n_times_all_frames=100, lr=0.005, gm2=0, gm3=0, aug=aug)
+    run = _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, hyper, "-step1-final--0",
+                        "  exists! DGP with labeled frames has already been run.", ns, nc, n_max_frames)
+    if run is None:
+        return None
+    data_batcher = run[0]
+
+    def schedule():                              # `nepoch` uniform draws from the table of every (dataset, labeled frame)
+        nepoch = int(np.min([int(data_batcher.n_visible_frames_total * data_batcher.dlc_config.n_times_all_frames), maxiters]))
+        table = np.array([(i, vv) for i, d in enumerate(data_batcher.datasets) for vv in d.idxs["pv"]]).reshape(-1, 2)
+        return table[np.random.randint(0, table.shape[0], size=nepoch)]
+
+    _train(*run, labeled_only=True, max_frames=1, schedule=schedule, entry=_labeled_entry, progress=_labeled_progress,
+           finished="Finished training {} iterations\n", step=step, save_every=saveiters, displayiters=displayiters)
     return None
+
+
+def _window_entry(data_batcher, batch_ind):
+    """One window of gen_batch's schedule, [frame, ..., frame, dataset] -> its labeled and its unlabeled frames"""
+    dataset_i = int(batch_ind[-1])
+    idxs = data_batcher.datasets[dataset_i].idxs
+    all_frame_batch = batch_ind[:-1]
+    visible_frame_i = idxs["pv"]
+    all_frame_i = list(idxs["chunk"]) + list(idxs["ph"])
+    vis_b = np.sort(np.array([i for i in all_frame_batch if i in visible_frame_i], dtype=int))
+    if len(vis_b) == 0 and len(visible_frame_i) > 0:              # guarantee one labeled frame (fitdgp.py:755-758)
+        vis_b = np.array([visible_frame_i[randint(0, len(visible_frame_i) - 1)]])
+    hid_b = np.sort(np.array([i for i in all_frame_batch if (i in all_frame_i) and (i not in visible_frame_i)], dtype=int))
+    return dataset_i, vis_b, hid_b
+
+
+def _window_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
+    print("dataset_i: ", dataset_i, flush=True)
+    print("visible_frame_batch_i: ", vis_b, flush=True)
+    print("hidden_frame_batch_i: ", hid_b, flush=True)
+    print("\n running time: ", time.time() - t0, flush=True)
+    print("\n loss: ", loss_eval, flush=True)
 
 
 def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000, displayiters=5, maxiters=200000, ns=10,
@@ -552,87 +545,23 @@ def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000,
     the batch's uploaded frames (engine.optical_flow) and handed to the loss as a device tensor: it never crosses to the host."""
     from .fitdgp_util import resolve_flow_backend
     flow_backend = resolve_flow_backend(flow_backend) if wt > 0 else None
-    rank, world, local_rank = _dp_setup()
-    data_batcher, init_weights = _setup(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources)
-    dgp_cfg = data_batcher.dlc_config
-    dgp_cfg.update(ws=1000, ws_max=1.2, wt=wt, wt_max=0, wn_visible=5, wn_hidden=3, gamma=1, gauss_len=1, lengthscale=1,
-                   max_to_keep=5, batch_size=batch_size, n_times_all_frames=nepoch, lr=0.005, gm2=gm2, gm3=gm3, aug=aug)
-    from .. import weights_io
-    final = dgp_cfg.snapshot_prefix + "-step{}{}-final--0".format(step, debug)
-    if weights_io.exists(final):
-        print(final, "  exists! DGP has already been run.", flush=True)
+    hyper = dict(ws=1000, ws_max=1.2, wt=wt, wt_max=0, wn_visible=5, wn_hidden=3, gamma=1, gauss_len=1, lengthscale=1,
+                 max_to_keep=5, batch_size=batch_size, n_times_all_frames=nepoch, lr=0.005, gm2=gm2, gm3=gm3, aug=aug)
+    run = _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, hyper, "-step{}{}-final--0".format(step, debug),
+                        "  exists! DGP has already been run.", ns, nc, n_max_frames)
+    if run is None:
         return None
-    data_batcher.create_batches_from_resnet_output(0, ns_jump=None, step=1, ns=ns, nc=nc, n_max_frames=n_max_frames)
-    nj = data_batcher.nj
+    data_batcher = run[0]
     print("n_hidden_frames_total", data_batcher.n_frames_total - data_batcher.n_visible_frames_total, flush=True)
     print("n_visible_frames_total", data_batcher.n_visible_frames_total, flush=True)
     print("n_frames_total", data_batcher.n_frames_total, flush=True)
-    visible_frame_total = [d.idxs["pv"] for d in data_batcher.datasets]
-    hidden_frame_total = [d.idxs["ph"] for d in data_batcher.datasets]
-    all_frame_total = [d.idxs["chunk"] for d in data_batcher.datasets]
-    from .session import Placeholder, TrainSession
-    loss, total_loss, total_loss_visible, placeholders = dgp_loss(data_batcher, dgp_cfg)
-    pipeline = _augment(dgp_cfg)
-    trainer = _make_trainer(data_batcher, init_weights, max_frames=batch_size + 1, device=local_rank)
-    learning_rate = Placeholder("learning_rate")
-    train_op = loss.graph.minimize(total_loss, learning_rate)                  # fitdgp.py:708-713
-    sess = TrainSession(trainer, loss.graph)
-    saver = weights_io.Saver(max_to_keep=dgp_cfg.max_to_keep)     # fitdgp.py:401, 696
-    uploader = _FrameUploader(trainer.device) if PREFETCH_DEPTH > 0 else None
-    batch_ind_all = gen_batch(visible_frame_total, hidden_frame_total, all_frame_total, dgp_cfg, maxiters)
-    save_iters = max(int(saveiters / dgp_cfg.batch_size), 1)
-    n_sched = len(batch_ind_all)
-    maxiters = max(1, n_sched // world)
-    data_batcher.reset()
-    print("Begin Training for {} iterations".format(maxiters))
-    t_start = time.time()
-    it = -1
 
-    def make_batch(it):                          # host side of one iteration (runs one iteration ahead on the prefetch thread)
-        batch_ind = batch_ind_all[_dp_index(it, n_sched)]
-        dataset_i = int(batch_ind[-1])
-        d = data_batcher.datasets[dataset_i]
-        all_frame_batch = batch_ind[:-1]
-        visible_frame_i = visible_frame_total[dataset_i]
-        all_frame_i = list(all_frame_total[dataset_i]) + list(hidden_frame_total[dataset_i])
-        vis_b = np.sort(np.array([i for i in all_frame_batch if i in visible_frame_i], dtype=int))
-        if len(vis_b) == 0 and len(visible_frame_i) > 0:              # guarantee one labeled frame (fitdgp.py:755-758)
-            vis_b = np.array([visible_frame_i[randint(0, len(visible_frame_i) - 1)]])
-        hid_b = np.sort(np.array([i for i in all_frame_batch if (i in all_frame_i) and (i not in visible_frame_i)],
-                                 dtype=int))
-        (vis, hid, _, images, joint_loc, wt_mask, _, addn), _ = data_batcher.next_batch(0, dataset_i, vis_b, hid_b)
-        all_frame = np.sort(list(vis) + list(hid))
-        vis_within = [int(np.where(all_frame == i)[0][0]) for i in vis]
-        if pipeline is not None and dgp_cfg.wt == 0 and len(vis_within) > 0:      # fitdgp.py:778-779
-            from ..augment import data_aug
-            images, joint_loc = data_aug(images, vis_within, joint_loc, pipeline, dgp_cfg)
-        lmap, lmask = _locref_targets(joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
-        vector_field, dev_images = None, None
-        if dgp_cfg.wt > 0 and flow_backend == "hip":                  # temporal clique: flow magnitude on the device
-            dev_images, vector_field = _device_flow(uploader, trainer.device, images)
-        elif dgp_cfg.wt > 0:                                          # temporal clique: flow field from the host hook
-            from .fitdgp_util import learn_wt
-            vector_field = learn_wt(images, backend=flow_backend)
-        feed_dict = _feed(placeholders, images, joint_loc, lmap, lmask, addn, wt_mask, vector_field, dgp_cfg.wt, d.nx_out,
-                          d.ny_out, learning_rate, dgp_cfg.lr)
-        if dev_images is not None:
-            feed_dict[placeholders["inputs"]] = dev_images
-        elif uploader is not None:
-            feed_dict[placeholders["inputs"]] = uploader(images)
-        return dataset_i, vis_b, hid_b, feed_dict
+    def schedule():                              # gen_batch's windows over every dataset's selected frames
+        idxs = [d.idxs for d in data_batcher.datasets]
+        return gen_batch([i["pv"] for i in idxs], [i["ph"] for i in idxs], [i["chunk"] for i in idxs], data_batcher.dlc_config,
+                         maxiters)
 
-    for it, (dataset_i, vis_b, hid_b, feed_dict) in enumerate(_prefetched(make_batch, maxiters)):
-        t0 = time.time()
-        loss_eval, _ = sess.run([loss, train_op], feed_dict)
-        if it % displayiters == 0 and it > 0:
-            print("\nIteration {}/{}".format(it, maxiters))
-            print("dataset_i: ", dataset_i, flush=True)
-            print("visible_frame_batch_i: ", vis_b, flush=True)
-            print("hidden_frame_batch_i: ", hid_b, flush=True)
-            print("\n running time: ", time.time() - t0, flush=True)
-            print("\n loss: ", loss_eval, flush=True)
-        if (it % save_iters == 0) or (it + 1) == maxiters:
-            _save(saver, trainer, dgp_cfg.snapshot_prefix, step, it, (it + 1) == maxiters, debug)
-    print("Finished {} iterations\n".format(it), flush=True)
-    print("\n\n TOTAL TIME ELAPSED: ", time.time() - t_start)
+    _train(*run, labeled_only=False, max_frames=batch_size + 1, schedule=schedule, entry=_window_entry, progress=_window_progress,
+           finished="Finished {} iterations\n", step=step, save_every=max(int(saveiters / batch_size), 1), displayiters=displayiters,
+           debug=debug, flow_backend=flow_backend)
     return None

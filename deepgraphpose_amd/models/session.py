@@ -11,6 +11,10 @@ from __future__ import annotations
 from typing import Dict
 
 import numpy as np
+import torch
+
+from .. import dist as ddist
+from ..staged import Staged, _frames_to_device
 
 PLACEHOLDER_KEYS = ("inputs", "targets", "locref_map", "locref_mask", "visible_marker_pl", "hidden_marker_pl",
                     "visible_marker_in_targets_pl", "wt_batch_mask_pl", "vector_field_tf", "nt_batch_pl", "wt_batch_pl",
@@ -82,9 +86,9 @@ class TrainSession:
             if ph[k] not in feed:
                 raise KeyError("feed_dict lacks placeholder %r" % k)
         images = feed[ph["inputs"]]
-        if not (hasattr(images, "is_cuda") and images.is_cuda):      # (a device tensor: frames the fit drivers uploaded ahead of time)
+        if not isinstance(images, (Staged, torch.Tensor)):      # (a pair: frames the fit drivers uploaded ahead of time; a tensor: a caller's)
             images = np.asarray(images)
-        nt = images.shape[0]
+        nt = (images.tensor if isinstance(images, Staged) else images).shape[0]
         if ph["nt_batch_pl"] in feed and int(feed[ph["nt_batch_pl"]]) != nt:
             raise ValueError("nt_batch_pl = %s but inputs hold %d frames" % (feed[ph["nt_batch_pl"]], nt))
         batch = dict(targets=np.asarray(feed[ph["targets"]], dtype=np.float64),
@@ -105,7 +109,6 @@ class TrainSession:
         return images, batch
 
     def run(self, fetches, feed_dict):
-        from .fitdgp import _frames_to_device
         single = not isinstance(fetches, (list, tuple))
         fl = [fetches] if single else list(fetches)
         train_ops = [f for f in fl if isinstance(f, TrainOp)]
@@ -126,8 +129,7 @@ class TrainSession:
                 if lr not in feed_dict:
                     raise KeyError("feed_dict lacks the learning-rate placeholder")
                 lr = feed_dict[lr]
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            if ddist.data_parallel():
                 tr.allreduce_gradients()
             losses["grad_norm"] = tr.apply_gradients(float(lr), op.momentum, op.clip_norm)
         out = []

@@ -10,7 +10,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, engine
+from . import _lib, dist as ddist, engine
 from .engine import _ptr, _stream
 from .loss import DGPHyper, LOSS_NAMES
 
@@ -253,14 +253,13 @@ class Trainer:
         the event the backward pass recorded behind that group's finalisation -- the heads and block4 (60 % of the parameters) are on the
         wire while the pass is still computing blocks 3 .. 1; the caller's stream then waits for the collectives.  The result is the same
         sum (one all-reduce per contiguous range of the same buffer); overlap=False: one synchronisation, then 64-MB buckets (round 5)."""
-        from .dist import average_gradients
         import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        if not ddist.data_parallel(group):
             return
         groups = self.grad_groups() if overlap else []
         if not groups:
             torch.cuda.current_stream(self.device).synchronize()       # backward kernels ran on this stream via the C-ABI
-            average_gradients(self.grads_tensor(), group)
+            ddist.average_gradients(self.grads_tensor(), group)
             return
         flat = self.grads_tensor()
         world = dist.get_world_size(group)
@@ -295,8 +294,7 @@ class Trainer:
         forward, loss, backward, clip + momentum, the re-packing of the weights -- is enqueued without a read-back and ONE synchronisation
         at its end fetches losses, gradient norm and the pass status (dgp_trainer_step_status).  A 16-bit pass whose tensors left their
         predicted ranges has skipped its update on the device and is repeated here on the parity path."""
-        import torch.distributed as dist
-        dp = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        dp = ddist.data_parallel()
         from .loss import LOSS_NAMES
         nt = frames.shape[0]
         while True:

@@ -691,13 +691,34 @@ def test_frame_uploader_matches_plain_upload(lib_built):
     rng = np.random.RandomState(0)
     for shape in [(3, 64, 96, 3), (5, 64, 96, 3), (2, 32, 48, 3), (5, 64, 96, 3)]:
         img = rng.randint(0, 256, shape).astype(np.uint8)
-        dev = up(img)
-        torch.cuda.current_stream().wait_event(dev._dgp_ready)
+        dev, ready = up(img)
+        torch.cuda.current_stream().wait_event(ready)
         assert dev.dtype == torch.uint8 and tuple(dev.shape) == shape and np.array_equal(dev.cpu().numpy(), img)
     f = rng.uniform(0, 255, (2, 16, 16, 3))
-    dev = up(f)
-    torch.cuda.current_stream().wait_event(dev._dgp_ready)
+    dev, ready = up(f)
+    torch.cuda.current_stream().wait_event(ready)
     assert np.array_equal(dev.cpu().numpy(), np.clip(np.rint(f), 0, 255).astype(np.uint8))
+
+
+def test_device_flow_stages_frames_and_magnitude_behind_one_event(lib_built):
+    """staged._device_flow (fit_dgp's temporal clique with the HIP flow): frames and flow magnitude come back as two Staged pairs that share
+    ONE event, recorded on the uploader's stream behind the flow.  After the wait the frames are the input and the magnitude is, bit for
+    bit, engine.optical_flow of a plain upload (same kernels, same parameters); without an uploader (inline batches) the same two tensors
+    come back with no event."""
+    from deepgraphpose_amd import engine
+    from deepgraphpose_amd.staged import Staged, _FrameUploader, _device_flow
+    img = np.random.RandomState(1).randint(0, 256, (3, 48, 64, 3)).astype(np.uint8)
+    dev = torch.device("cuda", 0)
+    ref = engine.optical_flow(torch.from_numpy(img).to(dev))
+    assert ref.shape == (2, 48, 64) and float(ref.abs().max()) > 0
+    frames, mag = _device_flow(_FrameUploader(0, slots=2), dev, img)
+    assert isinstance(frames, Staged) and isinstance(mag, Staged) and frames.ready is mag.ready and mag.ready is not None
+    torch.cuda.current_stream().wait_event(mag.ready)
+    assert frames.tensor.dtype == torch.uint8 and np.array_equal(frames.tensor.cpu().numpy(), img)
+    assert mag.tensor.dtype == torch.float32 and torch.equal(mag.tensor, ref)
+    frames0, mag0 = _device_flow(None, dev, img)
+    assert frames0.ready is None and mag0.ready is None
+    assert np.array_equal(frames0.tensor.cpu().numpy(), img) and torch.equal(mag0.tensor, ref)
 
 
 def test_estimate_pose_keeps_its_engines_between_videos_without_changing_a_bit(lib_built, tmp_path, monkeypatch):
