@@ -124,6 +124,11 @@ SYMBOLS = {
     "dgp_resize_plan_size": (C.c_int, [_i32, _i32, C.POINTER(_i32)]),
     "dgp_resize_plan": (C.c_int, [_i32, _i32, _vp, _vp]),
     "dgp_resize_crop_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _vp, _vp, _vp, _i32, _i32, _vp]),
+    "dgp_resize_plan_size_f": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32)]),
+    "dgp_resize_plan_f": (C.c_int, [_i32, _i32, _i32, _vp, _vp]),
+    "dgp_window_resize_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "dgp_target_maps": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _i32,
+                                  _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

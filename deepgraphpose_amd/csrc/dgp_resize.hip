@@ -12,6 +12,10 @@
 // accumulator of every tile row whose window holds the input row (16 accumulators in registers; the test is uniform over the
 // workgroup and the vertical coefficients come through uniform loads).  No intermediate image, no atomics, no scratch; the vertical
 // factor is unbounded, the horizontal one by the LDS row buffers (checked on the host before the launch).
+//
+// dgp_window_resize_u8 runs the same kernel over a WINDOW of one image with Pillow's BOX or BILINEAR tables (dgp_resize_plan_f): crop_image +
+// imresize (+ np.fliplr) of the step-0 sample loader.  The window is addressed in place -- ResizeArgs::origin and ::pitch -- and ::mirror
+// stores column c at OW - 1 - c.  The tables are clamped to the window, so whatever a dword-staged segment holds beyond it meets zeros only.
 #include "dgp_engine.h"
 
 #include <cmath>
@@ -35,6 +39,12 @@ struct ResizeArgs {
     int left, upper;                    // output (oy, ox) is pixel (oy + upper, ox + left) of the resized image
     int ksize_x, ksize_y;
     int row_bytes;                      // bytes of one LDS row buffer (multiple of 16)
+    // the H x W pixels resampled are a window of a larger image: rows are `pitch` pixels apart, the window's first byte is `origin` bytes
+    // into the image and the image (what the descriptor bounds) has `image_bytes` bytes.  Whole frames: W, 0, H * W * 3
+    int pitch;
+    unsigned origin;
+    size_t image_bytes;
+    int mirror;                         // output column ox is stored at OW - 1 - ox
 };
 
 __device__ __forceinline__ int clip8(int v) { return min(max(v >> RSZ_PRECISION_BITS, 0), 255); }
@@ -90,7 +100,7 @@ __global__ __launch_bounds__(RSZ_THREADS) void resize_crop_kernel(const ResizeAr
     // ---- source rows through a bounded descriptor of this frame: dword-aligned base (the frame's first byte sits at `mis`) and a whole
     // number of dwords (the range check drops a dword that is only partly inside; the frame's last dword ends inside the same
     // aligned dword as its last byte, so reading it touches no other page)
-    const size_t frame_bytes = (size_t)p.H * p.W * 3;
+    const size_t frame_bytes = p.image_bytes;
     const uintptr_t fsrc = (uintptr_t)p.src + (size_t)b * frame_bytes;
     const unsigned mis = (unsigned)(fsrc & 3);
     const __amdgpu_buffer_rsrc_t rs_src =
@@ -102,7 +112,7 @@ __global__ __launch_bounds__(RSZ_THREADS) void resize_crop_kernel(const ResizeAr
 
     uint32_t stage[RSZ_LOADS];
     auto fetch = [&](int r, unsigned* shift) {                   // row r's segment -> registers; *shift: its first byte within the first dword
-        const unsigned off = mis + ((unsigned)r * (unsigned)p.W + (unsigned)seg0) * 3u;
+        const unsigned off = mis + p.origin + ((unsigned)r * (unsigned)p.pitch + (unsigned)seg0) * 3u;
         const unsigned a0 = off & ~3u;
         *shift = off & 3u;
         const int ndw = min((int)((*shift + (unsigned)seg_len * 3u + 3u) >> 2), p.row_bytes >> 2);
@@ -152,12 +162,13 @@ __global__ __launch_bounds__(RSZ_THREADS) void resize_crop_kernel(const ResizeAr
     const size_t out_bytes = (size_t)p.OH * p.OW * 3;
     const __amdgpu_buffer_rsrc_t rs_dst = __builtin_amdgcn_make_buffer_rsrc(p.dst + (size_t)b * out_bytes, 0, (int)out_bytes, 0x00020000);
     const int ox = ox0 + px;
+    const int oxs = p.mirror ? p.OW - 1 - ox : ox;
 #pragma unroll
     for (int yy = 0; yy < RSZ_TH; ++yy) {
         const int oy = oy0 + yy;
         if (oy < p.OH && ox < p.OW) {
             const int v = clip8(acc[yy] + (1 << (RSZ_PRECISION_BITS - 1)));
-            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, rs_dst, (int)(((unsigned)oy * (unsigned)p.OW + (unsigned)ox) * 3u + (unsigned)ch), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, rs_dst, (int)(((unsigned)oy * (unsigned)p.OW + (unsigned)oxs) * 3u + (unsigned)ch), 0, 0);
         }
     }
 }
@@ -173,16 +184,26 @@ static double bicubic_filter(double x) {
     return 0.0;
 }
 
+// Pillow's box_filter and bilinear_filter
+static double box_filter(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
+static double bilinear_filter(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+static bool filter_known(int filter) { return filter == DGP_FILTER_BOX || filter == DGP_FILTER_BILINEAR || filter == DGP_FILTER_BICUBIC; }
+static double filter_support(int filter) { return filter == DGP_FILTER_BOX ? 0.5 : filter == DGP_FILTER_BILINEAR ? 1.0 : 2.0; }
+
 struct AxisGeom {
     double scale, filterscale, support;
     int ksize;
 };
 
-static AxisGeom axis_geom(int in_size, int out_size) {
+static AxisGeom axis_geom(int in_size, int out_size, int filter = DGP_FILTER_BICUBIC) {
     AxisGeom g;
     g.scale = (double)in_size / (double)out_size;
     g.filterscale = g.scale < 1.0 ? 1.0 : g.scale;
-    g.support = 2.0 * g.filterscale;
+    g.support = filter_support(filter) * g.filterscale;
     g.ksize = (int)std::ceil(g.support) * 2 + 1;
     return g;
 }
@@ -193,9 +214,10 @@ static int plan_check(int in_size, int out_size) {
     return DGP_OK;
 }
 
-static void axis_plan(int in_size, int out_size, int32_t* bounds, int32_t* coeffs) {
+static void axis_plan(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int filter = DGP_FILTER_BICUBIC) {
 #pragma clang fp contract(off)
-    const AxisGeom g = axis_geom(in_size, out_size);
+    const AxisGeom g = axis_geom(in_size, out_size, filter);
+    const double ss = 1.0 / g.filterscale;       // BOX, BILINEAR: Pillow's argument (... ) * ss; BICUBIC keeps the division it was pinned with
     std::vector<double> w((size_t)g.ksize);
     for (int xx = 0; xx < out_size; ++xx) {
         const double center = (xx + 0.5) * g.scale;
@@ -206,7 +228,9 @@ static void axis_plan(int in_size, int out_size, int32_t* bounds, int32_t* coeff
         if (xmax > in_size) xmax = in_size;
         xmax -= xmin;
         for (int x = 0; x < xmax; ++x) {
-            w[x] = bicubic_filter((x + xmin - center + 0.5) / g.filterscale);
+            const double at = x + xmin - center + 0.5;
+            w[x] = filter == DGP_FILTER_BOX ? box_filter(at * ss) : filter == DGP_FILTER_BILINEAR ? bilinear_filter(at * ss)
+                                                                                                    : bicubic_filter(at / g.filterscale);
             ww += w[x];
         }
         int32_t* k = coeffs + (size_t)xx * g.ksize;
@@ -241,6 +265,23 @@ int dgp_resize_plan(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t*
     if (rc != DGP_OK) return rc;
     if (!bounds || !coeffs) return fail(DGP_ERR_INVALID, "dgp_resize_plan: null bounds or coeffs");
     axis_plan(in_size, out_size, bounds, coeffs);
+    return DGP_OK;
+}
+
+int dgp_resize_plan_size_f(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize) {
+    const int rc = plan_check(in_size, out_size);
+    if (rc != DGP_OK) return rc;
+    if (!filter_known(filter)) return fail(DGP_ERR_INVALID, "dgp_resize_plan_size_f: filter must be BOX, BILINEAR or BICUBIC");
+    if (ksize) *ksize = axis_geom(in_size, out_size, filter).ksize;
+    return DGP_OK;
+}
+
+int dgp_resize_plan_f(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* coeffs) {
+    const int rc = plan_check(in_size, out_size);
+    if (rc != DGP_OK) return rc;
+    if (!filter_known(filter)) return fail(DGP_ERR_INVALID, "dgp_resize_plan_f: filter must be BOX, BILINEAR or BICUBIC");
+    if (!bounds || !coeffs) return fail(DGP_ERR_INVALID, "dgp_resize_plan_f: null bounds or coeffs");
+    axis_plan(in_size, out_size, bounds, coeffs, filter);
     return DGP_OK;
 }
 
@@ -279,11 +320,61 @@ int dgp_resize_crop_u8(const uint8_t* src, int32_t B, int32_t H, int32_t W, int3
     a.OH = (int)oh; a.OW = (int)ow;
     a.ksize_x = ksize_x; a.ksize_y = ksize_y;
     a.row_bytes = (int)row_bytes;
+    a.pitch = W;
+    a.origin = 0;
+    a.image_bytes = (size_t)H * W * 3;
+    a.mirror = 0;
     const dim3 grid((unsigned)((ow + RSZ_TW - 1) / RSZ_TW), (unsigned)((oh + RSZ_TH - 1) / RSZ_TH), (unsigned)B);
     if (grid.y > 65535) return fail(DGP_ERR_INVALID, "dgp_resize_crop_u8: output too tall");
     hipLaunchKernelGGL(resize_crop_kernel, grid, dim3(RSZ_THREADS), (size_t)lds, (hipStream_t)stream, a, d_plan_x, d_plan_y);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_resize_crop_u8: ") + hipGetErrorString(e));
+    return DGP_OK;
+}
+
+int dgp_window_resize_u8(const uint8_t* src, int32_t src_H, int32_t src_W, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t RH,
+                         int32_t RW, int32_t filter, int32_t mirror, uint8_t* dst, const int32_t* d_plan_x, const int32_t* d_plan_y,
+                         int32_t ksize_x, int32_t ksize_y, void* stream) {
+    if (src_H <= 0 || src_W <= 0 || RH <= 0 || RW <= 0) return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: sizes must be positive");
+    if (!src || !dst) return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: null image");
+    if (!d_plan_x || !d_plan_y) return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: null plan");
+    if (!filter_known(filter)) return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: filter must be BOX, BILINEAR or BICUBIC");
+    if (x0 < 0 || y0 < 0 || x1 < x0 || y1 < y0 || x1 >= src_W || y1 >= src_H)
+        return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: the window must lie inside the image");
+    const int H = y1 - y0 + 1, W = x1 - x0 + 1;
+    int rc = plan_check(W, RW);
+    if (rc == DGP_OK) rc = plan_check(H, RH);
+    if (rc == DGP_OK) rc = plan_check(src_H, src_W);
+    if (rc != DGP_OK) return rc;
+    const AxisGeom gx = axis_geom(W, RW, filter), gy = axis_geom(H, RH, filter);
+    if (ksize_x != gx.ksize || ksize_y != gy.ksize)
+        return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: ksize does not belong to these sizes and this filter");
+    if ((long long)src_H * src_W * 3 + 4 > 0x7fffffffLL || (long long)RH * RW * 3 > 0x7fffffffLL)
+        return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: an image of 2 GiB or more");
+    // as in dgp_resize_crop_u8: the input pixels 64 consecutive horizontal windows span
+    const long long seg = std::min<long long>(W, (long long)std::ceil(63.0 * gx.scale + 2.0 * gx.support) + 3);
+    const long long row_dwords = (seg * 3 + 3 + 3) / 4;
+    const long long row_bytes = (row_dwords * 4 + 15) / 16 * 16;
+    const long long lds = 2 * row_bytes + (long long)gx.ksize * RSZ_TW * 4;
+    if (row_dwords > RSZ_ROW_DWORDS || lds > RSZ_LDS_BYTES)
+        return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: the horizontal reduction " + std::to_string(W) + " -> " + std::to_string(RW) +
+                                         " needs a row segment beyond the kernel's LDS budget");
+    ResizeArgs a{};
+    a.src = src;
+    a.dst = dst;
+    a.H = H; a.W = W; a.RH = RH; a.RW = RW;
+    a.OH = RH; a.OW = RW;
+    a.ksize_x = ksize_x; a.ksize_y = ksize_y;
+    a.row_bytes = (int)row_bytes;
+    a.pitch = src_W;
+    a.origin = ((unsigned)y0 * (unsigned)src_W + (unsigned)x0) * 3u;
+    a.image_bytes = (size_t)src_H * src_W * 3;
+    a.mirror = mirror ? 1 : 0;
+    const dim3 grid((unsigned)((RW + RSZ_TW - 1) / RSZ_TW), (unsigned)((RH + RSZ_TH - 1) / RSZ_TH), 1);
+    if (grid.y > 65535) return fail(DGP_ERR_INVALID, "dgp_window_resize_u8: output too tall");
+    hipLaunchKernelGGL(resize_crop_kernel, grid, dim3(RSZ_THREADS), (size_t)lds, (hipStream_t)stream, a, d_plan_x, d_plan_y);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_window_resize_u8: ") + hipGetErrorString(e));
     return DGP_OK;
 }
 

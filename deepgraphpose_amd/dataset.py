@@ -169,6 +169,22 @@ def coord2map(joint_loc, nx_out: int, ny_out: int, nj: int, pos_dist_thresh: flo
     return t, m
 
 
+def coord2map_entries(joint_loc, nj: int):
+    """coord2map's inputs to the target generator, without running it: -> (entries float64 [k, 3] = (joint id, x, y) px, offsets
+    int32 [nv + 1]; frame ii owns entries[offsets[ii]:offsets[ii + 1]]) -- what engine.target_maps takes.  coord2map's own rules: *8 + 4,
+    the flip to (x, y), and joints whose (NaN->0) coordinates sum to zero are dropped."""
+    joint_loc = np.asarray(joint_loc, dtype=np.float64)
+    if joint_loc.ndim != 3 or joint_loc.shape[1:] != (nj, 2):
+        raise ValueError("coord2map_entries: joint_loc must be [nv, %d, 2], got %s" % (nj, joint_loc.shape))
+    entries, offsets = [np.zeros((0, 3))], [0]
+    for ii in range(joint_loc.shape[0]):
+        xy = np.flip(joint_loc[ii] * 8 + 4, 1)            # (row, col) -> (x, y) px
+        present = np.where(np.nan_to_num(xy).sum(1) != 0)[0]
+        entries.append(np.column_stack([present.astype(np.float64), xy[present]]))
+        offsets.append(offsets[-1] + len(present))
+    return np.concatenate(entries), np.asarray(offsets, dtype=np.int32)
+
+
 def compute_pred_dims(frame_h: int, frame_w: int) -> Tuple[int, int]:
     """(nx_out, ny_out) of the scoremap for a frame: 2*ceil(H/16), 2*ceil(W/16).  The reference builds and
     runs the whole network on a zero frame just to read this shape (DGP/dataset.py:348-371)."""

@@ -38,9 +38,13 @@ def imresize(img: np.ndarray, scale: float) -> np.ndarray:
         return cv2.resize(img, None, fx=scale, fy=scale, interpolation=cv2.INTER_AREA)
     except ImportError:
         from PIL import Image
-        h, w = img.shape[:2]
-        nw, nh = max(1, int(round(w * scale))), max(1, int(round(h * scale)))
+        nh, nw = resized_hw(img.shape[0], img.shape[1], scale)
         return np.asarray(Image.fromarray(img).resize((nw, nh), Image.BOX if scale < 1 else Image.BILINEAR))
+
+
+def resized_hw(rows: int, cols: int, scale: float):
+    """(rows, cols) of imresize's output (Python's round: half-even, at least one pixel)"""
+    return max(1, int(round(rows * scale))), max(1, int(round(cols * scale)))
 
 
 def mirror_joints_map(all_joints, num_joints):
@@ -51,22 +55,34 @@ def mirror_joints_map(all_joints, num_joints):
     return res
 
 
-def crop_image(joints, im, x_label, y_label, cfg):
-    """Random crop around one labeled joint (pose_dataset.py:37-52)."""
+def crop_window(joints, im_hw, x_label, y_label, cfg):
+    """Random crop around one labeled joint (pose_dataset.py:37-52) without the pixels: the four draws, the inclusive window
+    (x0, y0, x1, y1) of an image of im_hw = (rows, cols), and the joints [1, k, 3] moved into it (in place) and filtered."""
     fwd = int(cfg["minsize"] + np.random.randint(cfg["rightwidth"]))
     back = int(cfg["minsize"] + np.random.randint(cfg["leftwidth"]))
     hup = int(cfg["minsize"] + np.random.randint(cfg["topheight"]))
     hdown = int(cfg["minsize"] + np.random.randint(cfg["bottomheight"]))
     x0 = max(0, int(x_label - back))
-    x1 = min(im.shape[1] - 1, int(x_label + fwd))
+    x1 = min(im_hw[1] - 1, int(x_label + fwd))
     y0 = max(0, int(y_label - hdown))
-    y1 = min(im.shape[0] - 1, int(y_label + hup))
+    y1 = min(im_hw[0] - 1, int(y_label + hup))
     joints[0, :, 1] -= x0
     joints[0, :, 2] -= y0
     # like the reference, the bounds test uses the un-cropped image size
-    inb = np.where((joints[0, :, 1] > 0) * (joints[0, :, 1] < im.shape[1]) * (joints[0, :, 2] > 0) *
-                   (joints[0, :, 2] < im.shape[0]))[0]
-    return joints[:, inb, :], im[y0:y1 + 1, x0:x1 + 1, :]
+    inb = np.where((joints[0, :, 1] > 0) * (joints[0, :, 1] < im_hw[1]) * (joints[0, :, 2] > 0) *
+                   (joints[0, :, 2] < im_hw[0]))[0]
+    return joints[:, inb, :], (x0, y0, x1, y1)
+
+
+def crop_image(joints, im, x_label, y_label, cfg):
+    """Random crop around one labeled joint (pose_dataset.py:37-52)."""
+    joints, (x0, y0, x1, y1) = crop_window(joints, im.shape[:2], x_label, y_label, cfg)
+    return joints, im[y0:y1 + 1, x0:x1 + 1, :]
+
+
+class SamplePlan:
+    """One sample's draws and geometry (PoseDataset.plan_batch): item, scale, mirror, crop = inclusive (x0, y0, x1, y1) or None,
+    in_hw (the cropped image), out_hw (after imresize), sm_size, joint_ids / coords (per person; coords already scaled)."""
 
 
 class PoseDataset:
@@ -162,45 +178,97 @@ class PoseDataset:
             for key in ("rightwidth", "leftwidth", "topheight", "bottomheight"):      # crop_image's draws, in its order
                 np.random.randint(cfg[key])
 
-    def make_batch(self, item, scale, mirror):
-        """-> dict(inputs uint8 [1,H,W,3], part_score_targets / part_score_weights [1,h,w,nj],
-        locref_targets / locref_mask [1,h,w,2nj], data_item)."""
+    def plan_batch(self):
+        """Every random draw of next_batch(), in its order, and the sample's geometry -- without touching pixels (the image size comes
+        from item.im_size): -> SamplePlan.  next_batch() is render_batch(plan_batch())."""
+        while True:
+            imidx, mirror = self.next_training_sample()
+            item = self.data[imidx]
+            scale = self.get_scale()
+            if self.is_valid_size(item.im_size, scale):
+                return self.plan_sample(item, scale, mirror)
+
+    def plan_sample(self, item, scale, mirror):
+        """make_batch's draws (the crop decision, the crop joint, the four extents) and what follows from them for an image of
+        item.im_size = (3, rows, cols): the crop window, the output size, the scoremap size and the transformed joints."""
         cfg = self.cfg
-        image = imread(os.path.join(cfg.project_path, item.im_path))
+        rows, cols = int(item.im_size[1]), int(item.im_size[2])
         joints = np.array(item.joints, dtype=np.float64) if self.has_gt else None      # [1, k, 3] copy
+        crop = None
         if self.has_gt and cfg.crop and np.random.rand() < cfg.cropratio and joints.shape[1] > 0:
             j = np.random.randint(joints.shape[1])
-            joints, image = crop_image(joints, image, joints[0, j, 1], joints[0, j, 2], cfg)
-        img = imresize(image, scale) if scale != 1 else image
-        size = np.array(img.shape[0:2])
-        if mirror:
-            img = np.fliplr(img)
-        batch = {"inputs": np.array(img)[None]}
+            joints, crop = crop_window(joints, (rows, cols), joints[0, j, 1], joints[0, j, 2], cfg)
+            rows, cols = crop[3] - crop[1] + 1, crop[2] - crop[0] + 1
+        plan = SamplePlan()
+        plan.item, plan.scale, plan.mirror, plan.crop = item, scale, bool(mirror), crop
+        plan.in_hw = (rows, cols)                                   # the (cropped) image before the resize
+        plan.out_hw = (rows, cols) if scale == 1 else resized_hw(rows, cols, scale)
+        plan.joint_ids = plan.coords = plan.sm_size = None
         if self.has_gt:
             if mirror:
                 jm = []
                 for pj in joints:
                     r = np.copy(pj)
-                    r[:, 1] = image.shape[1] - r[:, 1] - 1
+                    r[:, 1] = cols - r[:, 1] - 1
                     r[:, 0] = self.symmetric_joints[pj[:, 0].astype(int)]
                     jm.append(r)
                 joints = jm
-            sm_size = np.ceil(size / (self.stride * 2)).astype(int) * 2
-            coords = [pj[:, 1:3] * scale for pj in joints]
-            ids = [pj[:, 0].astype(int) for pj in joints]
-            scmap, lmap, lmask = compute_target_part_scoremap(ids, coords, sm_size, cfg.num_joints, cfg.pos_dist_thresh,
-                                                              stride=self.stride, locref_stdev=cfg.locref_stdev,
-                                                              scale=scale)
-            if cfg.weigh_only_present_joints:
-                weights = np.zeros(scmap.shape)
-                for pid in ids:
-                    weights[:, :, pid] = 1.0
-            else:
-                weights = np.ones(scmap.shape)
-            batch.update(part_score_targets=scmap[None].astype(np.float32), part_score_weights=weights[None].astype(np.float32),
-                         locref_targets=lmap[None].astype(np.float32), locref_mask=lmask[None].astype(np.float32))
-        batch["data_item"] = item
+            plan.sm_size = np.ceil(np.array(plan.out_hw) / (self.stride * 2)).astype(int) * 2
+            plan.coords = [pj[:, 1:3] * scale for pj in joints]
+            plan.joint_ids = [pj[:, 0].astype(int) for pj in joints]
+        return plan
+
+    def make_batch(self, item, scale, mirror):
+        """-> dict(inputs uint8 [1,H,W,3], part_score_targets / part_score_weights [1,h,w,nj],
+        locref_targets / locref_mask [1,h,w,2nj], data_item)."""
+        return self.render_batch(self.plan_sample(item, scale, mirror))
+
+    def render_batch(self, plan):
+        """The host pixels and maps of a planned sample: read, crop, imresize, flip; compute_target_part_scoremap."""
+        img = self.host_pixels(plan)
+        batch = {"inputs": img[None]}
+        if self.has_gt:
+            sm_size = np.ceil(np.array(img.shape[0:2]) / (self.stride * 2)).astype(int) * 2
+            batch.update(self.host_targets(plan, sm_size))
+        batch["data_item"] = plan.item
         return batch
+
+    def host_pixels(self, plan, image=None):
+        """The uint8 [h, w, 3] pixels of a planned sample, on the host: read (unless `image` is given), crop, imresize, flip."""
+        if image is None:
+            image = imread(os.path.join(self.cfg.project_path, plan.item.im_path))
+        if plan.crop is not None:
+            x0, y0, x1, y1 = plan.crop
+            image = image[y0:y1 + 1, x0:x1 + 1, :]
+        img = imresize(image, plan.scale) if plan.scale != 1 else image
+        if plan.mirror:
+            img = np.fliplr(img)
+        return np.array(img)
+
+    def host_targets(self, plan, sm_size=None):
+        """The four fp32 target maps of a planned sample, built on the host (the reference the device path is tested against)."""
+        cfg = self.cfg
+        ids = plan.joint_ids
+        scmap, lmap, lmask = compute_target_part_scoremap(ids, plan.coords, plan.sm_size if sm_size is None else sm_size, cfg.num_joints,
+                                                          cfg.pos_dist_thresh, stride=self.stride, locref_stdev=cfg.locref_stdev,
+                                                          scale=plan.scale)
+        if cfg.weigh_only_present_joints:
+            weights = np.zeros(scmap.shape)
+            for pid in ids:
+                weights[:, :, pid] = 1.0
+        else:
+            weights = np.ones(scmap.shape)
+        return dict(part_score_targets=scmap[None].astype(np.float32), part_score_weights=weights[None].astype(np.float32),
+                    locref_targets=lmap[None].astype(np.float32), locref_mask=lmask[None].astype(np.float32))
+
+
+def plan_entries(plan) -> np.ndarray:
+    """The (joint id, x, y) doubles of a planned sample, [k, 3] in compute_target_part_scoremap's person-then-joint order: the entries
+    of engine.target_maps."""
+    if not plan.joint_ids:
+        return np.zeros((0, 3))
+    return np.concatenate([np.column_stack([np.asarray(i, dtype=np.float64), np.asarray(c, dtype=np.float64).reshape(-1, 2)])
+                           for i, c in zip(plan.joint_ids, plan.coords)]).reshape(-1, 3)
 
 
 class LearningRate:

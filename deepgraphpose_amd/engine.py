@@ -938,3 +938,97 @@ def resize_frames(frames: torch.Tensor, new_size=None, crop_size=None, out: Opti
     _lib.check(lib.dgp_resize_crop_u8(_ptr(frames), B, H, W, rh, rw, box, _ptr(out), _ptr(plan_x), _ptr(plan_y), ksx, ksy, _stream(dev)),
                "dgp_resize_crop_u8")
     return out
+
+
+RESIZE_FILTERS = {"box": 4, "bilinear": 2, "bicubic": 3}         # Pillow's Image.BOX / BILINEAR / BICUBIC (include/dgp_hip.h, DGP_FILTER_*)
+
+
+def _filter_id(filter) -> int:
+    if filter in RESIZE_FILTERS:
+        return RESIZE_FILTERS[filter]
+    if filter in RESIZE_FILTERS.values():
+        return int(filter)
+    raise ValueError("resize filter must be one of %s, not %r" % ("|".join(RESIZE_FILTERS), filter))
+
+
+def resize_plan_f(in_size: int, out_size: int, filter) -> Tuple[int, np.ndarray, np.ndarray]:
+    """Pillow's tables of one axis for the BOX, BILINEAR or BICUBIC filter (dgp_resize_plan_f, host only), as resize_plan returns them."""
+    lib = _lib.load()
+    fid = _filter_id(filter)
+    ks = C.c_int32()
+    _lib.check(lib.dgp_resize_plan_size_f(int(in_size), int(out_size), fid, C.byref(ks)), "dgp_resize_plan_size_f")
+    bounds = np.empty((int(out_size), 2), np.int32)
+    coeffs = np.empty((int(out_size), ks.value), np.int32)
+    _lib.check(lib.dgp_resize_plan_f(int(in_size), int(out_size), fid, bounds.ctypes.data_as(C.c_void_p), coeffs.ctypes.data_as(C.c_void_p)),
+               "dgp_resize_plan_f")
+    return ks.value, bounds, coeffs
+
+
+def window_resize(image: torch.Tensor, window, out_hw, filter="box", mirror: bool = False) -> torch.Tensor:
+    """The inclusive window (x0, y0, x1, y1) of ONE device uint8 RGB image [H, W, 3] (None: the whole image), resampled to out_hw =
+    (rows, cols) with Pillow's `filter` ("box" | "bilinear" | "bicubic") and, with `mirror`, flipped left to right: what the step-0
+    loader's crop_image + imresize (+ np.fliplr) give (dlc_dataset.py), the bytes Pillow's.  The window is read in place.  One
+    dgp_window_resize_u8 launch on the current stream; the two tables are built on the host and uploaded in one small copy (samples
+    differ in size from one to the next, so they are not kept).  Returns uint8 [rows, cols, 3]."""
+    lib = _lib.load()
+    _need_cuda(image, torch.uint8, "image")
+    if image.dim() != 3 or image.shape[-1] != 3:
+        raise _lib.DgpError("window_resize: image must be [H, W, 3], got %s" % (tuple(image.shape),))
+    H, W = int(image.shape[0]), int(image.shape[1])
+    x0, y0, x1, y1 = (0, 0, W - 1, H - 1) if window is None else (int(v) for v in window)
+    rh, rw = int(out_hw[0]), int(out_hw[1])
+    if not (0 <= x0 <= x1 < W and 0 <= y0 <= y1 < H) or rh <= 0 or rw <= 0:
+        raise _lib.DgpError("window_resize: window %r / output %r do not fit a %d x %d image" % (window, out_hw, H, W))
+    fid = _filter_id(filter)
+    dev = image.device
+    ksx, bx, cx = resize_plan_f(x1 - x0 + 1, rw, fid)
+    ksy, by, cy = resize_plan_f(y1 - y0 + 1, rh, fid)
+    nx = bx.size + cx.size
+    plans = torch.from_numpy(np.concatenate([bx.ravel(), cx.ravel(), by.ravel(), cy.ravel()])).to(dev)
+    out = torch.empty((rh, rw, 3), dtype=torch.uint8, device=dev)
+    _lib.check(lib.dgp_window_resize_u8(_ptr(image), H, W, x0, y0, x1, y1, rh, rw, fid, 1 if mirror else 0, _ptr(out), _ptr(plans),
+                                        C.c_void_p(plans.data_ptr() + 4 * nx), ksx, ksy, _stream(dev)), "dgp_window_resize_u8")
+    return out
+
+
+def _target_out(given, shape, dev, name):
+    """an output of target_maps: None / False -> not computed, True -> allocated, a tensor -> filled in place"""
+    if given is None or given is False:
+        return None
+    if given is True:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    _need_cuda(given, torch.float32, name)
+    if tuple(given.shape) != tuple(shape) or given.device != dev:
+        raise _lib.DgpError("target_maps: %s must be %s on %s, got %s on %s" % (name, tuple(shape), dev, tuple(given.shape), given.device))
+    return given
+
+
+def target_maps(entries, offsets, n: int, H: int, W: int, nj: int, *, pos_dist_thresh: float, stride: float = 8.0, scale: float = 1.0,
+                locref_stdev: float = 7.2801, weigh_only_present_joints: bool = False, scmap=True, weights=True, lmap=True, lmask=True,
+                device=None):
+    """DLC's target maps of n frames on the device (dgp_target_maps; the host counterpart is dataset.compute_target_part_scoremap).
+    entries: float64 [k, 3] = (joint id, x, y) in the host function's person-then-joint order; offsets: int32 [n + 1], frame f owns
+    entries[offsets[f]:offsets[f + 1]].  -> (scmap [n, H, W, nj], weights [n, H, W, nj], lmap [n, H, W, 2 nj], lmask [n, H, W, 2 nj]),
+    fp32 device tensors written on the current stream: the host function's float64 values cast to fp32, every cell written.  Each of
+    the four keywords selects its output: True allocates it, a tensor of that shape is filled in place, None leaves it out (its place in
+    the result is None).  Bad entries or offsets raise before anything is launched."""
+    lib = _lib.load()
+    ent = np.ascontiguousarray(np.asarray(entries, dtype=np.float64).reshape(-1, 3))
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
+    n, H, W, nj = int(n), int(H), int(W), int(nj)
+    if off.size != n + 1 or n <= 0:
+        raise _lib.DgpError("target_maps: offsets must have n + 1 = %d values, got %d" % (n + 1, off.size))
+    if int(off[-1]) != ent.shape[0]:
+        raise _lib.DgpError("target_maps: offsets end at %d but there are %d entries" % (int(off[-1]), ent.shape[0]))
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    host = np.concatenate([ent.ravel().view(np.uint8), off.view(np.uint8)])      # one small copy: the doubles first (8-byte aligned)
+    packed = torch.from_numpy(host).to(dev)
+    outs = [_target_out(g, (n, H, W, c), dev, name) for g, c, name in
+            ((scmap, nj, "scmap"), (weights, nj, "weights"), (lmap, 2 * nj, "lmap"), (lmask, 2 * nj, "lmask"))]
+    _lib.check(lib.dgp_target_maps(_ptr(packed), C.c_void_p(packed.data_ptr() + ent.nbytes), ent.ctypes.data_as(C.c_void_p),
+                                   off.ctypes.data_as(C.c_void_p), n, H, W, nj, float(stride), float(pos_dist_thresh), float(scale),
+                                   float(locref_stdev), 1 if weigh_only_present_joints else 0, *(_ptr(t) for t in outs), _stream(dev)),
+               "dgp_target_maps")
+    return tuple(outs)

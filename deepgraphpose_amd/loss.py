@@ -116,10 +116,17 @@ def dgp_loss_prepare(nt: int, H: int, W: int, nj: int, batch: dict, hyper: DGPHy
     li = LossInputs()
     li.dev, li.shape = dev, (nt, H, W, nj)
     f32 = lambda a: np.asarray(a, dtype=np.float32)
-    lmap_h, lmask_h = f32(batch["locref_map"]), f32(batch["locref_mask"])
+    on_device = lambda t: isinstance(t, Staged) or (isinstance(t, torch.Tensor) and t.is_cuda)
+    maps_dev = {}                        # built on the device (engine.target_maps): used in place, left out of the packed upload
+    for name in ("locref_map", "locref_mask"):
+        if on_device(batch[name]):
+            maps_dev[name] = _on_current_stream(batch[name])
+            _need_cuda(maps_dev[name], torch.float32, name)
+    lmap_h, lmask_h = (maps_dev[k] if k in maps_dev else f32(batch[k]) for k in ("locref_map", "locref_mask"))
     for name, t in (("locref_map", lmap_h), ("locref_mask", lmask_h)):
         if vm_h.size and tuple(t.shape) != (nt, H, W, 2 * nj):
             raise ValueError("%s %s does not match the prediction grid %s" % (name, tuple(t.shape), (nt, H, W, 2 * nj)))
+    lmap_h, lmask_h = (np.zeros(0, np.float32) if k in maps_dev else t for k, t in (("locref_map", lmap_h), ("locref_mask", lmask_h)))
     S0 = f32(S0).reshape(-1, nj)
     nl = S0.shape[0]
     use_wt = hyper.wt > 0 and nt > 1 and batch.get("vector_field") is not None
@@ -147,6 +154,7 @@ def dgp_loss_prepare(nt: int, H: int, W: int, nj: int, batch: dict, hyper: DGPHy
         host += [np.ones(nt - 1, dtype=np.float32) * hyper.wt * mask]
     up = _upload_all(host, dev)          # one staging buffer, one asynchronous copy
     li.vm, li.hm, li.vt, li.targets, li.lmap, li.lmask, li.S0, li.ws, li.ws_max = up[:9]
+    li.lmap, li.lmask = maps_dev.get("locref_map", li.lmap), maps_dev.get("locref_mask", li.lmask)
     li.vf, li.wtb = (None, None)
     if use_wt:
         li.vf, li.wtb = (vf_dev, up[9]) if vf_dev is not None else (up[9], up[10])

@@ -34,10 +34,28 @@ from .. import config as dcfg
 from .. import dist as ddist
 from ..dataset import MultiDataset, coord2map
 from ..loss import DGPHyper
-from ..staged import _FrameUploader, _device_flow
+from ..staged import _FrameUploader, _ImageCache, _device_flow, _device_locref, _device_sample, _on_current_stream
 from .fitdgp_util import gen_batch
 
 PREFETCH_DEPTH = 2          # iterations of host batches built ahead on a background thread (0: inline); a measured setting, not a switch
+
+PREP_BACKENDS = ("auto", "host", "hip")
+PREP_STATS = {"backend": None}   # the sample-preparation backend of the last fit_* run ("host" | "hip"), like eval.RUN_STATS["prep_backend"]
+
+
+def resolve_prep_backend(backend: str = "auto", device=None) -> str:
+    """"host" | "hip" for fit_*(prep_backend=...): where a fit driver's samples are built -- crop, imresize and the DLC target maps of
+    fit_dlc, the locref maps of the DGP drivers.  "auto" follows flow_backend's rule: the host when OpenCV is importable (imresize then
+    runs cv2.INTER_AREA, the reference's own filter, which the device path does not restate), the HIP kernels otherwise -- when
+    `device`, the trainer's, is a GPU (None: only the name is checked, "auto" stays "auto")."""
+    if backend not in PREP_BACKENDS:
+        raise ValueError("prep backend must be one of %s, not %r" % (" | ".join(PREP_BACKENDS), backend))
+    if backend != "auto" or device is None:
+        return backend
+    import torch
+    from .fitdgp_util import _cv2_available
+    return "host" if _cv2_available() or torch.device(device).type != "cuda" else "hip"
+
 
 _VIDEO_EXT = ("avi", "mp4", "mov", "mkv")
 
@@ -285,13 +303,18 @@ def _fresh_heads(wts, depth, nj, seed=None):
 
 
 def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=100, maxiters=200000,
-            trainingsetindex=0):
+            trainingsetindex=0, prep_backend="auto"):
     """Run the DLC baseline trainer (step 0), DGP/models/fitdgp.py:53-254: one randomly scaled / cropped labeled
     image per iteration (PoseDataset), loss = sigmoid CE on binary target disks + locref Huber (pose_net.train),
     multi-step learning rate, MomentumOptimizer(0.9) without clipping; snapshots snapshot-step0-{it} and
     snapshot-step0-final--0.  `snapshot`: a 'snapshot-*' name inside the train folder, or anything else to start
-    from the ImageNet resnet_v1_<depth>.ckpt."""
+    from the ImageNet resnet_v1_<depth>.ckpt.
+    prep_backend: "host" | "hip" | "auto" (resolve_prep_backend).  "host": every sample is read, cropped, resized and its four target
+    maps are built by PoseDataset.next_batch, then uploaded.  "hip": the prefetch thread draws the sample's plan
+    (PoseDataset.plan_batch) and the pixels (engine.window_resize, from a device cache of the labeled images) and the maps
+    (engine.target_maps) are made on the device, bit for bit the host path's without OpenCV; the main thread uploads nothing."""
     import torch
+    prep_backend = resolve_prep_backend(prep_backend)
     from .. import weights_io
     from ..dlc_dataset import LearningRate, PoseDataset
     from ..train import Trainer
@@ -357,12 +380,22 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
     cumloss, partloss, locrefloss = 0.0, 0.0, 0.0
     print("Starting training....", flush=True)
     dev = trainer.device
+    prep_backend = resolve_prep_backend(prep_backend, dev)
+    PREP_STATS["backend"] = prep_backend
+    uploader = _make_uploader(trainer) if prep_backend == "hip" else None
+    cache = _ImageCache(dataset, dev, uploader) if prep_backend == "hip" else None
+
+    def own_sample():
+        if prep_backend != "hip":
+            return dataset.next_batch()
+        frames, maps = _device_sample(dataset, dataset.plan_batch(), cache, uploader, dev)
+        return dict(maps, inputs=frames)
 
     def next_sample(_i):                      # W samples per optimiser step: rank r trains on sample it * W + r of the common sequence
         batch = None
         for r in range(world):                # the other ranks' samples only advance the random streams (no image read, no target maps)
             if r == rank:
-                batch = dataset.next_batch()
+                batch = own_sample()
             else:
                 dataset.skip_batch()
         return batch
@@ -371,8 +404,8 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
     for it, batch in enumerate(_prefetched(next_sample, max_iter + 1)):      # image read / scale / targets one step ahead
         current_lr = lr_gen.get_lr(it * world)
         img = batch["inputs"]
-        trainer.set_input_size(img.shape[1], img.shape[2])
-        frames = torch.from_numpy(img).to(dev)
+        frames = _on_current_stream(img) if prep_backend == "hip" else torch.from_numpy(img).to(dev)
+        trainer.set_input_size(frames.shape[1], frames.shape[2])
         losses = trainer.forward_backward_dlc(
             frames, batch["part_score_targets"], batch["locref_targets"], batch["locref_mask"],
             part_score_weights=batch["part_score_weights"] if dlc_cfg.weigh_part_predictions else None,
@@ -421,11 +454,12 @@ def _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, h
 
 
 def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_frames, schedule, entry, progress, finished, step,
-           save_every, displayiters, debug="", flow_backend=None):
+           save_every, displayiters, debug="", flow_backend=None, prep_backend="host"):
     """The loop of both DGP drivers.  schedule() draws the run's entries, entry(data_batcher, e) -> (dataset_i, visible frames, hidden
     frames) of one of them, progress(...) prints a displayed iteration's lines, `finished` is the closing line.  Iteration `it` trains on
     entry _dp_index(it) and rank 0 saves every `save_every` iterations and after the last.  labeled_only: the objective is
-    total_loss_visible and the batch is the general one without hidden frames, frame pairs or flow."""
+    total_loss_visible and the batch is the general one without hidden frames, frame pairs or flow.  prep_backend "hip": the locref
+    maps are built on the device (_device_locref) and handed to the loss as Staged tensors instead of two host arrays."""
     from .. import weights_io
     from .session import Placeholder, TrainSession
     dgp_cfg, nj = data_batcher.dlc_config, data_batcher.nj
@@ -437,6 +471,8 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
     sess = TrainSession(trainer, loss.graph)
     saver = weights_io.Saver(max_to_keep=dgp_cfg.max_to_keep)     # fitdgp.py:401, 696
     uploader = _make_uploader(trainer)
+    prep_backend = resolve_prep_backend(prep_backend, trainer.device)
+    PREP_STATS["backend"] = prep_backend
     entries = schedule()
     n_sched = len(entries)
     maxiters = max(1, n_sched // world)          # data-parallel: W windows per optimiser step
@@ -454,7 +490,10 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
         if pipeline is not None and dgp_cfg.wt == 0 and len(vis_within) > 0:      # fitdgp.py:481-482, 778-779
             from ..augment import data_aug
             images, joint_loc = data_aug(images, vis_within, joint_loc, pipeline, dgp_cfg)
-        lmap, lmask = _locref_targets(joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
+        if prep_backend == "hip":                                     # (after data_aug, which moves joint_loc)
+            lmap, lmask = _device_locref(uploader, trainer.device, joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
+        else:
+            lmap, lmask = _locref_targets(joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
         vector_field, frames = None, None
         if dgp_cfg.wt > 0 and flow_backend == "hip":                  # temporal clique: flow magnitude on the device
             frames, vector_field = _device_flow(uploader, trainer.device, images)
@@ -493,9 +532,11 @@ def _labeled_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 
 
 def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, displayiters=5, maxiters=50000, ns=10,
-                        nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None):
+                        nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None, prep_backend="auto"):
     """Run DGP with labeled frames only (fitdgp.py:257-546): batch = one labeled frame, loss =
-    total_loss_visible.  `frame_sources` (new, optional) injects already-open frame sources per video."""
+    total_loss_visible.  `frame_sources` (new, optional) injects already-open frame sources per video.
+    prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built."""
+    prep_backend = resolve_prep_backend(prep_backend)
     hyper = dict(ws=0, ws_max=1.2, wt=0, wt_max=0, wn_visible=1, wn_hidden=0, gamma=1, gauss_len=1, lengthscale=1,
                  max_to_keep=5, batch_size=1, n_times_all_frames=100, lr=0.005, gm2=0, gm3=0, aug=aug)
     run = _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, hyper, "-step1-final--0",
@@ -510,7 +551,8 @@ def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, di
         return table[np.random.randint(0, table.shape[0], size=nepoch)]
 
     _train(*run, labeled_only=True, max_frames=1, schedule=schedule, entry=_labeled_entry, progress=_labeled_progress,
-           finished="Finished training {} iterations\n", step=step, save_every=saveiters, displayiters=displayiters)
+           finished="Finished training {} iterations\n", step=step, save_every=saveiters, displayiters=displayiters,
+           prep_backend=prep_backend)
     return None
 
 
@@ -538,12 +580,15 @@ def _window_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 
 def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000, displayiters=5, maxiters=200000, ns=10,
             nc=2048, n_max_frames=2000, gm2=0, gm3=0, nepoch=100, wt=0, aug=True, debug="", trainingsetindex=0,
-            frame_sources=None, flow_backend="auto"):
+            frame_sources=None, flow_backend="auto", prep_backend="auto"):
     """Run DGP (fitdgp.py:549-845): batches of `batch_size` consecutive frames of the selected windows, at least
     one labeled frame per batch, loss = total_loss (visible + hidden CE, locref, spatial clique; + the temporal clique when wt > 0).
     flow_backend (wt > 0): "cv2" | "hip" | "auto" as learn_wt's backend.  With "hip" the flow magnitude is computed on the device from
-    the batch's uploaded frames (engine.optical_flow) and handed to the loss as a device tensor: it never crosses to the host."""
+    the batch's uploaded frames (engine.optical_flow) and handed to the loss as a device tensor: it never crosses to the host.
+    prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built; with "hip" the two
+    [nt, H, W, 2 nj] maps are written on the device from the labeled frames' coordinates and never exist on the host."""
     from .fitdgp_util import resolve_flow_backend
+    prep_backend = resolve_prep_backend(prep_backend)
     flow_backend = resolve_flow_backend(flow_backend) if wt > 0 else None
     hyper = dict(ws=1000, ws_max=1.2, wt=wt, wt_max=0, wn_visible=5, wn_hidden=3, gamma=1, gauss_len=1, lengthscale=1,
                  max_to_keep=5, batch_size=batch_size, n_times_all_frames=nepoch, lr=0.005, gm2=gm2, gm3=gm3, aug=aug)
@@ -563,5 +608,5 @@ def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000,
 
     _train(*run, labeled_only=False, max_frames=batch_size + 1, schedule=schedule, entry=_window_entry, progress=_window_progress,
            finished="Finished {} iterations\n", step=step, save_every=max(int(saveiters / batch_size), 1), displayiters=displayiters,
-           debug=debug, flow_backend=flow_backend)
+           debug=debug, flow_backend=flow_backend, prep_backend=prep_backend)
     return None

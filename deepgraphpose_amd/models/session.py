@@ -97,7 +97,8 @@ class TrainSession:
                      visible_marker_in_targets=feed[ph["visible_marker_in_targets_pl"]])
         if ph["alpha_tf"] in feed:                 # the (row, col) grid: generated inside the kernels, checked here
             a = np.asarray(feed[ph["alpha_tf"]])
-            lm = np.asarray(batch["locref_map"])
+            lm = batch["locref_map"]               # (a Staged pair or a device tensor when the maps were built on the device)
+            lm = lm.tensor if isinstance(lm, Staged) else lm if isinstance(lm, torch.Tensor) else np.asarray(lm)
             if a.ndim != 3 or a.shape[0] != 2 or (lm.ndim == 4 and tuple(a.shape[1:]) != tuple(lm.shape[1:3])):
                 raise ValueError("alpha_tf must be [2, nx_out, ny_out]")
         hy = self.graph.hyper

@@ -170,7 +170,14 @@ class Trainer:
         frames = frames.contiguous()
         wsb, pred, loc = self._forward(frames)
         nt = frames.shape[0]
-        f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
+        from .staged import Staged, _on_current_stream
+
+        def f32(t):                          # a host array is uploaded here; a Staged pair or a device tensor (built by
+            if t is None:                    # engine.target_maps on the prefetch stream) is used in place, after its event
+                return None
+            if isinstance(t, Staged) or (isinstance(t, torch.Tensor) and t.is_cuda):
+                t = _on_current_stream(t)
+            return torch.as_tensor(t, dtype=torch.float32, device=self.device).contiguous()
         pt, pw, lt, lm = f32(part_score_targets), f32(part_score_weights), f32(locref_targets), f32(locref_mask)
         if tuple(pt.shape) != tuple(pred.shape) or (location_refinement and tuple(lt.shape) != tuple(loc.shape)):
             raise _lib.DgpError("target maps %s do not match the scoremap %s" % (tuple(pt.shape), tuple(pred.shape)))

@@ -495,6 +495,44 @@ int  dgp_resize_plan(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t
 int  dgp_resize_crop_u8(const uint8_t* src, int32_t B, int32_t H, int32_t W, int32_t RH, int32_t RW, const int32_t* box, uint8_t* dst,
                         const int32_t* d_plan_x, const int32_t* d_plan_y, int32_t ksize_x, int32_t ksize_y, void* stream);
 
+/* ---- The same resample with Pillow's other filters, over a window of one image (replaces crop_image + imresize (+ np.fliplr) of
+ * the step-0 sample loader, PET/dataset/pose_defaultdataset.py:160-190 with PIL's BOX below scale 1 and BILINEAR above).  Filter ids
+ * are Pillow's own constants.  Supports: BOX 0.5, BILINEAR 1, BICUBIC 2 (times filterscale); BOX is 1 on (-0.5, 0.5], BILINEAR is
+ * 1 - |x| on (-1, 1).  BOX and BILINEAR evaluate the filter at (x + xmin - center + 0.5) * (1.0 / filterscale), Pillow's order;
+ * BICUBIC keeps dgp_resize_plan's division, and its tables are dgp_resize_plan's integers. */
+enum { DGP_FILTER_BILINEAR = 2, DGP_FILTER_BICUBIC = 3, DGP_FILTER_BOX = 4 };
+/* Host only (no GPU): as dgp_resize_plan_size / dgp_resize_plan, for `filter`.  An unknown filter is DGP_ERR_INVALID. */
+int  dgp_resize_plan_size_f(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize);
+int  dgp_resize_plan_f(int32_t in_size, int32_t out_size, int32_t filter, int32_t* bounds, int32_t* coeffs);
+/* src: ONE device uint8 image [src_H][src_W][3].  The inclusive window src[y0 .. y1][x0 .. x1] (0 <= x0 <= x1 < src_W, same for y) is
+ * resampled to RH x RW with `filter`; mirror != 0 writes resized column c to column RW - 1 - c (np.fliplr after the resize).
+ * dst: device uint8 [RH][RW][3].  d_plan_x ((x1 - x0 + 1) -> RW) and d_plan_y ((y1 - y0 + 1) -> RH): dgp_resize_plan_f's tables of
+ * `filter`, laid out as for dgp_resize_crop_u8.  The window is addressed in place (origin + the image's row pitch): no copy is made,
+ * and no byte outside the window's rows and columns reaches the result -- the tables are clamped to the window, and the dword-staged
+ * bytes around a row segment are only ever multiplied by the zero padding of a table.  The LDS bound on the horizontal reduction is
+ * dgp_resize_crop_u8's (DGP_ERR_INVALID before the launch).  Integer arithmetic, no atomics: the bytes are Pillow's. */
+int  dgp_window_resize_u8(const uint8_t* src, int32_t src_H, int32_t src_W, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                          int32_t RH, int32_t RW, int32_t filter, int32_t mirror, uint8_t* dst, const int32_t* d_plan_x,
+                          const int32_t* d_plan_y, int32_t ksize_x, int32_t ksize_y, void* stream);
+
+/* ---- DLC target maps on the device (replaces compute_target_part_scoremap, PET/dataset/pose_defaultdataset.py:220-266, as called by
+ * PoseDataset.make_batch for fit_dlc and by coord2map, DGP/dataset.py:246-271, for the DGP drivers).
+ * entries: n_entries x (joint_id, x, y) doubles in the host function's person-then-joint order; offsets: int32 [n_frames + 1], frame f
+ * owns entries [offsets[f], offsets[f + 1]).  Both are given twice: d_* on the device (read by the kernel) and h_* on the host, the
+ * same values, checked before anything is launched: offsets[0] == 0 and non-decreasing, joint ids integral and in [0, nj), finite
+ * coordinates, positive H, W, nj, n_frames, stride and locref_stdev (DGP_ERR_INVALID otherwise).
+ * Outputs, fp32 on the device, any of them NULL: scmap [n][H][W][nj], weights [n][H][W][nj] (1 everywhere, or with
+ * weigh_only_present_joints 1 in the channels of the frame's entries and 0 elsewhere), lmap and lmask [n][H][W][2 nj].  EVERY cell of
+ * every given output is written (zeros included: no memset is needed, a frame without entries comes out zero).  A cell (y, x) takes
+ * joint j's target from the LAST entry of j whose window holds it: cx = rint((x_j - stride / 2) / stride), the window is
+ * [rint(max(cx - thr - 1, 0)), rint(min(cx + thr + 1, W - 1))] (skipped when empty), thr = pos_dist_thresh * scale, and the cell is
+ * inside when dx^2 + dy^2 <= thr^2 with dx = x_j - (x stride + stride / 2); lmap = d * (1.0 / locref_stdev).  Double arithmetic without
+ * contraction, cast to fp32 at the store: bit for bit the host function's values.  One thread per cell and joint group, no atomics. */
+int  dgp_target_maps(const double* d_entries, const int32_t* d_offsets, const double* h_entries, const int32_t* h_offsets,
+                     int32_t n_frames, int32_t H, int32_t W, int32_t nj, double stride, double pos_dist_thresh, double scale,
+                     double locref_stdev, int32_t weigh_only_present_joints, float* scmap, float* weights, float* lmap, float* lmask,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
