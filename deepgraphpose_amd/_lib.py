@@ -82,6 +82,7 @@ SYMBOLS = {
     "dgp_train_forward": (C.c_int, [_vp, _vp, _i32, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "dgp_train_backward": (C.c_int, [_vp, _i32, _vp, _sz, _vp, _vp, _vp]),
     "dgp_sgd_momentum_clip": (C.c_int, [_vp, _f32, _f32, _f32, C.POINTER(_f32), _vp]),
+    "dgp_adam_clip": (C.c_int, [_vp, _f32, _f32, _f32, _f32, _f32, C.POINTER(_f32), _vp]),
     "dgp_packed_weight_floats": (_sz, [_i32, _i32, _i32, _i32]),
     "dgp_pack_conv_weights": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp]),
     "dgp_conv2d": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1327,6 +1327,57 @@ __global__ void momentum_kernel(float* __restrict__ w, const float* __restrict__
     }
 }
 
+// tf.train.AdamOptimizer's dense update (ApplyAdam, fp32) behind tf.clip_by_global_norm, one stream over four arrays: per parameter it
+// reads w, g, m, v and writes w, m, v (28 bytes; sumsq_kernel read g once before: 32 in all).  16-byte accesses (hipMalloc'ed buffers),
+// the last n % 4 elements one by one.  pow_cur = {beta1^t, beta2^t} of THIS step (t = applied steps + 1), read by every workgroup;
+// pow_next is the other half of the ping-pong pair (nobody reads it now): thread 0 writes cur * beta into it, or cur itself when the
+// step is skipped -- the host flips the index per call either way and never learns whether the step was applied.
+__device__ __forceinline__ void adam_one(float& w, float g, float& m, float& v, float scale, float alpha, float omb1, float beta2, float omb2, float eps) {
+    const float gs = g * scale;
+    m += (gs - m) * omb1;                                     // m += (g - m) (1 - beta1)
+    // v += (g g - v) (1 - beta2), written as the convex combination it is: a second moment that overflowed to +inf (g g beyond fp32)
+    // stays +inf -- the step size stays 0 -- where the incremental form would turn it into inf - inf
+    v = beta2 * v + omb2 * (gs * gs);
+    w -= (m * alpha) / (sqrtf(v) + eps);                      // var -= (m alpha) / (sqrt(v) + eps), the grouping of TF's functor
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                   long long n, float lr, float beta1, float beta2, float eps, float clip,
+                                                   const double* __restrict__ sumsq, double* __restrict__ sumsq_next,
+                                                   const float* __restrict__ pow_cur, float* __restrict__ pow_next,
+                                                   float* __restrict__ gnorm_out, const int* __restrict__ skip) {
+    const float gn = (float)sqrt(*sumsq);
+    const float b1p = pow_cur[0], b2p = pow_cur[1];
+    const bool skipped = skip && *skip;                       // (see momentum_kernel)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *sumsq_next = 0.0;
+        if (gnorm_out) *gnorm_out = gn;
+        pow_next[0] = skipped ? b1p : b1p * beta1;
+        pow_next[1] = skipped ? b2p : b2p * beta2;
+    }
+    if (skipped) return;
+    const float scale = clip > 0.f ? clip / fmaxf(gn, clip) : 1.f;      // tf.clip_by_global_norm; clip <= 0: none
+    const float alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+    const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
+    const long long n4 = n >> 2;
+    float4* w4 = reinterpret_cast<float4*>(w);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float4 ww = w4[i], mm = m4[i], vv = v4[i];
+        const float4 gg = g4[i];
+        adam_one(ww.x, gg.x, mm.x, vv.x, scale, alpha, omb1, beta2, omb2, eps);
+        adam_one(ww.y, gg.y, mm.y, vv.y, scale, alpha, omb1, beta2, omb2, eps);
+        adam_one(ww.z, gg.z, mm.z, vv.z, scale, alpha, omb1, beta2, omb2, eps);
+        adam_one(ww.w, gg.w, mm.w, vv.w, scale, alpha, omb1, beta2, omb2, eps);
+        m4[i] = mm; v4[i] = vv; w4[i] = ww;
+    }
+    for (long long i = 4 * n4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        adam_one(w[i], g[i], m[i], v[i], scale, alpha, omb1, beta2, omb2, eps);
+}
+
 __global__ void step_status_kernel(const float* __restrict__ losses, int n_losses, const float* __restrict__ gnorm, const int* __restrict__ flag,
                                    float* __restrict__ host) {
     const int t = threadIdx.x;
@@ -1640,6 +1691,10 @@ struct dgp_trainer {
     double* d_sumsq = nullptr;        // TWO accumulators used in turn: the optimiser's kernel zeroes the other one for the next step (no fill launch)
     int sumsq_k = 0;
     float* d_gnorm = nullptr;
+    // Adam's slots (dgp_adam_clip): allocated by the first Adam step or the first upload into them, so a momentum-only trainer holds none.
+    // d_adam_pow: {beta1_power, beta2_power} twice, used in turn like d_sumsq -- pair adam_pow_k is current, the kernel writes the other
+    float *adam_m = nullptr, *adam_v = nullptr, *d_adam_pow = nullptr;
+    int adam_pow_k = 0;
     float* h_status = nullptr;        // pinned, device-visible: dgp_trainer_step_status' kernel writes [8 losses | gnorm | flag] straight into it
     float* d_rng_pool = nullptr;      // activation / gradient range slots (RANGE_POOL arrays), zeroed per pass
     float* d_rng_prev = nullptr;      // ... as the previous step left them (copied before the zeroing)
@@ -1687,7 +1742,7 @@ struct dgp_trainer {
         for (void* q : {(void*)d_rng_pool, (void*)d_rng_prev, (void*)d_fast_flag, (void*)d_wrng, d_pack_table, d_fin_table, d_h3_table, d_h1_table, (void*)d_stem_rows, d_stem_cells, (void*)d_hmT, (void*)d_hm_rng, d_hmT_h1}) if (q) (void)hipFree(q);
         for (auto& g : groups) if (g.ev) (void)hipEventDestroy(g.ev);
         for (auto& t : tl) { if (t.d_wT) (void)hipFree(t.d_wT); if (t.d_wTh3) (void)hipFree(t.d_wTh3); if (t.d_wTh1) (void)hipFree(t.d_wTh1); }
-        for (void* p : {(void*)params, (void*)grads, (void*)mom, (void*)stats, (void*)d_sumsq, (void*)d_gnorm})
+        for (void* p : {(void*)params, (void*)grads, (void*)mom, (void*)stats, (void*)d_sumsq, (void*)d_gnorm, (void*)adam_m, (void*)adam_v, (void*)d_adam_pow})
             if (p) (void)hipFree(p);
         if (h_status) (void)hipHostFree(h_status);
     }
@@ -2263,10 +2318,12 @@ int dgp_trainer_tensor_info(const dgp_trainer* tr, int32_t i, char* name, int32_
     return DGP_OK;
 }
 
-/* which: 0 params, 1 grads, 2 momentum, 3 frozen statistics */
+/* which: 0 params, 1 grads, 2 momentum, 3 frozen statistics; 5 / 6 / 7: Adam's m, v and {beta1_power, beta2_power} -- NULL until allocated */
 float* dgp_trainer_buffer(dgp_trainer* tr, int32_t which) {
     if (!tr) return nullptr;
     switch (which) {
+        case 5: return tr->adam_m; case 6: return tr->adam_v;
+        case 7: return tr->d_adam_pow ? tr->d_adam_pow + 2 * tr->adam_pow_k : nullptr;
         case 0: return tr->params; case 1: return tr->grads; case 2: return tr->mom; case 3: return tr->stats;
         case 4: return reinterpret_cast<float*>(tr->d_fast_flag);      // ONE int32: != 0 when a 16-bit pass left its predicted ranges (data-parallel: all-reduce MAX)
     }
@@ -3409,16 +3466,41 @@ int dgp_conv2d_dgrad(const dgp_conv_desc* d, const float* dy, const float* w_hwi
     return DGP_OK;
 }
 
-/* host <-> device copies of a slice of one of the flat buffers (which: 0 params, 1 grads, 2 momentum, 3 stats) */
+// Adam's slots on first use: m = v = 0, both power pairs {beta1, beta2} (TF's non-slot variables start there)
+static int adam_alloc(dgp_trainer* tr, float beta1, float beta2) {
+    if (tr->adam_m) return DGP_OK;
+    const size_t nb = (size_t)tr->n_train * sizeof(float);
+    float *m = nullptr, *v = nullptr, *p = nullptr;
+    const float pw[4] = {beta1, beta2, beta1, beta2};
+    if (hipMalloc(&m, nb) != hipSuccess || hipMalloc(&v, nb) != hipSuccess || hipMalloc(&p, sizeof(pw)) != hipSuccess ||
+        hipMemset(m, 0, nb) != hipSuccess || hipMemset(v, 0, nb) != hipSuccess ||
+        hipMemcpy(p, pw, sizeof(pw), hipMemcpyHostToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {                 // (once: the fills are done before a kernel on any stream reads the slots)
+        for (float* q : {m, v, p}) if (q) (void)hipFree(q);
+        return fail(DGP_ERR_HIP, "dgp_adam_clip: hipMalloc of the Adam slots failed");
+    }
+    tr->adam_m = m; tr->adam_v = v; tr->d_adam_pow = p; tr->adam_pow_k = 0;
+    return DGP_OK;
+}
+
+// floats behind dgp_trainer_buffer(tr, 5 .. 7): a copy must stay inside them
+static long long buffer_floats(const dgp_trainer* tr, int32_t which) { return which == 7 ? 2 : tr->n_train; }
+
+/* host <-> device copies of a slice of one of the flat buffers (which: 0 params, 1 grads, 2 momentum, 3 stats, 5 / 6 Adam's m / v, 7 its two
+ * powers; an upload into 5 - 7 allocates Adam's slots, a download from them before that fails) */
 int dgp_trainer_upload(dgp_trainer* tr, int32_t which, int64_t offset, const float* host, int64_t n) {
+    if (tr && which >= 5 && which <= 7 && adam_alloc(tr, 0.9f, 0.999f) != DGP_OK) return DGP_ERR_HIP;
     float* b = dgp_trainer_buffer(tr, which);
     if (!b || !host || offset < 0 || n < 0) return fail(DGP_ERR_INVALID, "dgp_trainer_upload: bad argument");
+    if (which >= 5 && offset + n > buffer_floats(tr, which)) return fail(DGP_ERR_INVALID, "dgp_trainer_upload: past the end of the buffer");
+    if (which >= 5) TRY_HIP(hipDeviceSynchronize());          // (the slots may be in use by an optimiser step still in flight)
     TRY_HIP(hipMemcpy(b + offset, host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     return DGP_OK;
 }
 int dgp_trainer_download(dgp_trainer* tr, int32_t which, int64_t offset, float* host, int64_t n) {
     float* b = dgp_trainer_buffer(tr, which);
     if (!b || !host || offset < 0 || n < 0) return fail(DGP_ERR_INVALID, "dgp_trainer_download: bad argument");
+    if (which >= 5 && offset + n > buffer_floats(tr, which)) return fail(DGP_ERR_INVALID, "dgp_trainer_download: past the end of the buffer");
     TRY_HIP(hipDeviceSynchronize());
     TRY_HIP(hipMemcpy(host, b + offset, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return DGP_OK;
@@ -3434,6 +3516,30 @@ int dgp_sgd_momentum_clip(dgp_trainer* tr, float lr, float momentum, float clip_
     hipLaunchKernelGGL(sumsq_kernel, dim3(sumsq_grid), dim3(256), 0, s, tr->grads, tr->n_train, tr->d_sumsq + k);
     hipLaunchKernelGGL(momentum_kernel, dim3(grid_for(tr->n_train)), dim3(256), 0, s, tr->params, tr->grads, tr->mom, tr->n_train,
                        lr, momentum, clip_norm, tr->d_sumsq + k, tr->d_sumsq + (k ^ 1), tr->d_gnorm, tr->fwd_fast ? tr->d_fast_flag : nullptr);
+    TRY_HIP(hipGetLastError());
+    if (gnorm_host_or_null) {
+        TRY_HIP(hipStreamSynchronize(s));
+        TRY_HIP(hipMemcpy(gnorm_host_or_null, tr->d_gnorm, sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return DGP_OK;
+}
+
+/* tf.clip_by_global_norm(clip_norm) + tf.train.AdamOptimizer's dense update; same contract as dgp_sgd_momentum_clip.  The powers advance
+ * on the device, and only when the step is applied (adam_kernel) */
+int dgp_adam_clip(dgp_trainer* tr, float lr, float beta1, float beta2, float eps, float clip_norm, float* gnorm_host_or_null, void* stream) {
+    if (!tr) return fail(DGP_ERR_INVALID, "dgp_adam_clip: null");
+    if (adam_alloc(tr, beta1, beta2) != DGP_OK) return DGP_ERR_HIP;
+    hipStream_t s = (hipStream_t)stream;
+    const int k = tr->sumsq_k, pk = tr->adam_pow_k;
+    tr->sumsq_k ^= 1;
+    tr->adam_pow_k ^= 1;
+    const int sumsq_grid = grid_for(tr->n_train) < 768 ? grid_for(tr->n_train) : 768;      // (see dgp_sgd_momentum_clip)
+    hipLaunchKernelGGL(sumsq_kernel, dim3(sumsq_grid), dim3(256), 0, s, tr->grads, tr->n_train, tr->d_sumsq + k);
+    // a grid-stride stream: 2 048 workgroups of 256 (eight per CU), each thread four parameters per trip
+    const int grid = grid_for((tr->n_train + 3) / 4) < 2048 ? grid_for((tr->n_train + 3) / 4) : 2048;
+    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, s, tr->params, tr->grads, tr->adam_m, tr->adam_v, tr->n_train,
+                       lr, beta1, beta2, eps, clip_norm, tr->d_sumsq + k, tr->d_sumsq + (k ^ 1), tr->d_adam_pow + 2 * pk,
+                       tr->d_adam_pow + 2 * (pk ^ 1), tr->d_gnorm, tr->fwd_fast ? tr->d_fast_flag : nullptr);
     TRY_HIP(hipGetLastError());
     if (gnorm_host_or_null) {
         TRY_HIP(hipStreamSynchronize(s));

@@ -39,6 +39,10 @@ class DGPHyper:
     locref_huber_loss: bool = True
     momentum: float = 0.9
     clip_norm: float = 10.0
+    optimizer: str = "sgd"          # "sgd": MomentumOptimizer(lr, momentum); "adam": AdamOptimizer(lr, beta1, beta2, adam_eps) (PET/train.py:94-113)
+    beta1: float = 0.9
+    beta2: float = 0.999
+    adam_eps: float = 1e-8
 
 
 class _PackedUpload:

@@ -57,6 +57,39 @@ def resolve_prep_backend(backend: str = "auto", device=None) -> str:
     return "host" if _cv2_available() or torch.device(device).type != "cuda" else "hip"
 
 
+OPTIMIZERS = ("sgd", "adam")
+
+
+def resolve_optimizer(optimizer=None, configured="sgd") -> str:
+    """The optimiser of a fit driver: `optimizer`, or pose_cfg.yaml's `optimizer` key when None (PET/train.py:94-113, get_optimizer):
+    "sgd" = MomentumOptimizer(lr, 0.9), "adam" = AdamOptimizer(lr); anything else is the reference's ValueError."""
+    name = configured if optimizer is None else optimizer
+    if name not in OPTIMIZERS:
+        raise ValueError("unknown optimizer {}".format(name))
+    return name
+
+
+_STATE_KEYS = {"sgd": lambda k: k.endswith("/Momentum"),
+               "adam": lambda k: k.endswith(("/Adam", "/Adam_1")) or k in ("beta1_power", "beta2_power")}
+
+
+def _restore_optimizer_state(trainer, init_weights, optimizer):
+    """keep_optimizer_state: when the snapshot a run starts from holds the state of the optimiser it is about to use, put it back"""
+    from .. import weights_io
+    state = {k: v for k, v in weights_io.load_optimizer_state(init_weights).items() if _STATE_KEYS[optimizer](k)}
+    if state:
+        trainer.load_optimizer_state(state)
+        print("Restored the {} optimizer state ({} tensors) from {}".format(optimizer, len(state), init_weights), flush=True)
+
+
+def _snapshot_tensors(trainer, keep_optimizer_state):
+    """What a snapshot holds: the model variables, and with keep_optimizer_state the optimiser's under the names tf.train.Saver gives them"""
+    w = trainer.get_weights()
+    if keep_optimizer_state:
+        w.update(trainer.get_optimizer_state())
+    return w
+
+
 _VIDEO_EXT = ("avi", "mp4", "mov", "mkv")
 
 
@@ -186,12 +219,12 @@ def _locref_targets(joint_loc, nt, vis_within, nx_out, ny_out, nj, dgp_cfg):
     return lmap, lmask
 
 
-def _save(saver, trainer, prefix, step, it, final, debug=""):
+def _save(saver, trainer, prefix, step, it, final, debug="", keep_optimizer_state=False):
     """The reference's three Saver.save calls (fitdgp.py:535-540, 832-839): `<prefix>-step{k}-` at global_step it and 0, and
     `<prefix>-step{k}-final-` at 0 after the last iteration."""
     if ddist.data_parallel() and dist.get_rank() != 0:      # every rank holds the same weights: one writer
         return
-    w = trainer.get_weights()
+    w = _snapshot_tensors(trainer, keep_optimizer_state)
     model_name = prefix + "-step" + str(step) + debug + "-"
     saver.save(w, model_name, global_step=it)
     saver.save(w, model_name, global_step=0)
@@ -303,7 +336,7 @@ def _fresh_heads(wts, depth, nj, seed=None):
 
 
 def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=100, maxiters=200000,
-            trainingsetindex=0, prep_backend="auto"):
+            trainingsetindex=0, prep_backend="auto", optimizer=None, keep_optimizer_state=False):
     """Run the DLC baseline trainer (step 0), DGP/models/fitdgp.py:53-254: one randomly scaled / cropped labeled
     image per iteration (PoseDataset), loss = sigmoid CE on binary target disks + locref Huber (pose_net.train),
     multi-step learning rate, MomentumOptimizer(0.9) without clipping; snapshots snapshot-step0-{it} and
@@ -312,7 +345,12 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
     prep_backend: "host" | "hip" | "auto" (resolve_prep_backend).  "host": every sample is read, cropped, resized and its four target
     maps are built by PoseDataset.next_batch, then uploaded.  "hip": the prefetch thread draws the sample's plan
     (PoseDataset.plan_batch) and the pixels (engine.window_resize, from a device cache of the labeled images) and the maps
-    (engine.target_maps) are made on the device, bit for bit the host path's without OpenCV; the main thread uploads nothing."""
+    (engine.target_maps) are made on the device, bit for bit the host path's without OpenCV; the main thread uploads nothing.
+    optimizer: None (pose_cfg.yaml's `optimizer`, default "sgd") | "sgd" | "adam" (resolve_optimizer): MomentumOptimizer(lr, 0.9) or
+    AdamOptimizer(lr) with TF's defaults, neither with clipping (PET/train.py:94-113).
+    keep_optimizer_state: snapshots also hold the optimiser's state (`<var>/Momentum`, or `<var>/Adam`, `<var>/Adam_1`, beta1_power,
+    beta2_power, as tf.train.Saver names them), and a run that starts from a snapshot holding the state of its optimiser restores it.
+    Default: snapshots hold the model variables alone and every run starts from zero state."""
     import torch
     prep_backend = resolve_prep_backend(prep_backend)
     from .. import weights_io
@@ -350,8 +388,7 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
         raise ValueError("fit_dlc: batch_size must be 1 (every sample has its own size)")
     if dlc_cfg.intermediate_supervision:
         raise NotImplementedError("intermediate_supervision is off in every DGP configuration and is not built")
-    if dlc_cfg.optimizer != "sgd":
-        raise ValueError("unknown optimizer {}".format(dlc_cfg.optimizer))
+    optimizer = resolve_optimizer(optimizer, dlc_cfg.optimizer)
 
     dataset = PoseDataset(dlc_cfg)
     wts = weights_io.load_weights(init_weights)
@@ -365,6 +402,8 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
     wts = _fresh_heads(wts, depth, nj)
     trainer = Trainer(depth, nj, 64, 64, max_frames=1, device=local_rank)
     trainer.load_weights(wts)
+    if keep_optimizer_state and "snapshot" in Path(init_weights).stem:
+        _restore_optimizer_state(trainer, init_weights, optimizer)
 
     display_iters = max(1, int(dlc_cfg.get("display_iters", 1000) if displayiters is None else displayiters))
     save_iters = max(1, int(dlc_cfg.get("save_iters", 50000) if saveiters is None else saveiters))
@@ -413,7 +452,7 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
             location_refinement=dlc_cfg.location_refinement)
         if world > 1:
             trainer.allreduce_gradients()         # mean gradient over the ranks (RCCL): replicas stay bit-identical
-        trainer.apply_gradients(current_lr, 0.9, clip_norm=0.0)  # MomentumOptimizer, no clipping (train.py:94-113)
+        trainer.apply_gradients(current_lr, 0.9, clip_norm=0.0, optimizer=optimizer)  # Momentum / Adam, no clipping (train.py:94-113)
 
         partloss += losses["part_loss"]
         if dlc_cfg.location_refinement:
@@ -427,7 +466,7 @@ def fit_dlc(snapshot, dlcpath, shuffle=1, step=0, saveiters=1000, displayiters=1
             lrf.write("iteration: {}, loss: {}, scmap loss: {}, locref loss: {}, lr: {}\n".format(*vals))
             lrf.flush()
         if rank == 0 and ((it % save_iters == 0 and it != 0) or it == max_iter):      # fitdgp.py:237-245
-            w = trainer.get_weights()
+            w = _snapshot_tensors(trainer, keep_optimizer_state)
             saver.save(w, dlc_cfg.snapshot_prefix + "-step" + str(step) + "-", global_step=it)
             if it == max_iter:
                 saver.save(w, dlc_cfg.snapshot_prefix + "-step" + str(step) + "-final-", global_step=0)
@@ -454,12 +493,13 @@ def _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, h
 
 
 def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_frames, schedule, entry, progress, finished, step,
-           save_every, displayiters, debug="", flow_backend=None, prep_backend="host"):
+           save_every, displayiters, debug="", flow_backend=None, prep_backend="host", optimizer="sgd", keep_optimizer_state=False):
     """The loop of both DGP drivers.  schedule() draws the run's entries, entry(data_batcher, e) -> (dataset_i, visible frames, hidden
     frames) of one of them, progress(...) prints a displayed iteration's lines, `finished` is the closing line.  Iteration `it` trains on
     entry _dp_index(it) and rank 0 saves every `save_every` iterations and after the last.  labeled_only: the objective is
     total_loss_visible and the batch is the general one without hidden frames, frame pairs or flow.  prep_backend "hip": the locref
-    maps are built on the device (_device_locref) and handed to the loss as Staged tensors instead of two host arrays."""
+    maps are built on the device (_device_locref) and handed to the loss as Staged tensors instead of two host arrays.  optimizer: "sgd"
+    (the reference's MomentumOptimizer) | "adam", both behind clip_by_global_norm(10); keep_optimizer_state as in fit_dlc."""
     from .. import weights_io
     from .session import Placeholder, TrainSession
     dgp_cfg, nj = data_batcher.dlc_config, data_batcher.nj
@@ -467,7 +507,10 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
     pipeline = _augment(dgp_cfg)                 # before the expensive setup: a broken augmentation stack fails here
     trainer = _make_trainer(data_batcher, init_weights, max_frames=max_frames, device=local_rank)
     learning_rate = Placeholder("learning_rate")
-    train_op = loss.graph.minimize(total_loss_visible if labeled_only else total_loss, learning_rate)     # fitdgp.py:412-418, 708-713
+    if keep_optimizer_state:
+        _restore_optimizer_state(trainer, init_weights, optimizer)
+    train_op = loss.graph.minimize(total_loss_visible if labeled_only else total_loss, learning_rate,      # fitdgp.py:412-418, 708-713
+                                   optimizer=optimizer)
     sess = TrainSession(trainer, loss.graph)
     saver = weights_io.Saver(max_to_keep=dgp_cfg.max_to_keep)     # fitdgp.py:401, 696
     uploader = _make_uploader(trainer)
@@ -515,7 +558,7 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
             print("\nIteration {}/{}".format(it, maxiters))
             progress(dataset_i, vis_b, hid_b, t0, loss_eval)
         if (it % save_every == 0) or (it + 1) == maxiters:
-            _save(saver, trainer, dgp_cfg.snapshot_prefix, step, it, (it + 1) == maxiters, debug)
+            _save(saver, trainer, dgp_cfg.snapshot_prefix, step, it, (it + 1) == maxiters, debug, keep_optimizer_state)
     print(finished.format(it), flush=True)
     print("\n\n TOTAL TIME ELAPSED: ", time.time() - t_start)
 
@@ -532,11 +575,15 @@ def _labeled_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 
 
 def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, displayiters=5, maxiters=50000, ns=10,
-                        nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None, prep_backend="auto"):
+                        nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None, prep_backend="auto", optimizer="sgd",
+                        keep_optimizer_state=False):
     """Run DGP with labeled frames only (fitdgp.py:257-546): batch = one labeled frame, loss =
     total_loss_visible.  `frame_sources` (new, optional) injects already-open frame sources per video.
-    prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built."""
+    prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built.
+    optimizer: "sgd", the reference's hard-coded MomentumOptimizer(lr, 0.9), or "adam", AdamOptimizer(lr); both on gradients clipped to a
+    global norm of 10.  keep_optimizer_state: see fit_dlc."""
     prep_backend = resolve_prep_backend(prep_backend)
+    optimizer = resolve_optimizer(optimizer)
     hyper = dict(ws=0, ws_max=1.2, wt=0, wt_max=0, wn_visible=1, wn_hidden=0, gamma=1, gauss_len=1, lengthscale=1,
                  max_to_keep=5, batch_size=1, n_times_all_frames=100, lr=0.005, gm2=0, gm3=0, aug=aug)
     run = _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, hyper, "-step1-final--0",
@@ -552,7 +599,7 @@ def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, di
 
     _train(*run, labeled_only=True, max_frames=1, schedule=schedule, entry=_labeled_entry, progress=_labeled_progress,
            finished="Finished training {} iterations\n", step=step, save_every=saveiters, displayiters=displayiters,
-           prep_backend=prep_backend)
+           prep_backend=prep_backend, optimizer=optimizer, keep_optimizer_state=keep_optimizer_state)
     return None
 
 
@@ -580,14 +627,16 @@ def _window_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 
 def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000, displayiters=5, maxiters=200000, ns=10,
             nc=2048, n_max_frames=2000, gm2=0, gm3=0, nepoch=100, wt=0, aug=True, debug="", trainingsetindex=0,
-            frame_sources=None, flow_backend="auto", prep_backend="auto"):
+            frame_sources=None, flow_backend="auto", prep_backend="auto", optimizer="sgd", keep_optimizer_state=False):
     """Run DGP (fitdgp.py:549-845): batches of `batch_size` consecutive frames of the selected windows, at least
     one labeled frame per batch, loss = total_loss (visible + hidden CE, locref, spatial clique; + the temporal clique when wt > 0).
     flow_backend (wt > 0): "cv2" | "hip" | "auto" as learn_wt's backend.  With "hip" the flow magnitude is computed on the device from
     the batch's uploaded frames (engine.optical_flow) and handed to the loss as a device tensor: it never crosses to the host.
     prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built; with "hip" the two
-    [nt, H, W, 2 nj] maps are written on the device from the labeled frames' coordinates and never exist on the host."""
+    [nt, H, W, 2 nj] maps are written on the device from the labeled frames' coordinates and never exist on the host.
+    optimizer / keep_optimizer_state: as in fit_dgp_labeledonly."""
     from .fitdgp_util import resolve_flow_backend
+    optimizer = resolve_optimizer(optimizer)
     prep_backend = resolve_prep_backend(prep_backend)
     flow_backend = resolve_flow_backend(flow_backend) if wt > 0 else None
     hyper = dict(ws=1000, ws_max=1.2, wt=wt, wt_max=0, wn_visible=5, wn_hidden=3, gamma=1, gauss_len=1, lengthscale=1,
@@ -608,5 +657,6 @@ def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000,
 
     _train(*run, labeled_only=False, max_frames=batch_size + 1, schedule=schedule, entry=_window_entry, progress=_window_progress,
            finished="Finished {} iterations\n", step=step, save_every=max(int(saveiters / batch_size), 1), displayiters=displayiters,
-           debug=debug, flow_backend=flow_backend, prep_backend=prep_backend)
+           debug=debug, flow_backend=flow_backend, prep_backend=prep_backend, optimizer=optimizer,
+           keep_optimizer_state=keep_optimizer_state)
     return None

@@ -46,9 +46,9 @@ class LossDict(dict):
 
 
 class TrainOp:
-    def __init__(self, graph, objective: LossTensor, learning_rate, momentum, clip_norm):
+    def __init__(self, graph, objective: LossTensor, learning_rate, momentum, clip_norm, optimizer="sgd"):
         self.graph, self.objective, self.learning_rate = graph, objective, learning_rate
-        self.momentum, self.clip_norm = momentum, clip_norm
+        self.momentum, self.clip_norm, self.optimizer = momentum, clip_norm, optimizer
 
 
 class LossGraph:
@@ -63,12 +63,16 @@ class LossGraph:
         self.total_loss = self.loss["total_loss"]
         self.total_loss_visible = LossTensor("total_loss_visible", self)
 
-    def minimize(self, objective: LossTensor, learning_rate, momentum: float = 0.9, clip_norm: float = 10.0) -> TrainOp:
+    def minimize(self, objective: LossTensor, learning_rate, momentum: float = 0.9, clip_norm: float = 10.0,
+                 optimizer: str = "sgd") -> TrainOp:
         """MomentumOptimizer(learning_rate, 0.9) on clip_by_global_norm(gradients, 10) of `objective` w.r.t. every trainable
-        (fitdgp.py:708-713; :414-418 for total_loss_visible).  learning_rate: a float or a Placeholder fed at run time."""
+        (fitdgp.py:708-713; :414-418 for total_loss_visible).  learning_rate: a float or a Placeholder fed at run time.
+        optimizer "adam": AdamOptimizer(learning_rate) with TF's defaults on the same clipped gradients (PET/train.py:99-100)."""
         if objective.name not in ("total_loss", "total_loss_visible"):
             raise ValueError("only total_loss / total_loss_visible can be minimised (fitdgp.py:416, 710)")
-        return TrainOp(self, objective, learning_rate, momentum, clip_norm)
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError("unknown optimizer {}".format(optimizer))
+        return TrainOp(self, objective, learning_rate, momentum, clip_norm, optimizer)
 
 
 class TrainSession:
@@ -132,7 +136,7 @@ class TrainSession:
                 lr = feed_dict[lr]
             if ddist.data_parallel():
                 tr.allreduce_gradients()
-            losses["grad_norm"] = tr.apply_gradients(float(lr), op.momentum, op.clip_norm)
+            losses["grad_norm"] = tr.apply_gradients(float(lr), op.momentum, op.clip_norm, optimizer=op.optimizer)
         out = []
         for f in fl:
             if isinstance(f, TrainOp):

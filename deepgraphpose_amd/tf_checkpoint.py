@@ -431,13 +431,21 @@ def is_tf_checkpoint(path: str) -> bool:
     return os.path.isfile(path + ".index") or (os.path.isfile(path) and _is_table(path))
 
 
-def load_checkpoint(path: str) -> Dict[str, np.ndarray]:
-    """V2 prefix (has <path>.index) or V1 file -> {TF variable name: fp32 array}.  Optimiser slots
-    (".../Momentum") and non-float tensors are dropped."""
+SLOT_SUFFIXES = ("/Momentum", "/Adam", "/Adam_1")       # the slot variables of MomentumOptimizer and AdamOptimizer
+SLOT_SCALARS = ("beta1_power", "beta2_power")            # AdamOptimizer's non-slot variables
+
+
+def is_optimizer_entry(name: str) -> bool:
+    return name.endswith(SLOT_SUFFIXES) or name in SLOT_SCALARS
+
+
+def load_checkpoint(path: str, slots: bool = False) -> Dict[str, np.ndarray]:
+    """V2 prefix (has <path>.index) or V1 file -> {TF variable name: fp32 array}.  Non-float tensors are dropped, and so is the
+    optimiser's state (".../Momentum", ".../Adam", ".../Adam_1", the scalars beta1_power / beta2_power) unless slots=True."""
     if os.path.isfile(path + ".index"):
         t = read_v2(path)
     elif os.path.isfile(path):
         t = read_v1(path)
     else:
         raise FileNotFoundError(path)
-    return {k: v for k, v in t.items() if not k.endswith("/Momentum") and not k.endswith("/Adam") and not k.endswith("/Adam_1")}
+    return t if slots else {k: v for k, v in t.items() if not is_optimizer_entry(k)}

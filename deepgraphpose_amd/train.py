@@ -45,6 +45,7 @@ class Trainer:
         self.fast_redos = 0
         self.fast_passes = 0
         self._comm_stream = None
+        self._ran_sgd = False                    # a momentum step has run (or its slots were loaded): get_optimizer_state reports them
         if tier is not None:
             self.set_tier(tier)
 
@@ -288,17 +289,85 @@ class Trainer:
             flat.mul_(1.0 / world)
         torch.cuda.current_stream(self.device).wait_stream(cs)         # the optimiser's kernels run behind the averaged gradients
 
-    def apply_gradients(self, lr: float, momentum: float = 0.9, clip_norm: float = 10.0) -> float:
+    def _enqueue_update(self, optimizer: str, lr, momentum, clip_norm, beta1, beta2, eps, gnorm=None):
+        """The optimiser's kernels behind the gradients on the current stream.  gnorm: a c_float to read the norm into (synchronises).
+
+        Data-parallel: nothing of the optimiser goes on the wire.  Either update is a deterministic function of the averaged gradient and of
+        state that is identical on every rank (momentum; Adam's m, v and powers), so the replicas stay bit-identical."""
+        out = C.byref(gnorm) if gnorm is not None else None
+        if optimizer == "sgd":
+            _lib.check(self.lib.dgp_sgd_momentum_clip(self._t, lr, momentum, clip_norm, out, _stream(self.device)), "dgp_sgd_momentum_clip")
+            self._ran_sgd = True
+        elif optimizer == "adam":
+            _lib.check(self.lib.dgp_adam_clip(self._t, lr, beta1, beta2, eps, clip_norm, out, _stream(self.device)), "dgp_adam_clip")
+        else:
+            raise ValueError("unknown optimizer {}".format(optimizer))
+
+    def apply_gradients(self, lr: float, momentum: float = 0.9, clip_norm: float = 10.0, optimizer: str = "sgd", beta1: float = 0.9,
+                        beta2: float = 0.999, eps: float = 1e-8) -> float:
+        """clip_by_global_norm(clip_norm) (<= 0: none), then optimizer "sgd": MomentumOptimizer(lr, momentum), or "adam":
+        AdamOptimizer(lr, beta1, beta2, eps) (csrc/dgp_train.hip: momentum_kernel / adam_kernel).  -> the gradient norm before clipping."""
         g = C.c_float()
-        _lib.check(self.lib.dgp_sgd_momentum_clip(self._t, lr, momentum, clip_norm, C.byref(g), _stream(self.device)),
-                   "dgp_sgd_momentum_clip")
+        self._enqueue_update(optimizer, lr, momentum, clip_norm, beta1, beta2, eps, g)
         self.sync()
         return g.value
+
+    # ---- optimiser state under the names tf.train.Saver gives it --------------------------------------------------------------------
+    _ADAM_POWERS = ("beta1_power", "beta2_power")
+
+    def _has_adam(self) -> bool:
+        return bool(self.lib.dgp_trainer_buffer(self._t, 7))
+
+    def get_optimizer_state(self) -> Dict[str, np.ndarray]:
+        """{TF name: array}: `<var>/Momentum` of every trainable once a momentum step has run; `<var>/Adam` (m), `<var>/Adam_1` (v) and the
+        scalars `beta1_power` / `beta2_power` once Adam's state exists (a step or load_optimizer_state); {} before any update."""
+        out = {}
+        if self._ran_sgd:
+            out.update({k + "/Momentum": a for k, a in self._download(2).items()})
+        if self._has_adam():
+            out.update({k + "/Adam": a for k, a in self._download(5).items()})
+            out.update({k + "/Adam_1": a for k, a in self._download(6).items()})
+            pw = np.empty(2, dtype=np.float32)
+            _lib.check(self.lib.dgp_trainer_download(self._t, 7, 0, pw.ctypes.data_as(C.c_void_p), 2))
+            out["beta1_power"], out["beta2_power"] = pw[0].reshape(()), pw[1].reshape(())
+        return out
+
+    def load_optimizer_state(self, state: Dict[str, np.ndarray]):
+        """Upload a dict of get_optimizer_state's form: the momentum slots, Adam's, or both.  A family must be complete: a slot that is missing
+        or whose size is not its variable's raises DgpError naming it."""
+        has_mom = any(k.endswith("/Momentum") for k in state)
+        has_adam = any(k.endswith(("/Adam", "/Adam_1")) or k in self._ADAM_POWERS for k in state)
+        if not (has_mom or has_adam):
+            raise _lib.DgpError("no optimizer state in the dict (expected <var>/Momentum, or <var>/Adam, <var>/Adam_1 and the two powers)")
+        todo = []                                        # (nothing is uploaded before everything has been checked)
+
+        def slots(suffix, which):
+            for k, (off, size, st) in self.table.items():
+                if st:
+                    continue
+                if k + suffix not in state:
+                    raise _lib.DgpError("optimizer state lacks %s" % (k + suffix))
+                a = np.ascontiguousarray(state[k + suffix], dtype=np.float32)
+                if a.size != size:
+                    raise _lib.DgpError("bad size for %s: %d != %d" % (k + suffix, a.size, size))
+                todo.append((which, off, a))
+        if has_mom:
+            slots("/Momentum", 2)
+        if has_adam:
+            slots("/Adam", 5)
+            slots("/Adam_1", 6)
+            for k in self._ADAM_POWERS:
+                if k not in state or np.size(state[k]) != 1:
+                    raise _lib.DgpError("optimizer state lacks the scalar %s" % k)
+            todo.append((7, 0, np.array([float(np.reshape(state[k], ())) for k in self._ADAM_POWERS], dtype=np.float32)))
+        for which, off, a in todo:
+            _lib.check(self.lib.dgp_trainer_upload(self._t, which, off, a.ctypes.data_as(C.c_void_p), a.size), "dgp_trainer_upload")
+        self._ran_sgd = self._ran_sgd or has_mom
 
     def step(self, frames, batch, hyper: DGPHyper, S0, ws, ws_max, n_frames_total, n_visible_frames_total,
              labeled_only: bool = False):
         """One optimisation step = the reference's sess.run([loss, train_op]) (DGP/models/fitdgp.py:818).  Single process: the whole step --
-        forward, loss, backward, clip + momentum, the re-packing of the weights -- is enqueued without a read-back and ONE synchronisation
+        forward, loss, backward, clip + momentum (or Adam: hyper.optimizer), the re-packing of the weights -- is enqueued without a read-back and ONE synchronisation
         at its end fetches losses, gradient norm and the pass status (dgp_trainer_step_status).  A 16-bit pass whose tensors left their
         predicted ranges has skipped its update on the device and is repeated here on the parity path."""
         dp = ddist.data_parallel()
@@ -312,8 +381,7 @@ class Trainer:
                 # data-parallel: the mean gradient over the ranks (RCCL), group by group while the backward pass is still running; the
                 # optimiser's kernels are enqueued behind it -- still ONE host synchronisation per step
                 self.allreduce_gradients()
-            _lib.check(self.lib.dgp_sgd_momentum_clip(self._t, hyper.lr, hyper.momentum, hyper.clip_norm, None, _stream(self.device)),
-                       "dgp_sgd_momentum_clip")
+            self._enqueue_update(hyper.optimizer, hyper.lr, hyper.momentum, hyper.clip_norm, hyper.beta1, hyper.beta2, hyper.adam_eps)
             self.sync()                              # master -> panels / cells for the next forward (same weights again after a skipped update)
             g, was, failed = C.c_float(), C.c_int32(), C.c_int32()
             lv = (C.c_float * 8)()
@@ -321,7 +389,7 @@ class Trainer:
                                                         _stream(self.device)), "dgp_trainer_step_status")
             if fast and was.value:
                 self.fast_passes += 1                # counted from the pass status the DEVICE wrote, not from the request
-            if fast and failed.value:                # the momentum kernel saw the flag and left parameters and momentum alone
+            if fast and failed.value:                # the optimiser's kernel saw the flag and left parameters and its state alone
                 self._fast_key = None
                 self.fast_redos += 1
                 continue

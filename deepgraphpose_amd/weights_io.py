@@ -64,6 +64,24 @@ def load_weights(path: str) -> Dict[str, np.ndarray]:
         return {k: np.asarray(z[k], dtype=np.float32) for k in z.files}
 
 
+def load_optimizer_state(path: str) -> Dict[str, np.ndarray]:
+    """Only the optimiser's entries of a snapshot (`<var>/Momentum`, `<var>/Adam`, `<var>/Adam_1`, beta1_power, beta2_power), the form
+    Trainer.load_optimizer_state takes; {} for a snapshot that holds none (every snapshot written without keep_optimizer_state)."""
+    from .tf_checkpoint import is_optimizer_entry, load_checkpoint
+    f = resolve(path)
+    if f.endswith(".index"):
+        t = load_checkpoint(f[:-len(".index")], slots=True)
+    elif not f.endswith((".npz", ".safetensors")) and _is_table(f):
+        t = load_checkpoint(f, slots=True)
+    elif f.endswith(".safetensors"):
+        from safetensors.numpy import load_file
+        t = load_file(f)
+    else:
+        with np.load(f) as z:
+            t = {k: z[k] for k in z.files}
+    return {k: np.asarray(v, dtype=np.float32) for k, v in t.items() if is_optimizer_entry(k)}
+
+
 def save_weights(path: str, weights: Dict[str, np.ndarray], fmt: str = None) -> str:
     p = str(path)
     if fmt is None:

@@ -229,7 +229,8 @@ int  dgp_dlc_loss_fwd_bwd(const float* pred, const float* locref_pred, const flo
  *   dgp_train_forward        : forward pass retaining activations; returns device pointers of both head outputs
  *   dgp_loss_fwd_bwd         : (above) loss and d loss / d heads
  *   dgp_train_backward       : gradients of all trainables into the flat grads buffer
- *   dgp_sgd_momentum_clip    : tf.clip_by_global_norm(clip) + MomentumOptimizer(momentum) */
+ *   dgp_sgd_momentum_clip    : tf.clip_by_global_norm(clip) + MomentumOptimizer(momentum)
+ *   dgp_adam_clip            : tf.clip_by_global_norm(clip) + AdamOptimizer(beta1, beta2, eps) */
 typedef struct dgp_trainer dgp_trainer;
 int    dgp_trainer_create(dgp_net* net, dgp_trainer** out);            /* net must have with_locref = 1 */
 void   dgp_trainer_destroy(dgp_trainer* tr);
@@ -239,6 +240,9 @@ int    dgp_trainer_tensor_info(const dgp_trainer* tr, int32_t i, char* name, int
                                int64_t* size, int32_t* is_stat);
 float* dgp_trainer_buffer(dgp_trainer* tr, int32_t which);  /* 0 params, 1 grads, 2 momentum, 3 BN statistics; 4: the 16-bit pass's failure flag
                                                               * (ONE int32 on the device; data-parallel runs all-reduce it with MAX before the update) */
+/* Adam's state: which = 5: m, 6: v (n_trainable floats each, laid out like the parameters), 7: {beta1_power, beta2_power} as two floats.
+ * They exist from the first dgp_adam_clip or the first dgp_trainer_upload into one of them (m = v = 0, powers 0.9 / 0.999 until
+ * uploaded); before that dgp_trainer_buffer returns NULL for them and a download fails. */
 int    dgp_trainer_upload(dgp_trainer* tr, int32_t which, int64_t offset, const float* host, int64_t n);
 int    dgp_trainer_download(dgp_trainer* tr, int32_t which, int64_t offset, float* host, int64_t n);
 int    dgp_trainer_workspace_bytes(const dgp_trainer* tr, int32_t nt, size_t* out_bytes);
@@ -251,6 +255,13 @@ int    dgp_train_backward(dgp_trainer* tr, int32_t nt, void* workspace, size_t w
  * that raised the range flag leaves parameters and momentum untouched -- see dgp_trainer_step_status.) */
 int    dgp_sgd_momentum_clip(dgp_trainer* tr, float lr, float momentum, float clip_norm, float* gnorm_host_or_null,
                              void* stream);
+/* TF-1's dense ApplyAdam in fp32 behind tf.clip_by_global_norm, same contract (clip_norm <= 0: no clipping; the norm goes to
+ * dgp_trainer_step_status; a pass that raised the range flag leaves parameters, m, v AND the two powers untouched):
+ *   g' = g * clip / max(|g|, clip);  alpha = lr sqrt(1 - beta2_power) / (1 - beta1_power)
+ *   m += (g' - m)(1 - beta1);  v += (g' g' - v)(1 - beta2);  var -= alpha m / (sqrt(v) + eps);  then the powers *= beta1, beta2.
+ * The powers start at beta1 / beta2 (the values of the first call) and live on the device. */
+int    dgp_adam_clip(dgp_trainer* tr, float lr, float beta1, float beta2, float eps, float clip_norm, float* gnorm_host_or_null,
+                     void* stream);
 /* Fast pass of the training step (no reference counterpart; the step's results are the same fp32-class numbers either way).
  * dgp_trainer_fast_mode(tr, 1): the NEXT dgp_train_forward keeps the retained activations of blocks 2-4 as H2 tensors (fp16 high / low
  * cells, no fp32 twin) whose power-of-two scales are PREDICTED from the ranges the same tensors had in the previous pass (max -> [2^10,
