@@ -130,6 +130,7 @@ SYMBOLS = {
     "dgp_window_resize_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "dgp_target_maps": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _i32,
                                   _vp, _vp, _vp, _vp, _vp]),
+    "dgp_gather_frames_u8": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _i32, _vp, _i32, C.c_int64, _vp, _vp]),
 }
 
 _lib = None

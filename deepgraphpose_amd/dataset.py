@@ -350,21 +350,25 @@ class Dataset:
         self.curr_batch = 0
 
     # -- batches -------------------------------------------------------------------------------------
-    def load_data(self, idxs_video, pv_idxs):
-        """Random-access frames + the labels of the visible ones (DGP/dataset.py:811-821)."""
-        got = {i: np.asarray(self.video_clip.frame_at(i)) for i in set(int(i) for i in idxs_video)}
-        images = np.stack([got[int(i)] for i in idxs_video]).astype(np.uint8)
+    def load_data(self, idxs_video, pv_idxs, pixels=True):
+        """Random-access frames + the labels of the visible ones (DGP/dataset.py:811-821).  pixels=False: no frame is read and
+        `images` is None (the batch's frames come from a device frame store, staged._FrameStore)."""
+        images = None
+        if pixels:
+            got = {i: np.asarray(self.video_clip.frame_at(i)) for i in set(int(i) for i in idxs_video)}
+            images = np.stack([got[int(i)] for i in idxs_video]).astype(np.uint8)
         idxs_labels = [int(np.where(self.labels_idxs == i)[0][0]) for i in pv_idxs]
         return images, self.labels[idxs_labels]
 
-    def next_batch(self, schedule, batch_dict, pv_idxs=None, ph_idxs=None):
+    def next_batch(self, schedule, batch_dict, pv_idxs=None, ph_idxs=None, pixels=True):
         """-> (pv_idxs, ph_idxs, pv_idxs_b, images u8 [nt,H,W,3], labels [nv,nj,2], batch_mask [nt-1], batch_ts,
-        (visible_marker, hidden_marker, visible_marker_in_targets)); DGP/dataset.py:672-750."""
+        (visible_marker, hidden_marker, visible_marker_in_targets)); DGP/dataset.py:672-750.  pixels=False: the same index sets and
+        labels with images = None, and no frame is read."""
         if pv_idxs is None and ph_idxs is None:
             raise NotImplementedError("schedule-driven batching is legacy; fit_dgp passes explicit frame lists")
         pv_idxs, ph_idxs = np.asarray(pv_idxs, dtype=int), np.asarray(ph_idxs, dtype=int)
         idxs_video = np.sort(np.concatenate([pv_idxs, ph_idxs]))
-        images, labels = self.load_data(idxs_video, pv_idxs)
+        images, labels = self.load_data(idxs_video, pv_idxs, pixels)
         pv_idxs_b = np.where(np.isin(idxs_video, pv_idxs))[0]
         ph_idxs_b = np.where(np.isin(idxs_video, ph_idxs))[0]
         batch_mask = np.zeros(max(len(idxs_video) - 1, 0), dtype=int)
@@ -440,7 +444,7 @@ class MultiDataset:
             d.reset()
         self.curr_batch = 0
 
-    def next_batch(self, schedule, dataset=None, pv_idxs=None, ph_idxs=None):
+    def next_batch(self, schedule, dataset=None, pv_idxs=None, ph_idxs=None, pixels=True):
         if dataset is None or pv_idxs is None or ph_idxs is None:
             raise NotImplementedError("schedule-driven batching is legacy; pass dataset, pv_idxs, ph_idxs")
-        return self.datasets[dataset].next_batch(schedule, self.batch_info, pv_idxs=pv_idxs, ph_idxs=ph_idxs), dataset
+        return self.datasets[dataset].next_batch(schedule, self.batch_info, pv_idxs=pv_idxs, ph_idxs=ph_idxs, pixels=pixels), dataset

@@ -7,7 +7,7 @@ falls back to torch ops or to the CPU oracle.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1032,3 +1032,56 @@ def target_maps(entries, offsets, n: int, H: int, W: int, nj: int, *, pos_dist_t
                                    float(locref_stdev), 1 if weigh_only_present_joints else 0, *(_ptr(t) for t in outs), _stream(dev)),
                "dgp_target_maps")
     return tuple(outs)
+
+
+class FrameSlots(NamedTuple):
+    """Frames kept on the device for gather_frames: `data` uint8 [n_slots, slot_stride], slot s holds one [H, W, 3] frame in its first
+    H * W * 3 bytes; slot_stride (bytes) is a multiple of 16.  `shape` = (H, W)."""
+    data: torch.Tensor
+    shape: Tuple[int, int]
+
+
+def gather_frames(store, src, patch: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A batch of frames assembled on the device (dgp_gather_frames_u8): out[f] = slot src[f] of `store` (a FrameSlots, or any
+    (data, (H, W)) pair) when src[f] >= 0, frame -1 - src[f] of `patch` (uint8 [m, H, W, 3]: the frames uploaded for this batch) otherwise.
+    `src` is a HOST sequence of nt ints; every entry is checked against the store's slots and the patch's frames HERE and a bad one
+    raises DgpError before anything is launched; the table then travels inside the launch arguments, so no copy is issued for it.
+    -> uint8 [nt, H, W, 3] (`out` when given: contiguous, that shape), written by one launch on the current stream; nt == 0 returns an
+    empty batch without a launch."""
+    lib = _lib.load()
+    data, (H, W) = store
+    H, W = int(H), int(W)
+    frame_bytes = H * W * 3
+    _need_cuda(data, torch.uint8, "store")
+    if data.dim() != 2 or H <= 0 or W <= 0:
+        raise _lib.DgpError("gather_frames: the store must be [n_slots, slot_stride] with a positive frame shape, got %s, %r"
+                            % (tuple(data.shape), (H, W)))
+    n_slots, stride = int(data.shape[0]), int(data.shape[1])
+    if stride % 16 != 0 or stride < frame_bytes:
+        raise _lib.DgpError("gather_frames: slot_stride %d must be a multiple of 16 and hold a %d-byte frame" % (stride, frame_bytes))
+    dev = data.device
+    m = 0
+    if patch is not None:
+        _need_cuda(patch, torch.uint8, "patch")
+        if patch.dim() != 4 or tuple(patch.shape[1:]) != (H, W, 3) or patch.device != dev:
+            raise _lib.DgpError("gather_frames: patch must be [m, %d, %d, 3] on %s, got %s on %s" % (H, W, dev, tuple(patch.shape), patch.device))
+        m = int(patch.shape[0])
+    table = np.asarray(src, dtype=np.int64).reshape(-1)
+    nt = int(table.size)
+    bad = np.nonzero((table >= n_slots) | (table < -m))[0]
+    if bad.size:
+        raise _lib.DgpError("gather_frames: src[%d] = %d is outside the store's %d slots and the patch's %d frames"
+                            % (int(bad[0]), int(table[bad[0]]), n_slots, m))
+    if out is None:
+        out = torch.empty((nt, H, W, 3), dtype=torch.uint8, device=dev)
+    else:
+        _need_cuda(out, torch.uint8, "out")
+        if tuple(out.shape) != (nt, H, W, 3) or out.device != dev:
+            raise _lib.DgpError("gather_frames: out must be %s on %s, got %s on %s" % ((nt, H, W, 3), dev, tuple(out.shape), out.device))
+    if nt == 0:
+        return out
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    _lib.check(lib.dgp_gather_frames_u8(_ptr(data) if n_slots else None, n_slots, stride, _ptr(patch) if m else None, m,
+                                        table.ctypes.data_as(C.c_void_p), nt, frame_bytes, _ptr(out), _stream(dev)),
+               "dgp_gather_frames_u8")
+    return out

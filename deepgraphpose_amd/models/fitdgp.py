@@ -34,13 +34,16 @@ from .. import config as dcfg
 from .. import dist as ddist
 from ..dataset import MultiDataset, coord2map
 from ..loss import DGPHyper
-from ..staged import _FrameUploader, _ImageCache, _device_flow, _device_locref, _device_sample, _on_current_stream
+from ..staged import _FrameStore, _FrameUploader, _ImageCache, _device_flow, _device_locref, _device_sample, _flow_of, _on_current_stream
 from .fitdgp_util import gen_batch
 
 PREFETCH_DEPTH = 2          # iterations of host batches built ahead on a background thread (0: inline); a measured setting, not a switch
 
 PREP_BACKENDS = ("auto", "host", "hip")
-PREP_STATS = {"backend": None}   # the sample-preparation backend of the last fit_* run ("host" | "hip"), like eval.RUN_STATS["prep_backend"]
+# the sample-preparation backend of the last fit_* run ("host" | "hip"), like eval.RUN_STATS["prep_backend"], and its frame stores: None
+# with frame_store="off", else {"frames": stored, "bytes": on the device, "refused": selected frames without a slot, "fill_s": seconds
+# of the fill, "patched": frames of the LAST batch that were uploaded instead of gathered from a slot}
+PREP_STATS = {"backend": None, "frame_store": None}
 
 
 def resolve_prep_backend(backend: str = "auto", device=None) -> str:
@@ -55,6 +58,23 @@ def resolve_prep_backend(backend: str = "auto", device=None) -> str:
     import torch
     from .fitdgp_util import _cv2_available
     return "host" if _cv2_available() or torch.device(device).type != "cuda" else "hip"
+
+
+FRAME_STORES = ("off", "hip")
+
+
+def resolve_frame_store(frame_store: str = "off", wt=0, flow_backend=None) -> str:
+    """"off" | "hip" for fit_dgp*(frame_store=...).  "off": every batch reads its frames from the source (Dataset.load_data) and uploads
+    them.  "hip": the run's selected frames are decoded once into a device store (staged._FrameStore) and every batch is gathered from it
+    (engine.gather_frames).  `wt`, `flow_backend`: the run's temporal-clique weight and its RESOLVED flow backend -- a flow computed on the
+    host (cv2) needs every frame of every batch on the host, which is what the store does away with, so that pair is refused."""
+    if frame_store not in FRAME_STORES:
+        raise ValueError("frame store must be one of %s, not %r" % (" | ".join(FRAME_STORES), frame_store))
+    if frame_store == "hip" and wt > 0 and flow_backend != "hip":
+        raise ValueError("frame_store='hip' keeps the batch's frames on the device, but flow_backend=%r computes the optical flow of the "
+                         "temporal clique (wt > 0) on the host and needs every frame there; use flow_backend='hip' or frame_store='off'"
+                         % (flow_backend,))
+    return frame_store
 
 
 OPTIMIZERS = ("sgd", "adam")
@@ -493,13 +513,17 @@ def _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, h
 
 
 def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_frames, schedule, entry, progress, finished, step,
-           save_every, displayiters, debug="", flow_backend=None, prep_backend="host", optimizer="sgd", keep_optimizer_state=False):
+           save_every, displayiters, debug="", flow_backend=None, prep_backend="host", optimizer="sgd", keep_optimizer_state=False,
+           frame_store="off"):
     """The loop of both DGP drivers.  schedule() draws the run's entries, entry(data_batcher, e) -> (dataset_i, visible frames, hidden
     frames) of one of them, progress(...) prints a displayed iteration's lines, `finished` is the closing line.  Iteration `it` trains on
     entry _dp_index(it) and rank 0 saves every `save_every` iterations and after the last.  labeled_only: the objective is
     total_loss_visible and the batch is the general one without hidden frames, frame pairs or flow.  prep_backend "hip": the locref
     maps are built on the device (_device_locref) and handed to the loss as Staged tensors instead of two host arrays.  optimizer: "sgd"
-    (the reference's MomentumOptimizer) | "adam", both behind clip_by_global_norm(10); keep_optimizer_state as in fit_dlc."""
+    (the reference's MomentumOptimizer) | "adam", both behind clip_by_global_norm(10); keep_optimizer_state as in fit_dlc.
+    frame_store "hip": every dataset's selected frames are put on the device before iteration 0 (_frame_stores) and make_batch
+    gathers the batch there: the Dataset gives the index sets and labels without pixels, only the labeled frames' host copies go
+    through data_aug (the same draws in the same order), and the augmented frames travel as the gather's patch."""
     from .. import weights_io
     from .session import Placeholder, TrainSession
     dgp_cfg, nj = data_batcher.dlc_config, data_batcher.nj
@@ -515,7 +539,8 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
     saver = weights_io.Saver(max_to_keep=dgp_cfg.max_to_keep)     # fitdgp.py:401, 696
     uploader = _make_uploader(trainer)
     prep_backend = resolve_prep_backend(prep_backend, trainer.device)
-    PREP_STATS["backend"] = prep_backend
+    PREP_STATS["backend"], PREP_STATS["frame_store"] = prep_backend, None
+    stores = _frame_stores(data_batcher, trainer.device, uploader) if frame_store == "hip" else None
     entries = schedule()
     n_sched = len(entries)
     maxiters = max(1, n_sched // world)          # data-parallel: W windows per optimiser step
@@ -527,18 +552,30 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
     def make_batch(it):                          # host side of one iteration (runs one iteration ahead on the prefetch thread)
         dataset_i, vis_b, hid_b = entry(data_batcher, entries[_dp_index(it, n_sched)])
         d = data_batcher.datasets[dataset_i]
-        (vis, hid, _, images, joint_loc, wt_mask, _, addn), _ = data_batcher.next_batch(0, dataset_i, vis_b, hid_b)
+        (vis, hid, _, images, joint_loc, wt_mask, _, addn), _ = data_batcher.next_batch(0, dataset_i, vis_b, hid_b, pixels=stores is None)
         all_frame = np.sort(list(vis) + list(hid))
         vis_within = [int(np.where(all_frame == i)[0][0]) for i in vis]
+        replaced = None
         if pipeline is not None and dgp_cfg.wt == 0 and len(vis_within) > 0:      # fitdgp.py:481-482, 778-779
             from ..augment import data_aug
-            images, joint_loc = data_aug(images, vis_within, joint_loc, pipeline, dgp_cfg)
+            if stores is None:
+                images, joint_loc = data_aug(images, vis_within, joint_loc, pipeline, dgp_cfg)
+            else:                                                     # the labeled frames alone: data_aug reads no other
+                labeled = np.stack([stores[dataset_i].host[int(i)] for i in vis])
+                labeled, joint_loc = data_aug(labeled, list(range(len(vis))), joint_loc, pipeline, dgp_cfg)
+                replaced = dict(zip(vis_within, labeled))
         if prep_backend == "hip":                                     # (after data_aug, which moves joint_loc)
             lmap, lmask = _device_locref(uploader, trainer.device, joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
         else:
             lmap, lmask = _locref_targets(joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
         vector_field, frames = None, None
-        if dgp_cfg.wt > 0 and flow_backend == "hip":                  # temporal clique: flow magnitude on the device
+        if stores is not None:                                        # the batch is gathered on the device, the flow computed from it
+            frames = stores[dataset_i].batch(all_frame, replaced)
+            PREP_STATS["frame_store"]["patched"] = stores[dataset_i].last_patched
+            images = frames.tensor
+            if dgp_cfg.wt > 0:
+                frames, vector_field = _flow_of(uploader, images)
+        elif dgp_cfg.wt > 0 and flow_backend == "hip":                # temporal clique: flow magnitude on the device
             frames, vector_field = _device_flow(uploader, trainer.device, images)
         elif dgp_cfg.wt > 0:                                          # temporal clique: flow field from the host hook
             from .fitdgp_util import learn_wt
@@ -563,6 +600,25 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
     print("\n\n TOTAL TIME ELAPSED: ", time.time() - t_start)
 
 
+def _frame_stores(data_batcher, device, uploader):
+    """frame_store="hip": one _FrameStore per Dataset, filled here, sharing staged.FRAME_STORE_BYTES (read now) in dataset order; what
+    does not fit is said once.  Every rank of a data-parallel run fills its own.  -> the stores, and PREP_STATS["frame_store"]."""
+    from .. import staged
+    left, said, stores = staged.FRAME_STORE_BYTES, [], []
+
+    def announce(line):
+        if not said:
+            said.append(line)
+            print(line, flush=True)
+
+    for d in data_batcher.datasets:
+        stores.append(_FrameStore(d, device, uploader, budget=left, announce=announce))
+        left -= stores[-1].bytes
+    PREP_STATS["frame_store"] = {"frames": sum(len(s.slots) for s in stores), "bytes": sum(s.bytes for s in stores),
+                                 "refused": sum(len(s.refused) for s in stores), "fill_s": sum(s.fill_s for s in stores), "patched": 0}
+    return stores
+
+
 def _labeled_entry(data_batcher, row):
     """(dataset, labeled frame) -> that frame alone"""
     dataset_i, frame_i = row
@@ -576,13 +632,16 @@ def _labeled_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 
 def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, displayiters=5, maxiters=50000, ns=10,
                         nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None, prep_backend="auto", optimizer="sgd",
-                        keep_optimizer_state=False):
+                        keep_optimizer_state=False, frame_store="off"):
     """Run DGP with labeled frames only (fitdgp.py:257-546): batch = one labeled frame, loss =
     total_loss_visible.  `frame_sources` (new, optional) injects already-open frame sources per video.
     prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built.
     optimizer: "sgd", the reference's hard-coded MomentumOptimizer(lr, 0.9), or "adam", AdamOptimizer(lr); both on gradients clipped to a
-    global norm of 10.  keep_optimizer_state: see fit_dlc."""
+    global norm of 10.  keep_optimizer_state: see fit_dlc.
+    frame_store: "off" | "hip" (resolve_frame_store).  "hip": the labeled frames are read once, kept on the device (and on the host, for
+    the augmentation), and every iteration's frame is gathered there; only an augmented frame is uploaded."""
     prep_backend = resolve_prep_backend(prep_backend)
+    frame_store = resolve_frame_store(frame_store)
     optimizer = resolve_optimizer(optimizer)
     hyper = dict(ws=0, ws_max=1.2, wt=0, wt_max=0, wn_visible=1, wn_hidden=0, gamma=1, gauss_len=1, lengthscale=1,
                  max_to_keep=5, batch_size=1, n_times_all_frames=100, lr=0.005, gm2=0, gm3=0, aug=aug)
@@ -599,7 +658,7 @@ def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, di
 
     _train(*run, labeled_only=True, max_frames=1, schedule=schedule, entry=_labeled_entry, progress=_labeled_progress,
            finished="Finished training {} iterations\n", step=step, save_every=saveiters, displayiters=displayiters,
-           prep_backend=prep_backend, optimizer=optimizer, keep_optimizer_state=keep_optimizer_state)
+           prep_backend=prep_backend, optimizer=optimizer, keep_optimizer_state=keep_optimizer_state, frame_store=frame_store)
     return None
 
 
@@ -627,18 +686,24 @@ def _window_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 
 def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000, displayiters=5, maxiters=200000, ns=10,
             nc=2048, n_max_frames=2000, gm2=0, gm3=0, nepoch=100, wt=0, aug=True, debug="", trainingsetindex=0,
-            frame_sources=None, flow_backend="auto", prep_backend="auto", optimizer="sgd", keep_optimizer_state=False):
+            frame_sources=None, flow_backend="auto", prep_backend="auto", optimizer="sgd", keep_optimizer_state=False,
+            frame_store="off"):
     """Run DGP (fitdgp.py:549-845): batches of `batch_size` consecutive frames of the selected windows, at least
     one labeled frame per batch, loss = total_loss (visible + hidden CE, locref, spatial clique; + the temporal clique when wt > 0).
     flow_backend (wt > 0): "cv2" | "hip" | "auto" as learn_wt's backend.  With "hip" the flow magnitude is computed on the device from
     the batch's uploaded frames (engine.optical_flow) and handed to the loss as a device tensor: it never crosses to the host.
     prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built; with "hip" the two
     [nt, H, W, 2 nj] maps are written on the device from the labeled frames' coordinates and never exist on the host.
-    optimizer / keep_optimizer_state: as in fit_dgp_labeledonly."""
+    optimizer / keep_optimizer_state: as in fit_dgp_labeledonly.
+    frame_store: "off" | "hip" (resolve_frame_store).  "hip": the selected frames (idxs chunk, pv, ph of every video) are read from their
+    source once, in ascending order, and kept on the device within staged.FRAME_STORE_BYTES; a batch is one engine.gather_frames launch
+    over them plus a patch of what was made for it (augmented labeled frames, frames the store could not hold), and with wt > 0 the
+    flow is computed from the gathered batch, which needs flow_backend "hip" (a host flow with "hip" is a ValueError)."""
     from .fitdgp_util import resolve_flow_backend
     optimizer = resolve_optimizer(optimizer)
     prep_backend = resolve_prep_backend(prep_backend)
     flow_backend = resolve_flow_backend(flow_backend) if wt > 0 else None
+    frame_store = resolve_frame_store(frame_store, wt, flow_backend)
     hyper = dict(ws=1000, ws_max=1.2, wt=wt, wt_max=0, wn_visible=5, wn_hidden=3, gamma=1, gauss_len=1, lengthscale=1,
                  max_to_keep=5, batch_size=batch_size, n_times_all_frames=nepoch, lr=0.005, gm2=gm2, gm3=gm3, aug=aug)
     run = _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, hyper, "-step{}{}-final--0".format(step, debug),
@@ -658,5 +723,5 @@ def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000,
     _train(*run, labeled_only=False, max_frames=batch_size + 1, schedule=schedule, entry=_window_entry, progress=_window_progress,
            finished="Finished {} iterations\n", step=step, save_every=max(int(saveiters / batch_size), 1), displayiters=displayiters,
            debug=debug, flow_backend=flow_backend, prep_backend=prep_backend, optimizer=optimizer,
-           keep_optimizer_state=keep_optimizer_state)
+           keep_optimizer_state=keep_optimizer_state, frame_store=frame_store)
     return None

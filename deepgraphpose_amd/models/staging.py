@@ -1,6 +1,7 @@
 """The host side of estimate_pose's pipeline that never touches the GPU (models/eval.py drives it): the ring of staging buffers between
 the threads that fill batches and the one consumer that uploads them, the two producers, the chunk geometry and a shard's frames.
-No torch in here: the buffers are anything numpy can write to (eval.py passes the .numpy() views of its pinned tensors)."""
+No torch in here: the buffers are anything numpy can write to (eval.py passes the .numpy() views of its pinned tensors).
+Also the torch-free half of the fit drivers' device frame store (staged._FrameStore): which frames get a slot, and a batch's gather table."""
 from __future__ import annotations
 
 import itertools
@@ -137,3 +138,40 @@ def shard_frames(source, lo: int, hi: int, world: int, name="the video"):
     if first is None:
         raise ValueError("no frames in %s" % (name,))
     return first, itertools.islice(it, max(hi - lo - 1, 0))
+
+
+def slot_stride(frame_bytes: int) -> int:
+    """The byte pitch of a frame store's slots: frame_bytes rounded up to 16 (every slot starts 16-byte aligned)"""
+    return -(-int(frame_bytes) // 16) * 16
+
+
+def frame_slots(frames, frame_bytes: int, budget_bytes: int, last=()):
+    """Which of a video's selected frames get a slot in the device frame store (staged._FrameStore) when the store may hold
+    budget_bytes: -> ({frame: slot}, refused frames, sorted).  `frames`: any sequence of frame numbers; its sorted unique values are
+    the candidates, and a slot costs slot_stride(frame_bytes).  All of them are stored when they fit.  Otherwise the frames in `last`
+    (the labeled ones, of which the drivers keep host copies anyway: leaving them out costs no decode) give way first, and inside
+    either group the lower frame numbers are kept.  Slots are numbered in ascending frame order, the order in which the store is
+    filled, so a decoder reads forward."""
+    cand = sorted(set(int(f) for f in frames))
+    n_fit = max(0, int(budget_bytes)) // slot_stride(frame_bytes)
+    late = set(int(f) for f in last)
+    order = [f for f in cand if f not in late] + [f for f in cand if f in late]
+    kept = sorted(order[:n_fit])
+    return {f: s for s, f in enumerate(kept)}, sorted(order[n_fit:])
+
+
+def gather_table(batch_frames, slots, patched=()):
+    """The `src` table of engine.gather_frames for one batch: batch_frames[p] is the frame number at position p of the batch, `slots`
+    maps the stored frames to their slots, `patched` holds the POSITIONS whose pixels are uploaded for this batch (augmented labeled
+    frames).  A position whose frame has no slot is patched as well.  -> (src int32 [nt], patch positions in patch order): position p
+    reads slot slots[frame] (src >= 0; a frame that occurs twice reads the same slot twice), or patch frame k (src = -1 - k) when it
+    is the k-th patched position."""
+    forced = set(int(p) for p in patched)
+    src, order = [], []
+    for p, f in enumerate(batch_frames):
+        if p in forced or int(f) not in slots:
+            src.append(-1 - len(order))
+            order.append(p)
+        else:
+            src.append(slots[int(f)])
+    return np.asarray(src, dtype=np.int32), order

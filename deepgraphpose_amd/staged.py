@@ -4,8 +4,8 @@ The fit drivers build the batch of iteration it + 1 on a prefetch thread while t
 batch's frames on a stream of its own.  What crosses from that stream to the consumer's is a `Staged` pair: the device tensor and the event
 behind the last work that wrote it.  The pair is a value, so the event cannot get lost on the way the way an attribute of the tensor would
 (a slice, a view or .to() returns a new tensor object): whoever derives another tensor from `tensor` wraps it with the same `ready`.
-Producers: _FrameUploader, _device_flow.  Consumers: _frames_to_device (TrainSession.run) and dgp_loss_prepare (loss.py), both through
-_on_current_stream."""
+Producers: _FrameUploader, _device_flow, _FrameStore.batch.  Consumers: _frames_to_device (TrainSession.run) and dgp_loss_prepare
+(loss.py), both through _on_current_stream."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -50,8 +50,8 @@ class _FrameUploader:
         self.slots, self.pinned, self.turn = slots, [None] * slots, 0
         self.copied = [None] * slots              # event behind the last H2D copy issued from each staging buffer
 
-    def __call__(self, images) -> Staged:
-        img = _as_uint8(images)
+    def _stage(self, img):
+        """img -> (its copy in the next pinned staging buffer, that buffer's index); blocks until the buffer's last copy has read it"""
         k = self.turn
         self.turn = (k + 1) % self.slots
         if self.copied[k] is not None:
@@ -60,12 +60,25 @@ class _FrameUploader:
             self.pinned[k] = torch.empty(img.size, dtype=torch.uint8).pin_memory()
         stage = self.pinned[k][:img.size].view(img.shape)
         stage.numpy()[...] = img
+        return stage, k
+
+    def __call__(self, images) -> Staged:
+        stage, k = self._stage(_as_uint8(images))
         with torch.cuda.stream(self.stream):
             dev = stage.to(self.device, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         self.copied[k] = ev
         return Staged(dev, ev)
+
+    def into(self, dst: torch.Tensor, images):
+        """As __call__, but the copy lands in `dst`, an existing device tensor of the images' shape (a run of a _FrameStore's slots)"""
+        stage, k = self._stage(_as_uint8(images))
+        with torch.cuda.stream(self.stream):
+            dst.copy_(stage, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self.copied[k] = ev
 
 
 def _device_flow(uploader, device, images):
@@ -74,9 +87,15 @@ def _device_flow(uploader, device, images):
     -> (Staged frames, Staged magnitude) sharing ONE event, recorded behind the flow (the frames are ready no later than the flow that
     read them); without an uploader everything runs on the current stream and both events are None."""
     if uploader is None:
-        dev = torch.from_numpy(np.ascontiguousarray(np.asarray(images).astype(np.uint8))).to(device)
+        return _flow_of(None, torch.from_numpy(np.ascontiguousarray(np.asarray(images).astype(np.uint8))).to(device))
+    return _flow_of(uploader, uploader(images).tensor)      # (same stream as the flow: no wait on the copy's own event)
+
+
+def _flow_of(uploader, dev):
+    """_device_flow's second half, for frames that are on the device already (uploaded or gathered on the uploader's stream, or on the
+    current one without an uploader) -> (Staged frames, Staged magnitude)"""
+    if uploader is None:
         return Staged(dev, None), Staged(engine.optical_flow(dev), None)
-    dev = uploader(images).tensor                 # (same stream as the flow below: no wait on the copy's own event)
     with torch.cuda.stream(uploader.stream):
         mag = engine.optical_flow(dev)
         ev = torch.cuda.Event()
@@ -130,6 +149,106 @@ class _ImageCache:
         self.images[key] = dev
         self.bytes += img.nbytes
         return dev
+
+
+FRAME_STORE_BYTES = 16 << 30        # device bytes the _FrameStores of ONE run may hold together; read when a store is filled.  A choice, not
+#                                     a measurement: a 2000-frame selection (n_max_frames) of 1280 x 720 video is 5.5 GB, so this holds
+#                                     three such videos, and is 6 % of an MI355X's 288 GB
+FRAME_STORE_RUN_BYTES = 32 << 20    # frames uploaded per copy while a store is filled (the size the uploader's pinned buffers grow to)
+
+
+class _FrameStore:
+    """The frames a DGP driver trains on -- the sorted unique union of one Dataset's idxs["chunk"], idxs["pv"] and idxs["ph"] -- decoded
+    ONCE, in ascending order (a decoder reads forward), and kept on the device as equal-pitch slots (engine.FrameSlots); the schedule
+    then visits each about n_times_all_frames = 100 times without touching the source again.  The fill uploads runs of
+    FRAME_STORE_RUN_BYTES through the uploader's pinned buffers on its stream (plain copies on the current stream without one), the
+    stream every later gather runs on, so no event is kept.  The labeled frames (pv) are also kept as host arrays: data_aug needs their
+    pixels.  `budget`: the device bytes this store may take (what is left of FRAME_STORE_BYTES in its run); models/staging.frame_slots
+    decides which frames get a slot, the others are `refused`: their batches read them from the source (a labeled one from its host
+    copy) and send them through gather_frames' patch (announced once per run by the caller's `announce`)."""
+
+    def __init__(self, dataset, device, uploader=None, budget=None, announce=None):
+        import time
+        from .models.staging import frame_slots, slot_stride
+        self.dataset, self.uploader = dataset, uploader
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        idxs = dataset.idxs
+        selected = np.unique(np.concatenate([np.asarray(idxs[k], dtype=np.int64).reshape(-1) for k in ("chunk", "pv", "ph")]))
+        labeled = set(int(i) for i in idxs["pv"])
+        H, W = int(dataset.nx_in), int(dataset.ny_in)
+        self.shape, self.frame_bytes = (H, W, 3), H * W * 3
+        stride = slot_stride(self.frame_bytes)
+        self.slots, self.refused = frame_slots(selected, self.frame_bytes, FRAME_STORE_BYTES if budget is None else budget, last=labeled)
+        self.bytes = len(self.slots) * stride
+        self.host, self.last_patched = {}, 0
+        if self.refused and announce is not None:
+            announce("frame store: %d of %s's %d selected frames do not fit the %d-byte budget; their batches read them from the source"
+                     % (len(self.refused), dataset.video_name, len(selected), FRAME_STORE_BYTES))
+        t0 = time.perf_counter()
+        with torch.cuda.stream(uploader.stream if uploader is not None else torch.cuda.current_stream(self.device)):
+            data = torch.empty((len(self.slots), stride), dtype=torch.uint8, device=self.device)
+        self.frames = engine.FrameSlots(data, (H, W))
+        per_run = max(1, FRAME_STORE_RUN_BYTES // self.frame_bytes)
+        run, first = [], 0
+
+        def flush():
+            nonlocal run, first
+            if run:
+                dst = data[first:first + len(run), :self.frame_bytes]
+                block = np.stack(run).reshape(len(run), self.frame_bytes)
+                if uploader is not None:
+                    uploader.into(dst, block)
+                else:
+                    dst.copy_(torch.from_numpy(block))
+                first += len(run)
+                run = []
+
+        for f in selected.tolist():                      # ascending: slots are numbered in this order (frame_slots)
+            if f not in self.slots and f not in labeled:
+                continue
+            img = self._read(f)
+            if f in labeled:
+                self.host[f] = img
+            if f in self.slots:
+                run.append(img)
+                if len(run) == per_run:
+                    flush()
+        flush()
+        if uploader is not None:
+            uploader.stream.synchronize()                # (the fill's seconds are the copies' too; nothing trains before iteration 0)
+        self.fill_s = time.perf_counter() - t0
+        print("frame store: %s: %d frames, %d bytes on %s, filled in %.2f s" % (dataset.video_name, len(self.slots), self.bytes, self.device,
+                                                                              self.fill_s), flush=True)
+
+    def _read(self, f):
+        img = np.array(self.dataset.video_clip.frame_at(f), dtype=np.uint8)      # (a copy: an ArraySource hands out views)
+        if img.shape != self.shape:
+            raise ValueError("frame %d of %s is %s, not %s" % (f, self.dataset.video_name, img.shape, self.shape))
+        return img
+
+    def batch(self, batch_frames, replaced=None) -> Staged:
+        """The frames numbered batch_frames, in that order, as one device batch uint8 [nt, H, W, 3].  `replaced`: {position: pixels} of
+        the positions whose pixels were made for this batch (the augmented labeled frames).  Those and the frames without a slot are
+        uploaded as ONE patch; everything else comes from the store; one engine.gather_frames on the uploader's stream (the current
+        one without an uploader: event None) writes the batch.  With nothing replaced and every frame stored no pixel is uploaded."""
+        from .models.staging import gather_table
+        replaced = replaced or {}
+        src, order = gather_table(batch_frames, self.slots, replaced)
+        pixels = []
+        for p in order:
+            f = int(batch_frames[p])
+            pixels.append(replaced[p] if p in replaced else self.host[f] if f in self.host else self._read(f))
+        self.last_patched = len(order)
+        host = _as_uint8(np.stack(pixels)) if pixels else None
+        if self.uploader is None:
+            patch = torch.from_numpy(host).to(self.device) if host is not None else None
+            return Staged(engine.gather_frames(self.frames, src, patch), None)
+        patch = self.uploader(host).tensor if host is not None else None      # (same stream as the gather: no wait on the copy's event)
+        with torch.cuda.stream(self.uploader.stream):
+            out = engine.gather_frames(self.frames, src, patch)
+            ev = torch.cuda.Event()
+            ev.record(self.uploader.stream)
+        return Staged(out, ev)
 
 
 _RESIZE_REFUSED = [False]

@@ -7,7 +7,7 @@ rewriting around the run):
   step 2  fit_dgp (gm2=1, gm3=3)     -> snapshot-step2-final--0
   step 3  plot_dgp / estimate_pose   -> <proj>/videos_pred/<video>_labeled.{csv,h5[,mp4]}
 
-    python demo/run_dgp_demo.py --dlcpath data/Reaching-Mackenzie-2018-08-30 [--dlcsnapshot snapshot-step0-final--0] [--test]
+    python demo/run_dgp_demo.py --dlcpath data/Reaching-Mackenzie-2018-08-30 [--dlcsnapshot snapshot-step0-final--0] [--test] [--frame_store hip]
 
 `update_config_files` / `return_configs` (reference demo/run_dgp_demo.py:30-99) make the bundled project's relative paths absolute
 for the run and restore them afterwards; they apply to the Reaching demo project (a path that ends in
@@ -130,10 +130,12 @@ def main(argv=None):
     parser.add_argument("--batch_size", type=int, default=10,
                         help="size of the batch, if there are memory issues, decrease it value")
     parser.add_argument("--test", action="store_true", default=False)
+    parser.add_argument("--frame_store", type=str, default="off", choices=["off", "hip"],
+                        help="steps 1 and 2: 'hip' decodes the selected frames once into a device store and gathers every batch there")
     input_params = parser.parse_known_args(argv)[0]
     print(input_params)
     dlcpath, shuffle, dlcsnapshot = input_params.dlcpath, input_params.shuffle, input_params.dlcsnapshot
-    batch_size, test = input_params.batch_size, input_params.test
+    batch_size, test, frame_store = input_params.batch_size, input_params.test, input_params.frame_store
     if dlcpath is None:
         raise SystemExit("--dlcpath is required")
 
@@ -160,9 +162,9 @@ def main(argv=None):
         # step 1: DGP with labeled frames only
         _banner("Running DGP with labeled frames only")
         if test:
-            fit_dgp_labeledonly(snapshot, dlcpath, shuffle=shuffle, step=1, maxiters=2, displayiters=1)
+            fit_dgp_labeledonly(snapshot, dlcpath, shuffle=shuffle, step=1, maxiters=2, displayiters=1, frame_store=frame_store)
         else:
-            fit_dgp_labeledonly(snapshot, dlcpath, shuffle=shuffle, step=1)
+            fit_dgp_labeledonly(snapshot, dlcpath, shuffle=shuffle, step=1, frame_store=frame_store)
         snapshot = "snapshot-step1-final--0"
 
         # step 2: DGP
@@ -170,9 +172,9 @@ def main(argv=None):
         step, gm2, gm3 = 2, 1, 3
         if test:
             fit_dgp(snapshot, dlcpath, batch_size=batch_size, shuffle=shuffle, step=step, maxiters=5, displayiters=1, gm2=gm2,
-                    gm3=gm3)
+                    gm3=gm3, frame_store=frame_store)
         else:
-            fit_dgp(snapshot, dlcpath, batch_size=batch_size, shuffle=shuffle, step=step, gm2=gm2, gm3=gm3)
+            fit_dgp(snapshot, dlcpath, batch_size=batch_size, shuffle=shuffle, step=step, gm2=gm2, gm3=gm3, frame_store=frame_store)
         snapshot = "snapshot-step{}-final--0".format(step)
 
         # step 3: predict on all videos in videos_dgp

@@ -544,6 +544,19 @@ int  dgp_target_maps(const double* d_entries, const int32_t* d_offsets, const do
                      double locref_stdev, int32_t weigh_only_present_joints, float* scmap, float* weights, float* lmap, float* lmask,
                      void* stream);
 
+/* ---- A DGP batch gathered on the device from frames kept there (replaces the per-iteration frame reads of Dataset.load_data,
+ * DGP/dataset.py:811-821, and the host stack fed at fitdgp.py:762-764).
+ * store: device uint8, n_slots frames at `store + slot * slot_stride`; slot_stride is in BYTES, a multiple of 16 and at least
+ * frame_bytes (offsets are 64-bit: a store may pass 4 GiB).  patch: device uint8 [m][frame_bytes], packed: the frames uploaded for
+ * this batch alone.  h_src: HOST int32 [nt]; output frame f is slot h_src[f] when h_src[f] >= 0 and patch frame -1 - h_src[f]
+ * otherwise.  out: device uint8 [nt][frame_bytes], packed.  The table is checked here, before anything is launched (an entry at or
+ * above n_slots or below -m, a bad pitch, a null pointer that would be read: DGP_ERR_INVALID), and reaches the kernel inside the
+ * launch arguments, 64 frames per launch: no copy is issued and h_src may be reused as soon as the call returns.  nt == 0 launches
+ * nothing.  A pure copy with plain vector loads and stores: 16 bytes per access when frame_bytes is a multiple of 16 and store, patch
+ * and out are 16-byte aligned, single bytes otherwise.  store and patch may be NULL when n_slots / m is 0. */
+int  dgp_gather_frames_u8(const uint8_t* store, int64_t n_slots, int64_t slot_stride, const uint8_t* patch, int32_t m,
+                          const int32_t* h_src, int32_t nt, int64_t frame_bytes, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
