@@ -131,6 +131,11 @@ SYMBOLS = {
     "dgp_target_maps": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _i32,
                                   _vp, _vp, _vp, _vp, _vp]),
     "dgp_gather_frames_u8": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _i32, _vp, _i32, C.c_int64, _vp, _vp]),
+    "dgp_aug_affine_u8": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(C.c_double), _vp]),
+    "dgp_aug_blur3_u8": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_f32), _vp]),
+    "dgp_aug_dropout_u8": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "dgp_aug_elastic_u8": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "dgp_aug_noise_u8": (C.c_int, [_vp, _vp, _i32, _i32, _f32, _i32, C.c_uint64, _vp]),
 }
 
 _lib = None

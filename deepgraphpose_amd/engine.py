@@ -964,12 +964,13 @@ def resize_plan_f(in_size: int, out_size: int, filter) -> Tuple[int, np.ndarray,
     return ks.value, bounds, coeffs
 
 
-def window_resize(image: torch.Tensor, window, out_hw, filter="box", mirror: bool = False) -> torch.Tensor:
+def window_resize(image: torch.Tensor, window, out_hw, filter="box", mirror: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The inclusive window (x0, y0, x1, y1) of ONE device uint8 RGB image [H, W, 3] (None: the whole image), resampled to out_hw =
     (rows, cols) with Pillow's `filter` ("box" | "bilinear" | "bicubic") and, with `mirror`, flipped left to right: what the step-0
     loader's crop_image + imresize (+ np.fliplr) give (dlc_dataset.py), the bytes Pillow's.  The window is read in place.  One
     dgp_window_resize_u8 launch on the current stream; the two tables are built on the host and uploaded in one small copy (samples
-    differ in size from one to the next, so they are not kept).  Returns uint8 [rows, cols, 3]."""
+    differ in size from one to the next, so they are not kept).  Returns uint8 [rows, cols, 3]; `out` (that shape, contiguous, not
+    overlapping the image) is filled in place and returned."""
     lib = _lib.load()
     _need_cuda(image, torch.uint8, "image")
     if image.dim() != 3 or image.shape[-1] != 3:
@@ -985,7 +986,12 @@ def window_resize(image: torch.Tensor, window, out_hw, filter="box", mirror: boo
     ksy, by, cy = resize_plan_f(y1 - y0 + 1, rh, fid)
     nx = bx.size + cx.size
     plans = torch.from_numpy(np.concatenate([bx.ravel(), cx.ravel(), by.ravel(), cy.ravel()])).to(dev)
-    out = torch.empty((rh, rw, 3), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((rh, rw, 3), dtype=torch.uint8, device=dev)
+    else:
+        _need_cuda(out, torch.uint8, "out")
+        if tuple(out.shape) != (rh, rw, 3) or out.device != dev:
+            raise _lib.DgpError("window_resize: out must be %s on %s, got %s on %s" % ((rh, rw, 3), dev, tuple(out.shape), out.device))
     _lib.check(lib.dgp_window_resize_u8(_ptr(image), H, W, x0, y0, x1, y1, rh, rw, fid, 1 if mirror else 0, _ptr(out), _ptr(plans),
                                         C.c_void_p(plans.data_ptr() + 4 * nx), ksx, ksy, _stream(dev)), "dgp_window_resize_u8")
     return out
@@ -1085,3 +1091,190 @@ def gather_frames(store, src, patch: Optional[torch.Tensor] = None, out: Optiona
                                         table.ctypes.data_as(C.c_void_p), nt, frame_bytes, _ptr(out), _stream(dev)),
                "dgp_gather_frames_u8")
     return out
+
+
+# ---- the augmenters of the DGP drivers' labeled frames (csrc/dgp_augment.hip): one frame, one stage, one launch on the current stream
+
+def _aug_pair(src: torch.Tensor, dst: torch.Tensor, who: str):
+    _need_cuda(src, torch.uint8, "src")
+    _need_cuda(dst, torch.uint8, "dst")
+    if src.dim() != 3 or src.shape[-1] != 3 or src.shape != dst.shape or src.device != dst.device:
+        raise _lib.DgpError("%s: src and dst must be [H, W, 3] frames of one shape on one device, got %s and %s"
+                            % (who, tuple(src.shape), tuple(dst.shape)))
+    return int(src.shape[0]), int(src.shape[1])
+
+
+def aug_affine(src: torch.Tensor, dst: torch.Tensor, coef) -> torch.Tensor:
+    """dst = Image.transform(AFFINE, coef, BILINEAR) of src, Pillow's bytes (dgp_aug_affine_u8).  coef: Pillow's six coefficients;
+    (-1, 0, W, 0, 1, 0) is np.fliplr.  src, dst: device uint8 [H, W, 3], distinct."""
+    H, W = _aug_pair(src, dst, "aug_affine")
+    coef = [float(v) for v in coef]
+    if len(coef) != 6:
+        raise _lib.DgpError("aug_affine: six coefficients, got %d" % len(coef))
+    _lib.check(_lib.load().dgp_aug_affine_u8(_ptr(src), _ptr(dst), H, W, (C.c_double * 6)(*coef), _stream(src.device)), "dgp_aug_affine_u8")
+    return dst
+
+
+def aug_blur3(src: torch.Tensor, dst: torch.Tensor, kernel) -> torch.Tensor:
+    """dst = the host motion blur of src with the 3 x 3 fp32 `kernel` (augment.apply_motion_blur's bytes; dgp_aug_blur3_u8)"""
+    H, W = _aug_pair(src, dst, "aug_blur3")
+    k = np.ascontiguousarray(kernel, dtype=np.float32).reshape(-1)
+    if k.size != 9:
+        raise _lib.DgpError("aug_blur3: a 3 x 3 kernel, got %d weights" % k.size)
+    _lib.check(_lib.load().dgp_aug_blur3_u8(_ptr(src), _ptr(dst), H, W, (C.c_float * 9)(*k.tolist()), _stream(src.device)), "dgp_aug_blur3_u8")
+    return dst
+
+
+def aug_dropout(src: torch.Tensor, dst: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """dst = src with the pixels under the coarse mask zeroed (augment.apply_coarse_dropout's bytes; dgp_aug_dropout_u8).  mask: device
+    uint8 [h, w], non-zero = dropped, 1 <= h <= H and 1 <= w <= W."""
+    H, W = _aug_pair(src, dst, "aug_dropout")
+    _need_cuda(mask, torch.uint8, "mask")
+    if mask.dim() != 2 or mask.device != src.device:
+        raise _lib.DgpError("aug_dropout: mask must be [h, w] on %s, got %s on %s" % (src.device, tuple(mask.shape), mask.device))
+    _lib.check(_lib.load().dgp_aug_dropout_u8(_ptr(src), _ptr(dst), H, W, _ptr(mask), int(mask.shape[0]), int(mask.shape[1]),
+                                              _stream(src.device)), "dgp_aug_dropout_u8")
+    return dst
+
+
+def aug_elastic(src: torch.Tensor, dst: torch.Tensor, field: torch.Tensor) -> torch.Tensor:
+    """dst[p] = src[p + d(p)], bilinear with zeros outside, d the 4 x bilinear upsampling of the coarse field (dgp_aug_elastic_u8).
+    field: device fp32 [2, hc, wc] (dx, dy), hc = ceil((H - 1) / 4) + 1 and wc alike (augment.draw_elastic's)."""
+    H, W = _aug_pair(src, dst, "aug_elastic")
+    _need_cuda(field, torch.float32, "field")
+    if field.dim() != 3 or field.shape[0] != 2 or field.device != src.device:
+        raise _lib.DgpError("aug_elastic: field must be [2, hc, wc] on %s, got %s on %s" % (src.device, tuple(field.shape), field.device))
+    _lib.check(_lib.load().dgp_aug_elastic_u8(_ptr(src), _ptr(dst), H, W, _ptr(field), int(field.shape[1]), int(field.shape[2]),
+                                              _stream(src.device)), "dgp_aug_elastic_u8")
+    return dst
+
+
+def aug_noise(src: torch.Tensor, dst: torch.Tensor, scale: float, per_channel: bool, key: int) -> torch.Tensor:
+    """dst = clip(rint(src + scale z)), z standard normal from Philox4x32-10 under the 64-bit `key`, addressed by the element index
+    (one z per pixel without per_channel): the same key gives the same bytes whatever the launch shape (dgp_aug_noise_u8)"""
+    H, W = _aug_pair(src, dst, "aug_noise")
+    key = int(key)
+    if not 0 <= key < 2 ** 64:
+        raise _lib.DgpError("aug_noise: key must be a uint64, got %r" % (key,))
+    _lib.check(_lib.load().dgp_aug_noise_u8(_ptr(src), _ptr(dst), H, W, float(scale), 1 if per_channel else 0, key, _stream(src.device)),
+               "dgp_aug_noise_u8")
+    return dst
+
+
+# two scratch frames per (device, H, W): the stages of a plan run from one into the other
+_AUG_SCRATCH: Dict[tuple, torch.Tensor] = {}
+
+
+def _aug_scratch(dev, H: int, W: int) -> torch.Tensor:
+    key = (str(dev), H, W)
+    if key not in _AUG_SCRATCH:
+        if len(_AUG_SCRATCH) >= 16:                # as _RESIZE_PLANS: drop the oldest, after whatever stream still reads it
+            old = next(iter(_AUG_SCRATCH))
+            torch.cuda.synchronize(_AUG_SCRATCH[old].device)
+            del _AUG_SCRATCH[old]
+        _AUG_SCRATCH[key] = torch.empty((2, H, W, 3), dtype=torch.uint8, device=dev)
+    scratch = _AUG_SCRATCH[key]
+    scratch.record_stream(torch.cuda.current_stream(dev))
+    return scratch
+
+
+def _aug_crop_and_pad(src: torch.Tensor, dst: torch.Tensor, params) -> None:
+    """CropAndPad(keep_size=True): the core of src, inside zeros where a side pads, resized back by window_resize (Pillow's BILINEAR)"""
+    from .augment import crop_geometry
+    H, W = int(src.shape[0]), int(src.shape[1])
+    x0, x1, y0, y1, pt, pb, pl, pr = crop_geometry(params, H, W)
+    if pt or pb or pl or pr:
+        padded = torch.zeros((y1 - y0 + pt + pb, x1 - x0 + pl + pr, 3), dtype=torch.uint8, device=src.device)
+        padded[pt:pt + y1 - y0, pl:pl + x1 - x0] = src[y0:y1, x0:x1]
+        window_resize(padded, None, (H, W), "bilinear", out=dst)
+    else:
+        window_resize(src, (x0, y0, x1 - 1, y1 - 1), (H, W), "bilinear", out=dst)
+
+
+def augment_frames(frames: torch.Tensor, plans, positions) -> torch.Tensor:
+    """Apply host-drawn augmentation plans (augment.NumpyAugPipeline.plan(H, W, noise="key")) to frames of a device batch, in place:
+    plans[i] is the plan of frames[positions[i]].  frames: uint8 [n, H, W, 3].  A plan's stages run one launch each on the current
+    stream, chained through two scratch frames kept per (device, H, W); the last one writes frames[position].  The plans' tables (dropout
+    masks, elastic fields) go up in one small pinned copy per call.  fliplr, rotate, motion_blur, coarse_dropout and crop_and_pad give
+    the bytes of augment.apply_<stage>; elastic is within rounding of the float64 value like the host's fp32 stage; gaussian_noise is a
+    different stream from the same distribution as the host's (Philox4x32-10 under the plan's key).  Everything is checked before the
+    first launch; a plan built with noise="field" is a ValueError.  An empty plan launches nothing.  Returns `frames`."""
+    from .augment import ELASTIC_STEP, STAGES
+    _need_cuda(frames, torch.uint8, "frames")
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise _lib.DgpError("augment_frames: frames must be [n, H, W, 3], got %s" % (tuple(frames.shape),))
+    n, H, W = (int(v) for v in frames.shape[:3])
+    positions = [int(p) for p in positions]
+    plans = list(plans)
+    if len(plans) != len(positions):
+        raise _lib.DgpError("augment_frames: %d plans for %d positions" % (len(plans), len(positions)))
+    if len(set(positions)) != len(positions) or any(not 0 <= p < n for p in positions):
+        raise _lib.DgpError("augment_frames: positions %r must be distinct frames of a batch of %d" % (positions, n))
+    hc, wc = -(-(H - 1) // ELASTIC_STEP) + 1, -(-(W - 1) // ELASTIC_STEP) + 1
+    fields, masks, work = [], [], []
+    for plan in plans:                                               # ---- check everything, collect the tables
+        ops = []
+        for stage, params in plan:
+            if stage not in STAGES:
+                raise _lib.DgpError("augment_frames: unknown stage %r" % (stage,))
+            if stage == "fliplr" and not params["flip"]:
+                continue
+            table = None
+            if stage == "gaussian_noise" and params.get("key") is None:
+                raise ValueError("augment_frames: this plan carries the host's noise field; build plans for the device with "
+                                 "plan(H, W, noise=\"key\")")
+            if stage == "coarse_dropout":
+                m = np.ascontiguousarray(params["mask"]).astype(np.uint8)
+                if m.ndim != 2 or not (1 <= m.shape[0] <= H and 1 <= m.shape[1] <= W):
+                    raise _lib.DgpError("augment_frames: a dropout mask of shape %s does not belong to a %d x %d frame" % (m.shape, H, W))
+                table = ("mask", len(masks))
+                masks.append(m)
+            if stage == "elastic":
+                f = np.ascontiguousarray(params["field"], dtype=np.float32)
+                if f.shape != (2, hc, wc):
+                    raise _lib.DgpError("augment_frames: an elastic field of shape %s does not belong to a %d x %d frame (2, %d, %d)"
+                                        % (f.shape, H, W, hc, wc))
+                table = ("field", len(fields))
+                fields.append(f)
+            ops.append((stage, params, table))
+        work.append(ops)
+    if min(H, W) < 2 and any(work):
+        raise _lib.DgpError("augment_frames: frames must be at least 2 x 2, got %d x %d" % (H, W))
+    dev = frames.device
+    dev_fields, dev_masks = [], []
+    if fields or masks:                                              # ---- one pinned copy: the fp32 fields first, then the masks
+        host = np.concatenate([f.ravel().view(np.uint8) for f in fields] + [m.ravel() for m in masks])
+        pinned = torch.empty(host.size, dtype=torch.uint8).pin_memory()
+        pinned.numpy()[...] = host
+        packed = pinned.to(dev, non_blocking=True)
+        at = 0
+        for f in fields:
+            dev_fields.append(packed[at:at + f.nbytes].view(torch.float32).view(f.shape))
+            at += f.nbytes
+        for m in masks:
+            dev_masks.append(packed[at:at + m.size].view(m.shape))
+            at += m.size
+    scratch = _aug_scratch(dev, H, W) if any(work) else None
+    for ops, pos in zip(work, positions):                            # ---- the launches
+        frame = frames[pos]
+        src = frame
+        if len(ops) == 1:                                            # no stage runs in place: a lone stage reads a copy
+            src = scratch[0].copy_(frame)
+        for i, (stage, params, table) in enumerate(ops):
+            dst = frame if i == len(ops) - 1 else scratch[i % 2]
+            if stage == "fliplr":
+                aug_affine(src, dst, (-1.0, 0.0, float(W), 0.0, 1.0, 0.0))
+            elif stage == "rotate":
+                aug_affine(src, dst, params["coef"])
+            elif stage == "motion_blur":
+                aug_blur3(src, dst, params["kernel"])
+            elif stage == "coarse_dropout":
+                aug_dropout(src, dst, dev_masks[table[1]])
+            elif stage == "elastic":
+                aug_elastic(src, dst, dev_fields[table[1]])
+            elif stage == "gaussian_noise":
+                aug_noise(src, dst, params["scale"], params["per_channel"], params["key"])
+            else:
+                _aug_crop_and_pad(src, dst, params)
+            src = dst
+    return frames

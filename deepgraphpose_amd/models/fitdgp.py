@@ -14,7 +14,8 @@ TensorFlow V2 bundles `snapshot-step{k}--{it}.{index,data-00000-of-00001}`, `sna
 `snapshot-step{k}-final--0.*` plus the `checkpoint` state file, written without TensorFlow (weights_io.Saver,
 tf_checkpoint.py); DGP_SNAPSHOT_FORMAT=npz writes `.npz` files of the same names instead.
 Host-side hooks: augmentation of the labeled frames (`aug`; deepgraphpose_amd/augment.py: imgaug's pipeline when imgaug is
-installed, the numpy / scipy restatement of the same seven augmenters otherwise) and the Farneback optical flow feeding the
+installed, the numpy / scipy restatement of the same seven augmenters otherwise; fit_dgp*(aug_backend="hip") applies the numpy
+pipeline's plan on the device, csrc/dgp_augment.hip) and the Farneback optical flow feeding the
 temporal clique (`wt > 0`): OpenCV's on the host when cv2 is importable, otherwise the HIP kernels (csrc/dgp_flow.hip) on the
 device -- fit_dgp(flow_backend="cv2" | "hip" | "auto").
 """
@@ -34,7 +35,8 @@ from .. import config as dcfg
 from .. import dist as ddist
 from ..dataset import MultiDataset, coord2map
 from ..loss import DGPHyper
-from ..staged import _FrameStore, _FrameUploader, _ImageCache, _device_flow, _device_locref, _device_sample, _flow_of, _on_current_stream
+from ..staged import (_FrameStore, _FrameUploader, _ImageCache, _device_augment, _device_flow, _device_locref, _device_sample, _flow_of,
+                      _on_current_stream)
 from .fitdgp_util import gen_batch
 
 PREFETCH_DEPTH = 2          # iterations of host batches built ahead on a background thread (0: inline); a measured setting, not a switch
@@ -43,7 +45,8 @@ PREP_BACKENDS = ("auto", "host", "hip")
 # the sample-preparation backend of the last fit_* run ("host" | "hip"), like eval.RUN_STATS["prep_backend"], and its frame stores: None
 # with frame_store="off", else {"frames": stored, "bytes": on the device, "refused": selected frames without a slot, "fill_s": seconds
 # of the fill, "patched": frames of the LAST batch that were uploaded instead of gathered from a slot}
-PREP_STATS = {"backend": None, "frame_store": None}
+# "aug": None with aug=False, else {"backend": aug_backend, "frames": labeled frames augmented so far, "stages": {name: plans holding it}}
+PREP_STATS = {"backend": None, "frame_store": None, "aug": None}
 
 
 def resolve_prep_backend(backend: str = "auto", device=None) -> str:
@@ -252,12 +255,51 @@ def _save(saver, trainer, prefix, step, it, final, debug="", keep_optimizer_stat
         saver.save(w, prefix + "-step" + str(step) + debug + "-final-", global_step=0)
 
 
-def _augment(dgp_cfg):
-    """The augmentation pipeline of the labeled frames (fitdgp.py:446-447, 735-736: build_aug(apply_prob=0.8)), or None."""
+AUG_BACKENDS = ("host", "hip")
+_SAID_NUMPY_PLANS = [False]
+
+
+def resolve_aug_backend(aug_backend: str = "host", device=None) -> str:
+    """"host" | "hip" for fit_dgp*(aug_backend=...): where the pixels of the labeled frames are augmented.  "host": the pipeline object
+    runs on the prefetch thread (augment.data_aug).  "hip": the draws and the labels stay on the host (augment.plan_aug) and the pixels
+    are made on the device from the plan (engine.augment_frames); `device`, the trainer's, must then be a GPU (None: only the name is
+    checked)."""
+    if aug_backend not in AUG_BACKENDS:
+        raise ValueError("aug backend must be one of %s, not %r" % (" | ".join(AUG_BACKENDS), aug_backend))
+    if aug_backend == "hip" and device is not None:
+        import torch
+        if torch.device(device).type != "cuda":
+            raise ValueError("aug_backend='hip' augments the labeled frames on the GPU, but the trainer's device is %s; use "
+                             "aug_backend='host'" % (device,))
+    return aug_backend
+
+
+def _aug_pipeline(dgp_cfg, aug_backend="host"):
+    """The augmentation pipeline of the labeled frames (fitdgp.py:446-447, 735-736: build_aug(apply_prob=0.8)), or None.  aug_backend
+    "hip" needs a plan, which only the numpy pipeline draws: it is built even when imgaug is importable (said once)."""
     if not dgp_cfg.aug:
         return None
     from ..augment import build_aug
-    return build_aug(apply_prob=0.8)
+    if aug_backend != "hip":
+        return build_aug(apply_prob=0.8)
+    try:
+        import imgaug  # noqa: F401
+        if not _SAID_NUMPY_PLANS[0]:
+            _SAID_NUMPY_PLANS[0] = True
+            print("aug_backend='hip': the augmentation is planned by the numpy pipeline (imgaug's own pipeline object draws no plan)",
+                  flush=True)
+    except ImportError:
+        pass
+    return build_aug(apply_prob=0.8, backend="numpy")
+
+
+def _count_aug(plans):
+    """PREP_STATS["aug"]: the frames augmented so far in this run and how many of their plans hold each stage"""
+    from ..augment import plan_stages
+    stats = PREP_STATS["aug"]
+    stats["frames"] += len(plans)
+    for stage, k in plan_stages(plans).items():
+        stats["stages"][stage] = stats["stages"].get(stage, 0) + k
 
 
 def _dp_setup():
@@ -514,7 +556,7 @@ def _open_project(snapshot, dlcpath, shuffle, trainingsetindex, frame_sources, h
 
 def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_frames, schedule, entry, progress, finished, step,
            save_every, displayiters, debug="", flow_backend=None, prep_backend="host", optimizer="sgd", keep_optimizer_state=False,
-           frame_store="off"):
+           frame_store="off", aug_backend="host"):
     """The loop of both DGP drivers.  schedule() draws the run's entries, entry(data_batcher, e) -> (dataset_i, visible frames, hidden
     frames) of one of them, progress(...) prints a displayed iteration's lines, `finished` is the closing line.  Iteration `it` trains on
     entry _dp_index(it) and rank 0 saves every `save_every` iterations and after the last.  labeled_only: the objective is
@@ -523,13 +565,19 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
     (the reference's MomentumOptimizer) | "adam", both behind clip_by_global_norm(10); keep_optimizer_state as in fit_dlc.
     frame_store "hip": every dataset's selected frames are put on the device before iteration 0 (_frame_stores) and make_batch
     gathers the batch there: the Dataset gives the index sets and labels without pixels, only the labeled frames' host copies go
-    through data_aug (the same draws in the same order), and the augmented frames travel as the gather's patch."""
+    through data_aug (the same draws in the same order), and the augmented frames travel as the gather's patch.
+    aug_backend "hip": make_batch draws the plans of the labeled frames and moves their labels on the host (augment.plan_aug: data_aug's
+    draws in data_aug's order), gets the batch onto the device as it would anyway -- the store's gather, now without a patch for the
+    labeled frames, or the upload -- and has engine.augment_frames make the pixels there (_device_augment), on the uploader's stream
+    and before the batch's event is recorded."""
     from .. import weights_io
     from .session import Placeholder, TrainSession
     dgp_cfg, nj = data_batcher.dlc_config, data_batcher.nj
     loss, total_loss, total_loss_visible, placeholders = dgp_loss(data_batcher, dgp_cfg)
-    pipeline = _augment(dgp_cfg)                 # before the expensive setup: a broken augmentation stack fails here
+    pipeline = _aug_pipeline(dgp_cfg, aug_backend)        # before the expensive setup: a broken augmentation stack fails here
     trainer = _make_trainer(data_batcher, init_weights, max_frames=max_frames, device=local_rank)
+    if pipeline is not None:
+        resolve_aug_backend(aug_backend, trainer.device)
     learning_rate = Placeholder("learning_rate")
     if keep_optimizer_state:
         _restore_optimizer_state(trainer, init_weights, optimizer)
@@ -540,6 +588,7 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
     uploader = _make_uploader(trainer)
     prep_backend = resolve_prep_backend(prep_backend, trainer.device)
     PREP_STATS["backend"], PREP_STATS["frame_store"] = prep_backend, None
+    PREP_STATS["aug"] = None if pipeline is None else {"backend": aug_backend, "frames": 0, "stages": {}}
     stores = _frame_stores(data_batcher, trainer.device, uploader) if frame_store == "hip" else None
     entries = schedule()
     n_sched = len(entries)
@@ -555,15 +604,18 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
         (vis, hid, _, images, joint_loc, wt_mask, _, addn), _ = data_batcher.next_batch(0, dataset_i, vis_b, hid_b, pixels=stores is None)
         all_frame = np.sort(list(vis) + list(hid))
         vis_within = [int(np.where(all_frame == i)[0][0]) for i in vis]
-        replaced = None
+        replaced, plans = None, None
         if pipeline is not None and dgp_cfg.wt == 0 and len(vis_within) > 0:      # fitdgp.py:481-482, 778-779
-            from ..augment import data_aug
-            if stores is None:
+            from ..augment import data_aug, plan_aug
+            if aug_backend == "hip":                                  # the draws and the labels here, the pixels on the device below
+                plans, joint_loc = plan_aug(len(vis), int(d.nx_in), int(d.ny_in), joint_loc, pipeline, dgp_cfg)
+            elif stores is None:
                 images, joint_loc = data_aug(images, vis_within, joint_loc, pipeline, dgp_cfg)
             else:                                                     # the labeled frames alone: data_aug reads no other
                 labeled = np.stack([stores[dataset_i].host[int(i)] for i in vis])
                 labeled, joint_loc = data_aug(labeled, list(range(len(vis))), joint_loc, pipeline, dgp_cfg)
                 replaced = dict(zip(vis_within, labeled))
+            _count_aug(plans if plans is not None else getattr(pipeline, "last_plans", [[]] * len(vis)))
         if prep_backend == "hip":                                     # (after data_aug, which moves joint_loc)
             lmap, lmask = _device_locref(uploader, trainer.device, joint_loc, len(all_frame), vis_within, d.nx_out, d.ny_out, nj, dgp_cfg)
         else:
@@ -572,6 +624,8 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
         if stores is not None:                                        # the batch is gathered on the device, the flow computed from it
             frames = stores[dataset_i].batch(all_frame, replaced)
             PREP_STATS["frame_store"]["patched"] = stores[dataset_i].last_patched
+            if plans is not None:
+                frames = _device_augment(uploader, trainer.device, frames.tensor, plans, vis_within)
             images = frames.tensor
             if dgp_cfg.wt > 0:
                 frames, vector_field = _flow_of(uploader, images)
@@ -580,6 +634,8 @@ def _train(data_batcher, init_weights, world, local_rank, *, labeled_only, max_f
         elif dgp_cfg.wt > 0:                                          # temporal clique: flow field from the host hook
             from .fitdgp_util import learn_wt
             vector_field = learn_wt(images, backend=flow_backend)
+        elif plans is not None:                                       # the batch goes up now, the labeled frames are augmented there
+            frames = _device_augment(uploader, trainer.device, images, plans, vis_within)
         feed_dict = _feed(placeholders, images, joint_loc, lmap, lmask, addn, None if labeled_only else wt_mask, vector_field,
                           dgp_cfg.wt, d.nx_out, d.ny_out, learning_rate, dgp_cfg.lr)
         if frames is None and uploader is not None:
@@ -632,14 +688,20 @@ def _labeled_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 
 def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, displayiters=5, maxiters=50000, ns=10,
                         nc=2048, n_max_frames=2000, aug=True, trainingsetindex=0, frame_sources=None, prep_backend="auto", optimizer="sgd",
-                        keep_optimizer_state=False, frame_store="off"):
+                        keep_optimizer_state=False, frame_store="off", aug_backend="host"):
     """Run DGP with labeled frames only (fitdgp.py:257-546): batch = one labeled frame, loss =
     total_loss_visible.  `frame_sources` (new, optional) injects already-open frame sources per video.
     prep_backend: "host" | "hip" | "auto" (resolve_prep_backend): where the locref target maps are built.
     optimizer: "sgd", the reference's hard-coded MomentumOptimizer(lr, 0.9), or "adam", AdamOptimizer(lr); both on gradients clipped to a
     global norm of 10.  keep_optimizer_state: see fit_dlc.
     frame_store: "off" | "hip" (resolve_frame_store).  "hip": the labeled frames are read once, kept on the device (and on the host, for
-    the augmentation), and every iteration's frame is gathered there; only an augmented frame is uploaded."""
+    the augmentation), and every iteration's frame is gathered there; only an augmented frame is uploaded.
+    aug_backend: "host" | "hip" (resolve_aug_backend), with aug=True.  "hip": the augmentation is drawn on the host as a plan
+    (augment.NumpyAugPipeline.plan: the same draws in the same order, so the labels and every other feed are the host path's, bit for
+    bit) and applied to the frame on the device (engine.augment_frames, csrc/dgp_augment.hip); with a frame store nothing is uploaded.
+    Five of the seven stages give the host stages' bytes, elastic is within rounding of float64 like the host's, and the additive
+    noise is a different stream from the same distribution as the host's PCG64 ziggurat field."""
+    aug_backend = resolve_aug_backend(aug_backend)
     prep_backend = resolve_prep_backend(prep_backend)
     frame_store = resolve_frame_store(frame_store)
     optimizer = resolve_optimizer(optimizer)
@@ -658,7 +720,8 @@ def fit_dgp_labeledonly(snapshot, dlcpath, shuffle=1, step=1, saveiters=1000, di
 
     _train(*run, labeled_only=True, max_frames=1, schedule=schedule, entry=_labeled_entry, progress=_labeled_progress,
            finished="Finished training {} iterations\n", step=step, save_every=saveiters, displayiters=displayiters,
-           prep_backend=prep_backend, optimizer=optimizer, keep_optimizer_state=keep_optimizer_state, frame_store=frame_store)
+           prep_backend=prep_backend, optimizer=optimizer, keep_optimizer_state=keep_optimizer_state, frame_store=frame_store,
+           aug_backend=aug_backend)
     return None
 
 
@@ -687,7 +750,7 @@ def _window_progress(dataset_i, vis_b, hid_b, t0, loss_eval):
 def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000, displayiters=5, maxiters=200000, ns=10,
             nc=2048, n_max_frames=2000, gm2=0, gm3=0, nepoch=100, wt=0, aug=True, debug="", trainingsetindex=0,
             frame_sources=None, flow_backend="auto", prep_backend="auto", optimizer="sgd", keep_optimizer_state=False,
-            frame_store="off"):
+            frame_store="off", aug_backend="host"):
     """Run DGP (fitdgp.py:549-845): batches of `batch_size` consecutive frames of the selected windows, at least
     one labeled frame per batch, loss = total_loss (visible + hidden CE, locref, spatial clique; + the temporal clique when wt > 0).
     flow_backend (wt > 0): "cv2" | "hip" | "auto" as learn_wt's backend.  With "hip" the flow magnitude is computed on the device from
@@ -698,8 +761,11 @@ def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000,
     frame_store: "off" | "hip" (resolve_frame_store).  "hip": the selected frames (idxs chunk, pv, ph of every video) are read from their
     source once, in ascending order, and kept on the device within staged.FRAME_STORE_BYTES; a batch is one engine.gather_frames launch
     over them plus a patch of what was made for it (augmented labeled frames, frames the store could not hold), and with wt > 0 the
-    flow is computed from the gathered batch, which needs flow_backend "hip" (a host flow with "hip" is a ValueError)."""
+    flow is computed from the gathered batch, which needs flow_backend "hip" (a host flow with "hip" is a ValueError).
+    aug_backend: as in fit_dgp_labeledonly; with "hip" and a frame store only the frames the store refused are patched.  wt > 0 skips
+    the augmentation with either backend, as the reference does."""
     from .fitdgp_util import resolve_flow_backend
+    aug_backend = resolve_aug_backend(aug_backend)
     optimizer = resolve_optimizer(optimizer)
     prep_backend = resolve_prep_backend(prep_backend)
     flow_backend = resolve_flow_backend(flow_backend) if wt > 0 else None
@@ -723,5 +789,5 @@ def fit_dgp(snapshot, dlcpath, batch_size=10, shuffle=1, step=2, saveiters=1000,
     _train(*run, labeled_only=False, max_frames=batch_size + 1, schedule=schedule, entry=_window_entry, progress=_window_progress,
            finished="Finished {} iterations\n", step=step, save_every=max(int(saveiters / batch_size), 1), displayiters=displayiters,
            debug=debug, flow_backend=flow_backend, prep_backend=prep_backend, optimizer=optimizer,
-           keep_optimizer_state=keep_optimizer_state, frame_store=frame_store)
+           keep_optimizer_state=keep_optimizer_state, frame_store=frame_store, aug_backend=aug_backend)
     return None

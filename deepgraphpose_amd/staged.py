@@ -4,7 +4,7 @@ The fit drivers build the batch of iteration it + 1 on a prefetch thread while t
 batch's frames on a stream of its own.  What crosses from that stream to the consumer's is a `Staged` pair: the device tensor and the event
 behind the last work that wrote it.  The pair is a value, so the event cannot get lost on the way the way an attribute of the tensor would
 (a slice, a view or .to() returns a new tensor object): whoever derives another tensor from `tensor` wraps it with the same `ready`.
-Producers: _FrameUploader, _device_flow, _FrameStore.batch.  Consumers: _frames_to_device (TrainSession.run) and dgp_loss_prepare
+Producers: _FrameUploader, _device_flow, _FrameStore.batch, _device_augment.  Consumers: _frames_to_device (TrainSession.run) and dgp_loss_prepare
 (loss.py), both through _on_current_stream."""
 from __future__ import annotations
 
@@ -101,6 +101,23 @@ def _flow_of(uploader, dev):
         ev = torch.cuda.Event()
         ev.record(uploader.stream)
     return Staged(dev, ev), Staged(mag, ev)
+
+
+def _device_augment(uploader, device, images, plans, positions) -> Staged:
+    """aug_backend="hip": the batch -- a host array, uploaded here (by the uploader, on its stream, when prefetching), or a device
+    tensor written on that stream (a _FrameStore's gather) -- with the plans of its labeled frames applied on the device
+    (engine.augment_frames) on the same stream.  -> Staged(frames, the event behind the last stage); without an uploader everything
+    runs on the current stream and the event is None."""
+    on_device = isinstance(images, torch.Tensor) and images.is_cuda
+    if uploader is None:
+        dev = images if on_device else torch.from_numpy(_as_uint8(images)).to(device)
+        return Staged(engine.augment_frames(dev, plans, positions), None)
+    dev = images if on_device else uploader(images).tensor      # (same stream as the stages: no wait on the copy's own event)
+    with torch.cuda.stream(uploader.stream):
+        engine.augment_frames(dev, plans, positions)
+        ev = torch.cuda.Event()
+        ev.record(uploader.stream)
+    return Staged(dev, ev)
 
 
 def _frames_to_device(trainer, images):

@@ -557,6 +557,31 @@ int  dgp_target_maps(const double* d_entries, const int32_t* d_offsets, const do
 int  dgp_gather_frames_u8(const uint8_t* store, int64_t n_slots, int64_t slot_stride, const uint8_t* patch, int32_t m,
                           const int32_t* h_src, int32_t nt, int64_t frame_bytes, uint8_t* out, void* stream);
 
+/* ---- The augmenters of the DGP drivers' labeled frames on the device (replaces the pixel half of build_aug / data_aug,
+ * DGP/models/fitdgp_util.py:412-451; host counterpart: deepgraphpose_amd/augment.py).  Every random number is drawn on the host; a
+ * call gets the drawn parameters and ONE frame: src, dst device uint8 [H][W][3], packed, not overlapping, one launch on `stream`, one
+ * thread per pixel, plain loads and stores.  Checked before the launch (DGP_ERR_INVALID): null pointers, H, W >= 2, a frame below
+ * 2 GiB, src / dst overlap, finite parameters, table sizes that belong to (H, W).
+ * affine: Pillow's Image.transform(AFFINE, BILINEAR) with the six HOST coefficients coef = (a, b, c, d, e, f): the sample position is
+ *   (a (x + .5) + b (y + .5) + c, d (x + .5) + e (y + .5) + f) in double; 0 outside [0, W) x [0, H); else .5 off, floor, clamped
+ *   neighbours, p0 + (p1 - p0) t along x then y (the row below replaced by the row itself past the edge), truncated.  Pillow's bytes.
+ *   np.fliplr is coef = (-1, 0, W, 0, 1, 0), an exact permutation.
+ * blur3: k = 3 x 3 HOST fp32 weights; out = rint(sum over (yy, xx) in that order of k[2 - yy][2 - xx] * src[y + yy - 1][x + xx - 1]),
+ *   zero weights skipped, indices clamped to the frame, fp32 products and sums rounded one by one, clipped to [0, 255].
+ * dropout: d_mask = DEVICE uint8 [h][w], 1 <= h <= H, 1 <= w <= W; pixel (y, x) is 0 where d_mask[min(y h / H, h - 1)][min(x w / W, w - 1)]
+ *   is non-zero (integer division) and src elsewhere.
+ * elastic: d_field = DEVICE fp32 [2][hc][wc] (dx, then dy), node (i, j) on pixel (4 i, 4 j), hc = ceil((H - 1) / 4) + 1 and wc alike;
+ *   out[y][x] = bilinear sample of src, zeros outside, at (x + dx(y, x), y + dy(y, x)), d(y, x) the bilinear value of the coarse field
+ *   at (y / 4, x / 4); fp32, rint, clipped.
+ * noise: out = clip(rint(src + scale z)); z = Box-Muller over Philox4x32-10 with key (low, high half of `key`), counter (e / 4, 0, 0, 0),
+ *   output word pair (0, 1) for e % 4 < 2 and (2, 3) otherwise, u = ((word >> 8) + 0.5) 2^-24, z = sqrt(-2 ln u_a) cos | sin (2 pi u_b)
+ *   (cos for even e); e = (y W + x) 3 + c with per_channel, y W + x (one z for the three channels) without. */
+int  dgp_aug_affine_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, const double* coef, void* stream);
+int  dgp_aug_blur3_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, const float* k, void* stream);
+int  dgp_aug_dropout_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, const uint8_t* d_mask, int32_t h, int32_t w, void* stream);
+int  dgp_aug_elastic_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, const float* d_field, int32_t hc, int32_t wc, void* stream);
+int  dgp_aug_noise_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, float scale, int32_t per_channel, uint64_t key, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
