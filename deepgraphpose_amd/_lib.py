@@ -100,6 +100,8 @@ SYMBOLS = {
     "dgp_unit_h2": (C.c_int, [_i32] * 7 + [_vp, _i32, _vp, _i32] + [_vp] * 3 + [_i32] + [_vp] * 6 + [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "dgp_chain_h1": (C.c_int, [_i32] * 9 + [_vp, _i32, _vp, _i32] + [_vp] * 6 + [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "dgp_unit_h1": (C.c_int, [_i32] * 7 + [_vp, _i32, _vp, _i32] + [_vp] * 3 + [_i32] + [_vp] * 6 + [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "dgp_chain_xkeep": (C.c_int, [_i32] * 11 + [_vp, _i32, _vp, _i32] + [_vp] * 6 + [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "dgp_unit_xkeep": (C.c_int, [_i32] * 9 + [_vp, _i32, _vp, _i32] + [_vp] * 3 + [_i32] + [_vp] * 6 + [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "dgp_net_range_status": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp]),
     "dgp_net_recalibrate": (C.c_int, [_vp]),
     "dgp_net_reset_scales": (C.c_int, [_vp]),

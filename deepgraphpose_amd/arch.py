@@ -156,7 +156,16 @@ def launch_algorithmic_bytes(name: str, h: int, w: int, depth: int = 50, batch: 
             if (ui, "conv3") not in have:
                 total += pout * u.depth_bottleneck                                      # R2 out (unit kernel: stays in registers)
         elif which == "conv3":
-            total += u.depth_bottleneck * u.depth + pout * u.depth                      # weights, X' out
+            total += u.depth_bottleneck * u.depth                                       # weights
+            un = plan[ui + 1] if ui + 2 < len(plan) else None
+            if (ui + 1, "conv1") in have and un is not None and un.stride == 2 and not un.has_shortcut_conv:
+                # X' in front of a stride-2 subsample unit whose conv1 this launch computes: the one later reader is x[:, ::2, ::2],
+                # and only those pixels are stored (dgp_net.hip forward_unit_cells)
+                pin_n, pout_n = geo[ui + 1]
+                assert pin_n == pout
+                total += pout_n * u.depth                                               # X' out, kept pixels
+            else:
+                total += pout * u.depth                                                 # X' out
             if (ui, "conv2") not in have:
                 total += pout * u.depth_bottleneck                                      # R2 in
             if (ui, "shortcut") in have:

@@ -109,10 +109,14 @@ __device__ __forceinline__ void chain_prefetch(const ChainArgs& p, uint4 (&res)[
 // (pixel lane & 15, k-group lane >> 4) of conv3's K-steps -- R2 first, then the K-concatenated source.
 // H1 (the 16-bit tier): every tensor is an H1 tensor (one 16-byte cell of 8 halves per 8 channels), the weight chunks are the SAME
 // chunks -- only their high fragments are read -- and a product is one MFMA: pl is not used, X' / R1' leave as single cells.
+// xkeep[rb]: the lanes whose pixel's X' is stored (ChainArgs::xkeep), a lane mask in scalar registers -- the dropped lanes' stores go to
+// OOB, where the descriptor's range check discards them; xoff keeps its meaning (residual offset, the range's gate).  xwave (wave-
+// uniform): false when no lane of the wave stores X' for this tile (an odd row of the unit kernel): the store instructions are skipped.
 template <int C, int C1, int CIN2, int RES, int RB, int NS, int PD, int CHUNK, int WR, bool H1 = false>
 __device__ __forceinline__ void chain_tail(const ChainArgs& p, const uint4* ring, int& slot, const uint4 (&ph)[RB][(C + CIN2) / 32],
                                            const uint4 (&pl)[RB][(C + CIN2) / 32], const unsigned (&xoff)[RB], const unsigned (&roff)[RB],
-                                           const unsigned (&r1off)[RB], const __amdgpu_buffer_rsrc_t rs_s2, const __amdgpu_buffer_rsrc_t rs_xo,
+                                           const unsigned (&r1off)[RB], const unsigned long long (&xkeep)[RB], const bool xwave,
+                                           const __amdgpu_buffer_rsrc_t rs_s2, const __amdgpu_buffer_rsrc_t rs_xo,
                                            const __amdgpu_buffer_rsrc_t rs_r1, float& amax_x, float& amax_r1, const int lane,
                                            uint4 (&res)[PD][RB][2] UD_PARAM) {
 #ifdef DGP_DIAG
@@ -193,12 +197,15 @@ __device__ __forceinline__ void chain_tail(const ChainArgs& p, const uint4* ring
                 }
                 if constexpr (H1) { xh[rb] = h1_pack8(o, p.xout_scale); xl[rb] = xh[rb]; }
                 else h2_pack8(o, p.xout_scale, xh[rb], xl[rb]);
-                if (p.nt & 2) {
-                    st16nt(rs_xo, xh[rb], xoff[rb], jp * CB);
-                    if constexpr (!H1) st16nt(rs_xo, xl[rb], xoff[rb], jp * CB + 16);
-                } else {
-                    st16(rs_xo, xh[rb], xoff[rb], jp * CB);
-                    if constexpr (!H1) st16(rs_xo, xl[rb], xoff[rb], jp * CB + 16);
+                if (xwave) {
+                    const unsigned so = __builtin_amdgcn_inverse_ballot_w64(xkeep[rb]) ? xoff[rb] : OOB;
+                    if (p.nt & 2) {
+                        st16nt(rs_xo, xh[rb], so, jp * CB);
+                        if constexpr (!H1) st16nt(rs_xo, xl[rb], so, jp * CB + 16);
+                    } else {
+                        st16(rs_xo, xh[rb], so, jp * CB);
+                        if constexpr (!H1) st16(rs_xo, xl[rb], so, jp * CB + 16);
+                    }
                 }
                 if (xoff[rb] != OOB) {
 #pragma unroll
@@ -358,6 +365,21 @@ __global__ __launch_bounds__(64 * (NCW + NLW)) void chain_kernel(const ChainArgs
     __builtin_amdgcn_s_barrier();                                      // B(-1)
     for (int t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
         unsigned xoff[RB], roff[RB], r1off[RB];
+        unsigned long long xkeep[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) xkeep[rb] = ~0ull;
+        if (p.xkeep == 2) {                                            // X' only where a stride-2 subsample will read it: even ho, even wo
+            // (the divisors pass through an empty asm: as loop invariants their reciprocals were hoisted out of the tile loop into vector
+            //  registers and cost the identity instances up to 10 of them; two divisions per tile are noise next to its MFMAs)
+            unsigned HoWo = (unsigned)p.HoWo, Wo = (unsigned)p.Wo;
+            asm volatile("" : "+s"(HoWo), "+s"(Wo));
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) {
+                const unsigned m = (unsigned)(t * TILE + (wave * RB + rb) * 16 + l15);
+                const unsigned rem = m % HoWo, ho = rem / Wo, wo = rem - ho * Wo;
+                xkeep[rb] = __builtin_amdgcn_ballot_w64(((ho | wo) & 1) == 0);
+            }
+        }
         uint4 ph[RB][KS1], pl[RB][KS1];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -389,7 +411,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW)) void chain_kernel(const ChainArgs
 #ifdef DGP_DIAG
         unsigned long long ud[12] = {0};
 #endif
-        chain_tail<C, C1, CIN2, RES, RB, NS, PD, CHUNK, WR, H1>(p, ring, slot, ph, pl, xoff, roff, r1off, rs_s2, rs_xo, rs_r1, amax_x, amax_r1, lane, res UD_ARG);
+        chain_tail<C, C1, CIN2, RES, RB, NS, PD, CHUNK, WR, H1>(p, ring, slot, ph, pl, xoff, roff, r1off, xkeep, true, rs_s2, rs_xo, rs_r1, amax_x, amax_r1, lane, res UD_ARG);
 #ifdef DGP_DIAG
         if (wave == 0 && lane == 0) {
             for (int i = 4; i < 9; ++i) atomicAdd(&g_unit_diag[i], ud[i]);
@@ -599,6 +621,10 @@ __global__ __launch_bounds__(64 * (NCW + NLW + HWV)) void unit_kernel(const Chai
         xoff[0] = ok ? (unsigned)m * (unsigned)(C4 * EB) + (unsigned)(g * 8 * EB) : OOB;
         roff[0] = xoff[0];
         r1off[0] = ok ? (unsigned)m * (unsigned)(C1 * EB) + (unsigned)(g * 8 * EB) : OOB;
+        // X' only where a stride-2 subsample will read it (ChainArgs::xkeep): a wave is one row, so an odd row stores nothing
+        const bool xsub = p.xkeep == 2;
+        const bool xwave = !(xsub && (y & 1));
+        const unsigned long long xkeep[1] = {xsub ? __builtin_amdgcn_ballot_w64((x & 1) == 0) : ~0ull};
         uint4 ph[1][KS1], pl[1][KS1];
         if constexpr (CIN2 > 0) {                                      // the K-concatenated source at this wave's pixels (used after conv2)
             const unsigned boff = ok ? (unsigned)m * (unsigned)(CIN2 * EB) + (unsigned)(g * 8 * EB) : OOB;
@@ -702,7 +728,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW + HWV)) void unit_kernel(const Chai
 #ifdef DGP_DIAG
         ud[2] += u1 - u0; ud[9] += 1;
 #endif
-        chain_tail<C, C1, CIN2, RES, 1, NS, PD, CHUNK, WR, H1>(p, ring, slot, ph, pl, xoff, roff, r1off, rs_s2, rs_xo, rs_r1, amax_x, amax_r1, lane, res UD_ARG);
+        chain_tail<C, C1, CIN2, RES, 1, NS, PD, CHUNK, WR, H1>(p, ring, slot, ph, pl, xoff, roff, r1off, xkeep, xwave, rs_s2, rs_xo, rs_r1, amax_x, amax_r1, lane, res UD_ARG);
     }
 #ifdef DGP_DIAG
     UD_STAMP(uend);

@@ -192,6 +192,8 @@ struct ChainArgs {
     float* r2_absmax;
     int nt;                   // bit 0: residual loads, bit 1: X' stores with the non-temporal (evict-first) policy
     int h1;                   // 1: every tensor is an H1 tensor (the 16-bit tier): 2 bytes per channel, high weight fragments only, one MFMA per product
+    int xkeep;                // X' keep stride: 0 / 1 store every pixel; 2 store only pixels with even y and even x of the output grid (the one
+                              // later reader is a stride-2 unit's subsample shortcut x[:, ::2, ::2]).  Ranges and R1' cover every pixel either way
 };
 bool chain_supported(int C, int C1, int CIN2, int res);          // res: 0 K-concatenated shortcut, 1 identity, 2 subsample of a stride-2 unit
 int  chain_frags_per_chunk(int C, int C1, int CIN2, int planes = 2);

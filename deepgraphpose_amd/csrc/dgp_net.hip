@@ -726,12 +726,14 @@ int run_conv_fused_shortcut(dgp_net* net, const Unit& u, const float* r2, const 
 // The tensors of one chain / unit launch with their scale exponents.  All are H2 tensors, or all H1 (h1: 2 bytes per channel
 // instead of 4).  r2 [M][C]; src2: the unit's input -- identity shortcut [M][4C], stride-2 unit [N, H, W, 4C], or the K-concatenated
 // source of the shortcut conv [M][CIN2].  r1in != null: the unit kernel -- conv2 runs in the same launch, reading r1in [N, H, W, C]
-// with its halo (stride 1: Ho x Wo = H x W); r2 is not used
+// with its halo (stride 1: Ho x Wo = H x W); r2 is not used.  xkeep: ChainArgs::xkeep (0 / 1: all of xout is written; 2: its even
+// pixels only)
 struct ChainIo {
     bool h1; int N, Ho, Wo, H, W;
     const void *r2, *src2, *r1in; void *xout, *r1out;
     int r1in_exp, r2_exp, src2_exp, xout_exp, r1out_exp;
     float *r2_absmax, *xout_absmax, *r1_absmax;
+    int xkeep;
 };
 
 // ChainArgs of a plan's launch, ONE place for the engine and the layer-level entry points
@@ -751,6 +753,7 @@ int fill_chain_args(ChainArgs& a, const ChainPlan& cp, const ChainIo& io) {
     a.post1 = ldexpf(1.f, -(io.r2_exp + cp.w3_exp)); a.post2 = ldexpf(1.f, -(io.xout_exp + cp.w1_exp));
     a.res_inv_scale = ldexpf(1.f, -io.src2_exp); a.xout_scale = ldexpf(1.f, io.xout_exp); a.r1_scale = ldexpf(1.f, io.r1out_exp);
     a.xout_absmax = io.xout_absmax; a.r1_absmax = io.r1_absmax;
+    a.xkeep = io.xkeep;
     const double r2b = (double)a.M * cp.C * EB, xob = (double)a.M * cp.C * 4 * EB, r1b = (double)a.M * cp.C1 * EB;
     const double s2b = cp.res == 0 ? (double)a.M * cp.CIN2 * EB : (double)io.N * io.H * io.W * cp.C * 4 * EB;
     const double r1inb = unit ? (double)io.N * io.H * io.W * cp.C * EB : 0.0;
@@ -761,13 +764,13 @@ int fill_chain_args(ChainArgs& a, const ChainPlan& cp, const ChainIo& io) {
 
 // conv3 of unit ui (+ shortcut, ReLU) and conv1 of unit ui + 1 as one launch (dgp_chain.hip); r1in != null: the unit kernel
 int run_chain(dgp_net* net, int ui, const float* r2, const float* x, int N, float* xout, float* r1out, hipStream_t s, int x_exp,
-              const float* r1in = nullptr) {
+              const float* r1in = nullptr, int xkeep = 1) {
     const ChainPlan& cp = net->chains[ui];
     const Unit &u = net->units[ui], &un = net->units[ui + 1];
     const ConvLayer &l3 = net->layers[u.c3], &l1 = net->layers[un.c1];
     const ChainIo io{net->tier != 0, N, u.ho, u.wo, u.h, u.w, r2, x, r1in, xout, r1out,
                      net->act_exp[u.c1], net->act_exp[u.c2], x_exp, net->act_exp[u.c3], net->act_exp[un.c1],
-                     net->amax(u.c2), net->amax(u.c3), net->amax(un.c1)};
+                     net->amax(u.c2), net->amax(u.c3), net->amax(un.c1), xkeep};
     ChainArgs a{};
     if (int rc = fill_chain_args(a, cp, io)) return rc;
     double flops = conv_flops_of(l3, a.M, false) + conv_flops_of(l1, a.M, false);
@@ -796,6 +799,7 @@ struct FwdCtx {
     // conv3(k) + conv1(k + 1) as one launch (DGP_CHAIN=0: layer by layer).  Calibration runs layer by layer (it needs every tensor's
     // range before the next layer runs) and is followed by a second, chained pass, so results never depend on which pass produced them
     bool chain_tier, chain_on;
+    bool xsub_on;      // a chain / unit launch in front of a stride-2 subsample unit stores only the X' pixels that unit reads (forward_unit_cells)
     // the running tensor: X[cur] with its tracked range and (cells) scale exponent.  Cells: Ra holds the current unit's conv1 output, Rb its
     // conv2 output (R1 / R2, trading places); r1_ready: the previous unit's chain launch already wrote Ra
     int cur, x_exp;
@@ -855,6 +859,7 @@ int fwd_context(FwdCtx& c, dgp_net* net, const uint8_t* frames, int B, char* ws,
     static const bool chain_env = (dgp_env("DGP_CHAIN", 1) != 0);
     static const bool chain_h1_env = (dgp_env("DGP_CHAIN_H1", 1) != 0);      // the chain / unit kernels on H1 tensors (the 16-bit tier)
     static const bool unit_env = (dgp_tune("DGP_UNIT", 1) != 0);      // conv2 inside the chain launch (block1)
+    static const bool xsub_env = (dgp_env("DGP_XOUT_SUBSAMPLE", 1) != 0);      // A/B switch
     c = FwdCtx{};
     c.net = net; c.s = s; c.B = B; c.frames = frames;
     c.P0 = (float*)(ws + pl.off_p0); c.C1 = (float*)(ws + pl.off_c1); c.X[0] = (float*)(ws + pl.off_x0); c.X[1] = (float*)(ws + pl.off_x1);
@@ -863,7 +868,7 @@ int fwd_context(FwdCtx& c, dgp_net* net, const uint8_t* frames, int B, char* ws,
     const ConvLayer& lpart = net->layers[net->head_part];
     const ConvLayer* lloc = net->head_locref < 0 ? nullptr : &net->layers[net->head_locref];
     c.f16_mode = conv_mode() == ConvMode::F16x3 || conv_mode() == ConvMode::F16;
-    c.head_pw = head_pw; c.unit_on = unit_env;
+    c.head_pw = head_pw; c.unit_on = unit_env; c.xsub_on = xsub_env;
     c.fuse_on = fuse_env && conv_mode() != ConvMode::F32 && net->wmax_valid;
     c.tier = net->tier; c.FMT = c.tier ? 2 : 1;      // activation cells of this forward: H2 (parity tier) or H1 (16-bit tier)
     c.h2 = h2_env && cells_env && c.f16_mode && head_pw && net->wmax_valid && net->d_exps && lpart.d_wh3_pw && (!lloc || lloc->d_wh3_pw) &&
@@ -985,8 +990,23 @@ int forward_unit_cells(FwdCtx& c, int ui) {
         c3.residual(c.SC, 1, u.ho, u.wo);
         res_exp = net->act_exp[u.sc];
     }
-    if (unit_k) rc = run_chain(net, ui, nullptr, xin, c.B, xout, c.Rb, c.s, x_exp, c.Ra);
-    else if (chain) rc = run_chain(net, ui, c.Rb, xin, c.B, xout, c.Ra, c.s, x_exp);
+    // X' of a chain / unit launch in front of a stride-2 unit `un` with the subsample shortcut (block1/unit_3, block2/unit_4 at output
+    // stride 16): the launch writes un's conv1 output itself (r1_ready below), so xout's one later reader is un's shortcut x[:, ::2, ::2]
+    // and the launch stores those pixels only (DGP_XOUT_SUBSAMPLE=0: all).  The dropped pixels of X[cur ^ 1] keep stale bytes of an
+    // earlier layer until un's successor overwrites the buffer; what reads it in between:
+    //  * un's chain launch, RES == 2: the residual at (2 ho, 2 wo), ho < ceil(h / 2) -- kept pixels only;
+    //  * un's plain conv3 (its chain not available): residual(xin, 2, h, w) reads the same (2 ho, 2 wo) -- un.sc < 0 rules out the
+    //    shortcut conv and the K-concatenated GEMM, and un's conv1, the one full reader of X, is not run (r1_ready);
+    //  * an overflow / recalibration re-run of dgp_forward restarts from the frames: calibration passes run without chains and store
+    //    everything.
+    // Not for the last unit's input launch: X of the last unit is the block4 feature tensor.  Ranges cover every pixel either way
+    int xkeep = 1;
+    if ((unit_k || chain) && c.xsub_on && (size_t)ui + 2 < net->units.size()) {
+        const Unit& un = net->units[ui + 1];
+        if (un.stride == 2 && un.sc < 0) xkeep = 2;
+    }
+    if (unit_k) rc = run_chain(net, ui, nullptr, xin, c.B, xout, c.Rb, c.s, x_exp, c.Ra, xkeep);
+    else if (chain) rc = run_chain(net, ui, c.Rb, xin, c.B, xout, c.Ra, c.s, x_exp, nullptr, xkeep);
     else if (fuse)           // R2 shares X's scale (calibration)
         rc = c.layer(u.c3, [&] { return run_conv_fused_shortcut(net, u, c.Rb, xin, c.B, u.h, u.w, xout, c.s, nullptr, nullptr, c.spec(x_exp, u.c3)); });
     else
@@ -1534,6 +1554,29 @@ int dgp_unit_h1(int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t 
     const ChainIo io{true, N, H, W, H, W, nullptr, src2_h1, r1_h1, xout_h1, r1out_h1, r1_exp, r2_exp, src2_exp, xout_exp, r1out_exp,
                      r2_absmax, xout_absmax, r1_absmax};
     return launch_layer("dgp_unit_h1", io, C, C1, CIN2, res_mode, {w2, scale2, bias2, w3cat, scale3, bias3, w1, scale1, bias1}, (hipStream_t)stream);
+}
+/* dgp_chain_h2 / _h1 and dgp_unit_h2 / _h1 with the X' keep stride of the engine's launches in front of a stride-2 subsample unit:
+ * xout_keep 1 writes all of xout, 2 only its pixels with even row and even column (the others keep what the buffer held) */
+int dgp_chain_xkeep(int32_t h1, int32_t xout_keep, int32_t N, int32_t Ho, int32_t Wo, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode,
+                    int32_t res_H, int32_t res_W, const void* r2, int32_t r2_exp, const void* src2, int32_t src2_exp,
+                    const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
+                    void* xout, int32_t xout_exp, void* r1, int32_t r1_exp, float* xout_absmax, float* r1_absmax, void* stream) {
+    if (xout_keep != 1 && xout_keep != 2) return fail(DGP_ERR_INVALID, "dgp_chain_xkeep: xout_keep must be 1 or 2");
+    const ChainIo io{h1 != 0, N, Ho, Wo, res_H, res_W, r2, src2, nullptr, xout, r1, 0, r2_exp, src2_exp, xout_exp, r1_exp,
+                     nullptr, xout_absmax, r1_absmax, xout_keep};
+    return launch_layer("dgp_chain_xkeep", io, C, C1, CIN2, res_mode, {nullptr, nullptr, nullptr, w3cat, scale3, bias3, w1, scale1, bias1}, (hipStream_t)stream);
+}
+int dgp_unit_xkeep(int32_t h1, int32_t xout_keep, int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode,
+                   const void* r1, int32_t r1_exp, const void* src2, int32_t src2_exp,
+                   const float* w2, const float* scale2, const float* bias2, int32_t r2_exp,
+                   const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
+                   void* xout, int32_t xout_exp, void* r1out, int32_t r1out_exp, float* r2_absmax, float* xout_absmax, float* r1_absmax,
+                   void* stream) {
+    if (xout_keep != 1 && xout_keep != 2) return fail(DGP_ERR_INVALID, "dgp_unit_xkeep: xout_keep must be 1 or 2");
+    if (!w2) return fail(DGP_ERR_INVALID, "dgp_unit_xkeep: null argument");
+    const ChainIo io{h1 != 0, N, H, W, H, W, nullptr, src2, r1, xout, r1out, r1_exp, r2_exp, src2_exp, xout_exp, r1out_exp,
+                     r2_absmax, xout_absmax, r1_absmax, xout_keep};
+    return launch_layer("dgp_unit_xkeep", io, C, C1, CIN2, res_mode, {w2, scale2, bias2, w3cat, scale3, bias3, w1, scale1, bias1}, (hipStream_t)stream);
 }
 
 int dgp_net_range_status(dgp_net* net, int32_t* overflow, int32_t* calibrations, void* stream) {

@@ -425,6 +425,22 @@ int  dgp_unit_h1(int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t
                  const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
                  void* xout_h1, int32_t xout_exp, void* r1out_h1, int32_t r1out_exp, float* r2_absmax, float* xout_absmax, float* r1_absmax,
                  void* stream);
+/* The same launches with the X' keep stride (tests).  slim's resnet_v1 puts a block's stride on its last unit, whose shortcut is
+ * subsample(x, 2) = x[:, ::2, ::2]; the engine's launch in front of such a unit already computes that unit's conv1, so X' is read at
+ * even rows and columns only and the engine stores only those (DGP_XOUT_SUBSAMPLE).  xout_keep 1: all of xout is written, as by the
+ * entry points above; 2: only pixels (y, x) with y and x even -- the other pixels of xout keep the bytes they held.  r1 and all range
+ * slots (xout_absmax included) cover every pixel either way.  Any other xout_keep: DGP_ERR_INVALID.  h1 != 0: every device tensor is H1
+ * (dgp_chain_h1 / dgp_unit_h1), else H2.  Other arguments as dgp_chain_h2 / dgp_unit_h2. */
+int  dgp_chain_xkeep(int32_t h1, int32_t xout_keep, int32_t N, int32_t Ho, int32_t Wo, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode,
+                     int32_t res_H, int32_t res_W, const void* r2, int32_t r2_exp, const void* src2, int32_t src2_exp,
+                     const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
+                     void* xout, int32_t xout_exp, void* r1, int32_t r1_exp, float* xout_absmax, float* r1_absmax, void* stream);
+int  dgp_unit_xkeep(int32_t h1, int32_t xout_keep, int32_t N, int32_t H, int32_t W, int32_t C, int32_t C1, int32_t CIN2, int32_t res_mode,
+                    const void* r1, int32_t r1_exp, const void* src2, int32_t src2_exp,
+                    const float* w2, const float* scale2, const float* bias2, int32_t r2_exp,
+                    const float* w3cat, const float* scale3, const float* bias3, const float* w1, const float* scale1, const float* bias1,
+                    void* xout, int32_t xout_exp, void* r1out, int32_t r1out_exp, float* r2_absmax, float* xout_absmax, float* r1_absmax,
+                    void* stream);
 /* Synchronises `stream`, then: *overflow = 1 if any forward since the last call outgrew a calibrated scale (the flag is cleared
  * and the net re-calibrates on its next forward); *calibrations = calibration passes run so far. */
 int  dgp_net_range_status(dgp_net* net, int32_t* overflow, int32_t* calibrations, void* stream);
