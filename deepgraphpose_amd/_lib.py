@@ -34,6 +34,12 @@ class DgpFlowParams(C.Structure):
                 ("poly_n", C.c_int32), ("poly_sigma", C.c_double), ("flags", C.c_int32)]
 
 
+class DgpJpegInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "ncomp", "sampling", "mcus_x", "mcus_y")] + \
+               [("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3), ("blocks", C.c_int32 * 3)] + \
+               [(n, C.c_int32) for n in ("total_blocks", "restart_interval", "reserved")] + [("scan_offset", C.c_int64)]
+
+
 class DgpConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "N", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "rate", "pad_t", "pad_l", "Ho", "Wo", "relu",
@@ -138,6 +144,10 @@ SYMBOLS = {
     "dgp_aug_dropout_u8": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "dgp_aug_elastic_u8": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "dgp_aug_noise_u8": (C.c_int, [_vp, _vp, _i32, _i32, _f32, _i32, C.c_uint64, _vp]),
+    "dgp_jpeg_probe": (C.c_int, [_vp, C.c_int64, C.POINTER(DgpJpegInfo)]),
+    "dgp_jpeg_entropy_decode": (C.c_int, [_vp, C.c_int64, C.POINTER(DgpJpegInfo), _vp, _vp]),
+    "dgp_jpeg_scratch_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "dgp_jpeg_reconstruct_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_int64, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1300,3 +1300,73 @@ def augment_frames(frames: torch.Tensor, plans, positions) -> torch.Tensor:
                 _aug_crop_and_pad(src, dst, params)
             src = dst
     return frames
+
+
+# ---- baseline JPEG frames (csrc/dgp_jpeg_host.h + csrc/dgp_jpeg.hip): the host half lives in jpeg.py (no torch), re-exported here
+from .jpeg import probe as jpeg_probe, entropy_decode as jpeg_entropy_decode, SAMPLING_NAMES as JPEG_SAMPLING_NAMES  # noqa: E402
+
+
+def jpeg_block_count(H: int, W: int, sampling: int) -> Tuple[int, int]:
+    """(total_blocks, ncomp) of a frame: coefficients are int16 [total_blocks, 64], tables uint16 [ncomp, 64]"""
+    hs, vs = (2 if sampling in (2, 3) else 1), (2 if sampling == 3 else 1)
+    mx, my = -(-int(W) // (8 * hs)), -(-int(H) // (8 * vs))
+    return (mx * my * hs * vs, 1) if sampling == 0 else (mx * my * (hs * vs + 2), 3)
+
+
+def jpeg_reconstruct(coef: torch.Tensor, qt: torch.Tensor, H: int, W: int, sampling: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dgp_jpeg_reconstruct_u8: B frames of ONE geometry from their entropy-decoded coefficients.  coef: device int16
+    [B, total_blocks, 64] (or flat per frame), qt: device int16 / uint16 [B, ncomp, 64] (the bits of jpeg_entropy_decode's uint16
+    tables), both contiguous.  -> uint8 [B, H, W, 3], Pillow's bytes; `out` (that shape, each frame contiguous, frames any whole number
+    of bytes >= H W 3 apart: a slice of a larger buffer) is written in place and nothing around it is touched.  Two launches on the
+    current stream; the planar scratch comes from torch's allocator on that stream."""
+    lib = _lib.load()
+    H, W, sampling = int(H), int(W), int(sampling)
+    if not (0 <= sampling <= 3) or not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise _lib.DgpError("jpeg_reconstruct: H, W must be in 1..65535 and sampling in 0..3, got %d, %d, %d" % (H, W, sampling))
+    _need_cuda(coef, torch.int16, "coef")
+    if qt.dtype not in (torch.int16, torch.uint16):
+        raise _lib.DgpError("qt must have dtype int16 or uint16, got %s" % qt.dtype)
+    _need_cuda(qt, qt.dtype, "qt")
+    B = int(coef.shape[0])
+    nblk, ncomp = jpeg_block_count(H, W, sampling)
+    if coef.numel() != B * nblk * 64 or qt.numel() != B * ncomp * 64 or qt.device != coef.device:
+        raise _lib.DgpError("jpeg_reconstruct: %d frames of %d x %d, sampling %s, need coef [%d, %d, 64] and qt [%d, %d, 64], got %s and %s"
+                            % (B, H, W, JPEG_SAMPLING_NAMES[sampling], B, nblk, B, ncomp, tuple(coef.shape), tuple(qt.shape)))
+    dev = coef.device
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    else:
+        if not out.is_cuda or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (B, H, W, 3):
+            raise _lib.DgpError("jpeg_reconstruct: out must be uint8 %s on %s, got %s %s on %s" % ((B, H, W, 3), dev, out.dtype, tuple(out.shape), out.device))
+        if B and (tuple(out.stride()[1:]) != (W * 3, 3, 1) or (B > 1 and out.stride(0) < H * W * 3)):
+            raise _lib.DgpError("jpeg_reconstruct: every frame of out must be contiguous and the frames must not overlap (strides %s)" % (tuple(out.stride()),))
+    if B == 0:
+        return out
+    need = int(lib.dgp_jpeg_scratch_bytes(B, H, W, sampling))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    stride = int(out.stride(0)) if B > 1 else H * W * 3
+    _lib.check(lib.dgp_jpeg_reconstruct_u8(_ptr(coef), _ptr(qt), B, H, W, sampling, _ptr(out), stride, _ptr(scratch), need, _stream(dev)),
+               "dgp_jpeg_reconstruct_u8")
+    return out
+
+
+def jpeg_decode(frames, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """A list of baseline JPEG byte strings of ONE geometry -> uint8 [n, H, W, 3] on the device: jpeg_probe + jpeg_entropy_decode per
+    frame on the host (this thread), one upload, jpeg_reconstruct.  A frame whose size or sampling differs from the first frame's is a
+    ValueError naming it; a stream the decoder does not take is a DgpError."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("jpeg_decode: no frames")
+    infos = [jpeg_probe(f) for f in frames]
+    i0 = infos[0]
+    for i, inf in enumerate(infos):
+        if (inf.width, inf.height, inf.sampling) != (i0.width, i0.height, i0.sampling):
+            raise ValueError("jpeg_decode: frame %d is %d x %d %s, frame 0 is %d x %d %s" % (
+                i, inf.width, inf.height, JPEG_SAMPLING_NAMES[inf.sampling], i0.width, i0.height, JPEG_SAMPLING_NAMES[i0.sampling]))
+    n = len(frames)
+    coef = np.empty((n, i0.total_blocks, 64), np.int16)
+    qt = np.empty((n, i0.ncomp, 64), np.uint16)
+    for i, f in enumerate(frames):
+        jpeg_entropy_decode(f, infos[i], coef[i], qt[i])
+    dev = out.device if out is not None else torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return jpeg_reconstruct(torch.from_numpy(coef).to(dev), torch.from_numpy(qt.view(np.int16)).to(dev), i0.height, i0.width, i0.sampling, out=out)

@@ -8,7 +8,8 @@ Same entry points and signatures as the reference (DGP/models/eval.py):
 The TF session call `sess.run([mu_n, scmap], feed_dict={inputs: frame[None]})` (:328) is served by
 `EvalSession.run`, which batches frames through the fused HIP path (dgp_infer); the per-joint likelihood
 loop (:331-343) runs inside the soft-argmax kernel.  Video decode and movie rendering are untouched
-third-party territory (moviepy) and only used when installed.
+third-party territory (moviepy) and only used when installed -- except Motion-JPEG .avi files and .jpg frames, which are read
+(frames.MjpegAviSource) and decoded (decode_backend: Pillow on the host, or dgp_jpeg_entropy_decode + dgp_jpeg_reconstruct_u8) here.
 """
 from __future__ import annotations
 
@@ -192,7 +193,8 @@ def clear_session_cache():
 
 # counters of the last estimate_pose call (tests, soak runs): chunks processed and chunks re-run after a range overflow
 RUN_STATS = {"chunks": 0, "chunk_reruns": 0, "strict_passes": 0, "stage_s": 0.0, "wait_frames_s": 0.0, "wait_h2d_s": 0.0, "drain_s": 0.0,
-             "setup_s": 0.0, "alloc_s": 0.0, "calibrate_s": 0.0, "finish_s": 0.0, "prep_backend": "none", "loc_ref": None}
+             "setup_s": 0.0, "alloc_s": 0.0, "calibrate_s": 0.0, "finish_s": 0.0, "prep_backend": "none", "loc_ref": None,
+             "decode_backend": "host"}
 
 # location refinement of estimate_pose / plot_dgp (engine.LOC_REF_MODES): None = the reference's video path (soft-argmax only), "dgp" =
 # soft-argmax + the softmax-weighted locref offset, "dlc" = DLC's hard arg-max + the offset at that cell
@@ -222,6 +224,17 @@ def refined_pose(records, stride, locref_stdev, scale_x=1.0, scale_y=1.0):
 # frames cross PCIe), "pil" = Pillow per frame on the host (the reference's code), "auto" = "hip" unless the kernel refuses the shape
 RESIZE_BACKENDS = ("auto", "pil", "hip")
 
+# who decodes the frames of a source that holds baseline JPEG streams (frames.MjpegAviSource, a directory of .jpg files): "host" = the
+# source's frame_at / iter_frames (Pillow; one thread), "hip" = DECODE_THREADS host threads Huffman-decode whole batches into pinned
+# coefficient slots (staging.stage_jpeg) and engine.jpeg_reconstruct rebuilds the pixels on the copy stream -- the same bytes --, "auto" =
+# "hip" when the source offers jpeg_bytes and dgp_jpeg_probe takes its first frame, else "host" (with one printed line for a source
+# that decodes at all; an in-memory stack has nothing to decode and stays silent)
+DECODE_BACKENDS = ("auto", "host", "hip")
+# host threads of the "hip" decode path (at most 16).  Measured (profiles/jpeg_bench_line.json, 640x480 at quality 90): one thread
+# entropy-decodes 3130 frames/s, 8 threads 21 900 (7.0 x) -- 4.7 x what the parity engines take and 2.3 x the 16-bit tier's, with half of a
+# rank's 16 CPUs left to the staging consumer and the other ranks' threads; idle decoders wait on the ring and cost nothing
+DECODE_THREADS = 8
+
 # The host pipeline's geometry (measured settings, not run-time switches; tests patch the module attributes): engines / HIP streams the
 # batches are dealt to, pinned staging slots, host threads staging an in-memory stack, copy streams the uploads alternate on, bytes of
 # frames a chunk keeps resident for a re-run after a range overflow.
@@ -231,12 +244,13 @@ EVAL_STREAMS, PINNED_SLOTS, STAGE_THREADS, COPY_STREAMS, CHUNK_BYTES = 2, 8, 2, 
 _PINNED = {"key": None, "bufs": []}
 
 
-def _pinned_ring(nslots: int, shape):
+def _pinned_ring(nslots: int, shape, dtype=None):
     import torch
-    key = (nslots, tuple(shape))
+    dtype = dtype or torch.uint8
+    key = (nslots, tuple(shape)) if dtype == torch.uint8 else (nslots, tuple(shape), dtype)
     if _PINNED["key"] != key:
         _PINNED["bufs"] = []                       # (drop the old ring first)
-        _PINNED["bufs"] = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(nslots)]
+        _PINNED["bufs"] = [torch.empty(shape, dtype=dtype).pin_memory() for _ in range(nslots)]
         _PINNED["key"] = key
     return _PINNED["bufs"]
 
@@ -249,8 +263,10 @@ class _PoseRun:
     batch k+1 to the GPU while batch k runs through dgp_infer on the compute stream, and the keypoints of the whole video come back in
     ONE device-to-host copy at the end (the reference fetched the full scoremap every frame)."""
 
-    def __init__(self, sess, clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend, loc_ref=None):
+    def __init__(self, sess, clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend, loc_ref=None,
+                 decode_backend="host"):
         self.sess, self.clip, self.video_file, self.loc_ref = sess, clip, video_file, loc_ref
+        self.decode_backend, self.decode, self.jpeg_info = decode_backend, None, None      # decode: "host" | "hip", decided on the first frame
         self.lanes = 5 if loc_ref is None else 7          # fp32 lanes of a (frame, joint) record (engine.record_lanes)
         self.records = None                               # loc_ref: the whole video's 7-lane records, float32 [n_frames, nj, 7]
         self.lo, self.hi, self.world, self.n_frames, self.batch_size = lo, hi, world, int(clip.n_frames), batch_size
@@ -275,6 +291,36 @@ class _PoseRun:
             print("resize_backend auto: frames of %s are resized with Pillow on the host (%s)" % (self.video_file, e), flush=True)
             return "pil"
         return "hip"
+
+    def choose_decode_backend(self):
+        """"hip" when the source hands out JPEG streams, dgp_jpeg_probe takes the first one and no host resize stands between the decoder
+        and the engines; decode_backend "hip" raises ValueError otherwise, "auto" says why in one line and decodes on the host"""
+        from .. import jpeg, _lib
+        if self.decode_backend == "host":
+            return "host"
+        clip, why = self.clip, None
+        if not callable(getattr(clip, "jpeg_bytes", None)):
+            why = "the source holds no JPEG streams"
+        elif not getattr(clip, "jpeg_only", True):
+            why = "not every frame of the source is a .jpg file"
+        elif self.prep_backend == "pil":
+            why = "the frames are resized with Pillow on the host"
+        else:
+            try:
+                data = clip.jpeg_bytes(0)
+                if data is None:
+                    why = "the first frame is not a JPEG file"
+                else:
+                    self.jpeg_info = jpeg.probe(data)
+            except _lib.DgpError as e:
+                why = str(e)
+        if why is None:
+            return "hip"
+        if self.decode_backend == "hip":
+            raise ValueError("estimate_pose: decode_backend 'hip' cannot decode %s: %s" % (self.video_file, why))
+        if not hasattr(clip, "frames"):                # (an in-memory stack decodes nothing: no line)
+            print("decode_backend auto: frames of %s are decoded on the host (%s)" % (self.video_file, why), flush=True)
+        return "host"
 
     def prep(self, frame):
         """the frame as it is staged: the reference's PIL resize / crop (eval.py:307-326) on the "pil" backend, else the source frame"""
@@ -302,7 +348,17 @@ class _PoseRun:
         torch.cuda.synchronize(dev)
         RUN_STATS["setup_s"] += time.perf_counter() - t_      # the engines of this frame size: weights re-packed and uploaded (first call of a size)
         t_ = time.perf_counter()
-        self.pinned = _pinned_ring(PINNED_SLOTS, (B, sh, sw, 3))      # batches being staged / copied + slack for bursts
+        if self.decode == "hip":
+            # a slot holds a batch's quantised coefficients (int16 [B][total_blocks * 64]) followed by its tables (uint16 [B][ncomp * 64]);
+            # one device copy of it per copy stream: the upload lands there and jpeg_reconstruct behind it, on the same stream, writes the pixels
+            ji = self.jpeg_info
+            if (ji.height, ji.width) != (sh, sw):
+                raise ValueError("the first JPEG of %s is %d x %d, its decoded frame %d x %d" % (self.video_file, ji.width, ji.height, sw, sh))
+            self.coef_elems, self.qt_elems = ji.total_blocks * 64, ji.ncomp * 64
+            self.pinned = _pinned_ring(PINNED_SLOTS, (B * (self.coef_elems + self.qt_elems),), torch.int16)
+            self.dcoef = [torch.empty((B * (self.coef_elems + self.qt_elems),), dtype=torch.int16, device=dev) for _ in range(COPY_STREAMS)]
+        else:
+            self.pinned = _pinned_ring(PINNED_SLOTS, (B, sh, sw, 3))      # batches being staged / copied + slack for bursts
         self.chunk_batches, self.n_rounds = staging.chunk_plan(self.n_frames, self.world, B, B * hh * ww * 3,
                                                                int(os.environ.get("DGP_EVAL_CHUNK_BATCHES", "64")), CHUNK_BYTES)
         self.dchunk = torch.empty((self.chunk_batches, B, hh, ww, 3), dtype=torch.uint8, device=dev)
@@ -321,9 +377,12 @@ class _PoseRun:
         import torch
         from .. import engine
         nb0 = min(self.batch_size, self.n_frames)
-        for t in range(nb0):
-            np.copyto(self.pinned[0][t].numpy(), self.prep(self.clip.frame_at(t)))
-        self.cal_batch = self.pinned[0][:nb0].to(self.dev)
+        if self.decode == "hip":                   # (the ring holds coefficients; frame_at gives the same bytes the device decoder will)
+            self.cal_batch = torch.from_numpy(np.stack([np.asarray(self.clip.frame_at(t)) for t in range(nb0)])).to(self.dev)
+        else:
+            for t in range(nb0):
+                np.copyto(self.pinned[0][t].numpy(), self.prep(self.clip.frame_at(t)))
+            self.cal_batch = self.pinned[0][:nb0].to(self.dev)
         if self.on_gpu:
             self.cal_batch = engine.resize_frames(self.cal_batch, self.new_size, self.crop_size)
         self.net.calibrate(self.cal_batch, self.sess.gamma, self.sess.gauss_len, self.loc_ref)
@@ -334,6 +393,17 @@ class _PoseRun:
         import itertools
         import threading
         B, clip = self.batch_size, self.clip
+        if self.decode == "hip":                   # whole batches, dealt to DECODE_THREADS Huffman decoders as stage_stack deals its copies
+            nc = B * self.coef_elems
+            self.ring = ring = staging.StagingRing([(p.numpy()[:nc].reshape(B, self.coef_elems),
+                                                     p.numpy()[nc:].view(np.uint16).reshape(B, self.qt_elems)) for p in self.pinned])
+            ring.set_total(-(-(self.hi - self.lo) // B))
+            n_thr = max(1, min(int(DECODE_THREADS), 16))
+            threads = [threading.Thread(target=staging.stage_jpeg, daemon=True,
+                                        args=(ring, clip, self.jpeg_info, self.lo, self.hi, B, t, n_thr, self.video_file)) for t in range(n_thr)]
+            for th in threads:
+                th.start()
+            return threads
         self.ring = ring = staging.StagingRing([p.numpy() for p in self.pinned])
         if self.prep_backend != "pil" and hasattr(clip, "iter_batches") and hasattr(clip, "frames"):      # an in-memory stack: whole batches
             ring.set_total(-(-(self.hi - self.lo) // B))
@@ -375,7 +445,18 @@ class _PoseRun:
         net, sess, dst = self.net, self.sess, self.dchunk[k][:nb]
         cs = self.copy_streams[kb % len(self.copy_streams)]
         with torch.cuda.stream(cs):
-            if self.on_gpu:
+            if self.decode == "hip":
+                # (this stream's device slot: the next upload into it queues behind this reconstruct)
+                ji, h, d = self.jpeg_info, self.pinned[slot], self.dcoef[kb % len(self.copy_streams)]
+                nc, q0 = nb * self.coef_elems, self.batch_size * self.coef_elems
+                d[:nc].copy_(h[:nc], non_blocking=True)
+                d[q0:q0 + nb * self.qt_elems].copy_(h[q0:q0 + nb * self.qt_elems], non_blocking=True)
+                px = self.dsrc[kb % len(self.copy_streams)][:nb] if self.on_gpu else dst
+                engine.jpeg_reconstruct(d[:nc].view(nb, ji.total_blocks, 64), d[q0:q0 + nb * self.qt_elems].view(nb, ji.ncomp, 64),
+                                        ji.height, ji.width, ji.sampling, out=px)
+                if self.on_gpu:
+                    engine.resize_frames(px, self.new_size, self.crop_size, out=dst)
+            elif self.on_gpu:
                 src = self.dsrc[kb % len(self.copy_streams)]      # (this stream's: the next upload into it queues behind this resize)
                 src[:nb].copy_(self.pinned[slot][:nb], non_blocking=True)
                 engine.resize_frames(src[:nb], self.new_size, self.crop_size, out=dst)
@@ -454,6 +535,8 @@ class _PoseRun:
             self.scale_x, self.scale_y = first.shape[1] / self.new_size[1], first.shape[0] / self.new_size[0]
         if self.prep_backend is None:
             self.prep_backend = self.choose_prep_backend(first)
+        if self.decode is None:
+            self.decode = self.choose_decode_backend()
         f0 = self.prep(first)
         self.allocate(*f0.shape[:2])
         if first_pass:
@@ -500,7 +583,7 @@ class _PoseRun:
 
 def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle=1, save_pose=True, save_str="",
                   new_size=None, crop_size=None, batch_size: int = 32, tier: Optional[str] = None, resize_backend: str = "auto",
-                  loc_ref: Optional[str] = None):
+                  loc_ref: Optional[str] = None, decode_backend: str = "auto"):
     """Estimate pose on an arbitrary video (eval.py:217-372).  Returns {'x','y','likelihoods'} [T,nj] float64,
     or the csv path if labels already exist (:247-249).  `batch_size` is new: frames go through the GPU in
     batches instead of one sess.run per frame.  `tier` is new (resolve_tier): None = DGP_EVAL_TIER or the parity tier; "f16" = the
@@ -513,6 +596,11 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     offset, likelihood = the window sigmoid; "dlc": hard arg-max cell + the offset at that cell, likelihood = the arg-max probability
     (PET/nnet/predict.py:62-77).  Coordinates are composed by refined_pose (DLC's axis convention).  A snapshot without the head raises
     KeyError naming the variable.  RUN_STATS["loc_ref"] names the mode that ran.
+    `decode_backend` is new (DECODE_BACKENDS): who decodes a source of baseline JPEG streams (a Motion-JPEG .avi, a directory of .jpg
+    files) -- "host": the source's own Pillow decode, one thread; "hip": DECODE_THREADS threads Huffman-decode batches and
+    engine.jpeg_reconstruct rebuilds the pixels on the GPU, the same bytes (ValueError for a source without JPEG streams or a first frame
+    the decoder refuses); "auto": "hip" where that works, else "host" with one printed line.  RUN_STATS["decode_backend"] names the one
+    that ran.
 
     Multi-GPU: under torchrun (one process per GPU; RANK / WORLD_SIZE / LOCAL_RANK in the environment, or an
     already initialised torch.distributed group) rank r decodes and infers only the contiguous frame block
@@ -527,6 +615,8 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         raise ValueError("estimate_pose: resize_backend must be one of %s, not %r" % ("|".join(RESIZE_BACKENDS), resize_backend))
     if loc_ref not in LOC_REF_CHOICES:
         raise ValueError("estimate_pose: loc_ref must be None, 'dgp' or 'dlc', not %r" % (loc_ref,))
+    if decode_backend not in DECODE_BACKENDS:
+        raise ValueError("estimate_pose: decode_backend must be one of %s, not %r" % ("|".join(DECODE_BACKENDS), decode_backend))
     RUN_STATS.update(chunks=0, chunk_reruns=0, strict_passes=0, stage_s=0.0, wait_frames_s=0.0, wait_h2d_s=0.0, drain_s=0.0, setup_s=0.0,
                      alloc_s=0.0, calibrate_s=0.0, finish_s=0.0, loc_ref=loc_ref)
 
@@ -564,7 +654,7 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
     sess.max_batch = int(batch_size)
     sess.device = local_rank
     lo, hi = ddist.shard_range(int(video_clip.n_frames), rank, world)        # this rank's frames
-    run = _PoseRun(sess, video_clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend, loc_ref)
+    run = _PoseRun(sess, video_clip, video_file, lo, hi, world, batch_size, new_size, crop_size, resize_backend, loc_ref, decode_backend)
 
     # Bit-identity of a sharded run with a single-process run holds as long as no chunk overflows (or only the first one does).  After an
     # overflow in a LATER chunk the earlier chunks keep the (valid) results of the narrower scales, which a run that started with the
@@ -577,6 +667,7 @@ def estimate_pose(proj_cfg_file, dgp_model_file, video_file, output_dir, shuffle
         RUN_STATS["strict_passes"] += 1
         print("DGP_EVAL_STRICT: scales were widened after the first chunk; computing %s again on the final scales" % video_file, flush=True)
     RUN_STATS["prep_backend"] = run.prep_backend
+    RUN_STATS["decode_backend"] = run.decode
     sess.close()
     video_clip.close()
 
@@ -624,8 +715,8 @@ def load_pose_from_dlc_to_dict(filename):
 
 
 def plot_dgp(video_file, output_dir="", label_dir=None, proj_cfg_file=None, dgp_model_file=None, shuffle=1, dotsize=3,
-             colormap="jet", save_str="", mask_threshold=0.1, new_size=None, tier=None, loc_ref=None):
-    """eval.py:816-874 (`tier` and `loc_ref` are new: estimate_pose's).  Exports the labels when missing, then hands (clip, x, y, mask) to the movie
+             colormap="jet", save_str="", mask_threshold=0.1, new_size=None, tier=None, loc_ref=None, decode_backend="auto"):
+    """eval.py:816-874 (`tier`, `loc_ref` and `decode_backend` are new: estimate_pose's).  Exports the labels when missing, then hands (clip, x, y, mask) to the movie
     renderer.  Drawing the annotated movie is moviepy / matplotlib work outside this package's scope: when
     those are absent the labels are still produced and the csv path is returned."""
     f = os.path.basename(str(video_file)).rsplit(".", 1)
@@ -638,7 +729,7 @@ def plot_dgp(video_file, output_dir="", label_dir=None, proj_cfg_file=None, dgp_
     labels = None
     if not ddist.from_rank0(os.path.exists(label_file)):
         labels = estimate_pose(proj_cfg_file, dgp_model_file, video_file, label_dir, shuffle=shuffle, save_str=save_str,
-                               new_size=new_size, tier=tier, loc_ref=loc_ref)
+                               new_size=new_size, tier=tier, loc_ref=loc_ref, decode_backend=decode_backend)
     if not isinstance(labels, dict):                       # labels were there already (estimate_pose returns the csv path then)
         labels = load_pose_from_dlc_to_dict(label_file)
     mask_array = labels["likelihoods"].T > mask_threshold

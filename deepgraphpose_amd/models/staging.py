@@ -116,6 +116,35 @@ def stage_decoded(ring: StagingRing, frames, n_local: int, batch_size: int):
         ring.fail(e)
 
 
+def stage_jpeg(ring: StagingRing, source, info0, lo: int, hi: int, batch_size: int, tid: int, n_threads: int, name="the video"):
+    """Producer over a source of baseline JPEG streams (source.jpeg_bytes(t), thread-safe): stage_stack's dealing scheme -- thread tid
+    stages batches tid, tid + n_threads, ... of frames [lo, hi), the caller declares the total -- but a batch is Huffman-decoded, not
+    copied: frame i of the batch goes into row i of the slot's (coef int16 [B, total_blocks * 64], qt uint16 [B, ncomp * 64]) pair
+    through dgp_jpeg_entropy_decode, which holds no lock and no GIL.  A frame whose size or sampling differs from info0 (the first
+    frame's dgp_jpeg_probe) is a ValueError naming the frame; like any error it is recorded in the ring and raised in the consumer."""
+    from .. import jpeg
+    try:
+        for k in range(tid, -(-(hi - lo) // batch_size), n_threads):
+            a = lo + k * batch_size
+            nb = min(batch_size, hi - a)
+            slot = ring.take(k)
+            t_ = time.perf_counter()
+            coef, qt = ring.bufs[slot]
+            for i in range(nb):
+                data = source.jpeg_bytes(a + i)
+                if data is None:
+                    raise ValueError("frame %d of %s is not a JPEG file" % (a + i, name))
+                info = jpeg.probe(data)
+                if not jpeg.same_geometry(info, info0):
+                    raise ValueError("frame %d of %s is %d x %d %s, the first frame %d x %d %s" % (
+                        a + i, name, info.width, info.height, jpeg.SAMPLING_NAMES[info.sampling], info0.width, info0.height,
+                        jpeg.SAMPLING_NAMES[info0.sampling]))
+                jpeg.entropy_decode(data, info, coef[i], qt[i])
+            ring.publish(k, slot, nb, time.perf_counter() - t_)
+    except BaseException as e:
+        ring.fail(e)
+
+
 def chunk_plan(n_frames: int, world: int, batch_size: int, batch_bytes: int, env_batches: int, chunk_bytes: int):
     """-> (chunk_batches, n_rounds).  A chunk is the run of batches whose frames stay on the device until their range check has come back
     clean: env_batches (DGP_EVAL_CHUNK_BATCHES) of them, but at most chunk_bytes of frames (1 GiB: 36 batches of 32 at 640 x 480, 24 of

@@ -598,6 +598,51 @@ int  dgp_aug_dropout_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, 
 int  dgp_aug_elastic_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, const float* d_field, int32_t hc, int32_t wc, void* stream);
 int  dgp_aug_noise_u8(const uint8_t* src, uint8_t* dst, int32_t H, int32_t W, float scale, int32_t per_channel, uint64_t key, void* stream);
 
+/* ---- Baseline JPEG frames: entropy decode on the host, reconstruction on the device, Pillow's (libjpeg-turbo's) bytes (replaces the
+ * decode half of moviepy's VideoFileClip for Motion-JPEG input, DGP/models/eval.py:256, and Pillow's per-frame decode of a directory of
+ * JPEGs).  Accepted: SOF0 (baseline, 8-bit, Huffman), 1 or 3 components in ONE interleaved scan, luma sampling 1x1, 2x1 or 2x2 over
+ * 1x1 chroma, 8-bit quantisation tables, YCbCr (JFIF, an Adobe APP14 marker with transform 1, or neither).  Everything else is
+ * DGP_ERR_INVALID with the reason in dgp_last_error: progressive or arithmetic streams, 12-bit samples, 4 components, other
+ * samplings, an Adobe transform that is not YCbCr, several scans, 16-bit tables, truncated or inconsistent segments.
+ * Arithmetic: dequantise, libjpeg's "islow" inverse DCT (CONST_BITS 13, PASS1_BITS 2: columns first, descaled by 11 bits, then rows,
+ * descaled by 18, + 128, clipped), "fancy" triangle upsampling of chroma on its true size ceil(H v / vmax) x ceil(W h / hmax) with
+ * replicated edges (h2v1: (3 a + b + 1 | 2) >> 2; h2v2: column sums 3 a + b of the two nearest rows, then (3 s + t + 8 | 7) >> 4),
+ * YCbCr -> RGB as y + ((FIX(1.402) cr + 32768) >> 16) etc. with FIX(x) = (int)(x 65536 + 0.5), clipped; grey is replicated. */
+enum { DGP_JPEG_GRAY = 0, DGP_JPEG_444 = 1, DGP_JPEG_422 = 2, DGP_JPEG_420 = 3 };
+typedef struct dgp_jpeg_info {
+    int32_t width, height;
+    int32_t ncomp;              /* 1 | 3 */
+    int32_t sampling;           /* DGP_JPEG_* */
+    int32_t mcus_x, mcus_y;     /* MCUs per row / column: 8 hmax x 8 vmax pixels each */
+    int32_t blocks_x[3];        /* per component: blocks per row of its MCU-padded grid ... */
+    int32_t blocks_y[3];        /* ... rows of blocks ... */
+    int32_t blocks[3];          /* ... and their product */
+    int32_t total_blocks;       /* sum over the components: a frame has total_blocks x 64 coefficients */
+    int32_t restart_interval;   /* MCUs between RSTn markers, 0 = none */
+    int32_t reserved;
+    int64_t scan_offset;        /* offset of the first entropy-coded byte */
+} dgp_jpeg_info;
+/* Host only (no GPU), re-entrant: parses the marker segments of data[0 .. n) up to the scan header and fills *info. */
+int    dgp_jpeg_probe(const uint8_t* data, int64_t n, dgp_jpeg_info* info);
+/* Host only (no GPU), re-entrant, no globals, no allocation: any number of threads may decode at once.  info: dgp_jpeg_probe's of the
+ * SAME stream (checked).  coef: int16 [total_blocks][64], the quantised coefficients de-zigzagged (natural order), planar by
+ * component: all Y blocks row-major over the MCU-padded block grid, then Cb, then Cr.  qt: uint16 [ncomp][64], each component's table in
+ * natural order.  DC prediction, EOB / ZRL, byte stuffing and DRI / RSTn follow T.81; Huffman table slots 0 and 1 that no DHT segment
+ * defines get the typical tables of Annex K.3 (plain MJPEG frames carry none).  Every read is checked against n and every block address
+ * against the geometry: a code that runs past 16 bits, a coefficient index past 63, data that ends early, a wrong restart marker or a
+ * stream in which some |coefficient x table entry| exceeds 32767 (no encoder of 8-bit images writes one) is DGP_ERR_INVALID. */
+int    dgp_jpeg_entropy_decode(const uint8_t* data, int64_t n, const dgp_jpeg_info* info, int16_t* coef, uint16_t* qt);
+/* Host only: device scratch bytes dgp_jpeg_reconstruct_u8 needs for B frames (the component planes with their MCU padding); 0 for
+ * arguments it would refuse. */
+size_t dgp_jpeg_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t sampling);
+/* d_coef: device int16 [B][total_blocks][64] and d_qt: device uint16 [B][ncomp][64] as dgp_jpeg_entropy_decode writes them, B frames
+ * of ONE geometry (H, W, sampling), tables per frame.  dst: device uint8 [B][H][W][3] RGB, frames dst_frame_stride BYTES apart (at
+ * least H W 3): a slice of a larger buffer is written in place and no byte between the frames is touched.  scratch: device,
+ * 8-byte aligned, dgp_jpeg_scratch_bytes.  Two launches on `stream` (blocks -> planar uint8 in scratch; planes -> RGB), integer
+ * arithmetic, no atomics: bit-identical from run to run, and Pillow's bytes.  B == 0 launches nothing. */
+int    dgp_jpeg_reconstruct_u8(const int16_t* d_coef, const uint16_t* d_qt, int32_t B, int32_t H, int32_t W, int32_t sampling, uint8_t* dst,
+                               int64_t dst_frame_stride, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
