@@ -125,7 +125,12 @@ SYMBOLS = {
     "dgp_trainer_fast_status": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "dgp_conv2d_dgrad_scratch_bytes": (_sz, [C.POINTER(DgpConvDesc)]),
     "dgp_conv2d_dgrad": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
-    "dgp_motion_energy": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
+    "dgp_h1_to_f32_pred": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    "dgp_conv2d_wgrad_h1": (C.c_int, [C.POINTER(DgpConvDesc)] + [_vp] * 11),
+    "dgp_conv2d_dgrad_h1": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _vp, _vp, _vp, _vp, _i32] + [_vp] * 7),
+    "dgp_stem_wgrad_h1": (C.c_int, [_vp] * 4 + [_i32] * 7 + [_vp] * 4),
+    "dgp_heads_backward_h1": (C.c_int, [_vp] * 8 + [_i32] * 5 + [_vp] * 8),
+    "dgp_motion_energy":(C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "dgp_maxpool_3x3s2_same": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dgp_preprocess_u8": (C.c_int, [_vp, C.c_int64, C.POINTER(_f32), _vp, _vp]),
     "dgp_optical_flow_scratch_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(DgpFlowParams), C.POINTER(_sz), C.POINTER(_i32)]),

@@ -2946,6 +2946,19 @@ static int adopt_h1(TrainPass& p, const void* t, const void* src) {
     return DGP_OK;
 }
 
+// Both heads' parameter gradients of the 16-bit tier (the training step and the layer-level entry point dgp_heads_backward_h1): ONE
+// weight-gradient launch over the merged H1 tensor (wc.d.Cout = CT columns: the part head's phases from column 0, the locref head's from
+// column cpad0), then each head's finalisation from its own columns.
+static hipError_t heads_h1_param_grads(const WgradCall& wc, int njt0, int njt1, int cpad0, float* dw0, float* db0, float* dw1, float* db1,
+                                       hipStream_t hs) {
+    const int cin = wc.d.Cin, CT = wc.d.Cout;
+    hipError_t e = wgrad_launch(wc, hs);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt0 * cin)), dim3(256), 0, hs, wc.dwraw, wc.colsum, njt0, cin, CT, 0, dw0, db0);
+    hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt1 * cin)), dim3(256), 0, hs, wc.dwraw, wc.colsum, njt1, cin, CT, cpad0, dw1, db1);
+    return hipGetLastError();
+}
+
 // Heads of the 16-bit tier, both at once.  Their loss gradients are gathered into ONE H1 tensor (scale predicted from its range one
 // step ago, slot_dph); ONE weight-gradient launch reads it and the H1 features in place (second stream), ONE H1 -> H1 data-gradient launch
 // with the merged panel writes d features, gated by the features' ReLU, as the H1 tensor the last unit's backward reads.
@@ -2955,7 +2968,6 @@ static int backward_heads_h1(TrainPass& p, const float* dscmap, const float* dlo
     const ConvLayer &l0 = net->layers[net->head_part], &l1 = net->layers[net->head_locref];
     const TLayer &t0 = tr->tl[net->head_part], &t1 = tr->tl[net->head_locref];
     const int CT = tr->hm_ct, njt0 = l0.Cout / 4, njt1 = l1.Cout / 4;
-    float* const dwraw = p.F(p.pl.dwraw); float* const colsum = p.F(p.pl.colsum);
     float* const DPH = p.F(p.pl.dphh);
     const float* dprev = ctx.rng.prev_of(slot_dph);
     const float* featH = p.F(p.pl.xo[p.nu() - 1]);
@@ -2971,11 +2983,7 @@ static int backward_heads_h1(TrainPass& p, const float* dscmap, const float* dlo
     wc.x = {featH, ctx.rng.of(featH), featH, fp->second};
     wc.dy = {DPH, ctx.rng.of(DPH), DPH, dprev};
     wc.fail_flag = tr->d_fast_flag; wc.h1 = true;
-    TRY_HIP(wgrad_launch(wc, hs));
-    hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt0 * l0.Cin)), dim3(256), 0, hs, dwraw, colsum, njt0, l0.Cin, CT, 0,
-                       tr->grads + t0.w_off, tr->grads + t0.b_off);
-    hipLaunchKernelGGL(finalize_head_grads, dim3(grid_for(9ll * njt1 * l1.Cin)), dim3(256), 0, hs, dwraw, colsum, njt1, l1.Cin, CT, t0.cpad,
-                       tr->grads + t1.w_off, tr->grads + t1.b_off);
+    TRY_HIP(heads_h1_param_grads(wc, njt0, njt1, t0.cpad, tr->grads + t0.w_off, tr->grads + t0.b_off, tr->grads + t1.w_off, tr->grads + t1.b_off, hs));
     (void)ctx.rng.take();                    // (the slot the first head's launch takes in a plain pass: every pass takes its slots in one order)
     TRY_HIP(conv_launch(p, dgrad_call(l0, t0, DPH, B, fh, fw, p.GH[p.cur]).head_taps(CT).panel(tr->d_hmT, tr->hm_nk).cells(2).gate(featH, 2), p.s));
     return DGP_OK;
@@ -3174,6 +3182,19 @@ static int backward_unit_f32(TrainPass& p, int ui) {
     return DGP_OK;
 }
 
+// The fused stem weight gradient's two launches (the training step and the layer-level entry point dgp_stem_wgrad_h1): items of 4 conv rows
+// x 32 columns over a persistent grid, then the sum of the workgroups' slab rows.  sa: tensors, geometry and padding set; sa.slab: one
+// row of STEM_SLAB_ROW floats per workgroup (at most sa.nitems of them).
+static void stem_wgrad_launch(StemWgradArgs& sa, hipStream_t s) {
+    sa.bands = (sa.H1 + 3) / 4; sa.chunks = (sa.W1 + 31) / 32; sa.nitems = sa.B * sa.bands * sa.chunks;
+    static int n_cu_s = 0;
+    if (!n_cu_s) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu_s, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu_s <= 0) n_cu_s = 256; }
+    static const int wgs_per_cu = dgp_tune("DGP_STEM_WGRAD_WGS", 2);      // (1: 6.77, 2: 6.72, 3: 6.72, 4: 6.84 ms per step)
+    const int grid = sa.nitems < wgs_per_cu * n_cu_s ? sa.nitems : wgs_per_cu * n_cu_s;
+    hipLaunchKernelGGL(stem_wgrad_h1_kernel, dim3((unsigned)grid), dim3(256), 0, s, sa);
+    hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((STEM_SLAB_ROW + 255) / 256, (grid + 31) / 32), dim3(256), 0, s, sa, grid);
+}
+
 // Root block: max-pool backward (+ stem ReLU gate) and the stem's weight gradient -- or, 16-bit tier with the fused root block, both in
 // stem_wgrad_h1_kernel reading unit 0's H1 data gradient.  The stem's weight gradient is the pass's last launch and nothing else is left to
 // run beside it except the finalisation of all OTHER layers: that goes to the second stream behind the last of their weight gradients.
@@ -3190,14 +3211,8 @@ static int backward_root(TrainPass& p, bool fin_split) {
         sa.g_prev = p.stem_g_prev;
         sa.dw = reinterpret_cast<float*>(p.ws + pl.dw_l[net->conv1]); sa.colsum = reinterpret_cast<float*>(p.ws + pl.cs_l[net->conv1]);
         sa.B = B; sa.H = d.in_h; sa.W = d.in_w; sa.H1 = net->h1; sa.W1 = net->w1; sa.HP = net->hp; sa.WP = net->wp; sa.pt = pth / 2; sa.pl = ptw / 2;
-        sa.bands = (net->h1 + 3) / 4; sa.chunks = (net->w1 + 31) / 32; sa.nitems = B * sa.bands * sa.chunks;
-        static int n_cu_s = 0;
-        if (!n_cu_s) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu_s, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu_s <= 0) n_cu_s = 256; }
-        static const int wgs_per_cu = dgp_tune("DGP_STEM_WGRAD_WGS", 2);      // (1: 6.77, 2: 6.72, 3: 6.72, 4: 6.84 ms per step)
-        const int grid = sa.nitems < wgs_per_cu * n_cu_s ? sa.nitems : wgs_per_cu * n_cu_s;
         sa.slab = p.F(pl.dc1);                // (the d conv1 map's region: unused on this path; grid x 50 KB)
-        hipLaunchKernelGGL(stem_wgrad_h1_kernel, dim3((unsigned)grid), dim3(256), 0, s, sa);
-        hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((STEM_SLAB_ROW + 255) / 256, (grid + 31) / 32), dim3(256), 0, s, sa, grid);
+        stem_wgrad_launch(sa, s);
         return DGP_OK;
     }
     // (fused root block in the forward pass: no conv1 map -- unit 0's data gradient is already gated by pool > 0)
@@ -3463,6 +3478,214 @@ int dgp_conv2d_dgrad(const dgp_conv_desc* d, const float* dy, const float* w_hwi
         a.out_absmax = rng + 2 * ABSMAX_SLOTS;
     }
     TRY_HIP(launch_conv(a, pick_tile(a.M, cinP, nkT * BK, a.in_absmax && a.w_absmax), s));
+    return DGP_OK;
+}
+
+/* ---- the same for the 16-bit tier: fp32 tensors in, converted to H1 tensors by the trainer's own converter (f32_to_h1_pred_kernel) with
+ * the scales that "previous step" range slots predict, then the launchers of the 16-bit pass.  The H1 tensors stay in `scratch`. ---- */
+
+static void to_h1_pred(const float* x, long long n, const float* prev, void* out, hipStream_t s) {
+    hipLaunchKernelGGL(f32_to_h1_pred_kernel, dim3(grid_for(n / 8)), dim3(256), 0, s, reinterpret_cast<const float4*>(x), n / 8, prev,
+                       reinterpret_cast<uint4*>(out));
+}
+
+/* H1 cells with the scale `prev` predicts -> fp32 (h1_to_f32_pred_kernel); gate_h1: an H1 tensor of the same shape or NULL */
+int dgp_h1_to_f32_pred(const void* x_h1, size_t n_halves, const float* prev, const void* gate_h1, float* out, void* stream) {
+    if (!x_h1 || !prev || !out || (n_halves & 7)) return fail(DGP_ERR_INVALID, "dgp_h1_to_f32_pred: null argument or a count that is no multiple of 8");
+    const long long n8 = (long long)(n_halves / 8);
+    hipLaunchKernelGGL(h1_to_f32_pred_kernel, dim3(grid_for(n8)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(x_h1), n8, prev,
+                       reinterpret_cast<float4*>(out), reinterpret_cast<const uint4*>(gate_h1));
+    TRY_HIP(hipGetLastError());
+    return DGP_OK;
+}
+
+/* dgp_conv2d_wgrad on wgrad_dma_h1: scratch = [x as H1 | dy as H1] (2 * (numel(x) + numel(dy)) bytes).  *flag (device) is zeroed, then
+ * takes the kernel's failure bits: 2 when a tensor left the range its predicted scale covers -- dw_raw and colsum are then zero, there is
+ * no fp32 path behind this kernel. */
+int dgp_conv2d_wgrad_h1(const dgp_conv_desc* d, const float* x, const float* dy, const float* x_absmax, const float* dy_absmax,
+                        const float* x_prev, const float* dy_prev, void* scratch, float* dw_raw, float* colsum, int32_t* flag, void* stream) {
+    if (!d || !x || !dy || !dw_raw || !scratch || !x_absmax || !dy_absmax || !x_prev || !dy_prev || !flag)
+        return fail(DGP_ERR_INVALID, "dgp_conv2d_wgrad_h1: null argument");
+    if (d->Cin < 16 || (d->Cin & 15) || ((d->Cin / 8) & (d->Cin / 8 - 1)) || (d->Cout & 7))
+        return fail(DGP_ERR_INVALID, "dgp_conv2d_wgrad_h1: Cin must be 16 * 2^k, Cout a multiple of 8");
+    hipStream_t s = (hipStream_t)stream;
+    const long long nx = (long long)d->N * d->H * d->W * d->Cin, ny = (long long)d->N * d->Ho * d->Wo * d->Cout;
+    char* xh = (char*)scratch;
+    char* dyh = xh + 2 * nx;
+    TRY_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    to_h1_pred(x, nx, x_prev, xh, s);
+    to_h1_pred(dy, ny, dy_prev, dyh, s);
+    WgradCall c;
+    c.d = *d; c.x = {reinterpret_cast<const float*>(xh), x_absmax, xh, x_prev}; c.dy = {reinterpret_cast<const float*>(dyh), dy_absmax, dyh, dy_prev};
+    c.dwraw = dw_raw; c.colsum = colsum; c.fail_flag = flag; c.h1 = true;
+    hipError_t e = wgrad_launch(c, s);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_wgrad_h1: ") + hipGetErrorString(e));
+    return DGP_OK;
+}
+
+/* dgp_conv2d_dgrad as an H1 -> H1 launch.  scratch: dgp_conv2d_dgrad_scratch_bytes(d) bytes as in dgp_conv2d_dgrad (panel, its high-only
+ * cells, range slots), then [dy as H1][dx_add as H1][stride 2: dy zero-stuffed, N x 2 Ho x 2 Wo x Cout halves].  gate_h1: the gate as H1
+ * cells or NULL.  *flag (device, may be NULL): zeroed, then 1 | (1 << 8) when dx left the range dx_prev predicts (the pass's own check). */
+int dgp_conv2d_dgrad_h1(const dgp_conv_desc* d, const float* dy, const float* w_hwio, const float* scale, const void* gate_h1,
+                        const float* dx_add, int32_t add_mode, const float* dy_prev, const float* dx_prev, const float* add_prev,
+                        void* scratch, void* dx_h1, int32_t* flag, void* stream) {
+    if (!d || !dy || !w_hwio || !dx_h1 || !scratch || !dy_prev || !dx_prev || (dx_add && !add_prev))
+        return fail(DGP_ERR_INVALID, "dgp_conv2d_dgrad_h1: null argument");
+    if ((d->Cout & 63) || (d->Cin & 63)) return fail(DGP_ERR_INVALID, "dgp_conv2d_dgrad_h1: Cin % 64, Cout % 64 (a K-step is 64 channels)");
+    if (d->stride != 1 && d->stride != 2) return fail(DGP_ERR_INVALID, "dgp_conv2d_dgrad_h1: stride 1 or 2");
+    if (dx_add && add_mode != 1 && add_mode != -2) return fail(DGP_ERR_INVALID, "dgp_conv2d_dgrad_h1: add_mode 1 or -2");
+    hipStream_t s = (hipStream_t)stream;
+    const int taps = d->KH * d->KW, nkT = nk_for(d->KH, d->KW, d->Cout), cinP = coutp_for(d->Cin);
+    const size_t panel_bytes = (size_t)nkT * 8 * cinP * 16;
+    char* sp = (char*)scratch;
+    float* panel = (float*)sp; sp += panel_bytes;
+    void* cells = sp; sp += panel_bytes;
+    float* rng = (float*)sp;               // [0]: dy, [1]: panel, [2]: dx
+    float* ones = rng + 4 * ABSMAX_SLOTS;
+    sp = (char*)scratch + dgp_conv2d_dgrad_scratch_bytes(d);
+    const long long ny = (long long)d->N * d->Ho * d->Wo * d->Cout;
+    const int aH = add_mode == -2 ? (d->H + 1) / 2 : d->H, aW = add_mode == -2 ? (d->W + 1) / 2 : d->W;
+    const long long na = dx_add ? (long long)d->N * aH * aW * d->Cin : 0;
+    char* dyh = sp; sp += 2 * ny;
+    char* addh = sp; sp += 2 * na;
+    char* zs = sp;
+    TRY_HIP(hipMemsetAsync(rng, 0, 4 * ABSMAX_SLOTS * sizeof(float), s));
+    if (flag) TRY_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    if (!scale) {
+        std::vector<float> h(d->Cout, 1.f);
+        TRY_HIP(hipMemcpyAsync(ones, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        TRY_HIP(hipStreamSynchronize(s));
+        scale = ones;
+    }
+    const long long totT = (long long)nkT * 8 * cinP;
+    hipLaunchKernelGGL(pack_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, w_hwio, scale, taps, d->Cin, d->Cout, cinP, nkT * 8,
+                       panel, rng + ABSMAX_SLOTS);
+    TRY_HIP(launch_pack_h1(panel, nkT, cinP, rng + ABSMAX_SLOTS, cells, s));
+    TRY_HIP(launch_absmax(dy, ny, rng, s));
+    to_h1_pred(dy, ny, dy_prev, dyh, s);
+    if (dx_add) to_h1_pred(dx_add, na, add_prev, addh, s);
+    // the launch as the kernels see it: the transposed conv on dy's grid -- a stride-2 layer: on the zero-stuffed 2 Ho x 2 Wo grid
+    const int keff_h = (d->KH - 1) * d->rate + 1, keff_w = (d->KW - 1) * d->rate + 1;
+    const char* in = dyh;
+    int inH = d->Ho, inW = d->Wo;
+    if (d->stride == 2) {
+        TRY_HIP(hipMemsetAsync(zs, 0, (size_t)ny * 4 * 2, s));
+        const long long tot = (long long)d->N * d->Ho * d->Wo * (d->Cout / 8);
+        hipLaunchKernelGGL(h1_zero_stuff_kernel, dim3(grid_for(tot)), dim3(256), 0, s, reinterpret_cast<const uint4*>(dyh), d->N, d->Ho, d->Wo,
+                           d->Cout / 8, reinterpret_cast<uint4*>(zs));
+        in = zs; inH = 2 * d->Ho; inW = 2 * d->Wo;
+    }
+    dgp_conv_desc t{};
+    t.N = d->N; t.H = inH; t.W = inW; t.Cin = d->Cout; t.Cout = d->Cin; t.KH = d->KH; t.KW = d->KW; t.stride = 1; t.rate = d->rate;
+    t.pad_t = keff_h - 1 - d->pad_t; t.pad_l = keff_w - 1 - d->pad_l; t.Ho = d->H; t.Wo = d->W;
+    t.res_stride = dx_add ? add_mode : 0; t.res_H = aH; t.res_W = aW;
+    ConvArgs a{};
+    a.in = reinterpret_cast<const float*>(in); a.wpk = panel; a.out = reinterpret_cast<float*>(dx_h1);
+    a.mask = reinterpret_cast<const float*>(gate_h1); a.res = dx_add ? reinterpret_cast<const float*>(addh) : nullptr;
+    if (int rc = fill_conv_geometry(a, t, "dgp_conv2d_dgrad_h1: tensor exceeds 4 GiB")) return rc;      // (CoutP = cinP, nk = nkT, w_bytes = panel_bytes)
+    a.mask_fmt = gate_h1 ? 2 : 0;
+    a.in_fmt = a.out_fmt = 2; a.res_fmt = dx_add ? 2 : 0;
+    a.in_scale_dev = dy_prev; a.out_scale_dev = dx_prev; a.res_scale_dev = dx_add ? add_prev : nullptr;
+    a.in_absmax = rng; a.w_absmax = rng + ABSMAX_SLOTS; a.wh3 = cells; a.wh3_bytes = a.w_bytes;
+    a.out_absmax = rng + 2 * ABSMAX_SLOTS;
+    hipError_t e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), s);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_dgrad_h1: ") + hipGetErrorString(e));
+    if (flag) {
+        H2CheckList list{};
+        list.n = 1; list.idx[0] = 0;
+        hipLaunchKernelGGL(h2_pred_check_kernel, dim3(1), dim3(64), 0, s, list, rng + 2 * ABSMAX_SLOTS, dx_prev, reinterpret_cast<int*>(flag));
+    }
+    TRY_HIP(hipGetLastError());
+    return DGP_OK;
+}
+
+/* stem_wgrad_h1_kernel + stem_wgrad_reduce_kernel as backward_root launches them.  scratch: [d pool as H1: 2 * numel(dpool) bytes][slab:
+ * B * ceil(H1 / 4) * ceil(W1 / 32) rows of (196 * 64 + 64) floats].  dw [49 * 4][64] and colsum [64] are overwritten. */
+int dgp_stem_wgrad_h1(const float* x_centred, const float* dpool, const float* dpool_prev, const uint8_t* idx, int32_t B, int32_t H, int32_t W,
+                      int32_t H1, int32_t W1, int32_t HP, int32_t WP, void* scratch, float* dw, float* colsum, void* stream) {
+    if (!x_centred || !dpool || !dpool_prev || !idx || !scratch || !dw || !colsum) return fail(DGP_ERR_INVALID, "dgp_stem_wgrad_h1: null argument");
+    if (B < 1 || H < 1 || W < 1 || H1 != (H + 1) / 2 || W1 != (W + 1) / 2 || HP != (H1 + 1) / 2 || WP != (W1 + 1) / 2)
+        return fail(DGP_ERR_INVALID, "dgp_stem_wgrad_h1: the maps must be those of the root block (conv 7x7 / 2, pool 3x3 / 2, SAME)");
+    hipStream_t s = (hipStream_t)stream;
+    const long long ng = (long long)B * HP * WP * 64;
+    int pth = (HP - 1) * 2 + 3 - H1; if (pth < 0) pth = 0;
+    int ptw = (WP - 1) * 2 + 3 - W1; if (ptw < 0) ptw = 0;
+    to_h1_pred(dpool, ng, dpool_prev, scratch, s);
+    TRY_HIP(hipMemsetAsync(dw, 0, (size_t)196 * 64 * sizeof(float), s));
+    TRY_HIP(hipMemsetAsync(colsum, 0, 64 * sizeof(float), s));
+    StemWgradArgs sa{};
+    sa.x = x_centred; sa.g = reinterpret_cast<const uint4*>(scratch); sa.idx = idx; sa.g_prev = dpool_prev;
+    sa.dw = dw; sa.colsum = colsum;
+    sa.B = B; sa.H = H; sa.W = W; sa.H1 = H1; sa.W1 = W1; sa.HP = HP; sa.WP = WP; sa.pt = pth / 2; sa.pl = ptw / 2;
+    sa.slab = reinterpret_cast<float*>((char*)scratch + (((size_t)ng * 2 + 255) & ~(size_t)255));
+    stem_wgrad_launch(sa, s);
+    TRY_HIP(hipGetLastError());
+    return DGP_OK;
+}
+
+/* backward_heads_h1's sequence on one stream: gather both heads' loss gradients into one H1 tensor of heads_ct(nj) columns, pack the merged
+ * data-gradient panel, one weight-gradient launch, the two finalisations, one 2x2-tap H1 data gradient gated by the features.
+ * scratch (bytes, each part rounded up to 256): [feat as H1: 2 N h w Cin][merged gradient as H1: 2 N h w CT][panel: nk 8 cinP 16][its cells:
+ * half of that][dwraw: 4 Cin CT floats][colsum: 2 CT floats][4 range slots: features, merged gradient, panel, d features]. */
+int dgp_heads_backward_h1(const float* feat, const float* feat_prev, const float* dscmap, const float* dlocref, const float* dph_prev,
+                          const float* w_part, const float* w_locref, const float* dfeat_prev, int32_t N, int32_t h, int32_t w, int32_t Cin,
+                          int32_t nj, void* scratch, float* dw_part, float* db_part, float* dw_locref, float* db_locref, void* dfeat_h1,
+                          int32_t* flag, void* stream) {
+    if (!feat || !feat_prev || !dscmap || !dlocref || !dph_prev || !w_part || !w_locref || !dfeat_prev || !scratch || !dw_part || !db_part ||
+        !dw_locref || !db_locref || !dfeat_h1 || !flag)
+        return fail(DGP_ERR_INVALID, "dgp_heads_backward_h1: null argument");
+    if (N < 1 || h < 1 || w < 1 || nj < 1 || Cin < 64 || ((Cin / 8) & (Cin / 8 - 1)))
+        return fail(DGP_ERR_INVALID, "dgp_heads_backward_h1: Cin must be 64 * 2^k");
+    const int njt0 = nj, njt1 = 2 * nj, cpad0 = next_pow2(4 * njt0), cpad1 = next_pow2(4 * njt1);
+    const int CT = heads_ct(nj), nkT = nk_for(2, 2, CT), cinP = coutp_for(Cin);
+    // (the trainer's condition for the merged panel, dgp_trainer_sync_weights)
+    if (!(cpad0 + cpad1 <= CT && (nkT % 2) == 0 && cinP % 64 == 0))
+        return fail(DGP_ERR_INVALID, "dgp_heads_backward_h1: the merged panel does not take these head widths");
+    hipStream_t s = (hipStream_t)stream;
+    auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const long long M = (long long)N * h * w;
+    const size_t pbytes = (size_t)nkT * 8 * cinP * 16;
+    char* sp = (char*)scratch;
+    char* featH = sp; sp += up256((size_t)M * Cin * 2);
+    char* DPH = sp; sp += up256((size_t)M * CT * 2);
+    float* panel = (float*)sp; sp += up256(pbytes);
+    void* cells = sp; sp += up256(pbytes / 2);
+    float* dwraw = (float*)sp; sp += up256((size_t)4 * Cin * CT * sizeof(float));
+    float* colsum = (float*)sp; sp += up256((size_t)2 * CT * sizeof(float));
+    float* rng = (float*)sp;               // [0]: features, [1]: merged gradient, [2]: panel, [3]: d features
+    TRY_HIP(hipMemsetAsync(rng, 0, 4 * ABSMAX_SLOTS * sizeof(float), s));
+    TRY_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    TRY_HIP(launch_absmax(feat, M * Cin, rng, s));
+    to_h1_pred(feat, M * Cin, feat_prev, featH, s);
+    float* slot_dph = rng + ABSMAX_SLOTS;
+    hipLaunchKernelGGL(head_gather_h1_kernel, dim3(grid_for(M * (CT / 8))), dim3(256), 0, s, dscmap, dlocref, N, h, w, njt0, cpad0, njt1, cpad1, CT,
+                       dph_prev, reinterpret_cast<uint4*>(DPH), slot_dph);
+    const long long totT = (long long)nkT * 8 * cinP;
+    hipLaunchKernelGGL(pack_heads_dgrad_kernel, dim3(grid_for(totT)), dim3(256), 0, s, w_part, njt0, cpad0, w_locref, njt1, cpad1, Cin, CT, cinP,
+                       nkT * 8, panel, rng + 2 * ABSMAX_SLOTS);
+    TRY_HIP(launch_pack_h1(panel, nkT, cinP, rng + 2 * ABSMAX_SLOTS, cells, s));
+    WgradCall wc;
+    wc.d.N = N; wc.d.H = wc.d.Ho = h; wc.d.W = wc.d.Wo = w; wc.d.Cin = Cin; wc.d.Cout = CT;
+    wc.d.KH = wc.d.KW = 2; wc.d.stride = wc.d.rate = 1; wc.d.pad_t = wc.d.pad_l = 1;      // (head_wgrad_call)
+    wc.dwraw = dwraw; wc.colsum = colsum;
+    wc.x = {reinterpret_cast<const float*>(featH), rng, featH, feat_prev};
+    wc.dy = {reinterpret_cast<const float*>(DPH), slot_dph, DPH, dph_prev};
+    wc.fail_flag = reinterpret_cast<int*>(flag); wc.h1 = true;
+    hipError_t e = heads_h1_param_grads(wc, njt0, njt1, cpad0, dw_part, db_part, dw_locref, db_locref, s);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_heads_backward_h1: weight gradient: ") + hipGetErrorString(e));
+    // d features: the 2x2-conv form over the merged tensor (dgrad_call(...).head_taps(CT).panel(merged, nkT).cells(2).gate(features, 2))
+    dgp_conv_desc t{};
+    t.N = N; t.H = t.Ho = h; t.W = t.Wo = w; t.Cin = CT; t.Cout = Cin; t.KH = t.KW = 2; t.stride = 1; t.rate = 1;
+    ConvArgs a{};
+    a.in = reinterpret_cast<const float*>(DPH); a.wpk = panel; a.out = reinterpret_cast<float*>(dfeat_h1); a.mask = reinterpret_cast<const float*>(featH);
+    if (int rc = fill_conv_geometry(a, t, "dgp_heads_backward_h1: tensor exceeds 4 GiB")) return rc;
+    a.CoutP = cinP; a.nk = nkT; a.w_bytes = (unsigned)pbytes;
+    a.mask_fmt = 2; a.in_fmt = a.out_fmt = 2;
+    a.in_scale_dev = dph_prev; a.out_scale_dev = dfeat_prev;
+    a.in_absmax = slot_dph; a.w_absmax = rng + 2 * ABSMAX_SLOTS; a.wh3 = cells; a.wh3_bytes = a.w_bytes;
+    a.out_absmax = rng + 3 * ABSMAX_SLOTS;
+    e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), s);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_heads_backward_h1: data gradient: ") + hipGetErrorString(e));
     return DGP_OK;
 }
 

@@ -628,6 +628,141 @@ def conv2d_dgrad(dy: torch.Tensor, w_hwio: torch.Tensor, x_hw: Tuple[int, int], 
     return dx
 
 
+# ---- layer-level entry points of the 16-bit tier's backward pass (tests): fp32 tensors in, H1 tensors made by the trainer's converter ----
+def _slots(value: float, dev) -> torch.Tensor:
+    """Range slots whose maximum is `value` (what a producer's epilogue leaves: here every slot the same)."""
+    return torch.full((ABSMAX_SLOTS,), float(value), dtype=torch.float32, device=dev)
+
+
+def _measured(x: torch.Tensor) -> torch.Tensor:
+    rng = torch.zeros(ABSMAX_SLOTS, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().dgp_tensor_absmax(_ptr(x), x.numel(), _ptr(rng), _stream(x.device)), "dgp_tensor_absmax")
+    return rng
+
+
+def h1_to_f32_pred(x_h1: torch.Tensor, prev_max: float, gate_h1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """H1 cells written with the scale a previous maximum `prev_max` predicts -> fp32 (zero where gate_h1's half is not positive)."""
+    _need_cuda(x_h1, torch.float16, "x_h1")
+    out = torch.empty(x_h1.shape, dtype=torch.float32, device=x_h1.device)
+    prev = _slots(prev_max, x_h1.device)
+    _lib.check(_lib.load().dgp_h1_to_f32_pred(_ptr(x_h1), x_h1.numel(), _ptr(prev), _ptr(gate_h1), _ptr(out), _stream(x_h1.device)),
+               "dgp_h1_to_f32_pred")
+    return out
+
+
+def conv2d_wgrad_h1(x: torch.Tensor, dy: torch.Tensor, ksize: int, stride: int = 1, rate: int = 1, pad_t: int = 0, pad_l: int = 0,
+                    prev_max: Optional[Tuple[float, float]] = None):
+    """conv2d_wgrad through wgrad_dma_h1.  prev_max: last step's maxima of (x, dy) that predict the scales (None: this step's).
+    -> (dW [k,k,Cin,Cout], colsum [Cout], x cells, dy cells (float16, as the kernel read them), flag)."""
+    lib = _lib.load()
+    _need_cuda(x, torch.float32, "x")
+    _need_cuda(dy, torch.float32, "dy")
+    dev = x.device
+    N, H, W, Cin = x.shape
+    _, Ho, Wo, Cout = dy.shape
+    d = _conv_desc(x.shape, (ksize, ksize, Cin, Cout), stride, rate, pad_t, pad_l, (Ho, Wo))
+    dw = torch.empty((ksize, ksize, Cin, Cout), dtype=torch.float32, device=dev)
+    cs = torch.empty(2 * Cout, dtype=torch.float32, device=dev)
+    cur = (_measured(x), _measured(dy))
+    if prev_max is None:
+        prev_max = (float(cur[0].max()), float(cur[1].max()))
+    prev = (_slots(prev_max[0], dev), _slots(prev_max[1], dev))
+    scratch = torch.zeros(x.numel() + dy.numel(), dtype=torch.float16, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.dgp_conv2d_wgrad_h1(C.byref(d), _ptr(x), _ptr(dy), _ptr(cur[0]), _ptr(cur[1]), _ptr(prev[0]), _ptr(prev[1]),
+                                       _ptr(scratch), _ptr(dw), _ptr(cs), _ptr(flag), _stream(dev)), "dgp_conv2d_wgrad_h1")
+    return dw, cs[:Cout], scratch[:x.numel()].view(x.shape), scratch[x.numel():].view(dy.shape), int(flag.item())
+
+
+def conv2d_dgrad_h1(dy: torch.Tensor, w_hwio: torch.Tensor, x_hw: Tuple[int, int], stride: int = 1, rate: int = 1, pad_t: int = 0,
+                    pad_l: int = 0, scale: Optional[torch.Tensor] = None, gate_h1: Optional[torch.Tensor] = None,
+                    dx_add: Optional[torch.Tensor] = None, add_mode: int = 1, dy_prev: float = 0.0, dx_prev: float = 0.0,
+                    add_prev: float = 0.0):
+    """conv2d_dgrad as the 16-bit pass's H1 -> H1 launch.  *_prev: last step's maxima that predict the scales of dy, dx and dx_add;
+    gate_h1: the gate as float16 cells (f32_to_h1).  -> dict(dx: float16 cells [N,H,W,Cin], dx_f32: the same through the pass's H1 -> fp32
+    converter, dy / add: the cells the kernel read, flag)."""
+    lib = _lib.load()
+    _need_cuda(dy, torch.float32, "dy")
+    _need_cuda(w_hwio, torch.float32, "w_hwio")
+    dev = dy.device
+    N, Ho, Wo, Cout = dy.shape
+    kh, kw, Cin, _ = w_hwio.shape
+    H, W = x_hw
+    d = _conv_desc((N, H, W, Cin), w_hwio.shape, stride, rate, pad_t, pad_l, (Ho, Wo))
+    base = int(lib.dgp_conv2d_dgrad_scratch_bytes(C.byref(d)))
+    na = dx_add.numel() if dx_add is not None else 0
+    nbytes = base + 2 * dy.numel() + 2 * na + (8 * dy.numel() if stride == 2 else 0)
+    scratch = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    dx = torch.zeros((N, H, W, Cin), dtype=torch.float16, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    prevs = (_slots(dy_prev, dev), _slots(dx_prev, dev), _slots(add_prev, dev))
+    _lib.check(lib.dgp_conv2d_dgrad_h1(C.byref(d), _ptr(dy), _ptr(w_hwio), _ptr(scale), _ptr(gate_h1), _ptr(dx_add), add_mode,
+                                       _ptr(prevs[0]), _ptr(prevs[1]), _ptr(prevs[2]) if dx_add is not None else None, _ptr(scratch),
+                                       _ptr(dx), _ptr(flag), _stream(dev)), "dgp_conv2d_dgrad_h1")
+    out = dict(dx=dx, dx_f32=h1_to_f32_pred(dx, dx_prev), flag=int(flag.item()))
+    out["dy"] = scratch[base: base + 2 * dy.numel()].view(torch.float16).view(dy.shape)
+    if dx_add is not None:
+        out["add"] = scratch[base + 2 * dy.numel(): base + 2 * dy.numel() + 2 * na].view(torch.float16).view(dx_add.shape)
+    if stride == 2:
+        z0 = base + 2 * dy.numel() + 2 * na
+        out["stuffed"] = scratch[z0: z0 + 8 * dy.numel()].view(torch.float16).view(N, 2 * Ho, 2 * Wo, Cout)
+    return out
+
+
+def stem_wgrad_h1(x_centred: torch.Tensor, dpool: torch.Tensor, idx: torch.Tensor, dpool_prev: float):
+    """The fused stem weight gradient of the 16-bit pass: x_centred [B,H,W,4] fp32, dpool [B,HP,WP,64] fp32, idx uint8 first-maximum
+    record.  -> (dw [7,7,4,64], colsum [64], dpool cells float16)."""
+    lib = _lib.load()
+    _need_cuda(x_centred, torch.float32, "x_centred")
+    _need_cuda(dpool, torch.float32, "dpool")
+    _need_cuda(idx, torch.uint8, "idx")
+    dev = dpool.device
+    B, H, W, _ = x_centred.shape
+    H1, W1 = (H + 1) // 2, (W + 1) // 2
+    HP, WP = (H1 + 1) // 2, (W1 + 1) // 2
+    assert dpool.shape == (B, HP, WP, 64) and idx.shape == dpool.shape and x_centred.shape[3] == 4
+    cells_bytes = (2 * dpool.numel() + 255) // 256 * 256
+    rows = B * ((H1 + 3) // 4) * ((W1 + 31) // 32)
+    scratch = torch.zeros(cells_bytes + rows * (196 * 64 + 64) * 4, dtype=torch.uint8, device=dev)
+    dw = torch.empty((7, 7, 4, 64), dtype=torch.float32, device=dev)
+    cs = torch.empty(64, dtype=torch.float32, device=dev)
+    prev = _slots(dpool_prev, dev)
+    _lib.check(lib.dgp_stem_wgrad_h1(_ptr(x_centred), _ptr(dpool), _ptr(prev), _ptr(idx), B, H, W, H1, W1, HP, WP, _ptr(scratch), _ptr(dw),
+                                     _ptr(cs), _stream(dev)), "dgp_stem_wgrad_h1")
+    return dw, cs, scratch[:2 * dpool.numel()].view(torch.float16).view(dpool.shape)
+
+
+def heads_backward_h1(feat: torch.Tensor, dscmap: torch.Tensor, dlocref: torch.Tensor, w_part: torch.Tensor, w_locref: torch.Tensor,
+                      ct: int, feat_prev: float, dph_prev: float, dfeat_prev: float):
+    """Both heads' backward of the 16-bit pass.  w_*: [3,3,njt,Cin] (the trainer's layout); ct: columns of the merged gradient tensor
+    (only to size and slice the scratch).  -> dict(dw_part, db_part, dw_locref, db_locref, dfeat: float16 cells, feat / merged: the cells
+    the kernels read, flag)."""
+    lib = _lib.load()
+    for t, nm in ((feat, "feat"), (dscmap, "dscmap"), (dlocref, "dlocref"), (w_part, "w_part"), (w_locref, "w_locref")):
+        _need_cuda(t, torch.float32, nm)
+    dev = feat.device
+    N, h, w, Cin = feat.shape
+    nj = dscmap.shape[3]
+    up = lambda b: (b + 255) // 256 * 256
+    M = N * h * w
+    nbytes = up(2 * M * Cin) + up(2 * M * ct) + 48 * Cin * ct + 16384
+    scratch = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    res = dict(dw_part=torch.empty((3, 3, nj, Cin), dtype=torch.float32, device=dev), db_part=torch.empty(nj, dtype=torch.float32, device=dev),
+               dw_locref=torch.empty((3, 3, 2 * nj, Cin), dtype=torch.float32, device=dev),
+               db_locref=torch.empty(2 * nj, dtype=torch.float32, device=dev), dfeat=torch.zeros((N, h, w, Cin), dtype=torch.float16, device=dev))
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    prevs = (_slots(feat_prev, dev), _slots(dph_prev, dev), _slots(dfeat_prev, dev))
+    _lib.check(lib.dgp_heads_backward_h1(_ptr(feat), _ptr(prevs[0]), _ptr(dscmap), _ptr(dlocref), _ptr(prevs[1]), _ptr(w_part), _ptr(w_locref),
+                                         _ptr(prevs[2]), N, h, w, Cin, nj, _ptr(scratch), _ptr(res["dw_part"]), _ptr(res["db_part"]),
+                                         _ptr(res["dw_locref"]), _ptr(res["db_locref"]), _ptr(res["dfeat"]), _ptr(flag), _stream(dev)),
+               "dgp_heads_backward_h1")
+    res["flag"] = int(flag.item())
+    res["feat"] = scratch[:2 * M * Cin].view(torch.float16).view(N, h, w, Cin)
+    o = up(2 * M * Cin)
+    res["merged"] = scratch[o: o + 2 * M * ct].view(torch.float16).view(N, h, w, ct)
+    return res
+
+
 def h2_exp_for(absmax: float, headroom_bits: int = 4) -> int:
     """The engine's scale rule: exponent e with absmax * 2^e in [2^(14 - headroom), 2^(15 - headroom))."""
     import math

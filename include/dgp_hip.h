@@ -355,6 +355,47 @@ int    dgp_conv2d_wgrad_shadow(const dgp_conv_desc* d, const float* x, const flo
 size_t dgp_conv2d_dgrad_scratch_bytes(const dgp_conv_desc* d);
 int    dgp_conv2d_dgrad(const dgp_conv_desc* d, const float* dy, const float* w_hwio, const float* scale, const float* mask,
                         const float* dx_add, int32_t add_mode, float* dx, void* scratch, int32_t ranged, void* stream);
+/* ---- the same for the 16-bit tier (dgp_trainer_set_tier(tr, 1)), whose backward pass runs other kernels: every tensor is an H1 tensor
+ * (below) whose scale is PREDICTED from the range slots the same tensor had one step earlier -- max = m 2^E (1 <= m < 2) -> scale
+ * 2^(10 - E), no scale (nothing written) for a zero or non-finite maximum; usable while this step's maximum times the scale stays in
+ * [16, 65000).  These entry points take fp32 tensors plus such "previous step" slots (DGP_ABSMAX_SLOTS floats each), make the H1
+ * tensors with the trainer's own converter, leave them in `scratch` for the caller to read, and run the launchers of the 16-bit pass.
+ * No reference counterpart (the reference computes in fp32).  `d` describes the FORWARD conv. */
+/* H1 cells written with the scale `prev` predicts -> fp32; gate_h1: an H1 tensor of the same shape (out = 0 where its half is not
+ * positive) or NULL.  The converter the 16-bit pass uses where a gradient leaves the H1 units. */
+int    dgp_h1_to_f32_pred(const void* x_h1, size_t n_halves, const float* prev, const void* gate_h1, float* out, void* stream);
+/* dgp_conv2d_wgrad on wgrad_dma_h1: both operands H1 tensors read in place by LDS-DMA, one fp16 MFMA per product, the 128-column tile
+ * partly filled for narrower layers.  scratch: [x as H1 | dy as H1], 2 * (numel(x) + numel(dy)) bytes.  *flag (device int32): zeroed, then
+ * 2 when a tensor left its predicted range -- dw_raw / colsum are zero then: this kernel has no fp32 path behind it.
+ * Cin = 16 * 2^k, Cout % 8 == 0. */
+int    dgp_conv2d_wgrad_h1(const dgp_conv_desc* d, const float* x, const float* dy, const float* x_absmax, const float* dy_absmax,
+                           const float* x_prev, const float* dy_prev, void* scratch, float* dw_raw, float* colsum, int32_t* flag, void* stream);
+/* dgp_conv2d_dgrad as the H1 -> H1 launch of the 16-bit pass: dx_h1 (halves, [N,H,W,Cin]) = fp16(gate(convT(dy; w * scale) + dx_add) * the
+ * scale dx_prev predicts).  The panel comes from the same pack as dgp_conv2d_dgrad, as high-only fp16 cells; dy and dx_add are converted
+ * with dy_prev / add_prev; gate_h1 is the gate ALREADY as H1 cells (dgp_f32_to_h1, any scale: only its sign is read) or NULL; a stride-2
+ * layer reads dy from a zero-stuffed H1 copy on the 2 Ho x 2 Wo grid through a stride-1 launch, as the pass does.
+ * scratch: dgp_conv2d_dgrad_scratch_bytes(d) bytes, then [dy as H1: 2 numel(dy)][dx_add as H1: 2 numel(dx_add)][stride 2: 8 numel(dy)].
+ * *flag (device int32, may be NULL): zeroed, then odd when dx left the range dx_prev predicts.  Cin % 64 == 0, Cout % 64 == 0. */
+int    dgp_conv2d_dgrad_h1(const dgp_conv_desc* d, const float* dy, const float* w_hwio, const float* scale, const void* gate_h1,
+                           const float* dx_add, int32_t add_mode, const float* dy_prev, const float* dx_prev, const float* add_prev,
+                           void* scratch, void* dx_h1, int32_t* flag, void* stream);
+/* The stem's weight gradient with the max-pool's backward fused in (stem_wgrad_h1_kernel + stem_wgrad_reduce_kernel): x_centred
+ * [B,H,W,4] fp32, dpool [B,HP,WP,64] fp32 (converted with dpool_prev), idx [B,HP,WP,64] bytes: position a * 3 + b of each pool window's
+ * FIRST maximum (row-major, window origin 2 q - pad), H1 = ceil(H / 2), HP = ceil(H1 / 2) (same for W).  dw [49 * 4][64], colsum [64].
+ * scratch: 2 * numel(dpool) bytes rounded up to 256, then B * ceil(H1 / 4) * ceil(W1 / 32) rows of (196 * 64 + 64) floats. */
+int    dgp_stem_wgrad_h1(const float* x_centred, const float* dpool, const float* dpool_prev, const uint8_t* idx, int32_t B, int32_t H,
+                         int32_t W, int32_t H1, int32_t W1, int32_t HP, int32_t WP, void* scratch, float* dw, float* colsum, void* stream);
+/* Both heads' backward of the 16-bit pass on one stream: feat [N,h,w,Cin] (converted with feat_prev), dscmap [N,2h,2w,nj] and dlocref
+ * [N,2h,2w,2nj] gathered phase-major into ONE H1 tensor of CT columns with one scale (dph_prev), w_part / w_locref in the trainer's
+ * layout [3,3,njt,Cin]; one weight-gradient launch, two finalisations (dw_* [3,3,njt,Cin], db_* [njt]), one 2x2-tap data gradient
+ * dfeat_h1 (halves, scale from dfeat_prev, gated by feat).  DGP_ERR_INVALID for head widths the merged panel does not take.
+ * scratch, each part rounded up to 256 bytes: [feat H1: 2 N h w Cin][merged gradient H1: 2 N h w CT][panel: 16 CT Cin][its cells:
+ * 8 CT Cin][dwraw: 16 Cin CT][colsum: 8 CT][4 range slots] with CT = the merged tensor's columns (next_pow2(4 nj) + next_pow2(8 nj), rounded up to a multiple of 64);
+ * 2 N h w (Cin + CT) + 48 Cin CT + 16384 bytes suffice for Cin % 128 == 0.  *flag as dgp_conv2d_wgrad_h1. */
+int    dgp_heads_backward_h1(const float* feat, const float* feat_prev, const float* dscmap, const float* dlocref, const float* dph_prev,
+                             const float* w_part, const float* w_locref, const float* dfeat_prev, int32_t N, int32_t h, int32_t w,
+                             int32_t Cin, int32_t nj, void* scratch, float* dw_part, float* db_part, float* dw_locref, float* db_locref,
+                             void* dfeat_h1, int32_t* flag, void* stream);
 /* ---- "H2" activation format.  Inside dgp_forward / dgp_infer every tensor from the pool output to the block4 features lives
  * in HBM as fp16 high / low cell pairs: per pixel and 8 channels [8 halves hi | 8 halves lo] = 32 bytes (the footprint and the
  * addresses of 8 fp32 channels) holding x * 2^exp, hi = fp16(x 2^exp), lo = fp16(x 2^exp - hi): 22 significant bits.  The
