@@ -153,6 +153,11 @@ SYMBOLS = {
     "dgp_jpeg_entropy_decode": (C.c_int, [_vp, C.c_int64, C.POINTER(DgpJpegInfo), _vp, _vp]),
     "dgp_jpeg_scratch_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "dgp_jpeg_reconstruct_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_int64, _vp, _sz, _vp]),
+    "dgp_jpeg_quality_tables": (C.c_int, [_i32, _vp]),
+    "dgp_jpeg_encode_bound": (C.c_int64, [_i32, _i32, _i32]),
+    "dgp_jpeg_entropy_encode": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "dgp_jpeg_forward_scratch_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "dgp_jpeg_forward_u8": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

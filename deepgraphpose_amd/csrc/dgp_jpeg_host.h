@@ -1,5 +1,6 @@
-// Baseline JPEG on the host: a bounded parser and Huffman (entropy) decoder.  Plain C++, no HIP: dgp_jpeg.hip includes it for the
-// C-ABI's dgp_jpeg_probe / dgp_jpeg_entropy_decode, and a stand-alone program (tests/jpeg_host_main.cpp) includes it on its own.
+// Baseline JPEG on the host: a bounded parser and Huffman (entropy) decoder, and below them the entropy ENCODER with the quality
+// tables and the stream header.  Plain C++, no HIP: dgp_jpeg.hip includes it for the C-ABI's dgp_jpeg_probe / dgp_jpeg_entropy_decode /
+// dgp_jpeg_entropy_encode, and stand-alone programs (tests/jpeg_host_main.cpp, tests/jpeg_enc_host_main.cpp) include it on their own.
 //
 // Written from ITU-T T.81: marker segments (B.2), Huffman table generation (Annex C), the decode procedures (F.2.2), the typical
 // tables of Annex K.3 for streams that carry none (plain MJPEG frames).  Only SOF0 in one interleaved scan is accepted.  No globals,
@@ -383,6 +384,195 @@ static inline bool entropy_decode(const uint8_t* d, int64_t n, const dgp_jpeg_in
                     }
             }
         }
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the encoder's host half
+// The mirror image: quantised coefficients (dgp_jpeg_forward_u8's, in the layout entropy_decode writes) -> the complete stream Pillow
+// (libjpeg-turbo, default settings) writes for them: JFIF 1.01 header, the two tables, SOF0, the four Annex K.3 Huffman tables, one
+// interleaved scan without restart markers (F.1.2).  The same rules: no globals, no allocation, every write checked against `cap`.
+
+// Annex K.1 / K.2, natural order
+static const uint8_t kStdLumQuant[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
+                                         69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55, 64,
+                                         81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+static const uint8_t kStdChrQuant[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                         99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                         99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+constexpr int64_t kEncHeaderBytes = 2 + 18 + 2 * 69 + 19 + 2 * (33 + 183) + 14;      // SOI .. SOS
+// a block's worst case: a DC code of 11 bits + 11 value bits, 63 AC codes of 16 bits + 10 value bits = 1660 bits, every byte stuffed
+constexpr int64_t kEncBlockBytes = 2 * ((22 + 63 * 26 + 7) / 8);
+
+// libjpeg's jpeg_set_quality with force_baseline: qt[0] luminance, qt[1] chrominance, natural order
+static inline bool quality_tables(int32_t quality, uint16_t* qt) {
+    if (!qt || quality < 1 || quality > 100) return false;
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) {
+            const int v = ((t ? kStdChrQuant[k] : kStdLumQuant[k]) * scale + 50) / 100;
+            qt[t * 64 + k] = (uint16_t)(v < 1 ? 1 : v > 255 ? 255 : v);
+        }
+    return true;
+}
+
+// 0 for a geometry the encoder refuses (grey included)
+static inline int64_t encode_bound(int32_t H, int32_t W, int32_t sampling) {
+    dgp_jpeg_info g;
+    if (sampling == DGP_JPEG_GRAY || !geometry(W, H, sampling, &g)) return 0;
+    return kEncHeaderBytes + (int64_t)g.total_blocks * kEncBlockBytes + 2 + 2;          // + the padded last byte (stuffed if FF) + EOI
+}
+
+struct EncHuff {
+    uint16_t code[256];
+    uint8_t len[256];           // 0: the table has no code for the symbol
+};
+
+static inline void build_enc_huff(EncHuff* h, const uint8_t* bits, const uint8_t* vals) {
+    memset(h->len, 0, sizeof(h->len));
+    memset(h->code, 0, sizeof(h->code));
+    uint32_t code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < bits[l - 1]; ++i, ++k, ++code) {
+            h->code[vals[k]] = (uint16_t)code;
+            h->len[vals[k]] = (uint8_t)l;
+        }
+        code <<= 1;
+    }
+}
+
+struct Out {
+    uint8_t* d;
+    int64_t pos, cap;
+    uint64_t acc;
+    int nbits;
+    bool full;
+
+    inline void byte(uint8_t b) {
+        if (pos < cap) d[pos++] = b;
+        else full = true;
+    }
+    inline void bytes(const uint8_t* s, int n) {
+        for (int i = 0; i < n; ++i) byte(s[i]);
+    }
+    inline void u16(int v) {
+        byte((uint8_t)(v >> 8));
+        byte((uint8_t)(v & 255));
+    }
+    // `size` (1..32) bits of entropy-coded data, most significant first; a byte FF is followed by a stuffed 00 (B.1.1.5)
+    inline void put(uint32_t code, int size) {
+        acc = (acc << size) | code;      // at most 7 bits were left: 39 of the 64 in use
+        nbits += size;
+        while (nbits >= 8) {
+            const uint8_t b = (uint8_t)(acc >> (nbits - 8));
+            byte(b);
+            if (b == 0xFF) byte(0);
+            nbits -= 8;
+        }
+    }
+};
+
+static inline int bit_length(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+static inline void put_dht(Out* o, int tc_th, const uint8_t* bits, const uint8_t* vals, int nvals) {
+    o->byte(0xFF);
+    o->byte(0xC4);
+    o->u16(19 + nvals);
+    o->byte((uint8_t)tc_th);
+    o->bytes(bits, 16);
+    o->bytes(vals, nvals);
+}
+
+// coef: int16 [total_blocks][64] as entropy_decode writes it; qt: uint16 [2][64] natural order, entries 1..255.  *n = bytes written.
+static inline bool entropy_encode(const int16_t* coef, int32_t H, int32_t W, int32_t sampling, const uint16_t* qt, uint8_t* out, int64_t cap,
+                                  int64_t* n, const char** why) {
+    if (!coef || !qt || !out || !n || cap < 0) return err(why, "jpeg: null argument");
+    *n = 0;
+    dgp_jpeg_info g;
+    if (sampling == DGP_JPEG_GRAY) return err(why, "jpeg: the encoder writes 3-component streams only (sampling DGP_JPEG_444, _422 or _420)");
+    if (!geometry(W, H, sampling, &g)) return err(why, "jpeg: H, W must be in 1..65535 and sampling one of DGP_JPEG_444, _422, _420");
+    for (int k = 0; k < 128; ++k)
+        if (qt[k] < 1 || qt[k] > 255) return err(why, "jpeg: a quantisation table entry outside 1..255 (baseline tables are 8-bit)");
+    Out o{out, 0, cap, 0, 0, false};
+    static const uint8_t kApp0[20] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    o.bytes(kApp0, 20);
+    for (int t = 0; t < 2; ++t) {
+        o.byte(0xFF);
+        o.byte(0xDB);
+        o.u16(67);
+        o.byte((uint8_t)t);
+        for (int k = 0; k < 64; ++k) o.byte((uint8_t)qt[t * 64 + kZigzag[k]]);
+    }
+    const int hs = g.blocks_x[0] / g.mcus_x, vs = g.blocks_y[0] / g.mcus_y;
+    o.byte(0xFF);
+    o.byte(0xC0);
+    o.u16(17);
+    o.byte(8);
+    o.u16(H);
+    o.u16(W);
+    o.byte(3);
+    for (int c = 0; c < 3; ++c) {
+        o.byte((uint8_t)(c + 1));
+        o.byte((uint8_t)(c == 0 ? (hs << 4) | vs : 0x11));
+        o.byte((uint8_t)(c ? 1 : 0));
+    }
+    put_dht(&o, 0x00, kStdDcLumBits, kStdDcVals, 12);
+    put_dht(&o, 0x10, kStdAcLumBits, kStdAcLumVals, 162);
+    put_dht(&o, 0x01, kStdDcChrBits, kStdDcVals, 12);
+    put_dht(&o, 0x11, kStdAcChrBits, kStdAcChrVals, 162);
+    static const uint8_t kSos[14] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+    o.bytes(kSos, 14);
+    if (o.full) return err(why, "jpeg: the output buffer is smaller than the stream (dgp_jpeg_encode_bound gives a size that always fits)");
+
+    EncHuff dc[2], ac[2];
+    build_enc_huff(&dc[0], kStdDcLumBits, kStdDcVals);
+    build_enc_huff(&dc[1], kStdDcChrBits, kStdDcVals);
+    build_enc_huff(&ac[0], kStdAcLumBits, kStdAcLumVals);
+    build_enc_huff(&ac[1], kStdAcChrBits, kStdAcChrVals);
+    const int64_t comp_off[3] = {0, g.blocks[0], (int64_t)g.blocks[0] + g.blocks[1]};
+    int32_t pred[3] = {0, 0, 0};
+    for (int my = 0; my < g.mcus_y; ++my)
+        for (int mx = 0; mx < g.mcus_x; ++mx) {
+            for (int c = 0; c < 3; ++c) {
+                const int ch = c == 0 ? hs : 1, cv = c == 0 ? vs : 1;
+                const EncHuff* const hdc = &dc[c ? 1 : 0];
+                const EncHuff* const hac = &ac[c ? 1 : 0];
+                for (int by = 0; by < cv; ++by)
+                    for (int bx = 0; bx < ch; ++bx) {
+                        const int16_t* const blk = coef + (comp_off[c] + (int64_t)(my * cv + by) * g.blocks_x[c] + (mx * ch + bx)) * 64;
+                        // F.1.2.1: the DC difference, category = bit length of its magnitude, then the low bits of v (v - 1 when negative)
+                        int32_t v = (int32_t)blk[0] - pred[c];
+                        pred[c] = blk[0];
+                        int s = bit_length((uint32_t)(v < 0 ? -v : v));
+                        if (s > 11) return err(why, "jpeg: a DC difference outside what category 11 can code (|d| > 2047)");
+                        o.put(hdc->code[s], hdc->len[s]);
+                        if (s) o.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u), s);
+                        // F.1.2.2: run lengths of zeros in zigzag order, ZRL for runs past 15, EOB when the block ends in zeros
+                        int run = 0;
+                        for (int k = 1; k < 64; ++k) {
+                            v = blk[kZigzag[k]];
+                            if (v == 0) {
+                                ++run;
+                                continue;
+                            }
+                            for (; run > 15; run -= 16) o.put(hac->code[0xF0], hac->len[0xF0]);
+                            s = bit_length((uint32_t)(v < 0 ? -v : v));
+                            if (s > 10) return err(why, "jpeg: an AC coefficient outside what category 10 can code (|c| > 1023)");
+                            const int sym = (run << 4) | s;
+                            o.put(((uint32_t)hac->code[sym] << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u)), hac->len[sym] + s);
+                            run = 0;
+                        }
+                        if (run) o.put(hac->code[0], hac->len[0]);
+                    }
+            }
+            if (o.full) return err(why, "jpeg: the output buffer is smaller than the stream (dgp_jpeg_encode_bound gives a size that always fits)");
+        }
+    if (o.nbits) o.put((1u << (8 - o.nbits)) - 1u, 8 - o.nbits);      // the last byte is padded with 1-bits
+    o.byte(0xFF);
+    o.byte(0xD9);
+    if (o.full) return err(why, "jpeg: the output buffer is smaller than the stream (dgp_jpeg_encode_bound gives a size that always fits)");
+    *n = o.pos;
     return true;
 }
 

@@ -1505,3 +1505,86 @@ def jpeg_decode(frames, out: Optional[torch.Tensor] = None, device=None) -> torc
         jpeg_entropy_decode(f, infos[i], coef[i], qt[i])
     dev = out.device if out is not None else torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     return jpeg_reconstruct(torch.from_numpy(coef).to(dev), torch.from_numpy(qt.view(np.int16)).to(dev), i0.height, i0.width, i0.sampling, out=out)
+
+
+# ---- the other way (dgp_jpeg_forward_u8 + dgp_jpeg_entropy_encode): frames, with markers drawn over them, to Pillow's JPEG bytes
+from .jpeg import (quality_tables as jpeg_quality_tables, encode_bound as jpeg_encode_bound, entropy_encode as jpeg_entropy_encode,  # noqa: E402
+                   sampling_id as jpeg_sampling_id)
+
+_JPEG_QT_CACHE: Dict[Tuple[str, int], torch.Tensor] = {}
+
+
+def _jpeg_device_tables(dev, quality: int) -> torch.Tensor:
+    """the table pair of `quality` on the device, int16 [2, 64] holding jpeg_quality_tables' uint16 bits (uploaded once per device)"""
+    key = (str(dev), int(quality))
+    t = _JPEG_QT_CACHE.get(key)
+    if t is None:
+        t = _JPEG_QT_CACHE[key] = torch.from_numpy(jpeg_quality_tables(quality).view(np.int16)).to(dev)
+    return t
+
+
+def jpeg_forward(frames: torch.Tensor, quality: int = 90, subsampling="4:2:0", markers=None, dotsize: int = 3,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dgp_jpeg_forward_u8: B RGB frames of one size -> the quantised DCT coefficients libjpeg's baseline encoder makes of them, device
+    int16 [B, total_blocks, 64] in the layout jpeg_entropy_decode writes (jpeg_entropy_encode makes Pillow's stream of a frame's).
+    frames: device uint8 [B, H, W, 3], each frame contiguous, frames any whole number of bytes >= H W 3 apart (a slice of a larger
+    buffer is read in place; it is never written).  quality 1..100 and subsampling "4:4:4" | "4:2:2" | "4:2:0" as Pillow's save takes
+    them.  markers: None, or int32 [B, n, 6] = row, col, r, g, b, on (a device tensor, or a numpy array that is uploaded): squares of
+    half-width dotsize drawn over the pixels as they are read, the highest index on top, clipped to the frame (models/render.py's
+    marker_table makes one, draw_markers_host is the numpy statement).  Two launches on the current stream."""
+    lib = _lib.load()
+    sampling = jpeg_sampling_id(subsampling)
+    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise _lib.DgpError("jpeg_forward: frames must be a device uint8 [B, H, W, 3] tensor, got %s %s" % (frames.dtype, tuple(frames.shape)))
+    B, H, W = (int(v) for v in frames.shape[:3])
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise _lib.DgpError("jpeg_forward: H, W must be in 1..65535, got %d, %d" % (H, W))
+    if B and (tuple(frames.stride()[1:]) != (W * 3, 3, 1) or (B > 1 and frames.stride(0) < H * W * 3)):
+        raise _lib.DgpError("jpeg_forward: every frame must be contiguous and the frames must not overlap (strides %s)" % (tuple(frames.stride()),))
+    dev = frames.device
+    qt = _jpeg_device_tables(dev, quality)
+    if isinstance(dotsize, bool) or not isinstance(dotsize, (int, np.integer)) or not 0 <= int(dotsize) <= 65535:
+        raise _lib.DgpError("jpeg_forward: dotsize must be an integer in 0..65535, got %r" % (dotsize,))
+    nblk, _ = jpeg_block_count(H, W, sampling)
+    n_markers = 0
+    if markers is not None:
+        if isinstance(markers, np.ndarray):
+            if markers.dtype != np.int32:
+                raise _lib.DgpError("jpeg_forward: markers must be int32, got %s" % markers.dtype)
+            markers = torch.from_numpy(np.ascontiguousarray(markers)).to(dev)
+        _need_cuda(markers, torch.int32, "markers")
+        if markers.dim() != 3 or markers.shape[0] != B or markers.shape[2] != 6 or markers.device != dev:
+            raise _lib.DgpError("jpeg_forward: markers must be int32 [%d, n, 6] on %s, got %s on %s" % (B, dev, tuple(markers.shape), markers.device))
+        n_markers = int(markers.shape[1])
+        if n_markers == 0:
+            markers = None
+    if out is None:
+        out = torch.empty((B, nblk, 64), dtype=torch.int16, device=dev)
+    else:
+        _need_cuda(out, torch.int16, "out")
+        if out.numel() != B * nblk * 64 or out.device != dev:
+            raise _lib.DgpError("jpeg_forward: out must be int16 [%d, %d, 64] on %s, got %s on %s" % (B, nblk, dev, tuple(out.shape), out.device))
+    if B == 0:
+        return out
+    need = int(lib.dgp_jpeg_forward_scratch_bytes(B, H, W, sampling))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    stride = int(frames.stride(0)) if B > 1 else H * W * 3
+    _lib.check(lib.dgp_jpeg_forward_u8(_ptr(frames), B, H, W, stride, sampling, _ptr(qt), _ptr(markers), n_markers, int(dotsize), _ptr(out),
+                                       _ptr(scratch), need, _stream(dev)), "dgp_jpeg_forward_u8")
+    return out
+
+
+def jpeg_encode(frames: torch.Tensor, quality: int = 90, subsampling="4:2:0", markers=None, dotsize: int = 3) -> list:
+    """jpeg_forward, one download, jpeg_entropy_encode per frame on this thread -> a list of byte strings: what Pillow's
+    save(quality=, subsampling=) writes for each frame with its markers drawn.  For tests and small jobs: models/render.py's
+    write_annotated_movie runs the same three steps as a pipeline."""
+    coef = jpeg_forward(frames, quality, subsampling, markers, dotsize).cpu().numpy()
+    B, H, W = (int(v) for v in frames.shape[:3])
+    sampling = jpeg_sampling_id(subsampling)
+    qt = jpeg_quality_tables(quality)
+    buf = np.empty(jpeg_encode_bound(H, W, sampling), np.uint8)
+    out = []
+    for i in range(B):
+        n = jpeg_entropy_encode(coef[i], H, W, sampling, qt, buf)
+        out.append(buf[:n].tobytes())
+    return out

@@ -270,101 +270,165 @@ class MjpegAviSource:
             pass
 
 
-def write_mjpeg_avi(path, frames, fps: float = 30.0, quality: int = 90, subsampling="4:2:0", index: bool = True,
-                    segment_bytes: int = 1 << 30) -> int:
-    """Write frames (an iterable of uint8 [H, W, 3] RGB or [H, W] grey arrays of one size) as a Motion-JPEG .avi: every frame encoded by
-    Pillow (quality, subsampling as Image.save takes them) into a '00dc' chunk of a minimal AVI -- 'hdrl' (main header, one 'vids' / MJPG
-    stream, an OpenDML 'dmlh' with the total), 'movi', 'idx1'.  A .npy stack becomes a file about a tenth its size that
-    MjpegAviSource (and any player) reads.  A frame given as None is written as a zero-length chunk: it repeats the previous frame.
-    No RIFF segment grows past segment_bytes (1 GiB: the OpenDML rule); further frames go to 'AVIX' segments.  index=False leaves
-    'idx1' out (readers of this package never need it).  -> the number of frames written."""
-    import io
-    import struct
-    from fractions import Fraction
-    from PIL import Image
-    fr = Fraction(float(fps)).limit_denominator(1000000)
-    n = 0
-    size = None
-    with open(path, "wb") as f:
-        def patch(pos, value):
-            here = f.tell()
-            f.seek(pos)
-            f.write(struct.pack("<I", value))
-            f.seek(here)
+def _jpeg_size(data: bytes):
+    """(width, height) from the frame header (SOFn) of a JPEG stream"""
+    p, n = 2, len(data)
+    while p + 4 <= n and data[p] == 0xFF:
+        m, L = data[p + 1], (data[p + 2] << 8) | data[p + 3]
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC) and p + 9 <= n:
+            return ((data[p + 7] << 8) | data[p + 8], (data[p + 5] << 8) | data[p + 6])
+        if m == 0xDA:
+            break
+        p += 2 + L
+    raise ValueError("MjpegAviWriter: no frame header in the first JPEG stream (pass size=(width, height))")
 
+
+class MjpegAviWriter:
+    """The container half of a Motion-JPEG .avi: add(data) appends one frame's JPEG stream as a '00dc' chunk (None or b"": a zero-length
+    chunk, which repeats the previous frame), close() patches the sizes and headers -- 'hdrl' (main header, one 'vids' / MJPG stream,
+    an OpenDML 'dmlh' with the total), 'movi', 'idx1'.  No RIFF segment grows past segment_bytes (1 GiB: the OpenDML rule); further
+    frames go to 'AVIX' segments.  index=False leaves 'idx1' out (readers of this package never need it).  size = (width, height); when
+    it is not given it is read from the first stream's frame header.  Who encodes the frames is the caller's business: write_mjpeg_avi
+    feeds it Pillow's streams, models/render.py's write_annotated_movie the HIP encoder's.  One thread at a time."""
+
+    def __init__(self, path, fps: float = 30.0, index: bool = True, segment_bytes: int = 1 << 30, size=None):
+        import struct
+        self._struct = struct
+        self.fps, self.index, self.segment_bytes, self.size = fps, index, segment_bytes, size
+        self.n = 0
+        self._f = f = open(path, "wb")
         f.write(b"RIFF\0\0\0\0AVI LIST\0\0\0\0hdrl")
         hdrl_size_at = 16
         f.write(b"avih" + struct.pack("<I", 56))
-        avih_at = f.tell()
+        self._avih_at = f.tell()
         f.write(b"\0" * 56)
         f.write(b"LIST" + struct.pack("<I", 4 + 8 + 56 + 8 + 40) + b"strl")
         f.write(b"strh" + struct.pack("<I", 56))
-        strh_at = f.tell()
+        self._strh_at = f.tell()
         f.write(b"\0" * 56)
         f.write(b"strf" + struct.pack("<I", 40))
-        strf_at = f.tell()
+        self._strf_at = f.tell()
         f.write(b"\0" * 40)
         f.write(b"LIST" + struct.pack("<I", 4 + 8 + 4) + b"odmldmlh" + struct.pack("<I", 4))
-        dmlh_at = f.tell()
+        self._dmlh_at = f.tell()
         f.write(b"\0" * 4)
-        patch(hdrl_size_at, f.tell() - hdrl_size_at - 4)
-        seg_start, first = 0, True
+        self._patch(hdrl_size_at, f.tell() - hdrl_size_at - 4)
+        self._seg_start, self._first = 0, True
         f.write(b"LIST\0\0\0\0movi")
-        movi_at = f.tell() - 4                      # (of the 'movi' tag: idx1 offsets count from here)
-        idx = []
-        n_first = 0
+        self._movi_at = f.tell() - 4                # (of the 'movi' tag: idx1 offsets count from here)
+        self._idx = []
+        self._n_first = 0
 
-        def close_segment():
-            patch(movi_at - 4, f.tell() - movi_at)
-            if first and index:
-                f.write(b"idx1" + struct.pack("<I", 16 * len(idx)))
-                for off, ln in idx:
-                    f.write(b"00dc" + struct.pack("<III", 0x10 if ln else 0, off, ln))
-            patch(seg_start + 4, f.tell() - seg_start - 8)
+    def _patch(self, pos, value):
+        f = self._f
+        here = f.tell()
+        f.seek(pos)
+        f.write(self._struct.pack("<I", value))
+        f.seek(here)
 
+    def _close_segment(self):
+        f, struct = self._f, self._struct
+        self._patch(self._movi_at - 4, f.tell() - self._movi_at)
+        if self._first and self.index:
+            f.write(b"idx1" + struct.pack("<I", 16 * len(self._idx)))
+            for off, ln in self._idx:
+                f.write(b"00dc" + struct.pack("<III", 0x10 if ln else 0, off, ln))
+        self._patch(self._seg_start + 4, f.tell() - self._seg_start - 8)
+
+    def add(self, data) -> None:
+        f, struct = self._f, self._struct
+        if f is None:
+            raise ValueError("MjpegAviWriter: add after close")
+        data = b"" if data is None else data
+        if self.size is None and len(data):
+            self.size = _jpeg_size(data)
+        tail = 16 * (len(self._idx) + 1) + 8 if self._first and self.index else 0
+        if f.tell() - self._seg_start + 8 + len(data) + 1 + tail > self.segment_bytes and f.tell() > self._movi_at + 4:
+            self._close_segment()
+            if self._first:
+                self._n_first = self.n
+            self._first = False
+            self._seg_start = f.tell()
+            f.write(b"RIFF\0\0\0\0AVIXLIST\0\0\0\0movi")
+            self._movi_at = f.tell() - 4
+        if self._first:
+            self._idx.append((f.tell() - self._movi_at, len(data)))
+        f.write(b"00dc" + struct.pack("<I", len(data)))
+        f.write(data)
+        if len(data) & 1:
+            f.write(b"\0")
+        self.n += 1
+
+    def abort(self) -> None:
+        """close the file as it is (after an error: the file is incomplete)"""
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def close(self) -> int:
+        """-> the number of frames written"""
+        from fractions import Fraction
+        f, struct = self._f, self._struct
+        if f is None:
+            return self.n
+        try:
+            if self.size is None:
+                raise ValueError("write_mjpeg_avi: no frames")
+            fr = Fraction(float(self.fps)).limit_denominator(1000000)
+            n = self.n
+            self._close_segment()
+            if self._first:
+                self._n_first = n
+            w, h = self.size
+            self._patch(self._avih_at, int(round(1e6 / float(self.fps))))
+            f.seek(self._avih_at + 12)
+            f.write(struct.pack("<IIIIIII", 0x10 if self.index else 0, self._n_first, 0, 1, 0, w, h))
+            f.seek(self._strh_at)
+            f.write(b"vidsMJPG" + struct.pack("<IHHIIIIIIII", 0, 0, 0, 0, fr.denominator, fr.numerator, 0, n, 0, 0xFFFFFFFF, 0) +
+                    struct.pack("<hhhh", 0, 0, w, h))
+            f.seek(self._strf_at)
+            f.write(struct.pack("<IiiHH4sIiiII", 40, w, h, 1, 24, b"MJPG", w * h * 3, 0, 0, 0, 0))
+            self._patch(self._dmlh_at, n)
+        finally:
+            self.abort()
+        return self.n
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+
+
+def write_mjpeg_avi(path, frames, fps: float = 30.0, quality: int = 90, subsampling="4:2:0", index: bool = True,
+                    segment_bytes: int = 1 << 30) -> int:
+    """Write frames (an iterable of uint8 [H, W, 3] RGB or [H, W] grey arrays of one size) as a Motion-JPEG .avi: every frame encoded by
+    Pillow (quality, subsampling as Image.save takes them) and handed to MjpegAviWriter, which describes the container.  A .npy stack
+    becomes a file about a tenth its size that MjpegAviSource (and any player) reads.  A frame given as None is written as a
+    zero-length chunk: it repeats the previous frame.  -> the number of frames written."""
+    import io
+    from PIL import Image
+    size = None
+    with MjpegAviWriter(path, fps=fps, index=index, segment_bytes=segment_bytes) as w:
         for frame in frames:
             if frame is None:
                 data = b""
             else:
                 a = np.asarray(frame)
                 if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
-                    raise ValueError("write_mjpeg_avi: frame %d is %s %s, not uint8 [H, W, 3] or [H, W]" % (n, a.dtype, a.shape))
+                    raise ValueError("write_mjpeg_avi: frame %d is %s %s, not uint8 [H, W, 3] or [H, W]" % (w.n, a.dtype, a.shape))
                 if size is None:
-                    size = (a.shape[1], a.shape[0])
+                    size = w.size = (a.shape[1], a.shape[0])
                 elif size != (a.shape[1], a.shape[0]):
-                    raise ValueError("write_mjpeg_avi: frame %d is %d x %d, the first one %d x %d" % (n, a.shape[1], a.shape[0], size[0], size[1]))
+                    raise ValueError("write_mjpeg_avi: frame %d is %d x %d, the first one %d x %d" % (w.n, a.shape[1], a.shape[0], size[0], size[1]))
                 buf = io.BytesIO()
                 Image.fromarray(a).save(buf, "JPEG", quality=quality, **({"subsampling": subsampling} if a.ndim == 3 else {}))
                 data = buf.getvalue()
-            tail = 16 * (len(idx) + 1) + 8 if first and index else 0
-            if f.tell() - seg_start + 8 + len(data) + 1 + tail > segment_bytes and f.tell() > movi_at + 4:
-                close_segment()
-                if first:
-                    n_first = n
-                first = False
-                seg_start = f.tell()
-                f.write(b"RIFF\0\0\0\0AVIXLIST\0\0\0\0movi")
-                movi_at = f.tell() - 4
-            if first:
-                idx.append((f.tell() - movi_at, len(data)))
-            f.write(b"00dc" + struct.pack("<I", len(data)) + data + (b"\0" if len(data) & 1 else b""))
-            n += 1
-        if size is None:
-            raise ValueError("write_mjpeg_avi: no frames")
-        close_segment()
-        if first:
-            n_first = n
-        w, h = size
-        patch(avih_at, int(round(1e6 / float(fps))))
-        f.seek(avih_at + 12)
-        f.write(struct.pack("<IIIIIII", 0x10 if index else 0, n_first, 0, 1, 0, w, h))
-        f.seek(strh_at)
-        f.write(b"vidsMJPG" + struct.pack("<IHHIIIIIIII", 0, 0, 0, 0, fr.denominator, fr.numerator, 0, n, 0, 0xFFFFFFFF, 0) +
-                struct.pack("<hhhh", 0, 0, w, h))
-        f.seek(strf_at)
-        f.write(struct.pack("<IiiHH4sIiiII", 40, w, h, 1, 24, b"MJPG", w * h * 3, 0, 0, 0, 0))
-        patch(dmlh_at, n)
-    return n
+            w.add(data)
+        return w.close()
 
 
 def open_frame_source(video_file):

@@ -1,5 +1,6 @@
 """The host half of the JPEG path (csrc/dgp_jpeg_host.h through the C-ABI): parse a baseline JPEG frame and Huffman-decode it into
-quantised coefficients.  No torch and no GPU in here -- models/staging.py calls it from its decode threads (ctypes releases the GIL for
+quantised coefficients, and the other way (quality_tables, encode_bound, entropy_encode: coefficients to the complete stream, for
+models/render.py's movie writer and its encode threads).  No torch and no GPU in here -- models/staging.py calls it from its decode threads (ctypes releases the GIL for
 the duration of a call, and the C functions keep no state), engine.py re-exports it beside the device half (engine.jpeg_reconstruct)."""
 from __future__ import annotations
 
@@ -41,6 +42,62 @@ def entropy_decode(data, info: _lib.DgpJpegInfo, coef_out: np.ndarray, qt_out: n
     p, n = _buffer(data)
     _lib.check(lib.dgp_jpeg_entropy_decode(p, n, C.byref(info), coef_out.ctypes.data_as(C.c_void_p), qt_out.ctypes.data_as(C.c_void_p)),
                "dgp_jpeg_entropy_decode")
+
+
+def sampling_id(subsampling) -> int:
+    """DGP_JPEG_444 / _422 / _420 from what Pillow's save(subsampling=) takes ("4:4:4" | "4:2:2" | "4:2:0", or 0 | 1 | 2) -- NOT from a
+    DGP_JPEG_* value; anything else (grey included) is a ValueError"""
+    if isinstance(subsampling, str) and subsampling in SAMPLING_NAMES[1:]:
+        return SAMPLING_NAMES.index(subsampling)
+    if isinstance(subsampling, (int, np.integer)) and not isinstance(subsampling, bool) and 0 <= int(subsampling) <= 2:
+        return int(subsampling) + 1
+    raise ValueError("subsampling must be '4:4:4', '4:2:2' or '4:2:0' (or Pillow's 0, 1, 2), got %r: grey and other samplings are not written"
+                     % (subsampling,))
+
+
+def quality_tables(quality: int) -> np.ndarray:
+    """dgp_jpeg_quality_tables: libjpeg's table pair for quality 1..100, uint16 [2, 64] (luminance, chrominance) in natural order"""
+    lib = _lib.load()
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)):
+        raise _lib.DgpError("jpeg quality must be an integer in 1..100, got %r" % (quality,))
+    qt = np.zeros((2, 64), np.uint16)
+    _lib.check(lib.dgp_jpeg_quality_tables(int(quality), qt.ctypes.data_as(C.c_void_p)), "dgp_jpeg_quality_tables")
+    return qt
+
+
+def encode_bound(H: int, W: int, sampling: int) -> int:
+    """dgp_jpeg_encode_bound: a buffer size that holds the stream of any H x W frame"""
+    n = int(_lib.load().dgp_jpeg_encode_bound(int(H), int(W), int(sampling)))
+    if n <= 0:
+        raise _lib.DgpError("jpeg_encode_bound: H, W must be in 1..65535 and sampling DGP_JPEG_444, _422 or _420, got %d, %d, %d" % (H, W, sampling))
+    return n
+
+
+def entropy_encode(coef: np.ndarray, H: int, W: int, sampling: int, qt: np.ndarray, out: np.ndarray, cap=None) -> int:
+    """dgp_jpeg_entropy_encode from caller memory into caller memory: coef C-contiguous int16 with the frame's total_blocks * 64
+    elements (a pinned view in the pipeline), qt contiguous uint16 [2, 64], out a writable contiguous uint8 array of which at most `cap`
+    (default: all) bytes are written -> the stream's length.  Thread-safe; the GIL is released meanwhile."""
+    lib = _lib.load()
+    if sampling not in (1, 2, 3):
+        raise _lib.DgpError("jpeg_entropy_encode: sampling must be DGP_JPEG_444, _422 or _420 (grey is not written), got %r" % (sampling,))
+    if not (0 < H <= 65535 and 0 < W <= 65535):
+        raise _lib.DgpError("jpeg_entropy_encode: H, W must be in 1..65535, got %d, %d" % (H, W))
+    hs, vs = (2 if sampling >= 2 else 1), (2 if sampling == 3 else 1)
+    mcus = -(-W // (8 * hs)) * -(-H // (8 * vs))
+    need = mcus * (hs * vs + 2) * 64
+    if coef.dtype != np.int16 or not coef.flags.c_contiguous or coef.size != need:
+        raise _lib.DgpError("jpeg_entropy_encode: coef must be contiguous int16 with %d elements, got %s %s" % (need, coef.dtype, coef.shape))
+    if qt.dtype != np.uint16 or not qt.flags.c_contiguous or qt.size != 128:
+        raise _lib.DgpError("jpeg_entropy_encode: qt must be contiguous uint16 [2, 64]")
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise _lib.DgpError("jpeg_entropy_encode: out must be a writable contiguous uint8 array")
+    cap = out.size if cap is None else int(cap)
+    if not 0 <= cap <= out.size:
+        raise _lib.DgpError("jpeg_entropy_encode: cap %d is outside the %d bytes of out" % (cap, out.size))
+    n = C.c_int64(0)
+    _lib.check(lib.dgp_jpeg_entropy_encode(coef.ctypes.data_as(C.c_void_p), int(H), int(W), int(sampling), qt.ctypes.data_as(C.c_void_p),
+                                           out.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "dgp_jpeg_entropy_encode")
+    return int(n.value)
 
 
 def same_geometry(a: _lib.DgpJpegInfo, b: _lib.DgpJpegInfo) -> bool:

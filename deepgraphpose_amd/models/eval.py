@@ -9,7 +9,8 @@ The TF session call `sess.run([mu_n, scmap], feed_dict={inputs: frame[None]})` (
 `EvalSession.run`, which batches frames through the fused HIP path (dgp_infer); the per-joint likelihood
 loop (:331-343) runs inside the soft-argmax kernel.  Video decode and movie rendering are untouched
 third-party territory (moviepy) and only used when installed -- except Motion-JPEG .avi files and .jpg frames, which are read
-(frames.MjpegAviSource) and decoded (decode_backend: Pillow on the host, or dgp_jpeg_entropy_decode + dgp_jpeg_reconstruct_u8) here.
+(frames.MjpegAviSource) and decoded (decode_backend: Pillow on the host, or dgp_jpeg_entropy_decode + dgp_jpeg_reconstruct_u8) here,
+and plot_dgp's annotated movie, which without moviepy is written as a Motion-JPEG .avi by render.write_annotated_movie (movie_backend).
 """
 from __future__ import annotations
 
@@ -194,7 +195,7 @@ def clear_session_cache():
 # counters of the last estimate_pose call (tests, soak runs): chunks processed and chunks re-run after a range overflow
 RUN_STATS = {"chunks": 0, "chunk_reruns": 0, "strict_passes": 0, "stage_s": 0.0, "wait_frames_s": 0.0, "wait_h2d_s": 0.0, "drain_s": 0.0,
              "setup_s": 0.0, "alloc_s": 0.0, "calibrate_s": 0.0, "finish_s": 0.0, "prep_backend": "none", "loc_ref": None,
-             "decode_backend": "host"}
+             "decode_backend": "host", "movie_backend": None}      # movie_backend: plot_dgp's ("moviepy" | "hip" | "host", None = skipped)
 
 # location refinement of estimate_pose / plot_dgp (engine.LOC_REF_MODES): None = the reference's video path (soft-argmax only), "dgp" =
 # soft-argmax + the softmax-weighted locref offset, "dlc" = DLC's hard arg-max + the offset at that cell
@@ -715,10 +716,20 @@ def load_pose_from_dlc_to_dict(filename):
 
 
 def plot_dgp(video_file, output_dir="", label_dir=None, proj_cfg_file=None, dgp_model_file=None, shuffle=1, dotsize=3,
-             colormap="jet", save_str="", mask_threshold=0.1, new_size=None, tier=None, loc_ref=None, decode_backend="auto"):
+             colormap="jet", save_str="", mask_threshold=0.1, new_size=None, tier=None, loc_ref=None, decode_backend="auto",
+             movie_backend="auto", movie_quality=90):
     """eval.py:816-874 (`tier`, `loc_ref` and `decode_backend` are new: estimate_pose's).  Exports the labels when missing, then hands (clip, x, y, mask) to the movie
-    renderer.  Drawing the annotated movie is moviepy / matplotlib work outside this package's scope: when
-    those are absent the labels are still produced and the csv path is returned."""
+    renderer.  movie_backend (new): "moviepy" = the reference's route (render.create_annotated_movie, an .mp4); "hip" and "host" = this
+    package's own writer (render.write_annotated_movie: a Motion-JPEG <name>_labeled<save_str>.avi at movie_quality, the markers drawn and
+    the frames encoded on the GPU, or by numpy and Pillow -- the same bytes); "auto" = moviepy when it is installed, else "hip" when a
+    GPU is visible, else the labels alone: the csv path is returned and a line says why.  "hip" without a GPU is a ValueError.
+    RUN_STATS["movie_backend"] names the writer that ran (None: skipped)."""
+    if movie_backend not in ("auto", "moviepy", "hip", "host"):
+        raise ValueError("movie_backend must be 'auto', 'moviepy', 'hip' or 'host', got %r" % (movie_backend,))
+    if movie_backend == "hip":
+        import torch
+        if not torch.cuda.is_available():
+            raise ValueError("movie_backend 'hip' needs a GPU, and none is visible: use 'host' (the same file, written by Pillow) or 'auto'")
     f = os.path.basename(str(video_file)).rsplit(".", 1)
     save_file = join(output_dir, f[0] + "_labeled%s.mp4" % save_str)
     if label_dir is None:
@@ -735,15 +746,28 @@ def plot_dgp(video_file, output_dir="", label_dir=None, proj_cfg_file=None, dgp_
     mask_array = labels["likelihoods"].T > mask_threshold
     if tdist.is_available() and tdist.is_initialized() and tdist.get_rank() != 0:
         return label_file                                  # sharded run: rank 0 alone renders the movie
-    try:
-        from moviepy.editor import VideoFileClip  # noqa: F401
-    except ImportError:
-        print("moviepy not installed: labels written to %s, annotated movie skipped (%d/%d markers above the "
-              "%.2f likelihood mask)" % (label_file, int(mask_array.sum()), mask_array.size, mask_threshold))
-        return label_file
-    from .render import create_annotated_movie           # thin moviepy wrapper, optional
-    create_annotated_movie(video_file, labels["x"].T, labels["y"].T, mask_array=mask_array, filename=save_file,
-                           dotsize=dotsize, colormap=colormap)
+    RUN_STATS["movie_backend"] = None
+    if movie_backend == "auto":
+        try:
+            from moviepy.editor import VideoFileClip  # noqa: F401
+            movie_backend = "moviepy"
+        except ImportError:
+            import torch
+            if not torch.cuda.is_available():
+                print("moviepy not installed: labels written to %s, annotated movie skipped (%d/%d markers above the "
+                      "%.2f likelihood mask)" % (label_file, int(mask_array.sum()), mask_array.size, mask_threshold))
+                return label_file
+            movie_backend = "hip"
+    if movie_backend == "moviepy":
+        from .render import create_annotated_movie           # thin moviepy wrapper, optional
+        create_annotated_movie(video_file, labels["x"].T, labels["y"].T, mask_array=mask_array, filename=save_file,
+                               dotsize=dotsize, colormap=colormap)
+    else:
+        from .render import write_annotated_movie
+        save_file = join(output_dir, f[0] + "_labeled%s.avi" % save_str)
+        write_annotated_movie(video_file, labels["x"].T, labels["y"].T, mask_array, save_file, dotsize=dotsize, quality=movie_quality,
+                              backend=movie_backend)
+    RUN_STATS["movie_backend"] = movie_backend
     return save_file
 
 

@@ -5,7 +5,7 @@ rewriting around the run):
   step 0  fit_dlc                    -> snapshot-step0-final--0   (DLC baseline; needs resnet_v1_<d>.ckpt, or pass --dlcsnapshot)
   step 1  fit_dgp_labeledonly        -> snapshot-step1-final--0
   step 2  fit_dgp (gm2=1, gm3=3)     -> snapshot-step2-final--0
-  step 3  plot_dgp / estimate_pose   -> <proj>/videos_pred/<video>_labeled.{csv,h5[,mp4]}
+  step 3  plot_dgp / estimate_pose   -> <proj>/videos_pred/<video>_labeled.{csv,h5,avi} (.mp4 with moviepy)
 
     python demo/run_dgp_demo.py --dlcpath data/Reaching-Mackenzie-2018-08-30 [--dlcsnapshot snapshot-step0-final--0] [--test] [--frame_store hip]
 

@@ -684,6 +684,46 @@ size_t dgp_jpeg_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t sampling)
 int    dgp_jpeg_reconstruct_u8(const int16_t* d_coef, const uint16_t* d_qt, int32_t B, int32_t H, int32_t W, int32_t sampling, uint8_t* dst,
                                int64_t dst_frame_stride, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Baseline JPEG frames, the other way: markers drawn and frames turned into quantised coefficients on the device, Huffman-coded on
+ * the host, Pillow's (libjpeg-turbo's) bytes for save(quality=q, subsampling=s) of the drawn frame (replaces the draw + encode half of
+ * the reference's annotated movie, DGP/models/eval.py:46-119).  Three components only: DGP_JPEG_444, _422 (h2v1) or _420; grey is
+ * DGP_ERR_INVALID.  The coefficient buffer is the one dgp_jpeg_entropy_decode writes: the two halves are inverses on one format.
+ * Arithmetic: Y = (FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16, Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B + (128 << 16)
+ * + 32767) >> 16, Cr alike, FIX(x) = (int)(x 65536 + 0.5); chroma downsampled without smoothing (h2v1: (a + b + bias) >> 1, bias 0, 1, 0,
+ * 1 ... along the row; h2v2: (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2 ...); edges replicated (pixel rows to a multiple of the vertical
+ * factor, pixel columns to the component's real blocks, then the component's rows to its real blocks: ceil(ceil(W h / hmax) / 8) x
+ * ceil(ceil(H v / vmax) / 8)); libjpeg's "islow" forward DCT on samples - 128 (CONST_BITS 13, PASS1_BITS 2: rows first, outputs 0 and 4
+ * << 2, the rest descaled by 11; then columns, descaled by 2 and 15); quantised as sign(c) ((|c| + (8 q >> 1)) / (8 q)) with an exact
+ * truncating divide.  Blocks of the MCU-padded grid beyond the real ones are dummy: AC 0, DC = the DC of the block before them in MCU
+ * order (row-major inside the MCU), chains followed. */
+/* Host only: libjpeg's tables for `quality` 1..100 (Annex K.1 / K.2 scaled by 5000 / q below 50, 200 - 2 q from there, (base scale + 50)
+ * / 100 clamped to 1..255): qt uint16 [2][64], luminance then chrominance, natural order. */
+int     dgp_jpeg_quality_tables(int32_t quality, uint16_t* qt);
+/* Host only: bytes that always hold the stream of one H x W frame (header + every block at its worst case, stuffed); 0 for a geometry
+ * the encoder refuses. */
+int64_t dgp_jpeg_encode_bound(int32_t H, int32_t W, int32_t sampling);
+/* Host only (no GPU), re-entrant, no globals, no allocation: any number of threads may encode at once.  coef: int16 [total_blocks][64]
+ * (natural order, planar by component, row-major over the MCU-padded grid), qt: uint16 [2][64], entries 1..255.  Writes into out[0 .. cap)
+ * the complete stream: SOI, JFIF APP0 (1.01, units 0, density 1 x 1), DQT 0, DQT 1, SOF0, DHT DC0 / AC0 / DC1 / AC1 (Annex K.3), SOS,
+ * the entropy-coded data with byte stuffing and the last byte padded with 1-bits, EOI; no restart markers.  *n = its length.
+ * DGP_ERR_INVALID with the reason in dgp_last_error for a stream that would pass cap (nothing is written at or past out + cap), a DC
+ * difference beyond category 11 or an AC coefficient beyond category 10, a table entry outside 1..255, a bad geometry. */
+int     dgp_jpeg_entropy_encode(const int16_t* coef, int32_t H, int32_t W, int32_t sampling, const uint16_t* qt, uint8_t* out, int64_t cap,
+                                int64_t* n);
+/* Host only: device scratch bytes dgp_jpeg_forward_u8 needs for B frames (the padded component planes); 0 for arguments it refuses. */
+size_t  dgp_jpeg_forward_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t sampling);
+/* src: device uint8 [B][H][W][3] RGB, frames src_frame_stride BYTES apart (at least H W 3): a slice of a larger buffer is read in place,
+ * and src is never written.  d_qt: device uint16 [2][64], one table pair per call.  d_markers: null, or device int32 [B][n_markers][6] =
+ * row, col, r, g, b, on: a pixel inside [row - dotsize, row + dotsize] x [col - dotsize, col + dotsize] of a marker with on != 0 takes
+ * that marker's colour before the conversion, the highest marker index that covers it wins, squares are clipped to the frame.  The
+ * overlay happens in registers while the pixels are read: no pass over the frames of its own.  d_coef: device int16
+ * [B][total_blocks][64], 16-byte aligned.  scratch: device, 8-byte aligned, dgp_jpeg_forward_scratch_bytes.  Two launches on `stream`
+ * (pixels -> padded component planes in scratch; planes -> blocks), integer arithmetic, no atomics: bit-identical from run to run.
+ * B == 0 launches nothing. */
+int     dgp_jpeg_forward_u8(const uint8_t* src, int32_t B, int32_t H, int32_t W, int64_t src_frame_stride, int32_t sampling,
+                            const uint16_t* d_qt, const int32_t* d_markers, int32_t n_markers, int32_t dotsize, int16_t* d_coef,
+                            void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
