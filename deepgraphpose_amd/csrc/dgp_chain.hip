@@ -785,28 +785,24 @@ hipError_t launch_chain_t(const ChainArgs& a0, hipStream_t s) {
     constexpr int NF = ((C + CIN2) / 32 * 2 + C1 / 16) * (H1 ? 1 : 2) + 1;
     constexpr int LDS = NS * NF * 1024;
     static_assert(LDS <= 160 * 1024, "ring does not fit the LDS");
-    auto kern = chain_kernel<C, C1, CIN2, RES, RB, NCW, NLW, NS, PD, WR, H1>;
-    static bool attr_done[16] = {};
-    static int wgs_per_cu[16] = {};
-    const int dev = dgp_device_slot();
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
+    constexpr auto kern = chain_kernel<C, C1, CIN2, RES, RB, NCW, NLW, NS, PD, WR, H1>;
+    hipError_t e = ensure_dynamic_lds<kern>(LDS);
+    if (e != hipSuccess) return e;
+    const DeviceFacts dev = device_facts();
+    static int wgs_per_cu[16] = {};      // resident workgroups per CU, per device slot
+    if (!wgs_per_cu[dev.slot]) {
         int occ = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * (NCW + NLW), LDS);
         if (e != hipSuccess) return e;
         static const int force = dgp_tune("DGP_CHAIN_WGS", 0);      // tuning: resident workgroups per CU
-        wgs_per_cu[dev] = force > 0 ? force : (occ < 1 ? 1 : occ);
-        attr_done[dev] = true;
+        wgs_per_cu[dev.slot] = force > 0 ? force : (occ < 1 ? 1 : occ);
     }
     ChainArgs a = a0;
     static const int nt_env = dgp_tune("DGP_CHAIN_NT", 0);      // bit 0: residual loads, bit 1: X' stores non-temporal
     a.nt = nt_env;
     constexpr int TILE = 16 * RB * NCW;
     a.ntiles = (a.M + TILE - 1) / TILE;
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    int grid = ncu * wgs_per_cu[dev];
+    int grid = dev.n_cu * wgs_per_cu[dev.slot];
     if (grid > a.ntiles) grid = a.ntiles;
     if (grid < 1) return hipSuccess;
 #ifdef DGP_DIAG
@@ -832,28 +828,24 @@ hipError_t launch_unit_t(const ChainArgs& a0, int N, hipStream_t s) {
     constexpr int NFJ = ((C + CIN2) / 32 * 2 + C1 / 16) * (H1 ? 1 : 2) + 1, NF2 = (C / 32) * (C / 16) * (H1 ? 1 : 2) + 1, NFMAX = NFJ > NF2 ? NFJ : NF2;
     constexpr int LDS = ((NCW + 2) * 18 * C * (H1 ? 2 : 4) + 1023) / 1024 * 1024 + 3 * NFMAX * 1024;
     static_assert(LDS <= 160 * 1024, "halo tile + ring do not fit the LDS");
-    auto kern = unit_kernel<C, C1, CIN2, RES, NCW, NLW, PD, WR, HWV, H1>;
-    static bool attr_done[16] = {};
-    static int wgs_per_cu[16] = {};
-    const int dev = dgp_device_slot();
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
+    constexpr auto kern = unit_kernel<C, C1, CIN2, RES, NCW, NLW, PD, WR, HWV, H1>;
+    hipError_t e = ensure_dynamic_lds<kern>(LDS);
+    if (e != hipSuccess) return e;
+    const DeviceFacts dev = device_facts();
+    static int wgs_per_cu[16] = {};      // resident workgroups per CU, per device slot
+    if (!wgs_per_cu[dev.slot]) {
         int occ = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * (NCW + NLW + HWV), LDS);
         if (e != hipSuccess) return e;
         static const int force = dgp_tune("DGP_CHAIN_WGS", 0);
-        wgs_per_cu[dev] = force > 0 ? force : (occ < 1 ? 1 : occ);
-        attr_done[dev] = true;
+        wgs_per_cu[dev.slot] = force > 0 ? force : (occ < 1 ? 1 : occ);
     }
     ChainArgs a = a0;
     static const int nt_env = dgp_tune("DGP_CHAIN_NT", 0);
     a.nt = nt_env;
     a.TY = (a.H + NCW - 1) / NCW; a.TX = (a.W + 15) / 16;
     a.ntiles = N * a.TY * a.TX;
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    int grid = ncu * wgs_per_cu[dev];
+    int grid = dev.n_cu * wgs_per_cu[dev.slot];
     if (grid > a.ntiles) grid = a.ntiles;
     if (grid < 1) return hipSuccess;
 #ifdef DGP_DIAG

@@ -244,8 +244,33 @@ inline ConvMode conv_mode() {
     return m;
 }
 
-// hipFuncSetAttribute applies to the CURRENT device: the "done once" flags of the launchers are kept per device
-inline int dgp_device_slot() { int d = 0; (void)hipGetDevice(&d); return d & 15; }
+// Facts about the CURRENT device, cached per device slot: the slot (what per-device state of a launcher is indexed by) and the
+// number of CUs (256 when the query fails)
+struct DeviceFacts { int slot, n_cu; };
+inline DeviceFacts device_facts() {
+    static int n_cu[16] = {};
+    int d = 0;
+    (void)hipGetDevice(&d);
+    const int slot = d & 15;
+    if (!n_cu[slot]) {
+        (void)hipDeviceGetAttribute(&n_cu[slot], hipDeviceAttributeMultiprocessorCount, d);
+        if (n_cu[slot] <= 0) n_cu[slot] = 256;
+    }
+    return {slot, n_cu[slot]};
+}
+// Kernel may use `bytes` of dynamic LDS on the current device.  hipFuncSetAttribute applies to one kernel on one device, so what
+// has been granted is kept per instantiation (the static below) and per device slot; it only grows
+template <auto Kernel>
+inline hipError_t ensure_dynamic_lds(size_t bytes) {
+    static size_t granted[16] = {};
+    size_t& g = granted[device_facts().slot];
+    if (bytes > g) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+        g = bytes;
+    }
+    return hipSuccess;
+}
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 

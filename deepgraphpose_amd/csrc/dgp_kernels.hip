@@ -6,7 +6,8 @@
 //   conv_igemm_f32_ls    the same with loader / compute wave specialisation
 //   conv_igemm_split_ls  the dominant kernel: fp32-class products as 3 fp16 (or 6 bf16) MFMAs on the 16-bit matrix pipe; MODE 1 / 2 / 3 =
 //                        per-tap loaders, pointwise loaders, halo walk; H2 activations in and out (ls_epilogue_h2)
-//   tail_fixup*, launch_conv, pick_tile, conv_kernel_name
+//   tail_fixup*          second half of the tail K-split
+//   the launch layer     (end of the file) the launchers, the TILES table, pick_tile, conv_kernel_name, launch_conv
 //
 // Wavefront = 64 lanes everywhere.  No CUDA-compat shims; this file only targets gfx950.
 #include "dgp_internal.h"
@@ -17,6 +18,7 @@
 #include <vector>
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 namespace dgp {
 
@@ -777,43 +779,6 @@ __global__ __launch_bounds__(512, 4) void conv_igemm_f32_ls(const ConvArgs p) {
 #endif
 
     ls_epilogue<TM, TN, WN>(p, acc, smem, wave, lane, m0, n0, wave_m0, wave_n0);
-}
-
-template <int BM, int BN>
-static hipError_t launch_conv_ls(ConvArgs a, hipStream_t s) {
-    const size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
-    a.mtiles = (a.M + BM - 1) / BM;
-    a.ntiles = (a.CoutP + BN - 1) / BN;
-    if (a.CoutP % BN != 0 || a.Cin < 32 || a.out_mode != 0) return hipErrorInvalidValue;
-    auto kern = conv_igemm_f32_ls<BM, BN>;
-    static bool attr_done_dev[16] = {};
-    bool& attr_done = attr_done_dev[dgp_device_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    const long long nwg = (long long)a.mtiles * a.ntiles;
-#ifdef DGP_DIAG
-    static unsigned long long* dbg_buf = nullptr;
-    if (!dbg_buf) (void)hipMalloc(&dbg_buf, 10 * 8 * 65536);
-    a.dbg = nwg <= 65536 ? dbg_buf : nullptr;
-#endif
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), smem, s, a);
-#ifdef DGP_DIAG
-    if (a.dbg) {
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> h(10 * nwg);
-        (void)hipMemcpy(h.data(), a.dbg, 80 * nwg, hipMemcpyDeviceToHost);
-        double v[8] = {0};
-        for (long long b = 0; b < nwg; ++b) for (int k = 0; k < 8; ++k) v[k] += (double)h[10 * b + k];
-        for (int k = 0; k < 8; ++k) v[k] /= (double)nwg;
-        printf("[diag LS %dx%d] tiles %lld nk %d | compute wave 0: first barrier %.0f cyc | per K-step: mfma+ldsread %.0f barrier-wait %.0f\n",
-               BM, BN, nwg, a.nk, v[0], v[4] / a.nk, v[7] / a.nk);
-    }
-#endif
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------
@@ -2195,21 +2160,134 @@ __global__ __launch_bounds__(256) void tail_fixup_h2_kernel(const ConvArgs p) {
     if (p.out_absmax) track_absmax(p.out_absmax, amax, lane, (int)((blockIdx.y * gridDim.x + blockIdx.x) * 4u + (threadIdx.x >> 6)));
 }
 
-template <int BM, int BN, int NT, int BK, int CW = 4>
-static hipError_t launch_conv_split(ConvArgs a, hipStream_t s) {
-    constexpr int NP = NT == 6 ? 3 : 2;
-    constexpr int KG = BK / 8;
-    if (NT == 2 && ((!a.in_absmax && !a.in_fmt) || !a.w_absmax)) return hipErrorInvalidValue;      // fp16 split needs both ranges (H2 input carries its scale)
-    if ((a.in_fmt || a.out_fmt) && !(NT == 2 && BK == 32 && CW == 4 && a.wh3 && (a.Cout % 8) == 0 && (a.Cin % 8) == 0 && !a.up && !a.stem &&
-                                     (!a.mask || (a.in_fmt == 2 && a.out_fmt == 2 && a.mask_fmt == 2))))
-        return hipErrorInvalidValue;                                                 // H2 tensors: fp16-split cell kernels only (an H1 gate: H1 -> H1 launches)
-    // 16-bit tier (in_fmt 2: H1 cells, already in 4-byte units here -- launch_conv): H1 or fp32 output, H1 residual, no predicted scales
-    const bool h1 = a.in_fmt == 2;
-    if (h1 != (a.out_fmt == 2) && a.out_fmt != 0) return hipErrorInvalidValue;
-    if (a.out_fmt == 2 && !h1) return hipErrorInvalidValue;
-    if (a.res && (a.res_fmt == 2) != (a.out_fmt == 2)) return hipErrorInvalidValue;
-    if (h1 && a.shadow) return hipErrorInvalidValue;
-    if (a.res && a.res_s == -2 && !(h1 && a.out_fmt == 2)) { if (a.in_fmt) return hipErrorInvalidValue; }
+// ------------------------------------------------------------------------------------
+// Launch layer.  launch_conv looks the tile id up in TILES and calls its family's launcher.  A split-kernel launch goes through stages:
+// split_fill_args / split_decide (which path, how much LDS) -> split_kernel (the one instantiation of that path) -> plan_tail_ksplit /
+// plan_supertile (the grid) -> launch (+ the fix-up launch of a split tail).
+// ------------------------------------------------------------------------------------
+using ConvKernel = void (*)(const ConvArgs);
+
+#ifdef DGP_DIAG
+// Diagnostic build: the stamp buffer the kernels write through ConvArgs::dbg (10 counters per workgroup; behind 65536 of those, 3 timeline
+// words per workgroup of the split kernels), and the reports printed after a launch (parsed by scripts/diag_net.py, launch_causes.py, cu_phase.py)
+static unsigned long long* diag_buffer(long long nwg) {
+    static unsigned long long* buf = nullptr;
+    if (!buf) (void)hipMalloc(&buf, 13 * 8 * 65536);
+    return nwg <= 65536 ? buf : nullptr;
+}
+// waits for the launch; h: the 10 counters of every workgroup, v: the mean of the first 8
+static std::vector<unsigned long long> diag_fetch(const ConvArgs& a, long long nwg, hipStream_t s, double (&v)[8]) {
+    (void)hipStreamSynchronize(s);
+    std::vector<unsigned long long> h(10 * nwg);
+    (void)hipMemcpy(h.data(), a.dbg, 80 * nwg, hipMemcpyDeviceToHost);
+    for (int k = 0; k < 8; ++k) v[k] = 0;
+    for (long long b = 0; b < nwg; ++b) for (int k = 0; k < 8; ++k) v[k] += (double)h[10 * b + k];
+    for (int k = 0; k < 8; ++k) v[k] /= (double)nwg;
+    return h;
+}
+// the fp32 kernels (ls: the loader-specialised one)
+static void diag_report_f32(const ConvArgs& a, int BM, int BN, bool ls, long long nwg, hipStream_t s) {
+    if (!a.dbg) return;
+    double v[8];
+    diag_fetch(a, nwg, s, v);
+    if (ls)
+        printf("[diag LS %dx%d] tiles %lld nk %d | compute wave 0: first barrier %.0f cyc | per K-step: mfma+ldsread %.0f barrier-wait %.0f\n",
+               BM, BN, nwg, a.nk, v[0], v[4] / a.nk, v[7] / a.nk);
+    else
+        printf("[diag %dx%d] tiles %lld nk %d | cycles/tile: prologue %.0f loop %.0f epilogue %.0f | per K-step (wave 0): "
+               "gload-issue %.0f mfma+ldsread %.0f vmcnt-wait %.0f lds-store %.0f barrier %.0f\n", BM, BN, nwg, a.nk,
+               v[0], v[1], v[2], v[3] / a.nk, v[4] / a.nk, v[5] / a.nk, v[6] / a.nk, v[7] / a.nk);
+}
+// the split kernels: occupancy, stamp shares, per-CU timeline (and its raw dump), epilogue shares
+static void diag_report_split(const ConvArgs& a, int BM, int BN, int NT, int BK, int CW, ConvKernel kern, size_t smem, long long nwg, hipStream_t s) {
+    if (!a.dbg) return;
+    double v[8];
+    const std::vector<unsigned long long> h = diag_fetch(a, nwg, s, v);
+    const int nks = a.nk * (32 / BK);
+    int occ = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * (CW + 4), smem);
+    hipFuncAttributes fa{};
+    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
+    printf("[diag occupancy] blocks/CU %d (smem %zu B, regs %d, static smem %zu, local %zu)\n", occ, smem, fa.numRegs,
+           fa.sharedSizeBytes, fa.localSizeBytes);
+    printf("[diag split %dx%d NT%d BK%d CW%d] tiles %lld K-steps %d | compute wave 0: first barrier %.0f cyc, epilogue %.0f | per K-step: "
+           "ldsread+mfma %.0f barrier-wait %.0f || loader wave: wait+split+ds_write %.0f load-issue %.0f barrier-wait %.0f\n",
+           BM, BN, NT, BK, CW, nwg, nks, v[0], v[2], v[4] / nks, v[7] / nks, v[3] / nks, v[5] / nks, v[6] / nks);
+    double v8 = 0; for (long long b = 0; b < nwg; ++b) v8 += (double)h[10 * b + 8];
+    double v9 = 0; for (long long b = 0; b < nwg; ++b) v9 += (double)h[10 * b + 9];
+    {   // per-CU timeline of the launch: how many workgroups a CU holds over the launch's span, and how long a freed slot stays empty
+        std::vector<unsigned long long> tl(3 * nwg);
+        (void)hipMemcpy(tl.data(), a.dbg + 10ull * 65536, 24 * nwg, hipMemcpyDeviceToHost);
+        if (const char* dump = getenv("DGP_DIAG_DUMP")) {      // raw (start, end, CU) of every workgroup of every launch, for scripts/cu_phase.py
+            if (FILE* f = fopen(dump, "a")) {
+                fprintf(f, "# launch %dx%d tiles %lld K-steps %d\n", BM, BN, nwg, nks);
+                for (long long b = 0; b < nwg; ++b) fprintf(f, "%llu %llu %llu\n", tl[3 * b], tl[3 * b + 1], tl[3 * b + 2]);
+                fclose(f);
+            }
+        }
+        unsigned long long t_lo = ~0ull, t_hi = 0;
+        std::vector<std::pair<unsigned long long, std::pair<unsigned long long, int>>> ev;      // (cu key, (time, +1 / -1))
+        double dur = 0; long long nz = 0;
+        for (long long b = 0; b < nwg; ++b) {
+            const unsigned long long s0 = tl[3 * b], s1 = tl[3 * b + 1], k = tl[3 * b + 2];
+            if (!s1 || s1 < s0) continue;
+            ++nz; dur += (double)(s1 - s0);
+            if (s0 < t_lo) t_lo = s0;
+            if (s1 > t_hi) t_hi = s1;
+            ev.push_back({k, {s0, +1}}); ev.push_back({k, {s1, -1}});
+        }
+        std::sort(ev.begin(), ev.end(), [](const auto& x, const auto& y) {
+            return x.first != y.first ? x.first < y.first : x.second.first != y.second.first ? x.second.first < y.second.first : x.second.second < y.second.second; });
+        double res_t[4] = {0, 0, 0, 0}, gap_sum = 0; long long gaps = 0; int ncu = 0;
+        for (size_t i = 0; i < ev.size();) {
+            size_t j = i; while (j < ev.size() && ev[j].first == ev[i].first) ++j;
+            ++ncu;
+            int cnt = 0; unsigned long long tprev = t_lo, last_end = 0; bool pending = false;
+            for (size_t e = i; e < j; ++e) {
+                const unsigned long long tt = ev[e].second.first;
+                res_t[cnt > 3 ? 3 : cnt] += (double)(tt - tprev); tprev = tt;
+                if (ev[e].second.second > 0) { if (pending) { gap_sum += (double)(tt - last_end); ++gaps; pending = false; } ++cnt; }
+                else { --cnt; last_end = tt; pending = true; }
+            }
+            res_t[0] += (double)(t_hi - tprev);
+            i = j;
+        }
+        const double span = (double)(t_hi - t_lo), tot = span * ncu;
+        if (nz && span > 0)
+            printf("[diag timeline] span %.2f us on %d CUs | workgroup life %.2f us (%.0f shader cycles -> %.2f GHz) | CU time holding 0 / 1 / 2 / 3+ workgroups: %.3f %.3f %.3f %.3f | "
+                   "a freed slot waits %.2f us for its next workgroup (%lld hand-overs)\n",
+                   span / 100.0, ncu, dur / nz / 100.0, v[0] + v[1] + v[2] + v9 / nwg, (v[0] + v[1] + v[2] + v9 / nwg) / (dur / nz * 10.0),
+                   res_t[0] / tot, res_t[1] / tot, res_t[2] / tot, res_t[3] / tot, gaps ? gap_sum / gaps / 100.0 : 0.0, gaps);
+    }
+    printf("[diag epilogue, DMA kernels] last MFMAs + staging %.0f | set-up (scale / bias, residual requests) %.0f | chunk 0 %.0f | chunks 1.. %.0f | absmax %.0f (res %d)\n",
+           v9 / nwg, v[3], v[5], v[6], v8 / nwg, a.res ? 1 : 0);
+}
+#endif
+
+// The template parameters of a split-kernel tile and the limits that keep impossible combinations of conv_igemm_split_ls from compiling
+template <int BM_, int BN_, int NT_, int BK_, int CW_>
+struct SplitTile {
+    static constexpr int BM = BM_, BN = BN_, NT = NT_, BK = BK_, CW = CW_;
+    static constexpr int NP = NT == 6 ? 3 : 2;                         // operand planes
+    static constexpr int KG = BK / 8;                                  // k-groups per step
+    static constexpr bool CAN_PB = NT == 2 && CW == 4;                 // can read pre-split weight cells (ConvArgs::wh3)
+    static constexpr bool CAN_CS = CAN_PB && BK == 32;                 // compute-side split
+    static constexpr bool CAN_DMA = CAN_CS && BM == 128 && (BN == 128 || BN == 64);      // LDS-DMA loaders
+    static constexpr bool CAN_DEEP = CAN_DMA && BN == 128;             // deep DMA ring, halo walk
+};
+
+// The path of one split-kernel launch: the template flags of conv_igemm_split_ls and the dynamic LDS that goes with them
+struct SplitPath {
+    int mode;              // loader walk: 0 everything at run time, 1 per-tap, 2 pointwise, 3 halo ring
+    bool pb;               // weights come as pre-split cells
+    bool cs, dma, deep;    // compute-side split, LDS-DMA loaders, deep DMA ring
+    bool ah2, oh2, h1;     // input in cells, output in cells, the cells are H1 (16-bit tier)
+    size_t lds;
+};
+
+// Stage 1a: the ConvArgs fields every split kernel reads, whatever its path
+template <class T>
+static void split_fill_args(ConvArgs& a) {
     // non-temporal residual loads / output stores in the H2 epilogue (A/B switch DGP_EPI_NT; 0: off, 1: every layer, 2 (default): only
     // layers with >= 8 column tiles (N >= 1024: conv3 of block3 / block4), 3 / 4: their loads / stores only).  There the 128 KB a tile
     // streams through the epilogue evict the A rows the other column tiles of the row block still read: PMC FETCH_SIZE 1061 MB per
@@ -2217,27 +2295,53 @@ static hipError_t launch_conv_split(ConvArgs a, hipStream_t s) {
     // the conv1 that re-reads the tensor 0.070 -> 0.076, block4 conv3 0.268 -> 0.253; everywhere (1) loses: a small output written nt
     // (R2: 39 MB) is no longer cache-resident for its consumer
     static const int epi_nt_env = dgp_tune("DGP_EPI_NT", 2);
-    a.epi_nt = epi_nt_env == 1 ? 3 : (a.CoutP / BN >= 8 ? (epi_nt_env == 2 ? 3 : epi_nt_env == 3 ? 1 : epi_nt_env == 4 ? 2 : 0) : 0);   // bit 0: loads, bit 1: stores
+    a.epi_nt = epi_nt_env == 1 ? 3 : (a.CoutP / T::BN >= 8 ? (epi_nt_env == 2 ? 3 : epi_nt_env == 3 ? 1 : epi_nt_env == 4 ? 2 : 0) : 0);   // bit 0: loads, bit 1: stores
     static const int tap_minor = dgp_tune("DGP_TAP_MINOR", 1);
     a.tap_minor = (tap_minor && !a.stem && a.ntaps > 1 && a.nk * 32 == a.ntaps * a.Cin) ? 1 : 0;
-    const size_t smem_loop = (size_t)2 * (NP * KG * (BM + (BK == 32 ? 4 : 8)) + NP * KG * (BN + 4)) * 16;
-    const size_t smem_epi = (size_t)CW * 32 * (BN + 4) * 4;        // (upper bound: 4 x 1 compute-wave layout of the CS kernels)
-    size_t smem = smem_loop > smem_epi ? smem_loop : smem_epi;
-    a.mtiles = (a.M + BM - 1) / BM;
-    a.ntiles = (a.CoutP + BN - 1) / BN;
-    if (a.CoutP % BN != 0 || (a.Cin < 32 && !a.stem) || a.out_mode != 0) return hipErrorInvalidValue;
+    a.mtiles = (a.M + T::BM - 1) / T::BM;
+    a.ntiles = (a.CoutP + T::BN - 1) / T::BN;
     if (a.tap_rows == 0) a.tap_rows = a.Cin >> 2;
+    if (!T::CAN_PB) a.wh3 = nullptr;
+}
+
+// Stage 1b: validate and decide.  hipErrorInvalidValue for what no split kernel of this tile runs.  No HIP calls: n_cu comes from device_facts()
+template <class T>
+static hipError_t split_decide(const ConvArgs& a, int n_cu, SplitPath& p) {
+    constexpr hipError_t REFUSED = hipErrorInvalidValue;
+    const bool ah2 = a.in_fmt != 0, oh2 = a.out_fmt != 0;
+    const bool h1 = a.in_fmt == 2;      // 16-bit tier (H1 cells, already in 4-byte units here -- launch_conv): H1 or fp32 output, H1 residual, no predicted scales
+    // -- refused whatever the path
+    if (T::NT == 2 && ((!a.in_absmax && !ah2) || !a.w_absmax)) return REFUSED;      // fp16 split needs both ranges (H2 input carries its scale)
+    if ((ah2 || oh2) && !(T::CAN_CS && a.wh3 && (a.Cout % 8) == 0 && (a.Cin % 8) == 0 && !a.up && !a.stem &&
+                          (!a.mask || (a.in_fmt == 2 && a.out_fmt == 2 && a.mask_fmt == 2))))
+        return REFUSED;                                                  // H2 tensors: fp16-split cell kernels only (an H1 gate: H1 -> H1 launches)
+    if (oh2 && !ah2) return REFUSED;
+    if (h1 != (a.out_fmt == 2) && oh2) return REFUSED;
+    if (a.res && (a.res_fmt == 2) != (a.out_fmt == 2)) return REFUSED;
+    if (h1 && a.shadow) return REFUSED;
+    if (a.res && a.res_s == -2 && ah2 && !(h1 && a.out_fmt == 2)) return REFUSED;
+    if (a.CoutP % T::BN != 0 || (a.Cin < 32 && !a.stem) || a.out_mode != 0) return REFUSED;
     if (a.in2 && (a.ntaps != 1 || a.stride != 1 || a.up || a.cin_split % 32 || (a.Cin - a.cin_split) % 32 || a.cin_split <= 0 ||
-                  a.cin_split >= a.Cin || a.H != a.Ho || a.W != a.Wo)) return hipErrorInvalidValue;
-    // loader specialisation (template MODE): pointwise / plain / everything-at-run-time
+                  a.cin_split >= a.Cin || a.H != a.Ho || a.W != a.Wo)) return REFUSED;
+    // -- loader walk (template MODE): pointwise / per-tap / everything-at-run-time
     const bool pointwise = a.ntaps == 1 && a.stride == 1 && a.pad_t == 0 && a.pad_l == 0 && !a.up && !a.stem && a.H == a.Ho && a.W == a.Wo;
     const int mode = (pointwise && (unsigned long long)a.M * (a.in2 ? a.cin_split : a.Cin) * 4ull == a.in_bytes &&
                       (!a.in2 || (unsigned long long)a.M * (a.Cin - a.cin_split) * 4ull == a.in2_bytes) && a.in_bytes < 4200000000u)
                          ? 2 : ((a.up || a.in2 || a.stem) ? 0 : 1);
-    // halo walk (MODE 3, see the kernel): 3x3 / stride 1 convs of the H2 engine on 128 x 128 tiles whose tap shifts fit the pixel ring.
+    // -- compute-side split.  2 (default): every fp16 kernel with pre-split weights; 1: 128 x 128 tiles only; 0: loaders split (A/B switch)
+    static const int cs_env = dgp_tune("DGP_COMPUTE_SPLIT", 2);
+    const bool cs = T::CAN_CS && a.wh3 && (cs_env >= 2 || (cs_env == 1 && T::BN == 128));
+    const bool pb = cs;      // weight cells without the compute-side split: the loaders split the fp32 panel (PB = false) and the cells stay unread
+    // -- LDS-DMA loaders (A/B switch DGP_DMA=0): CS kernels on 128-row tiles with the per-tap or the pointwise walk
+    static const int dma_env = dgp_tune("DGP_DMA", 1);
+    const bool dma = T::CAN_DMA && cs && mode != 0 && dma_env;
+    // -- deep DMA ring (see the kernel) for grids of at most one tile per CU; A/B switch DGP_DEEP_RING=0, =2: every DMA launch
+    static const int deep_env = dgp_tune("DGP_DEEP_RING", 1);
+    const bool deep = T::CAN_DEEP && dma && deep_env && (deep_env == 2 || (long long)a.mtiles * a.ntiles <= (long long)n_cu) && a.nk >= 6 && !h1;
+    // -- halo walk (MODE 3, see the kernel): 3x3 / stride 1 convs of the cells engine on 128 x 128 tiles whose tap shifts fit the pixel ring.
     // A/B switch DGP_HALO=0
     static const int halo_env = dgp_env("DGP_HALO", 1);
-    const bool halo = halo_env && BM == 128 && BN == 128 && CW == 4 && NT == 2 && BK == 32 && mode == 1 && a.in_fmt && a.out_fmt && a.wh3 &&
+    const bool halo = halo_env && T::CAN_DEEP && dma && !deep && mode == 1 && ah2 && oh2 && a.wh3 &&
                       a.KH == 3 && a.KW == 3 && a.ntaps == 9 && a.stride == 1 && a.dil >= 1 && a.pad_t == a.dil && a.pad_l == a.dil && a.H == a.Ho &&
                       a.W == a.Wo && a.W >= 2 && (a.Cin % 32) == 0 && a.nk * 32 == 9 * a.Cin && a.tap_rows == (a.Cin >> 2) && !a.in_scale_dev &&
                       (unsigned long long)a.M * a.Cin * 4ull == a.in_bytes && a.in_bytes < 4000000000u &&
@@ -2245,271 +2349,221 @@ static hipError_t launch_conv_split(ConvArgs a, hipStream_t s) {
                       // a strip longer than the ring still works (the ring slides), but the loaders can then never run a chunk ahead and
                       // the walk measured 0.4 % behind the per-tap loaders (ResNet-101 1280 x 720: W = 80 at dilation 2); DGP_HALO=2 forces it
                       (halo_env >= 2 || 128 + 2 * a.dil * (a.W + 1) <= HALO_C);
-    constexpr bool CAN_PB = NT == 2 && CW == 4;
-    if (!(CAN_PB && a.wh3)) a.wh3 = nullptr;
-    auto kern = conv_igemm_split_ls<BM, BN, NT, BK, CW, false, 0>;
-    if (a.wh3) kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_PB, 2>
-                    : mode == 1 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_PB, 1> : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_PB, 0>;
-    constexpr bool CAN_CS = CAN_PB && BK == 32;
-    // 2 (default): every fp16 kernel with pre-split weights; 1: 128 x 128 tiles only; 0: loaders split (A/B switch)
-    static const int cs_env = dgp_tune("DGP_COMPUTE_SPLIT", 2);
-    const bool cs = CAN_CS && a.wh3 && (cs_env >= 2 || (cs_env == 1 && BN == 128));
-    if (cs) kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_CS, 2, CAN_CS>
-                 : mode == 1 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_CS, 1, CAN_CS> : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_CS, 0, CAN_CS>;
-    else kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, false, 2>
-              : mode == 1 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, false, 1> : conv_igemm_split_ls<BM, BN, NT, BK, CW, false, 0>;
-    // LDS-DMA loaders (A/B switch DGP_DMA=0): 128 x 128 CS kernels with the plain or the pointwise walk
-    constexpr bool CAN_DMA = CAN_CS && BM == 128 && (BN == 128 || BN == 64);
-    static const int dma_env = dgp_tune("DGP_DMA", 1);
-    const bool dma = CAN_DMA && cs && mode != 0 && dma_env;
-    // deep DMA ring (see the kernel) for grids of at most one tile per CU; A/B switch DGP_DEEP_RING=0, =2: every DMA launch
-    constexpr bool CAN_DEEP = CAN_DMA && BN == 128;
-    static const int deep_env = dgp_tune("DGP_DEEP_RING", 1);
-    bool deep = false, use_halo = false;
-    if (dma) {
-        kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 2, CAN_DMA, CAN_DMA>
-                         : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 1, CAN_DMA, CAN_DMA>;
-        smem = (size_t)(3 * BM * 8 + 2 * NP * KG * BN) * 16;           // 3 A stages + 2 B stages = 80 KB
-        static int n_cu_d = 0;
-        if (!n_cu_d) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu_d, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu_d <= 0) n_cu_d = 256; }
-        const long long ntile = (long long)((a.M + BM - 1) / BM) * ((a.CoutP + BN - 1) / BN);
-        deep = CAN_DEEP && deep_env && (deep_env == 2 || ntile <= (long long)n_cu_d) && a.nk >= 6 && !h1;
-        if (deep) {
-            if constexpr (CAN_DEEP)
-                kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DEEP, 2, CAN_DEEP, CAN_DEEP, false, false, CAN_DEEP>
-                                 : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DEEP, 1, CAN_DEEP, CAN_DEEP, false, false, CAN_DEEP>;
-            smem = (size_t)(5 * BM * 8 + 4 * NP * KG * BN) * 16;       // 5 A stages + 4 B stages = 144 KB
+    // -- tensor formats.  Cells in (AH2): the CS kernels without the split; H1 cells: their LDS-DMA variants only.  Cells out (OH2): the
+    // cell epilogue; fp32 out of cells: pointwise GEMMs only (the heads, layer tests), whose epilogue adds an fp32 residual (H2 cells
+    // would be read as floats) and none at all from H1
+    if (ah2 && !cs) return REFUSED;
+    if (h1 && !dma) return REFUSED;
+    if (ah2 && !oh2 && (mode != 2 || (a.res && (h1 || a.res_fmt)))) return REFUSED;
+    p.mode = halo ? 3 : mode;
+    p.pb = pb; p.cs = cs; p.dma = dma; p.deep = deep;
+    p.ah2 = ah2; p.oh2 = oh2; p.h1 = h1;
+    // -- LDS: the K loop's stages or the epilogue's staging tile, whichever is larger
+    const size_t b_stage = (size_t)T::NP * T::KG * T::BN * 16;
+    const size_t lds_loop = halo ? (size_t)HALO_B0 + 2 * b_stage                      // pixel ring + tables, 2 B stages = 80 KB
+                          : deep ? (size_t)5 * T::BM * 8 * 16 + 4 * b_stage           // 5 A stages + 4 B stages = 144 KB
+                          : dma  ? (size_t)3 * T::BM * 8 * 16 + 2 * b_stage           // 3 A stages + 2 B stages = 80 KB
+                                 : (size_t)2 * (T::NP * T::KG * (T::BM + (T::BK == 32 ? 4 : 8)) + T::NP * T::KG * (T::BN + 4)) * 16;
+    const size_t lds_epi = (size_t)T::CW * 32 * (T::BN + 4) * 4;        // (upper bound: 4 x 1 compute-wave layout of the CS kernels)
+    p.lds = lds_loop > lds_epi ? lds_loop : lds_epi;
+    return hipSuccess;
+}
+
+// Stage 2: the instantiation of a path.  split_inst is the one spelling of the kernel (PB = CS, see split_decide); split_kernel names
+// every reachable combination of flags once, walk012 / walk12 the loader walks of one
+struct SplitKernel { ConvKernel fn; hipError_t (*ensure_lds)(size_t); };
+template <class T, int MODE, bool CS = false, bool DMA = false, bool AH2 = false, bool OH2 = false, bool DEEP = false, bool H1 = false>
+static SplitKernel split_inst() {
+    constexpr ConvKernel k = conv_igemm_split_ls<T::BM, T::BN, T::NT, T::BK, T::CW, CS, MODE, CS, DMA, AH2, OH2, DEEP, H1>;
+    return {k, &ensure_dynamic_lds<k>};
+}
+template <class T, bool... FLAGS>
+static SplitKernel walk012(int mode) { return mode == 2 ? split_inst<T, 2, FLAGS...>() : mode == 1 ? split_inst<T, 1, FLAGS...>() : split_inst<T, 0, FLAGS...>(); }
+template <class T, bool... FLAGS>
+static SplitKernel walk12(int mode) { return mode == 2 ? split_inst<T, 2, FLAGS...>() : split_inst<T, 1, FLAGS...>(); }
+
+template <class T>
+static SplitKernel split_kernel(const SplitPath& p) {
+    constexpr bool Y = true, N = false;                                       // flags: CS DMA AH2 OH2 DEEP H1
+    if (!p.cs) return walk012<T>(p.mode);                                     // loaders split fp32 operands
+    if constexpr (T::CAN_CS) {
+        if (!p.dma) {                                                         // compute waves split; global loads through registers
+            if (!p.ah2) return walk012<T, Y>(p.mode);
+            if (p.oh2)  return walk012<T, Y, N, Y, Y>(p.mode);
+            return split_inst<T, 2, Y, N, Y, N>();
         }
-        if (smem < smem_epi) smem = smem_epi;
-    }
-    if (h1) {              // H1 input (16-bit tier): LDS-DMA kernels only; H1 output (O1 epilogue) or fp32 output (the heads' pointwise GEMM)
-        if (!cs || !dma) return hipErrorInvalidValue;
-        if constexpr (CAN_DMA) {
-            if (a.out_fmt) {
-                kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 2, CAN_DMA, CAN_DMA, CAN_DMA, CAN_DMA, false, CAN_DMA>
-                                 : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 1, CAN_DMA, CAN_DMA, CAN_DMA, CAN_DMA, false, CAN_DMA>;
-                if constexpr (CAN_DEEP) {
-                    if (halo) {
-                        kern = conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DEEP, CAN_DEEP ? 3 : 1, CAN_DEEP, CAN_DEEP, CAN_DEEP, CAN_DEEP, false, CAN_DEEP>;
-                        smem = (size_t)HALO_B0 + 2 * (size_t)(NP * KG * BN) * 16;
-                        if (smem < smem_epi) smem = smem_epi;
-                        use_halo = true;
-                    }
-                }
-            } else {
-                if (mode != 2 || a.res) return hipErrorInvalidValue;
-                kern = conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 2, CAN_DMA, CAN_DMA, CAN_DMA, false, false, CAN_DMA>;
+        if constexpr (T::CAN_DMA) {
+            if (p.h1) {                                                       // 16-bit tier
+                if (!p.oh2) return split_inst<T, 2, Y, Y, Y, N, N, Y>();
+                if constexpr (T::CAN_DEEP) { if (p.mode == 3) return split_inst<T, 3, Y, Y, Y, Y, N, Y>(); }
+                return walk12<T, Y, Y, Y, Y, N, Y>(p.mode);
             }
-        }
-    } else if (a.in_fmt) {        // H2 input: the same kernels without the split (AH2); H2 output: epilogue variant (OH2)
-        if (!cs) return hipErrorInvalidValue;
-        if constexpr (CAN_CS) {
-            if (a.out_fmt) {
-                if (dma) {
-                    if constexpr (CAN_DMA)
-                        kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 2, CAN_DMA, CAN_DMA, CAN_DMA, CAN_DMA>
-                                         : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 1, CAN_DMA, CAN_DMA, CAN_DMA, CAN_DMA>;
-                    if constexpr (CAN_DEEP) {
-                        if (halo && !deep) {
-                            kern = conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DEEP, CAN_DEEP ? 3 : 1, CAN_DEEP, CAN_DEEP, CAN_DEEP, CAN_DEEP>;
-                            smem = (size_t)HALO_B0 + 2 * (size_t)(NP * KG * BN) * 16;
-                            if (smem < smem_epi) smem = smem_epi;
-                            use_halo = true;
-                        }
-                    }
-                    if constexpr (CAN_DEEP) {
-                        if (deep) kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DEEP, 2, CAN_DEEP, CAN_DEEP, CAN_DEEP, CAN_DEEP, CAN_DEEP>
-                                                   : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DEEP, 1, CAN_DEEP, CAN_DEEP, CAN_DEEP, CAN_DEEP, CAN_DEEP>;
-                    }
-                } else {
-                    kern = mode == 2 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_CS, 2, CAN_CS, false, CAN_CS, CAN_CS>
-                         : mode == 1 ? conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_CS, 1, CAN_CS, false, CAN_CS, CAN_CS>
-                                     : conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_CS, 0, CAN_CS, false, CAN_CS, CAN_CS>;
+            if constexpr (T::CAN_DEEP) {
+                if (p.deep) {
+                    if (!p.ah2) return walk12<T, Y, Y, N, N, Y>(p.mode);
+                    if (p.oh2)  return walk12<T, Y, Y, Y, Y, Y>(p.mode);
+                    return split_inst<T, 2, Y, Y, Y, N, Y>();
                 }
-            } else {           // fp32 output: pointwise GEMMs only (the heads, layer tests)
-                if (mode != 2) return hipErrorInvalidValue;
-                if (a.res && a.res_fmt) return hipErrorInvalidValue;      // (its epilogue adds an fp32 residual: H2 cells would be read as floats)
-                if (dma) {
-                    if constexpr (CAN_DMA) kern = conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DMA, 2, CAN_DMA, CAN_DMA, CAN_DMA, false>;
-                    if constexpr (CAN_DEEP) if (deep) kern = conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_DEEP, 2, CAN_DEEP, CAN_DEEP, CAN_DEEP, false, CAN_DEEP>;
-                } else kern = conv_igemm_split_ls<BM, BN, NT, BK, CW, CAN_CS, 2, CAN_CS, false, CAN_CS, false>;
+                if (p.mode == 3) return split_inst<T, 3, Y, Y, Y, Y>();
             }
+            if (!p.ah2) return walk12<T, Y, Y>(p.mode);
+            if (p.oh2)  return walk12<T, Y, Y, Y, Y>(p.mode);
+            return split_inst<T, 2, Y, Y, Y, N>();
         }
-    } else if (a.out_fmt) return hipErrorInvalidValue;
-    static bool attr_done_dev[16][5][5][4] = {};
-    auto& attr_done = attr_done_dev[dgp_device_slot()];
-    const int mode_slot = use_halo ? 3 : mode;
-    const int fmt_slot = h1 ? (a.out_fmt ? 4 : 3) : a.in_fmt ? (a.out_fmt ? 2 : 1) : 0, path_slot = deep ? 4 : dma ? 3 : cs ? 2 : (a.wh3 ? 1 : 0);
-    if (!attr_done[fmt_slot][path_slot][mode_slot]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done[fmt_slot][path_slot][mode_slot] = true;
     }
+    return {nullptr, nullptr};      // (split_decide sets cs / dma only where the tile can)
+}
+
+// Stage 3a, grid tail: with `slots` workgroups resident, the last tiles % slots tiles run on a mostly idle chip.  Split their K range
+// over up to 4 blocks each (raw slabs + a fixup pass that sums them in fixed order: deterministic) so the last round is full.
+// Sets tail_ksplit and n_main; returns the grid size
+template <class T>
+static long long plan_tail_ksplit(ConvArgs& a, const SplitPath& p, int n_cu) {
     long long nwg = (long long)a.mtiles * a.ntiles;
-    // Grid tail: with `slots` workgroups resident, the last tiles % slots tiles run on a mostly idle chip.  Split their K range
-    // over up to 4 blocks each (raw slabs + a fixup pass that sums them in fixed order: deterministic) so the last round is full.
     a.tail_ksplit = 0; a.n_main = (int)nwg;
     static const int tail_env = dgp_env("DGP_TAIL_SPLIT", 1);      // A/B switch
     // (H2 tensors: with the split gone from the K loop the K-split of the tail + its fix-up launch no longer pays -- same-box A/B,
     //  block3 conv1 -7..-24 %, block4 conv1 -12 %, block4 conv2 -5 % without it, +2.5 % end to end -- so tail_env == 2 is needed to force it)
-    if (tail_env && (!a.in_fmt || tail_env == 2) && !h1 && a.slab && CW == 4 && BN == 128 && !use_halo) {      // (128 x 64 tiles fit three per CU and gain nothing)
-        static int n_cu = 0;
-        if (!n_cu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu <= 0) n_cu = 256; }
-        const long long slots = 2LL * n_cu;            // two workgroups of these kernels fit a CU
-        const long long rem = nwg % slots;
-        const int nks = a.nk * (32 / BK);
-        // (a grid smaller than one round is left alone: at the trainer's 11-frame batches splitting it measured 1.5 % slower per step)
-        if (rem > 0 && nwg >= slots && rem * 4 <= slots * 3) {
-            int ks = (int)(slots / rem);
-            if (ks > 4) ks = 4;
-            while (ks > 1 && (nks % ks != 0 || nks / ks < 4)) --ks;
-            // the fixup pass costs ~10-15 us: with two or more full rounds in front of the tail it only pays for deep-K layers
-            // (measured per layer with DGP_TAIL_SPLIT=0/1: block3 -17 %, block4 N=512 -3..-9 %, block2 +-5 % -> left alone)
-            if (nwg / slots >= 2 && nks < 48) ks = 1;
-            if (ks > 1 && (unsigned long long)rem * ks * BM * BN * 4ull <= a.slab_bytes) {
-                a.tail_ksplit = ks; a.n_main = (int)(nwg - rem);
-                nwg = a.n_main + rem * ks;
-            }
-        }
-    }
-#ifdef DGP_DIAG
-    static unsigned long long* dbg_buf = nullptr;
-    if (!dbg_buf) (void)hipMalloc(&dbg_buf, 13 * 8 * 65536);
-    a.dbg = nwg <= 65536 ? dbg_buf : nullptr;
-#endif
-    // supertile order (see the kernel): H2 engine, 128-wide tiles, >= 8 column tiles and a weight panel that cannot stay in an XCD's L2
+    // (128 x 64 tiles fit three per CU and gain nothing)
+    if (!(tail_env && (!p.ah2 || tail_env == 2) && !p.h1 && a.slab && T::CW == 4 && T::BN == 128 && p.mode != 3)) return nwg;
+    const long long slots = 2LL * n_cu;            // two workgroups of these kernels fit a CU
+    const long long rem = nwg % slots;
+    const int nks = a.nk * (32 / T::BK);
+    // (a grid smaller than one round is left alone: at the trainer's 11-frame batches splitting it measured 1.5 % slower per step)
+    if (!(rem > 0 && nwg >= slots && rem * 4 <= slots * 3)) return nwg;
+    int ks = (int)(slots / rem);
+    if (ks > 4) ks = 4;
+    while (ks > 1 && (nks % ks != 0 || nks / ks < 4)) --ks;
+    // the fixup pass costs ~10-15 us: with two or more full rounds in front of the tail it only pays for deep-K layers
+    // (measured per layer with DGP_TAIL_SPLIT=0/1: block3 -17 %, block4 N=512 -3..-9 %, block2 +-5 % -> left alone)
+    if (nwg / slots >= 2 && nks < 48) ks = 1;
+    if (!(ks > 1 && (unsigned long long)rem * ks * T::BM * T::BN * 4ull <= a.slab_bytes)) return nwg;
+    a.tail_ksplit = ks; a.n_main = (int)(nwg - rem);
+    return a.n_main + rem * ks;
+}
+
+// Stage 3b, supertile order (see the kernel): H2 engine, 128-wide tiles, >= 8 column tiles and a weight panel that cannot stay in an
+// XCD's L2.  Sets st_gn, st_mc, st_mb; returns the grid size (nwg where the order stays plain)
+template <class T>
+static long long plan_supertile(ConvArgs& a, const SplitPath& p, long long nwg) {
     a.st_gn = 0;
-    {
-        static const int st_env = dgp_tune("DGP_SUPERTILE", 1);       // A/B switch; > 1: force the row-chunk size
-        const long long panel_bytes = (long long)a.nk * 32 * a.CoutP * 4;
-        if (st_env && a.in_fmt && a.out_fmt && a.tail_ksplit <= 1 && BN == 128 && a.ntiles >= 8 && panel_bytes > (3LL << 20) && a.mtiles >= 64) {
-            const long long per_ntile = (long long)a.nk * 32 * BN * 4;
-            int gn = 1;
-            static const long long st_cap = (long long)dgp_tune("DGP_ST_CAP_KB", 1536) << 10;
-            while (gn * 2 <= a.ntiles && (long long)(gn * 2) * per_ntile <= st_cap && a.ntiles % (gn * 2) == 0) gn *= 2;      // <= 1.5 MB of weight cells per group
-            a.st_gn = gn; a.st_mc = st_env > 1 ? st_env : 8; a.st_mb = (a.mtiles + 7) / 8;
-            nwg = 8LL * a.st_mb * a.ntiles;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * (CW + 4)), smem, s, a);
-    if (a.tail_ksplit > 1) {
+    static const int st_env = dgp_tune("DGP_SUPERTILE", 1);       // A/B switch; > 1: force the row-chunk size
+    const long long panel_bytes = (long long)a.nk * 32 * a.CoutP * 4;
+    if (!(st_env && p.ah2 && p.oh2 && a.tail_ksplit <= 1 && T::BN == 128 && a.ntiles >= 8 && panel_bytes > (3LL << 20) && a.mtiles >= 64)) return nwg;
+    const long long per_ntile = (long long)a.nk * 32 * T::BN * 4;
+    int gn = 1;
+    static const long long st_cap = (long long)dgp_tune("DGP_ST_CAP_KB", 1536) << 10;
+    while (gn * 2 <= a.ntiles && (long long)(gn * 2) * per_ntile <= st_cap && a.ntiles % (gn * 2) == 0) gn *= 2;      // <= 1.5 MB of weight cells per group
+    a.st_gn = gn; a.st_mc = st_env > 1 ? st_env : 8; a.st_mb = (a.mtiles + 7) / 8;
+    return 8LL * a.st_mb * a.ntiles;
+}
+
+template <int BM, int BN, int NT, int BK, int CW = 4>
+static hipError_t launch_conv_split(ConvArgs a, hipStream_t s) {
+    using T = SplitTile<BM, BN, NT, BK, CW>;
+    const int n_cu = device_facts().n_cu;
+    split_fill_args<T>(a);
+    SplitPath p;
+    hipError_t e = split_decide<T>(a, n_cu, p);
+    if (e != hipSuccess) return e;
+    const SplitKernel k = split_kernel<T>(p);
+    if (!k.fn) return hipErrorInvalidValue;
+    e = k.ensure_lds(160 * 1024);
+    if (e != hipSuccess) return e;
+    const long long nwg = plan_supertile<T>(a, p, plan_tail_ksplit<T>(a, p, n_cu));
+#ifdef DGP_DIAG
+    a.dbg = diag_buffer(nwg);
+#endif
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)nwg), dim3(64 * (CW + 4)), p.lds, s, a);
+    if (a.tail_ksplit > 1) {      // second half of the tail K-split
         const int ntail = (int)((long long)a.mtiles * a.ntiles - a.n_main);
         if (a.out_fmt) hipLaunchKernelGGL((tail_fixup_h2_kernel<BM, BN>), dim3(BM * BN / 8 / 256, ntail), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((tail_fixup_kernel<BM, BN, NT == 2>), dim3(BM * BN / 4 / 256, ntail), dim3(256), 0, s, a);
     }
 #ifdef DGP_DIAG
-    if (a.dbg) {
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> h(10 * nwg);
-        (void)hipMemcpy(h.data(), a.dbg, 80 * nwg, hipMemcpyDeviceToHost);
-        double v[8] = {0};
-        for (long long b = 0; b < nwg; ++b) for (int k = 0; k < 8; ++k) v[k] += (double)h[10 * b + k];
-        for (int k = 0; k < 8; ++k) v[k] /= (double)nwg;
-        const int nks = a.nk * (32 / BK);
-        int occ = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * (CW + 4), smem);
-        hipFuncAttributes fa{};
-        (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-        printf("[diag occupancy] blocks/CU %d (smem %zu B, regs %d, static smem %zu, local %zu)\n", occ, smem, fa.numRegs,
-               fa.sharedSizeBytes, fa.localSizeBytes);
-        printf("[diag split %dx%d NT%d BK%d CW%d] tiles %lld K-steps %d | compute wave 0: first barrier %.0f cyc, epilogue %.0f | per K-step: "
-               "ldsread+mfma %.0f barrier-wait %.0f || loader wave: wait+split+ds_write %.0f load-issue %.0f barrier-wait %.0f\n",
-               BM, BN, NT, BK, CW, nwg, nks, v[0], v[2], v[4] / nks, v[7] / nks, v[3] / nks, v[5] / nks, v[6] / nks);
-        double v8 = 0; for (long long b = 0; b < nwg; ++b) v8 += (double)h[10 * b + 8];
-        double v9 = 0; for (long long b = 0; b < nwg; ++b) v9 += (double)h[10 * b + 9];
-        {   // per-CU timeline of the launch: how many workgroups a CU holds over the launch's span, and how long a freed slot stays empty
-            std::vector<unsigned long long> tl(3 * nwg);
-            (void)hipMemcpy(tl.data(), a.dbg + 10ull * 65536, 24 * nwg, hipMemcpyDeviceToHost);
-            if (const char* dump = getenv("DGP_DIAG_DUMP")) {      // raw (start, end, CU) of every workgroup of every launch, for scripts/cu_phase.py
-                if (FILE* f = fopen(dump, "a")) {
-                    fprintf(f, "# launch %dx%d tiles %lld K-steps %d\n", BM, BN, nwg, nks);
-                    for (long long b = 0; b < nwg; ++b) fprintf(f, "%llu %llu %llu\n", tl[3 * b], tl[3 * b + 1], tl[3 * b + 2]);
-                    fclose(f);
-                }
-            }
-            unsigned long long t_lo = ~0ull, t_hi = 0;
-            std::vector<std::pair<unsigned long long, std::pair<unsigned long long, int>>> ev;      // (cu key, (time, +1 / -1))
-            double dur = 0; long long nz = 0;
-            for (long long b = 0; b < nwg; ++b) {
-                const unsigned long long s0 = tl[3 * b], s1 = tl[3 * b + 1], k = tl[3 * b + 2];
-                if (!s1 || s1 < s0) continue;
-                ++nz; dur += (double)(s1 - s0);
-                if (s0 < t_lo) t_lo = s0;
-                if (s1 > t_hi) t_hi = s1;
-                ev.push_back({k, {s0, +1}}); ev.push_back({k, {s1, -1}});
-            }
-            std::sort(ev.begin(), ev.end(), [](const auto& x, const auto& y) {
-                return x.first != y.first ? x.first < y.first : x.second.first != y.second.first ? x.second.first < y.second.first : x.second.second < y.second.second; });
-            double res_t[4] = {0, 0, 0, 0}, gap_sum = 0; long long gaps = 0; int ncu = 0;
-            for (size_t i = 0; i < ev.size();) {
-                size_t j = i; while (j < ev.size() && ev[j].first == ev[i].first) ++j;
-                ++ncu;
-                int cnt = 0; unsigned long long tprev = t_lo, last_end = 0; bool pending = false;
-                for (size_t e = i; e < j; ++e) {
-                    const unsigned long long tt = ev[e].second.first;
-                    res_t[cnt > 3 ? 3 : cnt] += (double)(tt - tprev); tprev = tt;
-                    if (ev[e].second.second > 0) { if (pending) { gap_sum += (double)(tt - last_end); ++gaps; pending = false; } ++cnt; }
-                    else { --cnt; last_end = tt; pending = true; }
-                }
-                res_t[0] += (double)(t_hi - tprev);
-                i = j;
-            }
-            const double span = (double)(t_hi - t_lo), tot = span * ncu;
-            if (nz && span > 0)
-                printf("[diag timeline] span %.2f us on %d CUs | workgroup life %.2f us (%.0f shader cycles -> %.2f GHz) | CU time holding 0 / 1 / 2 / 3+ workgroups: %.3f %.3f %.3f %.3f | "
-                       "a freed slot waits %.2f us for its next workgroup (%lld hand-overs)\n",
-                       span / 100.0, ncu, dur / nz / 100.0, v[0] + v[1] + v[2] + v9 / nwg, (v[0] + v[1] + v[2] + v9 / nwg) / (dur / nz * 10.0),
-                       res_t[0] / tot, res_t[1] / tot, res_t[2] / tot, res_t[3] / tot, gaps ? gap_sum / gaps / 100.0 : 0.0, gaps);
-        }
-        printf("[diag epilogue, DMA kernels] last MFMAs + staging %.0f | set-up (scale / bias, residual requests) %.0f | chunk 0 %.0f | chunks 1.. %.0f | absmax %.0f (res %d)\n",
-               v9 / nwg, v[3], v[5], v[6], v8 / nwg, a.res ? 1 : 0);
-    }
+    diag_report_split(a, BM, BN, NT, BK, CW, k.fn, p.lds, nwg, s);
+#endif
+    return hipGetLastError();
+}
+
+template <int BM, int BN>
+static hipError_t launch_conv_ls(ConvArgs a, hipStream_t s) {
+    const size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
+    a.mtiles = (a.M + BM - 1) / BM;
+    a.ntiles = (a.CoutP + BN - 1) / BN;
+    if (a.CoutP % BN != 0 || a.Cin < 32 || a.out_mode != 0) return hipErrorInvalidValue;
+    constexpr auto kern = conv_igemm_f32_ls<BM, BN>;
+    hipError_t e = ensure_dynamic_lds<kern>(160 * 1024);
+    if (e != hipSuccess) return e;
+    const long long nwg = (long long)a.mtiles * a.ntiles;
+#ifdef DGP_DIAG
+    a.dbg = diag_buffer(nwg);
+#endif
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), smem, s, a);
+#ifdef DGP_DIAG
+    diag_report_f32(a, BM, BN, true, nwg, s);
 #endif
     return hipGetLastError();
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool WIDE>
 static hipError_t launch_conv_t(ConvArgs a, hipStream_t s) {
-    size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
+    const size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
     a.mtiles = (a.M + BM - 1) / BM;
     a.ntiles = (a.CoutP + BN - 1) / BN;
-#ifdef DGP_DIAG
-    static unsigned long long* dbg_buf = nullptr;
-    {
-        const long long nb = (long long)a.mtiles * a.ntiles;
-        if (!dbg_buf) (void)hipMalloc(&dbg_buf, 10 * 8 * 65536);
-        a.dbg = nb <= 65536 ? dbg_buf : nullptr;
-    }
-#endif
     if (a.CoutP % BN != 0) return hipErrorInvalidValue;       // weight panels are padded to the tile
-    auto kern = conv_igemm_f32<BM, BN, WAVES_M, WAVES_N, WIDE>;
-    static bool attr_done_dev[16] = {};   // per instantiation and device
-    bool& attr_done = attr_done_dev[dgp_device_slot()];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    constexpr auto kern = conv_igemm_f32<BM, BN, WAVES_M, WAVES_N, WIDE>;
+    hipError_t e = ensure_dynamic_lds<kern>(160 * 1024);
+    if (e != hipSuccess) return e;
     if (a.ksplit > 1 && (a.out_mode != 1 || a.nk % a.ksplit != 0)) return hipErrorInvalidValue;
     const long long nwg = (long long)a.mtiles * a.ntiles * (a.ksplit > 1 ? a.ksplit : 1);
+#ifdef DGP_DIAG
+    a.dbg = diag_buffer(nwg);
+#endif
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * WAVES_M * WAVES_N), smem, s, a);
 #ifdef DGP_DIAG
-    if (a.dbg) {
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> h(10 * nwg);
-        (void)hipMemcpy(h.data(), a.dbg, 80 * nwg, hipMemcpyDeviceToHost);
-        double v[8] = {0};
-        for (long long b = 0; b < nwg; ++b) for (int k = 0; k < 8; ++k) v[k] += (double)h[10 * b + k];
-        for (int k = 0; k < 8; ++k) v[k] /= (double)nwg;
-        printf("[diag %dx%d] tiles %lld nk %d | cycles/tile: prologue %.0f loop %.0f epilogue %.0f | per K-step (wave 0): "
-               "gload-issue %.0f mfma+ldsread %.0f vmcnt-wait %.0f lds-store %.0f barrier %.0f\n", BM, BN, nwg, a.nk,
-               v[0], v[1], v[2], v[3] / a.nk, v[4] / a.nk, v[5] / a.nk, v[6] / a.nk, v[7] / a.nk);
-    }
+    diag_report_f32(a, BM, BN, false, nwg, s);
 #endif
     return hipGetLastError();
 }
+
+// What every TileCfg id means, in id order: the kernel family and its template parameters, and the fp32 tiles that take the launch where
+// the tile's own kernel cannot.  pick_tile's DGP_FORCE_TILE check, conv_kernel_name and launch_conv all read this table.
+enum TileFamily { FAM_F32, FAM_LS, FAM_SPLIT };      // conv_igemm_f32 / conv_igemm_f32_ls / conv_igemm_split_ls
+struct TileInfo {
+    int id;
+    TileFamily family;
+    int BM, BN;
+    int WM, WN;              // fp32 family: waves along M and N
+    int NT, BK, CW;          // split family: MFMAs per product (6 / 3 bf16, 2 = three fp16), K floats per step, compute waves
+    bool needs_ranges;       // needs the operand ranges (fp16 split)
+    int f32_tile;            // the fp32 tile that runs out_mode != 0 (itself for the fp32 family)
+    int small_tile;          // the fp32 tile whose per-lane tap kernel runs Cin < 32
+    const char* name;        // conv_kernel_name (nullptr: "f32")
+    const char* name_h1;     // ... of an H1 launch, where it differs
+};
+constexpr TileInfo TILES[] = {
+    {TILE_128x128,         FAM_F32,   128, 128, 2, 2, 0, 0,  0, false, TILE_128x128,    TILE_128x128, nullptr, nullptr},
+    {TILE_128x64,          FAM_F32,   128, 64,  2, 2, 0, 0,  0, false, TILE_128x64,     TILE_128x64,  nullptr, nullptr},
+    {TILE_64x64,           FAM_F32,   64,  64,  2, 2, 0, 0,  0, false, TILE_64x64,      TILE_128x64,  nullptr, nullptr},
+    {TILE_128x32,          FAM_F32,   128, 32,  4, 1, 0, 0,  0, false, TILE_128x32,     TILE_128x32,  nullptr, nullptr},
+    {TILE_128x128_W8,      FAM_F32,   128, 128, 2, 4, 0, 0,  0, false, TILE_128x128_W8, TILE_128x128, nullptr, nullptr},
+    {TILE_128x128_LS,      FAM_LS,    128, 128, 0, 0, 0, 0,  0, false, TILE_128x128_W8, TILE_128x128, nullptr, nullptr},
+    {TILE_128x64_LS,       FAM_LS,    128, 64,  0, 0, 0, 0,  0, false, TILE_128x64,     TILE_128x64,  nullptr, nullptr},
+    {TILE_128x128_S6,      FAM_SPLIT, 128, 128, 0, 0, 6, 32, 4, false, TILE_128x128_W8, TILE_128x128, "split6_128x128_k32", nullptr},
+    {TILE_128x128_S3,      FAM_SPLIT, 128, 128, 0, 0, 3, 32, 4, false, TILE_128x128_W8, TILE_128x128, "split3_128x128_k32", nullptr},
+    {TILE_128x64_S6,       FAM_SPLIT, 128, 64,  0, 0, 6, 32, 4, false, TILE_128x64,     TILE_128x64,  "split6_128x64_k32", nullptr},
+    {TILE_128x128_S6K16,   FAM_SPLIT, 128, 128, 0, 0, 6, 16, 4, false, TILE_128x128_W8, TILE_128x128, "split6_128x128_k16", nullptr},
+    {TILE_128x128_S3K16,   FAM_SPLIT, 128, 128, 0, 0, 3, 16, 4, false, TILE_128x128_W8, TILE_128x128, "split3_128x128_k16", nullptr},
+    {TILE_128x128_S6K16W8, FAM_SPLIT, 128, 128, 0, 0, 6, 16, 8, false, TILE_128x128_W8, TILE_128x128, "split6_128x128_k16w8", nullptr},
+    {TILE_128x128_H3K16,   FAM_SPLIT, 128, 128, 0, 0, 2, 16, 4, true,  TILE_128x128_W8, TILE_128x128, "splith3_128x128_k16", nullptr},
+    {TILE_128x128_H3K16W8, FAM_SPLIT, 128, 128, 0, 0, 2, 16, 8, true,  TILE_128x128_W8, TILE_128x128, "splith3_128x128_k16w8", nullptr},
+    {TILE_128x64_H3,       FAM_SPLIT, 128, 64,  0, 0, 2, 32, 4, true,  TILE_128x64,     TILE_128x64,  "splith3_128x64_k32", "h1_128x64_k64"},
+    {TILE_128x128_H3K32,   FAM_SPLIT, 128, 128, 0, 0, 2, 32, 4, true,  TILE_128x128_W8, TILE_128x128, "splith3_128x128_k32", "h1_128x128_k64"},
+};
+constexpr int N_TILES = (int)(sizeof(TILES) / sizeof(TILES[0]));
+constexpr bool tiles_in_id_order() { for (int i = 0; i < N_TILES; ++i) if (TILES[i].id != i) return false; return true; }
+static_assert(N_TILES == TILE_128x128_H3K32 + 1 && tiles_in_id_order(), "TILES is indexed by TileCfg id");
 
 // Tile choice, from scripts/conv_sweep.py on MI355X (ResNet-50 640x480 batch-32 shapes, TFLOP/s for
 // 128x128 / 128x64 / 64x64): the small 64x64 tile (4 workgroups per CU, finest tail) wins for the
@@ -2520,13 +2574,8 @@ int pick_tile(int M, int CoutP, int K, bool have_absmax) {
     (void)M;
     if (CoutP <= 32) return TILE_128x32;
     if (const char* f = getenv("DGP_FORCE_TILE")) {     // tuning experiments only
-        const int v = atoi(f);
-        if ((v == TILE_128x128 || v == TILE_128x128_W8 || v == TILE_128x128_LS || v == TILE_128x128_S6 ||
-             v == TILE_128x128_S3 || v == TILE_128x128_S6K16 || v == TILE_128x128_S3K16 || v == TILE_128x128_S6K16W8 ||
-             ((v == TILE_128x128_H3K16 || v == TILE_128x128_H3K16W8 || v == TILE_128x128_H3K32) && have_absmax)) &&
-            CoutP % 128 == 0) return v;
-        if ((v == TILE_128x64_LS || v == TILE_128x64_S6 || (v == TILE_128x64_H3 && have_absmax)) && CoutP % 64 == 0) return v;
-        if ((v == TILE_128x64 || v == TILE_64x64) && CoutP % 64 == 0) return v;
+        const int v = atoi(f);      // any tile of 64 or 128 columns that divides the panel and has the ranges it needs
+        if (v >= 0 && v < N_TILES && TILES[v].BN >= 64 && (!TILES[v].needs_ranges || have_absmax) && CoutP % TILES[v].BN == 0) return v;
     }
     // rule 4 (default): fp16-split kernels where the caller tracks operand ranges (3 fp16 MFMAs per fp32-class
     //         product), bf16-split elsewhere;
@@ -2564,21 +2613,8 @@ int pick_tile(int M, int CoutP, int K, bool have_absmax) {
 
 // Name of the kernel launch_conv will run for (args, tile) -- for the profile table / roofline accounting.
 const char* conv_kernel_name(const ConvArgs& a, int tile_cfg) {
-    if ((a.Cin >= 32 || a.stem) && a.out_mode == 0) {
-        switch (tile_cfg) {
-            case TILE_128x128_S6K16: return "split6_128x128_k16";
-            case TILE_128x128_S6K16W8: return "split6_128x128_k16w8";
-            case TILE_128x128_H3K16:   return "splith3_128x128_k16";
-            case TILE_128x128_H3K16W8: return "splith3_128x128_k16w8";
-            case TILE_128x128_H3K32:   return a.in_fmt == 2 ? "h1_128x128_k64" : "splith3_128x128_k32";
-            case TILE_128x64_H3:       return a.in_fmt == 2 ? "h1_128x64_k64" : "splith3_128x64_k32";
-            case TILE_128x128_S6:    return "split6_128x128_k32";
-            case TILE_128x64_S6:     return "split6_128x64_k32";
-            case TILE_128x128_S3K16: return "split3_128x128_k16";
-            case TILE_128x128_S3:    return "split3_128x128_k32";
-            default: break;
-        }
-    }
+    if (tile_cfg >= 0 && tile_cfg < N_TILES && TILES[tile_cfg].family == FAM_SPLIT && (a.Cin >= 32 || a.stem) && a.out_mode == 0)
+        return a.in_fmt == 2 && TILES[tile_cfg].name_h1 ? TILES[tile_cfg].name_h1 : TILES[tile_cfg].name;
     return "f32";
 }
 
@@ -2595,38 +2631,35 @@ static bool to_h1_units(ConvArgs& a) {
     return true;
 }
 
+// the launcher of tile ID's own kernel, from its row of TILES
+template <int ID>
+static hipError_t launch_tile(const ConvArgs& a, hipStream_t s) {
+    constexpr TileInfo t = TILES[ID];
+    if constexpr (t.family == FAM_SPLIT) return launch_conv_split<t.BM, t.BN, t.NT, t.BK, t.CW>(a, s);
+    else if constexpr (t.family == FAM_LS) return launch_conv_ls<t.BM, t.BN>(a, s);
+    else return launch_conv_t<t.BM, t.BN, t.WM, t.WN, true>(a, s);
+}
+template <int... ID>
+static hipError_t launch_tile_by_id(int id, const ConvArgs& a, hipStream_t s, std::integer_sequence<int, ID...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((id == ID && ((e = launch_tile<ID>(a, s)), true)) || ...);
+    return e;
+}
+
 hipError_t launch_conv(const ConvArgs& a_in, int tile_cfg, hipStream_t s) {
     ConvArgs a = a_in;
     if (a.in_fmt == 2 && !(a.out_mode == 0 && to_h1_units(a))) return hipErrorInvalidValue;
     if (a.in_fmt != 2 && (a.out_fmt == 2 || a.res_fmt == 2)) return hipErrorInvalidValue;
+    const bool known = tile_cfg >= 0 && tile_cfg < N_TILES;
     if (a.Cin < 32 && !a.stem) {       // generic per-lane tap path (stem / small test shapes)
-        if (tile_cfg == TILE_128x32) return launch_conv_t<128, 32, 4, 1, false>(a, s);
-        if (tile_cfg == TILE_128x128_W8 || tile_cfg == TILE_128x128_LS || tile_cfg == TILE_128x128_S6 ||
-            tile_cfg == TILE_128x128_S3 || tile_cfg == TILE_128x128_S6K16 || tile_cfg == TILE_128x128_S3K16 ||
-            tile_cfg == TILE_128x128_S6K16W8 || tile_cfg == TILE_128x128_H3K16 || tile_cfg == TILE_128x128_H3K16W8 ||
-            tile_cfg == TILE_128x128_H3K32) tile_cfg = TILE_128x128;
-        if (a.CoutP % 128 == 0 && tile_cfg == TILE_128x128) return launch_conv_t<128, 128, 2, 2, false>(a, s);
+        const int small = known ? TILES[tile_cfg].small_tile : TILE_128x64;
+        if (small == TILE_128x32) return launch_conv_t<128, 32, 4, 1, false>(a, s);
+        if (small == TILE_128x128 && a.CoutP % 128 == 0) return launch_conv_t<128, 128, 2, 2, false>(a, s);
         return launch_conv_t<128, 64, 2, 2, false>(a, s);
     }
-    switch (tile_cfg) {
-        case TILE_128x32: return launch_conv_t<128, 32, 4, 1, true>(a, s);
-        case TILE_128x64: return launch_conv_t<128, 64, 2, 2, true>(a, s);
-        case TILE_64x64:  return launch_conv_t<64, 64, 2, 2, true>(a, s);
-        case TILE_128x128_W8: return launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_LS: return a.out_mode == 0 ? launch_conv_ls<128, 128>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x64_LS:  return a.out_mode == 0 ? launch_conv_ls<128, 64>(a, s) : launch_conv_t<128, 64, 2, 2, true>(a, s);
-        case TILE_128x128_S6: return a.out_mode == 0 ? launch_conv_split<128, 128, 6, 32>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_S3: return a.out_mode == 0 ? launch_conv_split<128, 128, 3, 32>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_S6K16: return a.out_mode == 0 ? launch_conv_split<128, 128, 6, 16>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_S3K16: return a.out_mode == 0 ? launch_conv_split<128, 128, 3, 16>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_S6K16W8: return a.out_mode == 0 ? launch_conv_split<128, 128, 6, 16, 8>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_H3K16:   return a.out_mode == 0 ? launch_conv_split<128, 128, 2, 16>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_H3K16W8: return a.out_mode == 0 ? launch_conv_split<128, 128, 2, 16, 8>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x128_H3K32:   return a.out_mode == 0 ? launch_conv_split<128, 128, 2, 32>(a, s) : launch_conv_t<128, 128, 2, 4, true>(a, s);
-        case TILE_128x64_H3:       return a.out_mode == 0 ? launch_conv_split<128, 64, 2, 32>(a, s) : launch_conv_t<128, 64, 2, 2, true>(a, s);
-        case TILE_128x64_S6:  return a.out_mode == 0 ? launch_conv_split<128, 64, 6, 32>(a, s) : launch_conv_t<128, 64, 2, 2, true>(a, s);
-        default:          return launch_conv_t<128, 128, 2, 2, true>(a, s);
-    }
+    if (!known) tile_cfg = TILE_128x128;
+    if (a.out_mode != 0) tile_cfg = TILES[tile_cfg].f32_tile;      // (the transposed-conv scatter exists in the fp32 kernels only)
+    return launch_tile_by_id(tile_cfg, a, s, std::make_integer_sequence<int, N_TILES>{});
 }
 
 }  // namespace dgp

@@ -644,14 +644,8 @@ hipError_t launch_loss(const LossArgs& a, hipStream_t s) {
     if (smem > LOSS_LDS_LIMIT || (force && atoi(force) != 0)) {
         hipLaunchKernelGGL(loss_ce_backward<true>, dim3(nm), dim3(LOSS_CE_THREADS), 0, s, a);
     } else {
-        static bool attr_dev[16] = {};
-        bool& attr = attr_dev[dgp_device_slot()];
-        if (!attr) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(loss_ce_backward<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            if (e != hipSuccess) return e;
-            attr = true;
-        }
+        e = ensure_dynamic_lds<loss_ce_backward<false>>(150 * 1024);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(loss_ce_backward<false>, dim3(nm), dim3(LOSS_CE_THREADS), smem, s, a);
     }
     if (a.n_v > 0) {

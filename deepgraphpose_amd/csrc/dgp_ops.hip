@@ -740,16 +740,9 @@ hipError_t launch_stem_pool_fused(const unsigned char* frames, int B, int H, int
     const int ph = h1t ? 3 : 5;
     a.tiles_h = (a.HP + ph - 1) / ph; a.tiles_w = (a.WP + 15) / 16; a.ntiles = B * a.tiles_h * a.tiles_w;
     const size_t smem = h1t ? (size_t)7 * 4 * 64 * 16 + (size_t)19 * 72 * 8 + (size_t)15 * 16 * 72 * 2 : (size_t)7 * 4 * 2 * 64 * 16 + (size_t)23 * 16 * 68 * 4;
-    static bool attr_dev[16][2] = {};
-    bool& attr = attr_dev[dgp_device_slot()][h1t ? 1 : 0];
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(h1t ? reinterpret_cast<const void*>(stem_pool_fused_kernel<true>) : reinterpret_cast<const void*>(stem_pool_fused_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    static int n_cu = 0;
-    if (!n_cu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu <= 0) n_cu = 256; }
+    const hipError_t e = h1t ? ensure_dynamic_lds<stem_pool_fused_kernel<true>>(160 * 1024) : ensure_dynamic_lds<stem_pool_fused_kernel<false>>(160 * 1024);
+    if (e != hipSuccess) return e;
+    const int n_cu = device_facts().n_cu;
     if (h1t) {
         const int grid = a.ntiles < 2 * n_cu ? a.ntiles : 2 * n_cu;
         hipLaunchKernelGGL(stem_pool_fused_kernel<true>, dim3((unsigned)grid), dim3(512), smem, s, a);
@@ -940,13 +933,9 @@ static hipError_t launch_soft_argmax_t(const float* scmap, const float* locref, 
                            mu, conf, idx, pmap, record_stride, locref, offs);
         return hipGetLastError();
     }
-    static size_t attr_set_dev[16] = {};      // (per instance: the attribute belongs to the kernel function)
-    size_t& attr_set = attr_set_dev[dgp_device_slot()];
-    if (smem > 64 * 1024 && smem > attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(soft_argmax_kernel<false, LOCREF>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (smem > 64 * 1024) {      // (grows with the largest map seen)
+        hipError_t e = ensure_dynamic_lds<soft_argmax_kernel<false, LOCREF>>(smem);
         if (e != hipSuccess) return e;
-        attr_set = smem;
     }
     hipLaunchKernelGGL((soft_argmax_kernel<false, LOCREF>), dim3((unsigned)(B * C)), dim3(SOFT_ARGMAX_THREADS), smem, s, scmap, H, W, C, gamma,
                        gauss_len, mu, conf, idx, pmap, record_stride, locref, offs);

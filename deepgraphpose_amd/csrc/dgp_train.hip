@@ -2169,8 +2169,6 @@ hipError_t wgrad_launch(const WgradCall& c, hipStream_t s) {
     if (mpb < 256) mpb = 256;
     split = (a.M + mpb - 1) / mpb;
     a.m_per_block = mpb;
-    static bool attr_dev[16][3] = {};
-    auto& attr = attr_dev[dgp_device_slot()];
     static const bool h3_env = (dgp_tune("DGP_WGRAD_F16", 1) != 0);       // A/B switch
     const float *rx = c.x.rng, *rdy = c.dy.rng;
     // both operands also exist as fp16 high / low copies written by their producers: LDS-DMA tile (falls back per workgroup to the
@@ -2188,11 +2186,8 @@ hipError_t wgrad_launch(const WgradCall& c, hipStream_t s) {
         return hipGetLastError();
     }
     if (dma_ok && h3_env) {
-        if (!attr[2]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_dma), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            if (e != hipSuccess) return e;
-            attr[2] = true;
-        }
+        e = ensure_dynamic_lds<wgrad_dma>(64 * 1024);
+        if (e != hipSuccess) return e;
         read_cells();
         if (c.fail_flag) { a.x = nullptr; a.fail_flag = c.fail_flag; }
         hipLaunchKernelGGL(wgrad_dma, dim3(kt, nt, split), dim3(256), 64 * 1024, s, a);
@@ -2200,20 +2195,14 @@ hipError_t wgrad_launch(const WgradCall& c, hipStream_t s) {
     }
     if (c.fail_flag) return hipErrorInvalidValue;          // (no other kernel reads H2 cells)
     if (big && h3_env && rx && rdy && Cin % 4 == 0) {      // both operand ranges known: 16-bit matrix pipe
-        if (!attr[0]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_h3p), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            if (e != hipSuccess) return e;
-            attr[0] = true;
-        }
+        e = ensure_dynamic_lds<wgrad_h3p>(64 * 1024);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(wgrad_h3p, dim3(kt, nt, split), dim3(256), 2 * 4 * 32 * 256, s, a, WgradRanges{rx, rdy});
         return hipGetLastError();
     }
     if (big) {
-        if (!attr[1]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_f32<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            if (e != hipSuccess) return e;
-            attr[1] = true;
-        }
+        e = ensure_dynamic_lds<wgrad_f32<2>>(64 * 1024);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(wgrad_f32<2>, dim3(kt, nt, split), dim3(256), 2 * 2 * 32 * 128 * 4, s, a);
     } else {
         hipLaunchKernelGGL(wgrad_f32<1>, dim3(kt, nt, split), dim3(256), 2 * 2 * 32 * 64 * 4, s, a);
@@ -3187,8 +3176,7 @@ static int backward_unit_f32(TrainPass& p, int ui) {
 // row of STEM_SLAB_ROW floats per workgroup (at most sa.nitems of them).
 static void stem_wgrad_launch(StemWgradArgs& sa, hipStream_t s) {
     sa.bands = (sa.H1 + 3) / 4; sa.chunks = (sa.W1 + 31) / 32; sa.nitems = sa.B * sa.bands * sa.chunks;
-    static int n_cu_s = 0;
-    if (!n_cu_s) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu_s, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu_s <= 0) n_cu_s = 256; }
+    const int n_cu_s = device_facts().n_cu;
     static const int wgs_per_cu = dgp_tune("DGP_STEM_WGRAD_WGS", 2);      // (1: 6.77, 2: 6.72, 3: 6.72, 4: 6.84 ms per step)
     const int grid = sa.nitems < wgs_per_cu * n_cu_s ? sa.nitems : wgs_per_cu * n_cu_s;
     hipLaunchKernelGGL(stem_wgrad_h1_kernel, dim3((unsigned)grid), dim3(256), 0, s, sa);
