@@ -46,6 +46,12 @@ class DgpConvDesc(C.Structure):
         "res_stride", "res_H", "res_W")]
 
 
+class DgpConvPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "tile", "family", "mode", "cs", "dma", "deep", "ah2", "oh2", "h1", "lds", "mtiles", "ntiles", "grid",
+        "tail_ksplit", "n_main", "st_gn", "st_mc", "st_mb", "n_cu")] + [("kernel_name", C.c_char * 32)]
+
+
 # every symbol include/dgp_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _f32, _sz = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -93,10 +99,14 @@ SYMBOLS = {
     "dgp_pack_conv_weights": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp]),
     "dgp_conv2d": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgp_conv2d_ranged": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgp_conv2d_ranged_slab": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dgp_conv2d_plan": (C.c_int, [C.POINTER(DgpConvDesc), _i32, _i32, _i32, _i32, _i32, _sz, _i32, _i32, C.POINTER(DgpConvPlan)]),
     "dgp_tensor_absmax": (C.c_int, [_vp, _sz, _vp, _vp]),
     "dgp_f32_to_h2": (C.c_int, [_vp, _sz, _i32, _vp, _vp]),
     "dgp_h2_to_f32": (C.c_int, [_vp, _sz, _i32, _vp, _vp]),
     "dgp_conv2d_h2": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "dgp_conv2d_h2_slab": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp,
+                                     _sz, _vp]),
     "dgp_net_set_tier": (C.c_int, [_vp, _i32]),
     "dgp_net_get_tier": (C.c_int, [_vp]),
     "dgp_f32_to_h1": (C.c_int, [_vp, _sz, _i32, _vp, _vp]),

@@ -89,6 +89,31 @@ constexpr int ABSMAX_SLOTS = 256;
 
 enum TileCfg { TILE_128x128 = 0, TILE_128x64 = 1, TILE_64x64 = 2, TILE_128x32 = 3, TILE_128x128_W8 = 4, TILE_128x128_LS = 5, TILE_128x64_LS = 6, TILE_128x128_S6 = 7, TILE_128x128_S3 = 8, TILE_128x64_S6 = 9, TILE_128x128_S6K16 = 10, TILE_128x128_S3K16 = 11, TILE_128x128_S6K16W8 = 12, TILE_128x128_H3K16 = 13, TILE_128x128_H3K16W8 = 14, TILE_128x64_H3 = 15, TILE_128x128_H3K32 = 16 };
 
+enum TileFamily { FAM_F32, FAM_LS, FAM_SPLIT };      // conv_igemm_f32 / conv_igemm_f32_ls / conv_igemm_split_ls
+
+// The path of one split-kernel launch: the template flags of conv_igemm_split_ls and the dynamic LDS that goes with them
+struct SplitPath {
+    int mode;              // loader walk: 0 everything at run time, 1 per-tap, 2 pointwise, 3 halo ring
+    bool pb;               // weights come as pre-split cells
+    bool cs, dma, deep;    // compute-side split, LDS-DMA loaders, deep DMA ring
+    bool ah2, oh2, h1;     // input in cells, output in cells, the cells are H1 (16-bit tier)
+    size_t lds;
+};
+
+// Everything launch_conv decides on the host before it launches: which kernel and which grid.  plan_conv is the one place that decides
+// it (no HIP calls; n_cu is an argument), launch_conv launches what it says, dgp_conv2d_plan reports it
+struct ConvPlan {
+    int tile;              // TileCfg after launch_conv's fallbacks (Cin < 32, out_mode != 0, unknown id)
+    TileFamily family;
+    bool wide;             // fp32 family: false = the per-lane tap kernel of Cin < 32
+    SplitPath path;        // split family only (zero elsewhere)
+    int mtiles, ntiles;
+    long long grid;        // workgroups of the main launch
+    int tail_ksplit, n_main;       // split family: K-split of the grid's tail (0: none)
+    int st_gn, st_mc, st_mb;       // split family: supertile order (st_gn 0: plain)
+};
+// Fills `a` as the kernel will get it (H1 units, tiles, tail split, supertile order) and `pl`; hipErrorInvalidValue for a launch no kernel runs
+hipError_t plan_conv(ConvArgs& a, int tile_cfg, int n_cu, ConvPlan& pl);
 hipError_t launch_conv(const ConvArgs& a, int tile_cfg, hipStream_t s);
 int        pick_tile(int M, int CoutP, int K, bool have_absmax = false);
 // fp32 panel [nk*8][CoutP][4] -> fp16 cells [nk*4 k-groups][2 planes][CoutP][8 halves] in the LDS order of the fp16-split kernels

@@ -2161,9 +2161,11 @@ __global__ __launch_bounds__(256) void tail_fixup_h2_kernel(const ConvArgs p) {
 }
 
 // ------------------------------------------------------------------------------------
-// Launch layer.  launch_conv looks the tile id up in TILES and calls its family's launcher.  A split-kernel launch goes through stages:
-// split_fill_args / split_decide (which path, how much LDS) -> split_kernel (the one instantiation of that path) -> plan_tail_ksplit /
-// plan_supertile (the grid) -> launch (+ the fix-up launch of a split tail).
+// Launch layer.  plan_conv decides everything on the host -- the tile after the fall-backs, its family, and through the family's plan
+// (plan_split / plan_ls / plan_f32) the path and the grid -- without a HIP call and for a given number of CUs; launch_conv launches
+// what it says, dgp_conv2d_plan (dgp_net.hip) reports it.  A split-kernel plan goes through stages: split_fill_args / split_decide
+// (which path, how much LDS) -> split_kernel (the one instantiation of that path) -> plan_tail_ksplit / plan_supertile (the grid);
+// then the launch (+ the fix-up launch of a split tail).
 // ------------------------------------------------------------------------------------
 using ConvKernel = void (*)(const ConvArgs);
 
@@ -2274,15 +2276,6 @@ struct SplitTile {
     static constexpr bool CAN_CS = CAN_PB && BK == 32;                 // compute-side split
     static constexpr bool CAN_DMA = CAN_CS && BM == 128 && (BN == 128 || BN == 64);      // LDS-DMA loaders
     static constexpr bool CAN_DEEP = CAN_DMA && BN == 128;             // deep DMA ring, halo walk
-};
-
-// The path of one split-kernel launch: the template flags of conv_igemm_split_ls and the dynamic LDS that goes with them
-struct SplitPath {
-    int mode;              // loader walk: 0 everything at run time, 1 per-tap, 2 pointwise, 3 halo ring
-    bool pb;               // weights come as pre-split cells
-    bool cs, dma, deep;    // compute-side split, LDS-DMA loaders, deep DMA ring
-    bool ah2, oh2, h1;     // input in cells, output in cells, the cells are H1 (16-bit tier)
-    size_t lds;
 };
 
 // Stage 1a: the ConvArgs fields every split kernel reads, whatever its path
@@ -2458,19 +2451,26 @@ static long long plan_supertile(ConvArgs& a, const SplitPath& p, long long nwg) 
     return 8LL * a.st_mb * a.ntiles;
 }
 
-template <int BM, int BN, int NT, int BK, int CW = 4>
-static hipError_t launch_conv_split(ConvArgs a, hipStream_t s) {
-    using T = SplitTile<BM, BN, NT, BK, CW>;
-    const int n_cu = device_facts().n_cu;
+// The plan of a split-kernel launch: stages 1 to 3.  Everything the launch depends on is in `a` and `pl` afterwards
+template <class T>
+static hipError_t plan_split(ConvArgs& a, int n_cu, ConvPlan& pl) {
     split_fill_args<T>(a);
-    SplitPath p;
-    hipError_t e = split_decide<T>(a, n_cu, p);
+    hipError_t e = split_decide<T>(a, n_cu, pl.path);
     if (e != hipSuccess) return e;
+    if (!split_kernel<T>(pl.path).fn) return hipErrorInvalidValue;
+    pl.grid = plan_supertile<T>(a, pl.path, plan_tail_ksplit<T>(a, pl.path, n_cu));
+    return hipSuccess;
+}
+
+template <int BM, int BN, int NT, int BK, int CW = 4>
+static hipError_t launch_conv_split(const ConvArgs& a_planned, const ConvPlan& pl, hipStream_t s) {
+    using T = SplitTile<BM, BN, NT, BK, CW>;
+    ConvArgs a = a_planned;
+    const SplitPath& p = pl.path;
     const SplitKernel k = split_kernel<T>(p);
-    if (!k.fn) return hipErrorInvalidValue;
-    e = k.ensure_lds(160 * 1024);
+    hipError_t e = k.ensure_lds(160 * 1024);
     if (e != hipSuccess) return e;
-    const long long nwg = plan_supertile<T>(a, p, plan_tail_ksplit<T>(a, p, n_cu));
+    const long long nwg = pl.grid;
 #ifdef DGP_DIAG
     a.dbg = diag_buffer(nwg);
 #endif
@@ -2486,16 +2486,31 @@ static hipError_t launch_conv_split(ConvArgs a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int BM, int BN>
-static hipError_t launch_conv_ls(ConvArgs a, hipStream_t s) {
-    const size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
+// The plans of the fp32 families: what the kernels refuse, the tiles and the grid
+static hipError_t plan_ls(ConvArgs& a, int BM, int BN, ConvPlan& pl) {
     a.mtiles = (a.M + BM - 1) / BM;
     a.ntiles = (a.CoutP + BN - 1) / BN;
     if (a.CoutP % BN != 0 || a.Cin < 32 || a.out_mode != 0) return hipErrorInvalidValue;
+    pl.grid = (long long)a.mtiles * a.ntiles;
+    return hipSuccess;
+}
+static hipError_t plan_f32(ConvArgs& a, int BM, int BN, ConvPlan& pl) {
+    a.mtiles = (a.M + BM - 1) / BM;
+    a.ntiles = (a.CoutP + BN - 1) / BN;
+    if (a.CoutP % BN != 0) return hipErrorInvalidValue;       // weight panels are padded to the tile
+    if (a.ksplit > 1 && (a.out_mode != 1 || a.nk % a.ksplit != 0)) return hipErrorInvalidValue;
+    pl.grid = (long long)a.mtiles * a.ntiles * (a.ksplit > 1 ? a.ksplit : 1);
+    return hipSuccess;
+}
+
+template <int BM, int BN>
+static hipError_t launch_conv_ls(const ConvArgs& a_planned, const ConvPlan& pl, hipStream_t s) {
+    ConvArgs a = a_planned;
+    const size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
     constexpr auto kern = conv_igemm_f32_ls<BM, BN>;
     hipError_t e = ensure_dynamic_lds<kern>(160 * 1024);
     if (e != hipSuccess) return e;
-    const long long nwg = (long long)a.mtiles * a.ntiles;
+    const long long nwg = pl.grid;
 #ifdef DGP_DIAG
     a.dbg = diag_buffer(nwg);
 #endif
@@ -2507,16 +2522,13 @@ static hipError_t launch_conv_ls(ConvArgs a, hipStream_t s) {
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool WIDE>
-static hipError_t launch_conv_t(ConvArgs a, hipStream_t s) {
+static hipError_t launch_conv_t(const ConvArgs& a_planned, const ConvPlan& pl, hipStream_t s) {
+    ConvArgs a = a_planned;
     const size_t smem = (size_t)(2 * 8 * (BM + 1) + 2 * 8 * BN) * 16;
-    a.mtiles = (a.M + BM - 1) / BM;
-    a.ntiles = (a.CoutP + BN - 1) / BN;
-    if (a.CoutP % BN != 0) return hipErrorInvalidValue;       // weight panels are padded to the tile
     constexpr auto kern = conv_igemm_f32<BM, BN, WAVES_M, WAVES_N, WIDE>;
     hipError_t e = ensure_dynamic_lds<kern>(160 * 1024);
     if (e != hipSuccess) return e;
-    if (a.ksplit > 1 && (a.out_mode != 1 || a.nk % a.ksplit != 0)) return hipErrorInvalidValue;
-    const long long nwg = (long long)a.mtiles * a.ntiles * (a.ksplit > 1 ? a.ksplit : 1);
+    const long long nwg = pl.grid;
 #ifdef DGP_DIAG
     a.dbg = diag_buffer(nwg);
 #endif
@@ -2529,7 +2541,6 @@ static hipError_t launch_conv_t(ConvArgs a, hipStream_t s) {
 
 // What every TileCfg id means, in id order: the kernel family and its template parameters, and the fp32 tiles that take the launch where
 // the tile's own kernel cannot.  pick_tile's DGP_FORCE_TILE check, conv_kernel_name and launch_conv all read this table.
-enum TileFamily { FAM_F32, FAM_LS, FAM_SPLIT };      // conv_igemm_f32 / conv_igemm_f32_ls / conv_igemm_split_ls
 struct TileInfo {
     int id;
     TileFamily family;
@@ -2631,35 +2642,68 @@ static bool to_h1_units(ConvArgs& a) {
     return true;
 }
 
-// the launcher of tile ID's own kernel, from its row of TILES
+// the plan and the launcher of tile ID's own kernel, from its row of TILES
 template <int ID>
-static hipError_t launch_tile(const ConvArgs& a, hipStream_t s) {
+static hipError_t plan_tile(ConvArgs& a, int n_cu, ConvPlan& pl) {
     constexpr TileInfo t = TILES[ID];
-    if constexpr (t.family == FAM_SPLIT) return launch_conv_split<t.BM, t.BN, t.NT, t.BK, t.CW>(a, s);
-    else if constexpr (t.family == FAM_LS) return launch_conv_ls<t.BM, t.BN>(a, s);
-    else return launch_conv_t<t.BM, t.BN, t.WM, t.WN, true>(a, s);
+    if constexpr (t.family == FAM_SPLIT) return plan_split<SplitTile<t.BM, t.BN, t.NT, t.BK, t.CW>>(a, n_cu, pl);
+    else if constexpr (t.family == FAM_LS) return plan_ls(a, t.BM, t.BN, pl);
+    else return plan_f32(a, t.BM, t.BN, pl);
+}
+template <int ID>
+static hipError_t launch_tile(const ConvArgs& a, const ConvPlan& pl, hipStream_t s) {
+    constexpr TileInfo t = TILES[ID];
+    if constexpr (t.family == FAM_SPLIT) return launch_conv_split<t.BM, t.BN, t.NT, t.BK, t.CW>(a, pl, s);
+    else if constexpr (t.family == FAM_LS) return launch_conv_ls<t.BM, t.BN>(a, pl, s);
+    else return launch_conv_t<t.BM, t.BN, t.WM, t.WN, true>(a, pl, s);
 }
 template <int... ID>
-static hipError_t launch_tile_by_id(int id, const ConvArgs& a, hipStream_t s, std::integer_sequence<int, ID...>) {
+static hipError_t plan_tile_by_id(int id, ConvArgs& a, int n_cu, ConvPlan& pl, std::integer_sequence<int, ID...>) {
     hipError_t e = hipErrorInvalidValue;
-    (void)((id == ID && ((e = launch_tile<ID>(a, s)), true)) || ...);
+    (void)((id == ID && ((e = plan_tile<ID>(a, n_cu, pl)), true)) || ...);
+    return e;
+}
+template <int... ID>
+static hipError_t launch_tile_by_id(int id, const ConvArgs& a, const ConvPlan& pl, hipStream_t s, std::integer_sequence<int, ID...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((id == ID && ((e = launch_tile<ID>(a, pl, s)), true)) || ...);
+    return e;
+}
+
+hipError_t plan_conv(ConvArgs& a, int tile_cfg, int n_cu, ConvPlan& pl) {
+    pl = ConvPlan{};
+    pl.wide = true;
+    if (a.in_fmt == 2 && !(a.out_mode == 0 && to_h1_units(a))) return hipErrorInvalidValue;
+    if (a.in_fmt != 2 && (a.out_fmt == 2 || a.res_fmt == 2)) return hipErrorInvalidValue;
+    const bool known = tile_cfg >= 0 && tile_cfg < N_TILES;
+    hipError_t e;
+    if (a.Cin < 32 && !a.stem) {       // generic per-lane tap path (stem / small test shapes)
+        const int small = known ? TILES[tile_cfg].small_tile : TILE_128x64;
+        pl.tile = small == TILE_128x32 ? TILE_128x32 : (small == TILE_128x128 && a.CoutP % 128 == 0) ? TILE_128x128 : TILE_128x64;
+        pl.family = FAM_F32; pl.wide = false;
+        e = plan_f32(a, TILES[pl.tile].BM, TILES[pl.tile].BN, pl);
+    } else {
+        if (!known) tile_cfg = TILE_128x128;
+        if (a.out_mode != 0) tile_cfg = TILES[tile_cfg].f32_tile;      // (the transposed-conv scatter exists in the fp32 kernels only)
+        pl.tile = tile_cfg; pl.family = TILES[tile_cfg].family;
+        e = plan_tile_by_id(tile_cfg, a, n_cu, pl, std::make_integer_sequence<int, N_TILES>{});
+    }
+    pl.mtiles = a.mtiles; pl.ntiles = a.ntiles;
+    pl.tail_ksplit = a.tail_ksplit; pl.n_main = a.n_main; pl.st_gn = a.st_gn; pl.st_mc = a.st_mc; pl.st_mb = a.st_mb;
     return e;
 }
 
 hipError_t launch_conv(const ConvArgs& a_in, int tile_cfg, hipStream_t s) {
     ConvArgs a = a_in;
-    if (a.in_fmt == 2 && !(a.out_mode == 0 && to_h1_units(a))) return hipErrorInvalidValue;
-    if (a.in_fmt != 2 && (a.out_fmt == 2 || a.res_fmt == 2)) return hipErrorInvalidValue;
-    const bool known = tile_cfg >= 0 && tile_cfg < N_TILES;
-    if (a.Cin < 32 && !a.stem) {       // generic per-lane tap path (stem / small test shapes)
-        const int small = known ? TILES[tile_cfg].small_tile : TILE_128x64;
-        if (small == TILE_128x32) return launch_conv_t<128, 32, 4, 1, false>(a, s);
-        if (small == TILE_128x128 && a.CoutP % 128 == 0) return launch_conv_t<128, 128, 2, 2, false>(a, s);
-        return launch_conv_t<128, 64, 2, 2, false>(a, s);
+    ConvPlan pl;
+    hipError_t e = plan_conv(a, tile_cfg, device_facts().n_cu, pl);
+    if (e != hipSuccess) return e;
+    if (!pl.wide) {
+        if (pl.tile == TILE_128x32) return launch_conv_t<128, 32, 4, 1, false>(a, pl, s);
+        if (pl.tile == TILE_128x128) return launch_conv_t<128, 128, 2, 2, false>(a, pl, s);
+        return launch_conv_t<128, 64, 2, 2, false>(a, pl, s);
     }
-    if (!known) tile_cfg = TILE_128x128;
-    if (a.out_mode != 0) tile_cfg = TILES[tile_cfg].f32_tile;      // (the transposed-conv scatter exists in the fp32 kernels only)
-    return launch_tile_by_id(tile_cfg, a, s, std::make_integer_sequence<int, N_TILES>{});
+    return launch_tile_by_id(pl.tile, a, pl, s, std::make_integer_sequence<int, N_TILES>{});
 }
 
 }  // namespace dgp

@@ -1404,18 +1404,35 @@ int dgp_conv2d(const dgp_conv_desc* d, const float* x, const float* packed_w, co
     return dgp_conv2d_ranged(d, x, packed_w, scale, bias, residual, y, nullptr, nullptr, nullptr, stream);
 }
 
-int dgp_conv2d_ranged(const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale, const float* bias,
-                      const float* residual, float* y, const float* x_absmax, const float* w_absmax, float* y_absmax,
-                      void* stream) {
+// The ConvArgs of dgp_conv2d_ranged, before the weight cells.  dgp_conv2d_plan calls it with placeholder pointers: nothing is read here
+static int conv2d_ranged_args(ConvArgs& a, const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale,
+                              const float* bias, const float* residual, float* y, const float* x_absmax, const float* w_absmax,
+                              float* y_absmax, float* tail_slab, size_t tail_slab_bytes) {
     if (!d || !x || !packed_w || !y) return fail(DGP_ERR_INVALID, "dgp_conv2d: null argument");
     if (d->Cin < 4 || (d->Cin & 3) || ((d->Cin / 4) & (d->Cin / 4 - 1)))
         return fail(DGP_ERR_INVALID, "dgp_conv2d: Cin must be 4 * 2^k");
     if (d->res_stride > 0 && !residual) return fail(DGP_ERR_INVALID, "dgp_conv2d: residual missing");
     if (d->Cout & 3) return fail(DGP_ERR_INVALID, "dgp_conv2d: Cout must be a multiple of 4");
-    ConvArgs a{};
+    if (tail_slab_bytes > 0xffffffffull) return fail(DGP_ERR_INVALID, "dgp_conv2d: tail slab exceeds 4 GiB");
     a.in = x; a.wpk = packed_w; a.scale = scale; a.bias = bias; a.res = d->res_stride > 0 ? residual : nullptr; a.out = y;
     if (int rc = fill_conv_geometry(a, *d, "dgp_conv2d: tensor exceeds 4 GiB")) return rc;
     a.in_absmax = x_absmax; a.w_absmax = w_absmax; a.out_absmax = y_absmax;
+    if (tail_slab && tail_slab_bytes) { a.slab = tail_slab; a.slab_bytes = (unsigned)tail_slab_bytes; }
+    return DGP_OK;
+}
+
+int dgp_conv2d_ranged(const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale, const float* bias,
+                      const float* residual, float* y, const float* x_absmax, const float* w_absmax, float* y_absmax,
+                      void* stream) {
+    return dgp_conv2d_ranged_slab(d, x, packed_w, scale, bias, residual, y, x_absmax, w_absmax, y_absmax, nullptr, 0, stream);
+}
+
+int dgp_conv2d_ranged_slab(const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale, const float* bias,
+                           const float* residual, float* y, const float* x_absmax, const float* w_absmax, float* y_absmax,
+                           float* tail_slab, size_t tail_slab_bytes, void* stream) {
+    ConvArgs a{};
+    if (int rc = conv2d_ranged_args(a, d, x, packed_w, scale, bias, residual, y, x_absmax, w_absmax, y_absmax, tail_slab, tail_slab_bytes))
+        return rc;
     // DGP_CONV2D_CELLS=1 (tests, tuning): split the panel into fp16 cells per call (grow-only scratch, stream-ordered) so that a single
     // layer runs on the engine's compute-side-split / LDS-DMA kernels; the network packs its cells once at load instead
     static const bool cells_env = (dgp_env("DGP_CONV2D_CELLS", 0) != 0);
@@ -1451,26 +1468,39 @@ int dgp_h1_to_f32(const void* x, size_t n_floats, int32_t scale_exp, float* out,
     return convert_cells("dgp_h1_to_f32", launch_h1_to_f32, x, n_floats, ldexpf(1.f, -scale_exp), out, stream);
 }
 
-static int conv2d_cells(int fmt, const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
-                        const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
-                        int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, void* stream) {
+// The ConvArgs of dgp_conv2d_h2 / dgp_conv2d_h1 (fmt 1 / 2).  dgp_conv2d_plan calls it with placeholder pointers: nothing is read here
+static int conv2d_cells_args(ConvArgs& a, int fmt, const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w,
+                             const float* w_absmax, const float* scale, const float* bias, const void* residual, int32_t res_is_h2,
+                             int32_t res_exp, void* y, int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch,
+                             float* tail_slab, size_t tail_slab_bytes) {
     if (!d || !x_h2 || !packed_w || !w_absmax || !y || !cells_scratch) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: null argument");
     if (d->Cin < 32 || (d->Cin & 7) || ((d->Cin / 4) & (d->Cin / 4 - 1)) || (d->Cout & 7))
         return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: Cin must be 4 * 2^k >= 32, Cout a multiple of 8");
     if (d->res_stride > 0 && !residual) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: residual missing");
     if (d->res_stride > 0 && res_is_h2 && !y_is_h2)
         return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: an H2 residual needs an H2 output (the fp32-output epilogue adds fp32 residuals only)");
-    ConvArgs a{};
+    if (tail_slab_bytes > 0xffffffffull) return fail(DGP_ERR_INVALID, "dgp_conv2d_h2: tail slab exceeds 4 GiB");
     a.in = (const float*)x_h2; a.wpk = packed_w; a.scale = scale; a.bias = bias; a.res = d->res_stride > 0 ? (const float*)residual : nullptr;
     a.out = (float*)y;
     if (int rc = fill_conv_geometry(a, *d, "dgp_conv2d_h2: tensor exceeds 4 GiB")) return rc;
     H2Spec h; h.in_fmt = fmt; h.in_exp = x_exp; h.out_fmt = y_is_h2 ? fmt : 0; h.out_exp = y_exp; h.res_fmt = (a.res && res_is_h2) ? fmt : 0; h.res_exp = res_exp;
     apply_h2(a, h);
     a.w_absmax = w_absmax; a.out_absmax = y_absmax;
+    a.wh3 = cells_scratch; a.wh3_bytes = a.w_bytes;
+    if (tail_slab && tail_slab_bytes) { a.slab = tail_slab; a.slab_bytes = (unsigned)tail_slab_bytes; }
+    return DGP_OK;
+}
+
+static int conv2d_cells(int fmt, const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
+                        const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
+                        int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, float* tail_slab, size_t tail_slab_bytes,
+                        void* stream) {
+    ConvArgs a{};
+    if (int rc = conv2d_cells_args(a, fmt, d, x_h2, x_exp, packed_w, w_absmax, scale, bias, residual, res_is_h2, res_exp, y, y_is_h2, y_exp,
+                                   y_absmax, cells_scratch, tail_slab, tail_slab_bytes)) return rc;
     hipError_t pe = fmt == 2 ? launch_pack_h1(packed_w, a.nk, a.CoutP, w_absmax, cells_scratch, (hipStream_t)stream)
                              : launch_pack_h3(packed_w, a.nk, a.CoutP, w_absmax, cells_scratch, (hipStream_t)stream);
     if (pe != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_h2: pack cells: ") + hipGetErrorString(pe));
-    a.wh3 = cells_scratch; a.wh3_bytes = a.w_bytes;
     hipError_t e = launch_conv(a, pick_tile(a.M, a.CoutP, a.nk * BK, true), (hipStream_t)stream);
     if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_conv2d_h2: ") + hipGetErrorString(e));
     return DGP_OK;
@@ -1480,7 +1510,15 @@ int dgp_conv2d_h2(const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const
                   const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
                   int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, void* stream) {
     return conv2d_cells(1, d, x_h2, x_exp, packed_w, w_absmax, scale, bias, residual, res_is_h2, res_exp, y, y_is_h2, y_exp, y_absmax,
-                        cells_scratch, stream);
+                        cells_scratch, nullptr, 0, stream);
+}
+
+int dgp_conv2d_h2_slab(const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
+                       const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
+                       int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, float* tail_slab, size_t tail_slab_bytes,
+                       void* stream) {
+    return conv2d_cells(1, d, x_h2, x_exp, packed_w, w_absmax, scale, bias, residual, res_is_h2, res_exp, y, y_is_h2, y_exp, y_absmax,
+                        cells_scratch, tail_slab, tail_slab_bytes, stream);
 }
 
 int dgp_conv2d_h1(const dgp_conv_desc* d, const void* x_h1, int32_t x_exp, const float* packed_w, const float* w_absmax,
@@ -1488,7 +1526,43 @@ int dgp_conv2d_h1(const dgp_conv_desc* d, const void* x_h1, int32_t x_exp, const
                   int32_t y_is_h1, int32_t y_exp, float* y_absmax, void* cells_scratch, void* stream) {
     if (d && (d->Cin & 63)) return fail(DGP_ERR_INVALID, "dgp_conv2d_h1: Cin must be a multiple of 64 (a K-step is 64 channels)");
     return conv2d_cells(2, d, x_h1, x_exp, packed_w, w_absmax, scale, bias, residual_h1, 1, res_exp, y, y_is_h1, y_exp, y_absmax,
-                        cells_scratch, stream);
+                        cells_scratch, nullptr, 0, stream);
+}
+
+// The plan of the launch dgp_conv2d_ranged (in_fmt 0) / dgp_conv2d_h2 (1) / dgp_conv2d_h1 (2) would make: the same ConvArgs (with
+// placeholders where those take device pointers: plan_conv reads none), the same tile choice, plan_conv.  No HIP call when n_cu > 0
+int dgp_conv2d_plan(const dgp_conv_desc* d, int32_t in_fmt, int32_t out_fmt, int32_t res_fmt, int32_t have_ranges, int32_t have_cells,
+                    size_t slab_bytes, int32_t force_tile, int32_t n_cu, dgp_conv_plan* out) {
+    if (!d || !out) return fail(DGP_ERR_INVALID, "dgp_conv2d_plan: null argument");
+    if (in_fmt < 0 || in_fmt > 2 || (in_fmt == 0 && (out_fmt || res_fmt)) || (out_fmt && out_fmt != in_fmt) || (res_fmt && res_fmt != in_fmt) || n_cu < 0)
+        return fail(DGP_ERR_INVALID, "dgp_conv2d_plan: formats are 0 (fp32), 1 (H2) or 2 (H1), cells of one kind per launch; n_cu >= 0");
+    static float placeholder[4];
+    float* const ph = placeholder;
+    ConvArgs a{};
+    bool ranged = true;
+    if (in_fmt == 0) {
+        ranged = have_ranges != 0;
+        if (int rc = conv2d_ranged_args(a, d, ph, ph, ph, ph, ph, ph, ranged ? ph : nullptr, ranged ? ph : nullptr, ph, ph, slab_bytes)) return rc;
+        if (have_cells && ranged && d->Cin >= 32) { a.wh3 = ph; a.wh3_bytes = a.w_bytes; }
+    } else {
+        if (in_fmt == 2 && (d->Cin & 63)) return fail(DGP_ERR_INVALID, "dgp_conv2d_h1: Cin must be a multiple of 64 (a K-step is 64 channels)");
+        if (int rc = conv2d_cells_args(a, in_fmt, d, ph, 0, ph, ph, ph, ph, ph, res_fmt != 0, 0, ph, out_fmt != 0, 0, ph, ph, ph, slab_bytes)) return rc;
+    }
+    const int tile = force_tile >= 0 ? force_tile : pick_tile(a.M, a.CoutP, a.nk * BK, ranged);
+    const char* name = conv_kernel_name(a, tile);
+    ConvPlan pl;
+    const int cus = n_cu > 0 ? n_cu : device_facts().n_cu;
+    hipError_t e = plan_conv(a, tile, cus, pl);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string(in_fmt ? "dgp_conv2d_h2: " : "dgp_conv2d: ") + hipGetErrorString(e));
+    *out = dgp_conv_plan{};
+    out->tile = pl.tile; out->family = (int32_t)pl.family;
+    out->mode = pl.path.mode; out->cs = pl.path.cs; out->dma = pl.path.dma; out->deep = pl.path.deep;
+    out->ah2 = pl.path.ah2; out->oh2 = pl.path.oh2; out->h1 = pl.path.h1; out->lds = (int32_t)pl.path.lds;
+    out->mtiles = pl.mtiles; out->ntiles = pl.ntiles; out->grid = (int32_t)pl.grid;
+    out->tail_ksplit = pl.tail_ksplit; out->n_main = pl.n_main; out->st_gn = pl.st_gn; out->st_mc = pl.st_mc; out->st_mb = pl.st_mb;
+    out->n_cu = cus;
+    snprintf(out->kernel_name, sizeof(out->kernel_name), "%s", name);
+    return DGP_OK;
 }
 
 // The chain / unit kernels at layer level (tests): weights and BN affines are HOST arrays, packed per call.  w2 != null: the unit kernel

@@ -514,8 +514,12 @@ ABSMAX_SLOTS = 256      # DGP_ABSMAX_SLOTS in include/dgp_hip.h
 
 def conv2d(x: torch.Tensor, w_hwio: np.ndarray, stride: int = 1, rate: int = 1, pad_t: int = 0, pad_l: int = 0,
            out_hw: Optional[Tuple[int, int]] = None, scale=None, bias=None, residual: Optional[torch.Tensor] = None,
-           res_stride: int = 0, relu: bool = False, ranged: bool = False, return_range: bool = False):
+           res_stride: int = 0, relu: bool = False, ranged: bool = False, return_range: bool = False,
+           tail_slab: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """Single conv layer through the implicit-GEMM kernel (NHWC fp32).
+
+    tail_slab: a float32 device tensor the launch may use for the K-split of its grid's tail (dgp_conv2d_ranged_slab; see
+    conv2d_plan for whether it does); out: the caller's output tensor [N,Ho,Wo,Cout] (float32, contiguous) instead of a new one.
 
     ranged=True measures max |x| and max |w| on the device first (dgp_tensor_absmax) and passes them on, which lets
     the fp16 high/low split kernels run (dgp_conv2d_ranged); return_range=True also returns max |y| as tracked by the
@@ -533,11 +537,13 @@ def conv2d(x: torch.Tensor, w_hwio: np.ndarray, stride: int = 1, rate: int = 1, 
     wp = torch.from_numpy(pack_conv_weights(w_hwio)).to(dev)
     sc = None if scale is None else torch.as_tensor(scale, dtype=torch.float32).contiguous().to(dev)
     bi = None if bias is None else torch.as_tensor(bias, dtype=torch.float32).contiguous().to(dev)
-    y = torch.empty((N, Ho, Wo, cout), dtype=torch.float32, device=dev)
+    y = _conv_out(out, (N, Ho, Wo, cout), dev)
     rh, rw = (residual.shape[1], residual.shape[2]) if residual is not None else (0, 0)
     d = _lib.DgpConvDesc(N, H, W, Cin, cout, kh, kw, stride, rate, pad_t, pad_l, Ho, Wo, int(relu),
                          res_stride if residual is not None else 0, rh, rw)
-    if not (ranged or return_range):
+    if tail_slab is not None:
+        _need_cuda(tail_slab, torch.float32, "tail_slab")
+    if not (ranged or return_range or tail_slab is not None):
         _lib.check(lib.dgp_conv2d(C.byref(d), _ptr(x), _ptr(wp), _ptr(sc), _ptr(bi), _ptr(residual), _ptr(y),
                                   _stream(dev)), "dgp_conv2d")
         return y
@@ -545,10 +551,45 @@ def conv2d(x: torch.Tensor, w_hwio: np.ndarray, stride: int = 1, rate: int = 1, 
     if ranged:
         _lib.check(lib.dgp_tensor_absmax(_ptr(x), x.numel(), _ptr(rng[0]), _stream(dev)), "dgp_tensor_absmax")
         _lib.check(lib.dgp_tensor_absmax(_ptr(wp), wp.numel(), _ptr(rng[1]), _stream(dev)), "dgp_tensor_absmax")
+    if tail_slab is not None:
+        _lib.check(lib.dgp_conv2d_ranged_slab(C.byref(d), _ptr(x), _ptr(wp), _ptr(sc), _ptr(bi), _ptr(residual), _ptr(y),
+                                              _ptr(rng[0]) if ranged else None, _ptr(rng[1]) if ranged else None, _ptr(rng[2]),
+                                              _ptr(tail_slab), tail_slab.numel() * 4, _stream(dev)), "dgp_conv2d_ranged_slab")
+        return (y, rng[2]) if return_range else y
     _lib.check(lib.dgp_conv2d_ranged(C.byref(d), _ptr(x), _ptr(wp), _ptr(sc), _ptr(bi), _ptr(residual), _ptr(y),
                                      _ptr(rng[0]) if ranged else None, _ptr(rng[1]) if ranged else None, _ptr(rng[2]),
                                      _stream(dev)), "dgp_conv2d_ranged")
     return (y, rng[2]) if return_range else y
+
+
+def _conv_out(out, shape, dev):
+    """the output tensor of a layer call: the caller's (checked) or a new one"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    _need_cuda(out, torch.float32, "out")
+    if tuple(out.shape) != tuple(shape) or out.device != dev:
+        raise _lib.DgpError("out must be a float32 tensor of shape %s on %s" % (tuple(shape), dev))
+    return out
+
+
+def conv2d_plan(x_shape, w_shape, stride: int = 1, rate: int = 1, pad_t: int = 0, pad_l: int = 0, out_hw=None, res_stride: int = 0,
+                res_hw=(0, 0), in_fmt: int = 0, out_fmt: int = 0, res_fmt: int = 0, ranged: bool = True, cells: bool = False,
+                slab_bytes: int = 0, tile: int = -1, n_cu: int = 0) -> dict:
+    """What the launch layer would run for this layer (dgp_conv2d_plan): tile, kernel family and path, grid, tail K-split, supertile
+    order.  Formats: 0 fp32, 1 H2, 2 H1.  n_cu > 0 plans for that many compute units and needs no GPU; 0 asks the current device."""
+    lib = _lib.load()
+    N, H, W, Cin = x_shape
+    kh, kw, _, cout = w_shape
+    if out_hw is None:
+        keh, kew = (kh - 1) * rate + 1, (kw - 1) * rate + 1
+        out_hw = ((H + 2 * pad_t - keh) // stride + 1, (W + 2 * pad_l - kew) // stride + 1)
+    d = _lib.DgpConvDesc(N, H, W, Cin, cout, kh, kw, stride, rate, pad_t, pad_l, out_hw[0], out_hw[1], 0, res_stride, res_hw[0], res_hw[1])
+    pl = _lib.DgpConvPlan()
+    _lib.check(lib.dgp_conv2d_plan(C.byref(d), in_fmt, out_fmt, res_fmt, int(ranged), int(cells), int(slab_bytes), int(tile), int(n_cu),
+                                   C.byref(pl)), "dgp_conv2d_plan")
+    res = {n: int(getattr(pl, n)) for n, _ in _lib.DgpConvPlan._fields_ if n != "kernel_name"}
+    res["kernel_name"] = pl.kernel_name.decode()
+    return res
 
 
 def _conv_desc(x_shape, w_shape, stride, rate, pad_t, pad_l, out_hw):
@@ -791,8 +832,8 @@ def h2_to_f32(x: torch.Tensor, scale_exp: int) -> torch.Tensor:
 def conv2d_h2(x_h2: torch.Tensor, x_exp: int, w_hwio: np.ndarray, stride: int = 1, rate: int = 1, pad_t: int = 0, pad_l: int = 0,
               out_hw: Optional[Tuple[int, int]] = None, scale=None, bias=None, residual: Optional[torch.Tensor] = None,
               res_stride: int = 0, res_is_h2: bool = False, res_exp: int = 0, relu: bool = False, y_is_h2: bool = True,
-              y_exp: int = 0):
-    """One conv layer on H2 tensors through the engine's cell kernels.  -> (y, y_absmax_slots)."""
+              y_exp: int = 0, tail_slab: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """One conv layer on H2 tensors through the engine's cell kernels.  -> (y, y_absmax_slots).  tail_slab, out: as in conv2d."""
     lib = _lib.load()
     _need_cuda(x_h2, torch.float32, "x_h2")
     N, H, W, Cin = x_h2.shape
@@ -806,13 +847,19 @@ def conv2d_h2(x_h2: torch.Tensor, x_exp: int, w_hwio: np.ndarray, stride: int = 
     wp = torch.from_numpy(pack_conv_weights(w_hwio)).to(dev)
     sc = None if scale is None else torch.as_tensor(scale, dtype=torch.float32).contiguous().to(dev)
     bi = None if bias is None else torch.as_tensor(bias, dtype=torch.float32).contiguous().to(dev)
-    y = torch.empty((N, Ho, Wo, cout), dtype=torch.float32, device=dev)
+    y = _conv_out(out, (N, Ho, Wo, cout), dev)
     rh, rw = (residual.shape[1], residual.shape[2]) if residual is not None else (0, 0)
     d = _lib.DgpConvDesc(N, H, W, Cin, cout, kh, kw, stride, rate, pad_t, pad_l, Ho, Wo, int(relu),
                          res_stride if residual is not None else 0, rh, rw)
     rng = torch.zeros((2, ABSMAX_SLOTS), dtype=torch.float32, device=dev)
     _lib.check(lib.dgp_tensor_absmax(_ptr(wp), wp.numel(), _ptr(rng[0]), _stream(dev)), "dgp_tensor_absmax")
     cells = torch.empty(wp.numel(), dtype=torch.float32, device=dev)
+    if tail_slab is not None:
+        _need_cuda(tail_slab, torch.float32, "tail_slab")
+        _lib.check(lib.dgp_conv2d_h2_slab(C.byref(d), _ptr(x_h2), int(x_exp), _ptr(wp), _ptr(rng[0]), _ptr(sc), _ptr(bi), _ptr(residual),
+                                          int(res_is_h2), int(res_exp), _ptr(y), int(y_is_h2), int(y_exp), _ptr(rng[1]), _ptr(cells),
+                                          _ptr(tail_slab), tail_slab.numel() * 4, _stream(dev)), "dgp_conv2d_h2_slab")
+        return y, rng[1]
     _lib.check(lib.dgp_conv2d_h2(C.byref(d), _ptr(x_h2), int(x_exp), _ptr(wp), _ptr(rng[0]), _ptr(sc), _ptr(bi), _ptr(residual),
                                  int(res_is_h2), int(res_exp), _ptr(y), int(y_is_h2), int(y_exp), _ptr(rng[1]), _ptr(cells),
                                  _stream(dev)), "dgp_conv2d_h2")

@@ -330,6 +330,33 @@ int  dgp_conv2d(const dgp_conv_desc* d, const float* x, const float* packed_w,
 int  dgp_conv2d_ranged(const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale, const float* bias,
                        const float* residual, float* y, const float* x_absmax, const float* w_absmax, float* y_absmax,
                        void* stream);
+/* Same, with room for the grid-tail K-split (the launch layer of csrc/dgp_kernels.hip: the tiles of an underfull last round split
+ * their K range over up to 4 workgroups, raw partial sums go to the slab, a fix-up launch sums them in fixed order).  tail_slab: the
+ * caller's device memory, tail_slab_bytes < 4 GiB (DGP_ERR_INVALID otherwise); nothing is allocated.  NULL / 0: dgp_conv2d_ranged. */
+int  dgp_conv2d_ranged_slab(const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale, const float* bias,
+                            const float* residual, float* y, const float* x_absmax, const float* w_absmax, float* y_absmax,
+                            float* tail_slab, size_t tail_slab_bytes, void* stream);
+/* What the launch layer would run for a layer: the host-side plan of dgp_conv2d_ranged (in_fmt 0), dgp_conv2d_h2 (in_fmt 1) or
+ * dgp_conv2d_h1 (in_fmt 2), without launching anything.  Formats: 0 fp32, 1 H2, 2 H1.  have_ranges: x_absmax and w_absmax are given
+ * (cell inputs always have them); have_cells: the weight panel also exists as fp16 cells (always with cell inputs; DGP_CONV2D_CELLS=1
+ * for dgp_conv2d_ranged); slab_bytes: the tail slab's size (0: none).  force_tile: a tile id, -1: the launch's own choice.  n_cu: the
+ * number of compute units to plan for, 0: the current device's; with n_cu > 0 no GPU is needed.  A launch the kernels refuse returns
+ * the error the launch would return. */
+typedef struct dgp_conv_plan {
+    int32_t tile;                    /* tile id after the launch's fall-backs */
+    int32_t family;                  /* 0 fp32 MFMA, 1 fp32 loader-specialised, 2 split (bf16 / fp16) */
+    int32_t mode, cs, dma, deep;     /* split family: loader walk (0 run time, 1 per tap, 2 pointwise, 3 halo ring), compute-side split,
+                                        LDS-DMA loaders, deep DMA ring */
+    int32_t ah2, oh2, h1;            /* input in cells, output in cells, the cells are H1 */
+    int32_t lds;                     /* dynamic LDS bytes */
+    int32_t mtiles, ntiles, grid;    /* row tiles, column tiles, workgroups of the main launch */
+    int32_t tail_ksplit, n_main;     /* K-split of the grid's tail (0: none): workgroups per tail tile, tiles in front of the tail */
+    int32_t st_gn, st_mc, st_mb;     /* supertile order (st_gn 0: plain): column tiles per group, row tiles per chunk and per band */
+    int32_t n_cu;                    /* compute units planned for */
+    char    kernel_name[32];
+} dgp_conv_plan;
+int  dgp_conv2d_plan(const dgp_conv_desc* d, int32_t in_fmt, int32_t out_fmt, int32_t res_fmt, int32_t have_ranges, int32_t have_cells,
+                     size_t slab_bytes, int32_t force_tile, int32_t n_cu, dgp_conv_plan* out);
 /* ---- single-layer BACKWARD entry points: the launchers dgp_train_backward uses, exposed so that the weight-gradient and
  * data-gradient kernels can be checked layer by layer at the real shapes (no reference counterpart: TF differentiates the graph,
  * DGP/models/fitdgp.py:708-713).  `d` always describes the FORWARD conv x [N,H,W,Cin] -> y [N,Ho,Wo,Cout].
@@ -415,6 +442,11 @@ int  dgp_h2_to_f32(const void* x, size_t n_floats, int32_t scale_exp, float* out
 int  dgp_conv2d_h2(const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
                    const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
                    int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, void* stream);
+/* dgp_conv2d_h2 with room for the grid-tail K-split (see dgp_conv2d_ranged_slab; cell inputs split only under DGP_TAIL_SPLIT=2) */
+int  dgp_conv2d_h2_slab(const dgp_conv_desc* d, const void* x_h2, int32_t x_exp, const float* packed_w, const float* w_absmax,
+                        const float* scale, const float* bias, const void* residual, int32_t res_is_h2, int32_t res_exp, void* y,
+                        int32_t y_is_h2, int32_t y_exp, float* y_absmax, void* cells_scratch, float* tail_slab, size_t tail_slab_bytes,
+                        void* stream);
 /* ---- "H1" activation format: the 16-bit tier.  dgp_net_set_tier(net, 1) makes dgp_forward / dgp_infer keep every tensor from the pool
  * output to the block4 features as ONE 16-byte cell of 8 halves per pixel and 8 channels -- fp16(x * 2^exp), bit for bit the high cell
  * of the H2 pair: plain NHWC fp16 with the same calibrated per-tensor scales -- and multiply them with fp16 weights on one MFMA per

@@ -1,0 +1,51 @@
+#!/usr/bin/env python
+"""Compare the device code of two builds of one HIP source, kernel by kernel.
+
+    hipcc -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S csrc/dgp_kernels.hip -o new.s      (same at the parent: old.s)
+    python scripts/device_asm_diff.py old.s new.s
+
+Splits each assembly file into its functions, keeps the instruction text (no directives, no comments) and drops the function-index part
+of local labels (.LBB<fn>_<n>, which moves when host-only edits reorder the instantiations).  Prints the functions only one side has
+and the ones whose instructions differ; exit status 1 if there are any.  Metadata (amdhsa.kernels: the order of the entries) is not
+compared."""
+import re
+import sys
+
+LABEL = re.compile(r"\.L(BB|tmp|func_begin|func_end)\d+(_\d+)?")
+
+
+def functions(path):
+    out, name, body = {}, None, []
+    for line in open(path):
+        m = re.match(r"^([A-Za-z_][\w.$]*):\s*(;.*)?$", line)
+        if m and not m.group(1).startswith(".L"):
+            if name:
+                out[name] = body
+            name, body = m.group(1), []
+            continue
+        if name is None:
+            continue
+        t = line.split(";")[0].strip()
+        if t.startswith(".Lfunc_end"):
+            out[name], name = body, None
+        elif t and not t.startswith("."):
+            body.append(LABEL.sub(lambda q: ".L" + q.group(1) + (q.group(2) or ""), t))
+    if name:
+        out[name] = body
+    return {k: v for k, v in out.items() if v and not k.startswith(("__hip_cuid", "amdhsa."))}
+
+
+def main(a_path, b_path):
+    a, b = functions(a_path), functions(b_path)
+    only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+    differ = sorted(k for k in a if k in b and a[k] != b[k])
+    print("%d / %d functions, %d / %d instructions" % (len(a), len(b), sum(map(len, a.values())), sum(map(len, b.values()))))
+    for what, names in (("only in " + a_path, only_a), ("only in " + b_path, only_b), ("instructions differ", differ)):
+        print("%s: %d" % (what, len(names)))
+        for n in names:
+            print("   ", n)
+    return 1 if only_a or only_b or differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1], sys.argv[2]))

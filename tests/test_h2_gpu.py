@@ -45,7 +45,7 @@ H2_CONV_CASES = [
     (2, 20, 24, 256, 512, 1, 2, 1, 0, True),       # strided shortcut conv
     (2, 10, 12, 512, 1024, 1, 1, 1, 3, True),      # conv3 of a strided unit: residual subsampled from the 2x finer grid
     (1, 30, 40, 2048, 128, 1, 1, 1, 0, False),     # the head's pointwise GEMM: H2 in, fp32 out
-    (32, 30, 40, 1024, 256, 1, 1, 1, 0, True),     # batch-32 block3 conv1: 600 tiles -> grid-tail K-split + tail_fixup_h2
+    (32, 30, 40, 1024, 256, 1, 1, 1, 0, True),     # batch-32 block3 conv1: 600 tiles in the pairing order of two column tiles (no tail slab here: tests/test_conv_plan_gpu.py splits it)
     (32, 30, 40, 512, 512, 3, 1, 2, 2, True),      # batch-32 block4 conv2 (+ an H2 residual): the deepest K loop at its real size
     (11, 30, 40, 2048, 512, 1, 1, 1, 0, True),     # block4 conv1 at 11 frames: 416 tiles, K = 2048
     # round 4, the halo walk (MODE 3 of the dominant kernel: 3x3 / stride 1 on a pixel ring in LDS, taps masked by the compute waves)
@@ -236,18 +236,6 @@ def test_reported_16_bit_tier_is_an_11_bit_version_of_the_same_network(lib_built
         gap = abs(float(a[b, ia[b, j, 0], ia[b, j, 1], j]) - float(a[b, it[b, j, 0], it[b, j, 1], j]))
         assert gap <= 2.0 * noise, (int(b), int(j), gap, noise)
     assert np.abs(mu_a.cpu().numpy() - t["mu"]).max() * 8.0 < 0.25
-
-
-def test_tail_split_fixup_on_h2_tensors_in_a_child_process(lib_built):
-    """The K-split of the grid tail is off by default for H2 launches (measured slower); DGP_TAIL_SPLIT=2 forces it.  The batch-32
-    block3 shape (600 tiles: 88 tail tiles split 4 ways + tail_fixup_h2_kernel) then has to give the same parity."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DGP_TAIL_SPLIT="2", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_h2_gpu.py"), "-q", "-m", "gpu", "-k",
-                        "test_conv_on_h2_tensors_matches_float64 and (case9 or case5)"], env=env, cwd=root, capture_output=True,
-                       text=True, timeout=900)
-    assert r.returncode == 0 and "2 passed" in r.stdout, r.stdout[-1500:] + r.stderr[-500:]
 
 
 def test_halo_walk_on_strips_longer_than_the_ring_in_a_child_process(lib_built):
