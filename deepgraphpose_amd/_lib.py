@@ -140,6 +140,10 @@ SYMBOLS = {
     "dgp_conv2d_dgrad_h1": (C.c_int, [C.POINTER(DgpConvDesc), _vp, _vp, _vp, _vp, _vp, _i32] + [_vp] * 7),
     "dgp_stem_wgrad_h1": (C.c_int, [_vp] * 4 + [_i32] * 7 + [_vp] * 4),
     "dgp_heads_backward_h1": (C.c_int, [_vp] * 8 + [_i32] * 5 + [_vp] * 8),
+    "dgp_maxpool_fwd_idx": (C.c_int, [_vp] + [_i32] * 5 + [_vp] * 5),
+    "dgp_maxpool_bwd_idx": (C.c_int, [_vp] * 3 + [_i32] * 5 + [_vp] * 2),
+    "dgp_root_block_scratch_bytes": (_sz, []),
+    "dgp_root_block": (C.c_int, [_vp] + [_i32] * 3 + [_vp] * 3 + [C.POINTER(_f32)] + [_i32] * 2 + [_vp] * 6),
     "dgp_motion_energy":(C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "dgp_maxpool_3x3s2_same": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dgp_preprocess_u8": (C.c_int, [_vp, C.c_int64, C.POINTER(_f32), _vp, _vp]),

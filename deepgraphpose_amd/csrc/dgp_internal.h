@@ -297,6 +297,12 @@ inline hipError_t ensure_dynamic_lds(size_t bytes) {
     return hipSuccess;
 }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// Leading padding of the 3x3 / stride-2 SAME max-pool over n_in positions with n_out = ceil(n_in / 2) windows (TF: the smaller half of
+// the total first): window q starts at 2 q - pool_pad_before
+inline int pool_pad_before(int n_in, int n_out) {
+    const int total = (n_out - 1) * 2 + 3 - n_in;
+    return total > 0 ? total / 2 : 0;
+}
 inline int ilog2(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 
 }  // namespace dgp

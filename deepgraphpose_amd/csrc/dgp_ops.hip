@@ -308,13 +308,11 @@ hipError_t launch_h2_range_check(const float* amax_slots, const int* exps, int n
 
 hipError_t launch_maxpool(const float* x, int N, int H, int W, int C, float* y, hipStream_t s, float h2_scale) {
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    const int pth = ((Ho - 1) * 2 + 3 - H) > 0 ? ((Ho - 1) * 2 + 3 - H) : 0;
-    const int ptw = ((Wo - 1) * 2 + 3 - W) > 0 ? ((Wo - 1) * 2 + 3 - W) : 0;
     const long long total = (long long)N * Ho * Wo * (C / 4);
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(maxpool3x3s2_same, dim3((unsigned)blocks), dim3(256), 0, s, x, N, H, W, C / 4, Ho, Wo,
-                       pth / 2, ptw / 2, y, h2_scale);
+                       pool_pad_before(H, Ho), pool_pad_before(W, Wo), y, h2_scale);
     return hipGetLastError();
 }
 
@@ -730,9 +728,7 @@ hipError_t launch_stem_pool_fused(const unsigned char* frames, int B, int H, int
     a.mean0 = roundf(m0); a.mean1 = roundf(m1); a.mean2 = roundf(m2); a.out_scale = out_scale; a.out = out; a.out_absmax = out_absmax;
     a.B = B; a.H = H; a.W = W; a.H1 = (H + 1) / 2; a.W1 = (W + 1) / 2;
     a.HP = (a.H1 + 1) / 2; a.WP = (a.W1 + 1) / 2;
-    const int pth = ((a.HP - 1) * 2 + 3 - a.H1) > 0 ? ((a.HP - 1) * 2 + 3 - a.H1) : 0;
-    const int ptw = ((a.WP - 1) * 2 + 3 - a.W1) > 0 ? ((a.WP - 1) * 2 + 3 - a.W1) : 0;
-    a.pbh = pth / 2; a.pbw = ptw / 2;
+    a.pbh = pool_pad_before(a.H1, a.HP); a.pbw = pool_pad_before(a.W1, a.WP);
     // the two-workgroup variant: the 16-bit tier's inference pass (the trainer's pool records the first maximum of the fp32 values)
     static const int h1t_env = dgp_tune("DGP_STEM_H1T", 1);
     static const int h1t_train_env = dgp_tune("DGP_STEM_H1T_TRAIN", 1);

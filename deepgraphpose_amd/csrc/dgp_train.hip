@@ -2353,6 +2353,34 @@ static int trainer_owner_sync(void* owner, void* stream) {
     return refresh_parity_panels(tr, (hipStream_t)stream);
 }
 
+// The fused root block's weight cells (stem_pool_fused_kernel) from conv1's forward panel [49 taps][CoutP][4]: the row panel
+// [7 kernel rows x 8 pixels][CoutP][4] whose fourth channel slot carries the fraction of the mean pixel, then its fp16 high / low cells
+// split with the PANEL's range slots.  rows / cells: 56 * CoutP * 4 floats each.  (The weight sync and dgp_root_block.)
+static hipError_t build_stem_cells(const float* panel, int CoutP, const float* mean_pixel, const float* panel_rng, float* rows, void* cells,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(stem_rows_kernel, dim3((56 * CoutP + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float4*>(panel), CoutP,
+                       roundf(mean_pixel[0]) - mean_pixel[0], roundf(mean_pixel[1]) - mean_pixel[1], roundf(mean_pixel[2]) - mean_pixel[2],
+                       reinterpret_cast<float4*>(rows));
+    return launch_pack_h3(rows, 7, CoutP, panel_rng, cells, s);
+}
+
+// The root block's unfused pool of the training step and its backward, as forward_root / backward_root launch them (and the layer-level
+// entry points dgp_maxpool_fwd_idx / dgp_maxpool_bwd_idx).  c1 [nB, h1, w1, 64] -> pool [nB, hp, wp, 64] + the first-maximum record;
+// y_h1 / y_prev: the optional H1 copy and the range slots that predict its scale.
+static void launch_maxpool_fwd_idx(const float* c1, int nB, int h1, int w1, int hp, int wp, float* pool, uchar4* idx, uint2* y_h1,
+                                   const float* y_prev, hipStream_t s) {
+    const long long totp = (long long)nB * hp * wp * 16;
+    hipLaunchKernelGGL(maxpool_fwd_idx_kernel, dim3(grid_for(totp)), dim3(256), 0, s, c1, nB, h1, w1, 16, hp, wp, pool_pad_before(h1, hp),
+                       pool_pad_before(w1, wp), pool, idx, y_h1, y_prev);
+}
+// c1 == nullptr: no ReLU gate (the 16-bit tier's fused root block keeps no conv1 map)
+static void launch_maxpool_bwd_idx(const float* c1, const float* dpool, const uchar4* idx, int B, int h1, int w1, int hp, int wp, float* dc1,
+                                   hipStream_t s) {
+    const long long tot = (long long)B * h1 * w1 * 16;
+    hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_for(tot)), dim3(256), 0, s, c1, dpool, idx, B, h1, w1, 64, hp, wp,
+                       pool_pad_before(h1, hp), pool_pad_before(w1, wp), dc1);
+}
+
 extern "C" {
 
 // master parameters -> forward panels / folded BN / data-gradient panels of the engine
@@ -2488,11 +2516,8 @@ int dgp_trainer_sync_weights(dgp_trainer* tr, void* stream) {
                 const size_t nrow = (size_t)56 * lc.CoutP * 4;
                 if (!tr->d_stem_rows) TRY_HIP(hipMalloc(&tr->d_stem_rows, nrow * sizeof(float)));
                 if (!tr->d_stem_cells) TRY_HIP(hipMalloc(&tr->d_stem_cells, nrow * sizeof(float)));
-                const float* mp = net->desc.mean_pixel;
-                hipLaunchKernelGGL(stem_rows_kernel, dim3((56 * lc.CoutP + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float4*>(lc.d_w),
-                                   lc.CoutP, roundf(mp[0]) - mp[0], roundf(mp[1]) - mp[1], roundf(mp[2]) - mp[2],
-                                   reinterpret_cast<float4*>(tr->d_stem_rows));
-                TRY_HIP(launch_pack_h3(tr->d_stem_rows, 7, lc.CoutP, tr->d_wrng + (size_t)net->conv1 * ABSMAX_SLOTS, tr->d_stem_cells, s));
+                TRY_HIP(build_stem_cells(lc.d_w, lc.CoutP, net->desc.mean_pixel, tr->d_wrng + (size_t)net->conv1 * ABSMAX_SLOTS, tr->d_stem_rows,
+                                         tr->d_stem_cells, s));
             }
         }
     }
@@ -2554,9 +2579,6 @@ static int forward_root(TrainPass& p, const Chain& c, const uint8_t* frames) {
     }
     TRY_HIP(conv_launch(p, conv_call(c1, at(pl.p0, px_in * 4), nB, d.in_h, d.in_w, at(pl.c1, px1 * 64)).grid(net->h1, net->w1, 3, 3).strided(2)
                                .keys(p.F(pl.p0), p.F(pl.c1)), cs));
-    int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
-    int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
-    const long long totp = (long long)nB * net->hp * net->wp * 16;
     uint2* yh1 = nullptr;
     const float* yprev = nullptr;
     if (p.h1p() && p.ub == 0) {        // H1 copy of the pool output for the first unit (scale: conv1's range one step ago)
@@ -2566,9 +2588,8 @@ static int forward_root(TrainPass& p, const Chain& c, const uint8_t* frames) {
         ctx.shadow_base[p.F(pl.pool)] = p.F(pl.sh_pool);
         ctx.shadow_prev[p.F(pl.pool)] = yprev;
     }
-    hipLaunchKernelGGL(maxpool_fwd_idx_kernel, dim3(grid_for(totp)), dim3(256), 0, cs, at(pl.c1, px1 * 64), nB, net->h1, net->w1, 16,
-                       net->hp, net->wp, pth / 2, ptw / 2, at(pl.pool, pxp * 64),
-                       reinterpret_cast<uchar4*>(p.ws + pl.pidx) + (size_t)n0 * pxp * 16, yh1, yprev);
+    launch_maxpool_fwd_idx(at(pl.c1, px1 * 64), nB, net->h1, net->w1, net->hp, net->wp, at(pl.pool, pxp * 64),
+                           reinterpret_cast<uchar4*>(p.ws + pl.pidx) + (size_t)n0 * pxp * 16, yh1, yprev, cs);
     rng.set(p.F(pl.pool), rng.of(p.F(pl.c1)));      // max-pooling cannot raise the maximum
     return DGP_OK;
 }
@@ -3190,24 +3211,21 @@ static int backward_root(TrainPass& p, bool fin_split) {
     dgp_trainer* tr = p.tr; const dgp_net* net = p.net; const TPlan& pl = p.pl; const dgp_net_desc& d = net->desc;
     const int B = p.B;
     hipStream_t s = p.s;
-    int pth = (net->hp - 1) * 2 + 3 - net->h1; if (pth < 0) pth = 0;
-    int ptw = (net->wp - 1) * 2 + 3 - net->w1; if (ptw < 0) ptw = 0;
     if (p.stem_g) {
         if (fin_split) finalise(p, 0, tr->groups.back().fin_count, p.ctx.s2);      // (what the gradient groups have not finalised yet)
         StemWgradArgs sa{};
         sa.x = p.F(pl.p0); sa.g = reinterpret_cast<const uint4*>(p.stem_g); sa.idx = reinterpret_cast<const unsigned char*>(p.ws + pl.pidx);
         sa.g_prev = p.stem_g_prev;
         sa.dw = reinterpret_cast<float*>(p.ws + pl.dw_l[net->conv1]); sa.colsum = reinterpret_cast<float*>(p.ws + pl.cs_l[net->conv1]);
-        sa.B = B; sa.H = d.in_h; sa.W = d.in_w; sa.H1 = net->h1; sa.W1 = net->w1; sa.HP = net->hp; sa.WP = net->wp; sa.pt = pth / 2; sa.pl = ptw / 2;
-        sa.slab = p.F(pl.dc1);                // (the d conv1 map's region: unused on this path; grid x 50 KB)
+        sa.B = B; sa.H = d.in_h; sa.W = d.in_w; sa.H1 = net->h1; sa.W1 = net->w1; sa.HP = net->hp; sa.WP = net->wp;
+        sa.pt = pool_pad_before(net->h1, net->hp); sa.pl = pool_pad_before(net->w1, net->wp);
+        sa.slab = p.F(pl.dc1);               // (the d conv1 map's region: unused on this path; grid x 50 KB)
         stem_wgrad_launch(sa, s);
         return DGP_OK;
     }
     // (fused root block in the forward pass: no conv1 map -- unit 0's data gradient is already gated by pool > 0)
-    const long long tot = (long long)B * net->h1 * net->w1 * 16;
-    hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(grid_for(tot)), dim3(256), 0, s, (p.h1p() && tr->fwd_stem_fused) ? (const float*)nullptr : p.F(pl.c1), p.G[p.cur],
-                       reinterpret_cast<const uchar4*>(p.ws + pl.pidx), B, net->h1, net->w1, 64, net->hp, net->wp, pth / 2, ptw / 2,
-                       p.F(pl.dc1));
+    launch_maxpool_bwd_idx((p.h1p() && tr->fwd_stem_fused) ? (const float*)nullptr : p.F(pl.c1), p.G[p.cur],
+                           reinterpret_cast<const uchar4*>(p.ws + pl.pidx), B, net->h1, net->w1, net->hp, net->wp, p.F(pl.dc1), s);
     if (fin_split) finalise(p, 0, tr->groups.back().fin_count, p.ctx.s2);
     // (0.3 ms at 11 frames, fp32 MFMA on a 216 MB gradient; with the finalisation beside it: on the chain's stream)
     return layer_param_grads(p, net->conv1, {p.F(pl.p0), d.in_h, d.in_w}, {p.F(pl.dc1), net->h1, net->w1}, 2, 3, 3, !fin_split);
@@ -3596,18 +3614,83 @@ int dgp_stem_wgrad_h1(const float* x_centred, const float* dpool, const float* d
         return fail(DGP_ERR_INVALID, "dgp_stem_wgrad_h1: the maps must be those of the root block (conv 7x7 / 2, pool 3x3 / 2, SAME)");
     hipStream_t s = (hipStream_t)stream;
     const long long ng = (long long)B * HP * WP * 64;
-    int pth = (HP - 1) * 2 + 3 - H1; if (pth < 0) pth = 0;
-    int ptw = (WP - 1) * 2 + 3 - W1; if (ptw < 0) ptw = 0;
     to_h1_pred(dpool, ng, dpool_prev, scratch, s);
     TRY_HIP(hipMemsetAsync(dw, 0, (size_t)196 * 64 * sizeof(float), s));
     TRY_HIP(hipMemsetAsync(colsum, 0, 64 * sizeof(float), s));
     StemWgradArgs sa{};
     sa.x = x_centred; sa.g = reinterpret_cast<const uint4*>(scratch); sa.idx = idx; sa.g_prev = dpool_prev;
     sa.dw = dw; sa.colsum = colsum;
-    sa.B = B; sa.H = H; sa.W = W; sa.H1 = H1; sa.W1 = W1; sa.HP = HP; sa.WP = WP; sa.pt = pth / 2; sa.pl = ptw / 2;
+    sa.B = B; sa.H = H; sa.W = W; sa.H1 = H1; sa.W1 = W1; sa.HP = HP; sa.WP = WP; sa.pt = pool_pad_before(H1, HP); sa.pl = pool_pad_before(W1, WP);
     sa.slab = reinterpret_cast<float*>((char*)scratch + (((size_t)ng * 2 + 255) & ~(size_t)255));
     stem_wgrad_launch(sa, s);
     TRY_HIP(hipGetLastError());
+    return DGP_OK;
+}
+
+/* ---- the root block's pool and its fused form as layers (tests): the launches of forward_root / backward_root / the inference engine ---- */
+static bool root_pool_maps(int B, int H1, int W1, int HP, int WP) {
+    return B >= 1 && H1 >= 1 && W1 >= 1 && HP == (H1 + 1) / 2 && WP == (W1 + 1) / 2;
+}
+
+/* forward_root's unfused pool: c1 [B,H1,W1,64] fp32 -> pool [B,HP,WP,64] fp32, idx [B,HP,WP,64] bytes (position a * 3 + b of each window's
+ * first maximum over its valid positions), and with prev + pool_h1 the H1 copy of the pool output at the scale prev predicts. */
+int dgp_maxpool_fwd_idx(const float* c1, int32_t B, int32_t H1, int32_t W1, int32_t HP, int32_t WP, const float* prev, float* pool, uint8_t* idx,
+                        void* pool_h1, void* stream) {
+    if (!c1 || !pool || !idx || (!prev) != (!pool_h1)) return fail(DGP_ERR_INVALID, "dgp_maxpool_fwd_idx: null argument, or only one of prev / pool_h1");
+    if (!root_pool_maps(B, H1, W1, HP, WP)) return fail(DGP_ERR_INVALID, "dgp_maxpool_fwd_idx: the maps must be those of the root block's pool (3x3 / 2, SAME)");
+    launch_maxpool_fwd_idx(c1, B, H1, W1, HP, WP, pool, reinterpret_cast<uchar4*>(idx), reinterpret_cast<uint2*>(pool_h1), prev, (hipStream_t)stream);
+    TRY_HIP(hipGetLastError());
+    return DGP_OK;
+}
+
+/* backward_root's pool backward: dc1 [B,H1,W1,64] = (c1 > 0) * the gradient of every window whose record names the pixel; c1 == NULL: no gate */
+int dgp_maxpool_bwd_idx(const float* c1, const float* dpool, const uint8_t* idx, int32_t B, int32_t H1, int32_t W1, int32_t HP, int32_t WP,
+                        float* dc1, void* stream) {
+    if (!dpool || !idx || !dc1) return fail(DGP_ERR_INVALID, "dgp_maxpool_bwd_idx: null argument");
+    if (!root_pool_maps(B, H1, W1, HP, WP)) return fail(DGP_ERR_INVALID, "dgp_maxpool_bwd_idx: the maps must be those of the root block's pool (3x3 / 2, SAME)");
+    launch_maxpool_bwd_idx(c1, dpool, reinterpret_cast<const uchar4*>(idx), B, H1, W1, HP, WP, dc1, (hipStream_t)stream);
+    TRY_HIP(hipGetLastError());
+    return DGP_OK;
+}
+
+/* stem_pool_fused_kernel on weights given as HWIO [7,7,3,64]: the forward panel (pack_all_kernel's job 0), the stem cells (build_stem_cells)
+ * and launch_stem_pool_fused.  cells 1: H2 pool cells (the parity tier's inference), 2: H1 (the 16-bit tier).  The scale is 2^out_exp, or with
+ * out_prev the one those range slots predict (the training step); idx: the first-maximum record [B,HP,WP,64], training step only.
+ * scratch: [PackDesc | panel range slots | panel | row panel | cells]. */
+size_t dgp_root_block_scratch_bytes(void) { return 256 + ABSMAX_SLOTS * sizeof(float) + (size_t)3 * 56 * 64 * 4 * sizeof(float); }
+
+int dgp_root_block(const uint8_t* frames, int32_t B, int32_t H, int32_t W, const float* w_hwio, const float* bn_scale, const float* bn_bias,
+                   const float* mean_pixel, int32_t cells, int32_t out_exp, const float* out_prev, uint8_t* idx, void* scratch, void* out,
+                   float* out_absmax, void* stream) {
+    if (B < 1 || H < 1 || W < 1 || (long long)B * H * W * 3 >= (1LL << 31))
+        return fail(DGP_ERR_INVALID, "dgp_root_block: the frame batch must be smaller than 2^31 bytes");
+    if (!frames || !w_hwio || !bn_scale || !bn_bias || !mean_pixel || !scratch || !out || !out_absmax)
+        return fail(DGP_ERR_INVALID, "dgp_root_block: null argument");
+    if (cells != 1 && cells != 2) return fail(DGP_ERR_INVALID, "dgp_root_block: cells 1 (H2) or 2 (H1)");
+    if ((out_prev || idx) && cells != 2) return fail(DGP_ERR_INVALID, "dgp_root_block: a predicted scale and the record belong to the 16-bit tier (H1 cells)");
+    if (idx && !out_prev) return fail(DGP_ERR_STATE, "16-bit tier: the root block's output has no predicted range");
+    static_assert(sizeof(PackDesc) <= 256, "the table's slot in the scratch");
+    hipStream_t s = (hipStream_t)stream;
+    char* sp = (char*)scratch;
+    PackDesc* table = reinterpret_cast<PackDesc*>(sp); sp += 256;
+    float* wrng = (float*)sp; sp += ABSMAX_SLOTS * sizeof(float);
+    const size_t nrow = (size_t)56 * 64 * 4;
+    float* panel = (float*)sp; sp += nrow * sizeof(float);
+    float* rows = (float*)sp; sp += nrow * sizeof(float);
+    void* wcells = sp;
+    PackDesc d{};                 // conv1 as the trainer's table describes it: 49 taps, 3 real input channels in slots of 4, 64 columns
+    d.taps = 49; d.cin_real = 3; d.cin = 4; d.cout = 64; d.coutP = 64; d.nchunks_f = nk_for(7, 7, 4) * 8;
+    d.d_w = panel; d.rng_f = wrng;
+    TRY_HIP(hipMemsetAsync(wrng, 0, ABSMAX_SLOTS * sizeof(float), s));
+    TRY_HIP(hipMemsetAsync(out_absmax, 0, ABSMAX_SLOTS * sizeof(float), s));
+    TRY_HIP(hipMemcpyAsync(table, &d, sizeof(d), hipMemcpyHostToDevice, s));
+    TRY_HIP(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(pack_all_kernel, dim3(256, 1, 1), dim3(256), 0, s, table, w_hwio, (const float*)nullptr, 0.f);
+    TRY_HIP(build_stem_cells(panel, 64, mean_pixel, wrng, rows, wcells, s));
+    hipError_t e = launch_stem_pool_fused(frames, B, H, W, wcells, wrng, bn_scale, bn_bias, mean_pixel[0], mean_pixel[1], mean_pixel[2],
+                                          out_prev ? 0.f : ldexpf(1.f, out_exp), reinterpret_cast<float*>(out), out_absmax, s, cells == 2 ? 1 : 0,
+                                          out_prev, idx);
+    if (e != hipSuccess) return fail(DGP_ERR_HIP, std::string("dgp_root_block: ") + hipGetErrorString(e));
     return DGP_OK;
 }
 

@@ -804,6 +804,87 @@ def heads_backward_h1(feat: torch.Tensor, dscmap: torch.Tensor, dlocref: torch.T
     return res
 
 
+# ---- the root block's pool with its first-maximum record, and the fused root block, as layers (tests) ----
+def _pool_hw(h1: int, w1: int) -> Tuple[int, int]:
+    return (h1 + 1) // 2, (w1 + 1) // 2
+
+
+def maxpool_fwd_idx(c1: torch.Tensor, prev_max: Optional[float] = None):
+    """The training step's unfused pool as forward_root launches it: c1 [B,H1,W1,64] fp32 -> (pool fp32 [B,HP,WP,64], record uint8
+    [B,HP,WP,64], H1 copy float16 at the scale prev_max predicts, or None without prev_max)."""
+    lib = _lib.load()
+    _need_cuda(c1, torch.float32, "c1")
+    dev = c1.device
+    B, H1, W1, Cn = c1.shape
+    if Cn != 64:
+        raise _lib.DgpError("c1 must have 64 channels")
+    HP, WP = _pool_hw(H1, W1)
+    pool = torch.empty((B, HP, WP, 64), dtype=torch.float32, device=dev)
+    rec = torch.empty((B, HP, WP, 64), dtype=torch.uint8, device=dev)
+    prev = None if prev_max is None else _slots(prev_max, dev)
+    h1c = None if prev_max is None else torch.zeros((B, HP, WP, 64), dtype=torch.float16, device=dev)
+    _lib.check(lib.dgp_maxpool_fwd_idx(_ptr(c1), B, H1, W1, HP, WP, _ptr(prev), _ptr(pool), _ptr(rec), _ptr(h1c), _stream(dev)),
+               "dgp_maxpool_fwd_idx")
+    return pool, rec, h1c
+
+
+def maxpool_bwd_idx(c1: Optional[torch.Tensor], dpool: torch.Tensor, record: torch.Tensor,
+                    hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """The pool's backward as backward_root launches it: dpool [B,HP,WP,64] fp32, record uint8 -> dc1 [B,H1,W1,64] gated by c1 > 0.
+    c1 None: the 16-bit tier's ungated form; hw = (H1, W1) then names the conv1 map (two sizes share one pool map)."""
+    lib = _lib.load()
+    _need_cuda(dpool, torch.float32, "dpool")
+    _need_cuda(record, torch.uint8, "record")
+    dev = dpool.device
+    B, HP, WP, Cn = dpool.shape
+    if c1 is not None:
+        _need_cuda(c1, torch.float32, "c1")
+        hw = (c1.shape[1], c1.shape[2])
+        if c1.shape[0] != B or c1.shape[3] != 64:
+            raise _lib.DgpError("c1 must be [B,H1,W1,64]")
+    if hw is None:
+        raise _lib.DgpError("maxpool_bwd_idx: without c1 the conv1 map's size hw = (H1, W1) is needed")
+    if Cn != 64 or tuple(record.shape) != tuple(dpool.shape):
+        raise _lib.DgpError("dpool and record must be [B,HP,WP,64]")
+    H1, W1 = int(hw[0]), int(hw[1])
+    dc1 = torch.empty((B, H1, W1, 64), dtype=torch.float32, device=dev)
+    _lib.check(lib.dgp_maxpool_bwd_idx(_ptr(c1), _ptr(dpool), _ptr(record), B, H1, W1, HP, WP, _ptr(dc1), _stream(dev)),
+               "dgp_maxpool_bwd_idx")
+    return dc1
+
+
+def root_block(frames_u8: torch.Tensor, w_hwio: torch.Tensor, bn_scale: torch.Tensor, bn_bias: torch.Tensor, mean_pixel=MEAN_PIXEL, *,
+               cells: str, prev_max: Optional[float] = None, out_exp: Optional[int] = None, record: bool = False):
+    """The fused root block (stem_pool_fused_kernel) as a layer: frames_u8 [B,H,W,3] uint8 (any byte alignment: a view into a larger
+    buffer is fine as long as it is contiguous), w_hwio [7,7,3,64], bn_scale / bn_bias [64] -> (pool cells, record or None, tracked maximum).
+    cells "h2": the parity tier's inference kernel, cells as f32_to_h2 lays them out (fp32-typed [B,HP,WP,64]) at 2^out_exp;
+    cells "h1": the 16-bit tier's kernel, float16 [B,HP,WP,64] at 2^out_exp, or at the scale prev_max predicts; record=True (with prev_max)
+    also returns the first-maximum record, as the training step launches it."""
+    lib = _lib.load()
+    _need_cuda(frames_u8, torch.uint8, "frames_u8")
+    for t, nm in ((w_hwio, "w_hwio"), (bn_scale, "bn_scale"), (bn_bias, "bn_bias")):
+        _need_cuda(t, torch.float32, nm)
+    if tuple(w_hwio.shape) != (7, 7, 3, 64) or bn_scale.numel() != 64 or bn_bias.numel() != 64 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise _lib.DgpError("root_block: frames [B,H,W,3], w_hwio [7,7,3,64], bn_scale / bn_bias [64]")
+    if cells not in ("h1", "h2"):
+        raise _lib.DgpError("root_block: cells 'h1' or 'h2'")
+    if (prev_max is None) == (out_exp is None) and not record:
+        raise _lib.DgpError("root_block: exactly one of prev_max (predicted scale) and out_exp (fixed scale)")
+    dev = frames_u8.device
+    B, H, W, _ = frames_u8.shape
+    HP, WP = _pool_hw((H + 1) // 2, (W + 1) // 2)
+    out = torch.zeros((B, HP, WP, 64), dtype=torch.float16 if cells == "h1" else torch.float32, device=dev)
+    rec = torch.zeros((B, HP, WP, 64), dtype=torch.uint8, device=dev) if record else None
+    amax = torch.zeros(ABSMAX_SLOTS, dtype=torch.float32, device=dev)
+    prev = None if prev_max is None else _slots(prev_max, dev)
+    scratch = torch.zeros(int(lib.dgp_root_block_scratch_bytes()), dtype=torch.uint8, device=dev)
+    m = (C.c_float * 3)(*mean_pixel)
+    _lib.check(lib.dgp_root_block(_ptr(frames_u8), B, H, W, _ptr(w_hwio), _ptr(bn_scale), _ptr(bn_bias), m, 2 if cells == "h1" else 1,
+                                  int(out_exp or 0), _ptr(prev), _ptr(rec), _ptr(scratch), _ptr(out), _ptr(amax), _stream(dev)),
+               "dgp_root_block")
+    return out, rec, float(amax.max())
+
+
 def h2_exp_for(absmax: float, headroom_bits: int = 4) -> int:
     """The engine's scale rule: exponent e with absmax * 2^e in [2^(14 - headroom), 2^(15 - headroom))."""
     import math

@@ -412,6 +412,29 @@ int    dgp_conv2d_dgrad_h1(const dgp_conv_desc* d, const float* dy, const float*
  * scratch: 2 * numel(dpool) bytes rounded up to 256, then B * ceil(H1 / 4) * ceil(W1 / 32) rows of (196 * 64 + 64) floats. */
 int    dgp_stem_wgrad_h1(const float* x_centred, const float* dpool, const float* dpool_prev, const uint8_t* idx, int32_t B, int32_t H,
                          int32_t W, int32_t H1, int32_t W1, int32_t HP, int32_t WP, void* scratch, float* dw, float* colsum, void* stream);
+/* ---- the root block's max-pool (3x3 / 2, SAME) with its first-maximum record, and the fused root block, as layers.  Maps: H1 = ceil(H / 2),
+ * HP = ceil(H1 / 2) (same for W); anything else is DGP_ERR_INVALID.  The record idx [B,HP,WP,64] holds per window and channel the position
+ * a * 3 + b (row-major from the window origin 2 q - pad) of its FIRST maximum under `>`.  Two conventions for windows that hold nothing
+ * positive: the unfused pool records the first VALID position whatever the values are; the fused root block records 0. */
+/* The training step's unfused pool (maxpool_fwd_idx_kernel): c1 [B,H1,W1,64] fp32 -> pool [B,HP,WP,64] fp32 + idx; prev and pool_h1 both
+ * set: also the H1 copy fp16(pool * the scale prev predicts) (halves [B,HP,WP,64]; nothing is written when prev predicts no scale). */
+int    dgp_maxpool_fwd_idx(const float* c1, int32_t B, int32_t H1, int32_t W1, int32_t HP, int32_t WP, const float* prev, float* pool,
+                           uint8_t* idx, void* pool_h1, void* stream);
+/* Its backward (maxpool_bwd_idx_kernel): dc1 [B,H1,W1,64] = (c1 > 0) * sum of dpool over the windows whose record names the pixel, windows
+ * added in ascending (row, column) order in fp32; c1 == NULL: no gate (the 16-bit tier).  A record that names a position outside the map
+ * routes that window's gradient nowhere. */
+int    dgp_maxpool_bwd_idx(const float* c1, const float* dpool, const uint8_t* idx, int32_t B, int32_t H1, int32_t W1, int32_t HP, int32_t WP,
+                           float* dc1, void* stream);
+/* The fused root block (stem_pool_fused_kernel) on its own: frames [B,H,W,3] bytes at any byte alignment, w_hwio [7,7,3,64], bn_scale /
+ * bn_bias [64] (device), mean_pixel [3] (HOST) -> out [B,HP,WP,64] as cells: cells 1 = H2 (fp32-sized, the parity tier's inference
+ * instantiation), 2 = H1 (halves, the 16-bit tier's).  The weight cells are built as dgp_trainer_sync_weights builds them.  Scale: 2^out_exp,
+ * or with out_prev (cells 2 only) the one those range slots predict, as the training step launches it; idx (cells 2 with out_prev only;
+ * DGP_ERR_STATE without out_prev): the first-maximum record.  out_absmax [DGP_ABSMAX_SLOTS]: zeroed, then the tracked range of the output.
+ * A batch of 2^31 bytes or more is DGP_ERR_INVALID.  scratch: dgp_root_block_scratch_bytes() device bytes. */
+size_t dgp_root_block_scratch_bytes(void);
+int    dgp_root_block(const uint8_t* frames, int32_t B, int32_t H, int32_t W, const float* w_hwio, const float* bn_scale, const float* bn_bias,
+                      const float* mean_pixel, int32_t cells, int32_t out_exp, const float* out_prev, uint8_t* idx, void* scratch, void* out,
+                      float* out_absmax, void* stream);
 /* Both heads' backward of the 16-bit pass on one stream: feat [N,h,w,Cin] (converted with feat_prev), dscmap [N,2h,2w,nj] and dlocref
  * [N,2h,2w,2nj] gathered phase-major into ONE H1 tensor of CT columns with one scale (dph_prev), w_part / w_locref in the trainer's
  * layout [3,3,njt,Cin]; one weight-gradient launch, two finalisations (dw_* [3,3,njt,Cin], db_* [njt]), one 2x2-tap data gradient

@@ -10,6 +10,15 @@ design -- there and nowhere else:
                             and the sum is rounded to fp16 in dPool's scaled units; the column sums add the ROUNDED values
   4. the panel's cells      float16(float32(w * scale) * 2^(14 - E)) for max |w * scale| = m 2^E: high-only cells of the data-gradient panel
   5. the fp16 output cells  float16(float32 result * s_out): not applied here -- the tests bound |cell - reference * s_out| by half an ulp
+The fused root block (root_forward) rounds at three more places:
+  6. its pixels             float16(u8 - round(mean_c)): small integers, exact; the kernel's fourth input channel is 1 inside the frame and 0
+                            in the padding
+  7. the fourth weight      sum_c (round(mean_c) - mean_c) w_c carries the mean's fraction: the differences are fp32 values (of the fp32
+                            mean), the sum is rounded to fp32 (the device's sum may differ from it by an fp32 ulp: 1e-9 of a conv1 value)
+  8. the stem's cells       launch_pack_h3 of the row panel with the scale of rounding point 4 taken from max |w| over the three real
+                            channels: high = float16(float32(w * s)), low = float16(w * s - high); the 16-bit tier multiplies by the
+                            high cells, the parity tier by high + low
+BN and ReLU are float64 there; the pool output's cells are rounding point 5 (the parity tier's H2 cells: 22 bits instead of 11).
 
 Everything between two rounding points (products of two fp16 values, their sums) is exact or fp32-accumulated in the kernels and float64 here.
 Tensors are NHWC torch tensors on any device; weights are HWIO.
@@ -166,22 +175,40 @@ def pool_geometry(n):
     return out, tot // 2
 
 
-def pool_first_max(c1):
-    """c1 [B,H1,W1,C] -> (pool [B,HP,WP,C], record uint8 [B,HP,WP,C]): per window and channel the position a * 3 + b of its FIRST maximum
-    in row-major window order (a, b from the window origin 2 q - pad; padding never wins)."""
+def pool_windows(c1, fill=-float("inf")):
+    """c1 [B,H1,W1,C] -> [9, B,HP,WP,C]: element a * 3 + b of every window (views of one padded copy); `fill` outside the map."""
     B, H1, W1, C = c1.shape
     HP, pt = pool_geometry(H1)
     WP, pl = pool_geometry(W1)
-    neg = torch.full((B, 2 * HP + 1, 2 * WP + 1, C), -float("inf"), dtype=c1.dtype, device=c1.device)
-    neg[:, pt:pt + H1, pl:pl + W1] = c1
+    pad = torch.full((B, 2 * HP + 1, 2 * WP + 1, C), fill, dtype=c1.dtype, device=c1.device)
+    pad[:, pt:pt + H1, pl:pl + W1] = c1
+    return [pad[:, a:a + 2 * HP - 1:2, b:b + 2 * WP - 1:2] for a in range(3) for b in range(3)]
+
+
+def pool_valid(H1, W1, device="cpu"):
+    """[9, HP, WP] bool: position a * 3 + b of window (qy, qx) lies inside the map."""
+    ones = torch.ones((1, H1, W1, 1), dtype=torch.float32, device=device)
+    return torch.stack([v[0, :, :, 0] > 0 for v in pool_windows(ones, 0.0)])
+
+
+def pool_first_max(c1, first_valid=False):
+    """c1 [B,H1,W1,C] -> (pool [B,HP,WP,C], record uint8 [B,HP,WP,C]): per window and channel the position a * 3 + b of its FIRST maximum
+    in row-major window order (a, b from the window origin 2 q - pad; padding never wins).  first_valid: the first position inside the
+    map is taken whatever it holds (maxpool_fwd_idx_kernel's rule: a window of -inf records its first valid position, not 0)."""
+    B, H1, W1, C = c1.shape
+    HP, WP = pool_geometry(H1)[0], pool_geometry(W1)[0]
     best = torch.full((B, HP, WP, C), -float("inf"), dtype=c1.dtype, device=c1.device)
     rec = torch.zeros((B, HP, WP, C), dtype=torch.uint8, device=c1.device)
-    for a in range(3):
-        for b in range(3):
-            v = neg[:, a:a + 2 * HP - 1:2, b:b + 2 * WP - 1:2]
-            win = v > best                      # strictly greater: an equal later value does not replace the first maximum
-            best = torch.where(win, v, best)
-            rec = torch.where(win, torch.full_like(rec, a * 3 + b), rec)
+    seen = torch.zeros((1, HP, WP, 1), dtype=torch.bool, device=c1.device)
+    valid = pool_valid(H1, W1, c1.device)
+    for k, v in enumerate(pool_windows(c1)):
+        win = v > best                          # strictly greater: an equal later value does not replace the first maximum
+        if first_valid:
+            ok = valid[k][None, :, :, None]
+            win = win | (ok & ~seen)
+            seen = seen | ok
+        best = torch.where(win, v, best)
+        rec = torch.where(win, torch.full_like(rec, k), rec)
     return best, rec
 
 
@@ -198,6 +225,52 @@ def pool_backward(dpool, rec, H1, W1, dtype=torch.float64):
             sel = torch.where(rec == a * 3 + b, g, torch.zeros_like(g))
             buf[:, a:a + 2 * HP - 1:2, b:b + 2 * WP - 1:2] += sel
     return buf[:, pt:pt + H1, pl:pl + W1].clone()
+
+
+def stem_cells(w, mean):
+    """w [7,7,3,64] -> (high, low) [7,7,4,64] float64 in scaled units and the scale: rounding points 7 and 8."""
+    wf = w.to(torch.float32)
+    m32 = np.asarray(mean, dtype=np.float32)
+    d = torch.tensor((np.round(m32) - m32).astype(np.float64), dtype=torch.float64, device=w.device)
+    w4 = (wf.double() * d[None, None, :, None]).sum(2, keepdim=True).to(torch.float32)
+    s = panel_scale(float(wf.abs().max()))
+    ws = torch.cat([wf, w4], 2) * float(s)                           # fp32, exact (a power of two)
+    high = ws.to(torch.float16)
+    low = (ws - high.float()).to(torch.float16)                      # the residual is exact in fp32
+    return high.double(), low.double(), s
+
+
+def root_forward(frames, w, bn_scale, bn_bias, mean, cells, scale=1.0):
+    """The root block in float64 on the operands the kernel holds: frames [B,H,W,3] uint8, w [7,7,3,64] -> (conv1 map after BN + ReLU
+    [B,H1,W1,64], pool maxima [B,HP,WP,64]), both times `scale` (the scaled units of the output cells).
+    cells "h1": the 16-bit tier (high weight cells), "h2": the parity tier's fused kernel (high + low), "f32": the unfused layers (fp32
+    pixels u8 - mean, fp32 weights, no cells).  The sum runs tap by tap and channel by channel with elementwise float64 operations, so
+    that two conv1 pixels with identical patches get bitwise identical values (a library GEMM need not promise that)."""
+    B, H, W, _ = frames.shape
+    pad_t, H1 = same_pads(H, 7, 2, 1)
+    pad_l, W1 = same_pads(W, 7, 2, 1)
+    dev = frames.device
+    if cells == "f32":
+        m32 = torch.tensor(np.asarray(mean, dtype=np.float32), device=dev)
+        x = (frames.to(torch.float32) - m32).double()                                     # one fp32 rounding, as preprocess_u8
+        wq, s = w.to(torch.float32).double(), 1.0
+    else:
+        mr = torch.tensor(np.round(np.asarray(mean, dtype=np.float32)), device=dev)
+        x = torch.cat([(frames.to(torch.float32) - mr).to(torch.float16).double(),          # rounding point 6
+                       torch.ones((B, H, W, 1), dtype=torch.float64, device=dev)], 3)
+        high, low, s = stem_cells(w, mean)
+        wq = high if cells == "h1" else high + low
+    C = x.shape[3]
+    xp = torch.zeros((B, 2 * H1 + 5, 2 * W1 + 5, C), dtype=torch.float64, device=dev)
+    xp[:, pad_t:pad_t + H, pad_l:pad_l + W] = x
+    acc = torch.zeros((B, H1, W1, 64), dtype=torch.float64, device=dev)
+    for kh in range(7):
+        for kw in range(7):
+            v = xp[:, kh:kh + 2 * H1 - 1:2, kw:kw + 2 * W1 - 1:2]
+            for c in range(C):
+                acc += v[..., c:c + 1] * wq[kh, kw, c]
+    c1 = torch.relu(acc / float(s) * bn_scale.double() + bn_bias.double()) * float(scale)
+    return c1, torch.stack(pool_windows(c1)).amax(0)
 
 
 def stem_wgrad(x_centred, dpool_cells, rec, s):

@@ -170,3 +170,66 @@ def test_stem_reference_rounds_the_patch_and_dc1_only():
     dwr, csr = R.wgrad(x.double(), d64, 7, 2, 1, 3, 3)
     assert torch.equal(dw, dwr / 4.0) and torch.equal(cs, csr / 4.0)
     assert dw.shape == (7, 7, 4, 64) and float(dw[:, :, 3].abs().sum()) == 0.0
+
+
+def test_pool_first_valid_rule_matches_plain_loops():
+    """pool_first_max(first_valid=True): the first position inside the map is taken whatever it holds (a window of -inf records it, not 0);
+    afterwards only strictly greater values.  Against loops written from that sentence, on a padded and an unpadded grid."""
+    g = torch.Generator().manual_seed(5)
+    for H1, W1 in ((5, 7), (6, 4)):
+        x = torch.round(torch.randn((1, H1, W1, 3), generator=g) * 2) / 2                  # coarse values: ties
+        x[torch.rand(x.shape, generator=g) < 0.3] = -float("inf")
+        x[:, :3, :3] = -float("inf")                                                       # whole windows of -inf
+        x[0, -1, -1, 0] = -0.0
+        pool, rec = R.pool_first_max(x, first_valid=True)
+        (HP, pt), (WP, pl) = R.pool_geometry(H1), R.pool_geometry(W1)
+        for ho in range(HP):
+            for wo in range(WP):
+                for c in range(3):
+                    m, k = None, None
+                    for a in range(3):
+                        for b in range(3):
+                            hi, wi = 2 * ho - pt + a, 2 * wo - pl + b
+                            if 0 <= hi < H1 and 0 <= wi < W1 and (k is None or float(x[0, hi, wi, c]) > m):
+                                m, k = float(x[0, hi, wi, c]), a * 3 + b
+                    assert int(rec[0, ho, wo, c]) == k and float(pool[0, ho, wo, c]) == m, (H1, W1, ho, wo, c)
+        valid = R.pool_valid(H1, W1)
+        assert bool(valid[int(rec[0, 0, 0, 0]), 0, 0]) and int(rec[0, 0, 0, 0]) == (4 if pt and pl else 0)
+        # without the rule a window of -inf keeps position 0; everywhere else the two agree
+        pool0, rec0 = R.pool_first_max(x)
+        assert torch.equal(rec0[pool0 > -float("inf")], rec[pool0 > -float("inf")]) and int(rec0[0, 0, 0, 0]) == 0
+
+
+@pytest.mark.parametrize("hw", [(9, 12), (10, 7)])
+def test_root_forward_is_the_root_block(hw):
+    """root_forward against torch's float64 conv + BN + ReLU + max-pool; the cell modes differ from it by what their cells drop."""
+    H, W = hw
+    g = torch.Generator().manual_seed(H * 100 + W)
+    fr = torch.randint(0, 256, (2, H, W, 3), generator=g, dtype=torch.uint8)
+    w = torch.randn((7, 7, 3, 64), generator=g) * 0.05
+    sc, bi = torch.rand(64, generator=g) + 0.5, torch.randn(64, generator=g) * 20
+    mean = (123.68, 116.779, 103.939)
+    x = (fr.float() - torch.tensor(mean)).double().permute(0, 3, 1, 2)
+    y = F.conv2d(x, w.double().permute(3, 2, 0, 1), stride=2, padding=3)
+    c1 = torch.relu(y * sc.double()[None, :, None, None] + bi.double()[None, :, None, None])
+    H1, W1 = (H + 1) // 2, (W + 1) // 2
+    pt, pl = R.pool_geometry(H1)[1], R.pool_geometry(W1)[1]
+    HP, WP = R.pool_geometry(H1)[0], R.pool_geometry(W1)[0]
+    padded = F.pad(c1, (pl, 2 * WP + 1 - W1 - pl, pt, 2 * HP + 1 - H1 - pt), value=-float("inf"))
+    pool = F.max_pool2d(padded, 3, 2)[:, :, :HP, :WP]
+    top = float(c1.max())
+    got_c1, got_pool = R.root_forward(fr, w, sc, bi, mean, "f32")
+    assert got_c1.shape == (2, H1, W1, 64) and got_pool.shape == (2, HP, WP, 64)
+    assert float((got_c1 - c1.permute(0, 2, 3, 1)).abs().max()) < 1e-12 * top
+    assert float((got_pool - pool.permute(0, 2, 3, 1)).abs().max()) < 1e-12 * top
+    # H2 cells keep 22 bits of every weight and the mean's fraction rides on the fourth channel: 49 x 4 products of |x| <= 132
+    h2 = R.root_forward(fr, w, sc, bi, mean, "h2")[0]
+    assert float((h2 - got_c1).abs().max()) < 196 * 132 * 2.0 ** -22 * float(w.abs().max()) * 1.5
+    # H1 cells keep 11 bits; scaled units scale both results
+    h1 = R.root_forward(fr, w, sc, bi, mean, "h1", scale=4.0)
+    assert float((h1[0] / 4.0 - got_c1).abs().max()) < 196 * 132 * 2.0 ** -11 * float(w.abs().max()) * 1.5
+    assert float((h1[0] / 4.0 - got_c1).abs().max()) > 100 * float((h2 - got_c1).abs().max())     # (and the two modes are different things)
+    # identical patches give bitwise identical values: a frame of one colour, away from the border
+    flat = torch.full((1, 40, 40, 3), 77, dtype=torch.uint8)
+    inner = R.root_forward(flat, w, sc, bi, mean, "h1")[0][0, 2:-2, 2:-2]
+    assert bool((inner == inner[0, 0]).all())
