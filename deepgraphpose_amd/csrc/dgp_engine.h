@@ -1,4 +1,4 @@
-// Engine-internal types shared by dgp_net.hip (inference engine) and dgp_train.hip (training step).
+// Engine-internal types shared by dgp_net.hip (inference engine) and the files of the training step (dgp_train.h).
 #pragma once
 #include "../../include/dgp_hip.h"
 #include "dgp_internal.h"
@@ -131,7 +131,7 @@ struct dgp_net {
     std::vector<dgp::ChainPlan> chains;       // chains[ui]: conv3 of unit ui + conv1 of unit ui + 1 (ok = false: layer by layer)
     bool loaded = false;
     // a trainer that owns this net (dgp_trainer_create) re-packs its panels every step and may defer the ones only the parity path reads;
-    // dgp_forward calls this first so that a forward on a trainer-owned net never reads a stale panel (dgp_train.hip, refresh_parity_panels)
+    // dgp_forward calls this first so that a forward on a trainer-owned net never reads a stale panel (dgp_train_pack.hip, refresh_parity_panels)
     int (*owner_sync)(void* owner, void* stream) = nullptr;
     void* owner = nullptr;
     // precision tier (dgp_net_set_tier): 0 = parity tier (H2 cells, 22-bit operands as fp16 pairs, three MFMAs per product);

@@ -306,7 +306,7 @@ class Trainer:
     def apply_gradients(self, lr: float, momentum: float = 0.9, clip_norm: float = 10.0, optimizer: str = "sgd", beta1: float = 0.9,
                         beta2: float = 0.999, eps: float = 1e-8) -> float:
         """clip_by_global_norm(clip_norm) (<= 0: none), then optimizer "sgd": MomentumOptimizer(lr, momentum), or "adam":
-        AdamOptimizer(lr, beta1, beta2, eps) (csrc/dgp_train.hip: momentum_kernel / adam_kernel).  -> the gradient norm before clipping."""
+        AdamOptimizer(lr, beta1, beta2, eps) (csrc/dgp_optim.hip: momentum_kernel / adam_kernel).  -> the gradient norm before clipping."""
         g = C.c_float()
         self._enqueue_update(optimizer, lr, momentum, clip_norm, beta1, beta2, eps, g)
         self.sync()

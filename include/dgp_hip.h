@@ -369,7 +369,7 @@ int  dgp_conv2d_plan(const dgp_conv_desc* d, int32_t in_fmt, int32_t out_fmt, in
  *                      Cout % 32 == 0, Cin % 4 == 0; ranged bit 1 (the gate is an H2 tensor): bit 0, a mask, Cin % 8 == 0 and Cin >= 64. */
 int    dgp_conv2d_wgrad(const dgp_conv_desc* d, const float* x, const float* dy, const float* x_absmax, const float* dy_absmax,
                         float* dw_raw, float* colsum, void* stream);
-/* dgp_conv2d_wgrad on the LDS-DMA tile of the training step (csrc/dgp_train.hip, wgrad_dma).  Inside dgp_train_backward both operands
+/* dgp_conv2d_wgrad on the LDS-DMA tile of the training step (csrc/dgp_wgrad.hip, wgrad_dma).  Inside dgp_train_backward both operands
  * of a 128 x 128 weight-gradient tile also exist as fp16 high / low cells (the H2 layout below), written by their producers' epilogues
  * with a power-of-two scale PREDICTED from the range the same tensor had one step earlier (max -> [2^10, 2^11)); the kernel moves the
  * cells by LDS-DMA (no split arithmetic, no register staging) and checks this step's ranges against the predicted scales: outside

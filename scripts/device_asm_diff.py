@@ -3,11 +3,12 @@
 
     hipcc -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S csrc/dgp_kernels.hip -o new.s      (same at the parent: old.s)
     python scripts/device_asm_diff.py old.s new.s
+    python scripts/device_asm_diff.py old.s -- a.s b.s c.s      (a source split into several: each side is the union of its files)
 
 Splits each assembly file into its functions, keeps the instruction text (no directives, no comments) and drops the function-index part
 of local labels (.LBB<fn>_<n>, which moves when host-only edits reorder the instantiations).  Prints the functions only one side has
 and the ones whose instructions differ; exit status 1 if there are any.  Metadata (amdhsa.kernels: the order of the entries) is not
-compared."""
+compared.  A function that more than one file of a side defines is reported as well."""
 import re
 import sys
 
@@ -35,17 +36,30 @@ def functions(path):
     return {k: v for k, v in out.items() if v and not k.startswith(("__hip_cuid", "amdhsa."))}
 
 
-def main(a_path, b_path):
-    a, b = functions(a_path), functions(b_path)
+def side(paths):
+    out, twice = {}, []
+    for p in paths:
+        f = functions(p)
+        twice += sorted(set(f) & set(out))
+        out.update(f)
+    return out, twice
+
+
+def main(a_paths, b_paths):
+    (a, a2), (b, b2) = side(a_paths), side(b_paths)
+    a_path, b_path = " ".join(a_paths), " ".join(b_paths)
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     differ = sorted(k for k in a if k in b and a[k] != b[k])
     print("%d / %d functions, %d / %d instructions" % (len(a), len(b), sum(map(len, a.values())), sum(map(len, b.values()))))
-    for what, names in (("only in " + a_path, only_a), ("only in " + b_path, only_b), ("instructions differ", differ)):
+    for what, names in (("only in " + a_path, only_a), ("only in " + b_path, only_b), ("instructions differ", differ),
+                        ("defined in more than one file of a side", a2 + b2)):
         print("%s: %d" % (what, len(names)))
         for n in names:
             print("   ", n)
-    return 1 if only_a or only_b or differ else 0
+    return 1 if only_a or only_b or differ or a2 or b2 else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    args = sys.argv[1:]
+    cut = args.index("--") if "--" in args else 1
+    sys.exit(main(args[:cut], [x for x in args[cut:] if x != "--"]))
