@@ -10,7 +10,7 @@ namespace dgp {
 
 constexpr int BK = 32;            // K floats per main-loop step (8 chunks of 4)
 
-// Arguments of the implicit-GEMM convolution kernel (see dgp_kernels.hip).
+// Arguments of the implicit-GEMM convolution kernels (dgp_conv_f32.hip, dgp_conv_split.hip; launched through dgp_kernels.hip).
 struct ConvArgs {
     const float* in;      // NHWC [N,H,W,Cin]
     const float* wpk;     // packed weight panels [nk*8][CoutP][4]
@@ -94,8 +94,7 @@ enum TileFamily { FAM_F32, FAM_LS, FAM_SPLIT };      // conv_igemm_f32 / conv_ig
 // The path of one split-kernel launch: the template flags of conv_igemm_split_ls and the dynamic LDS that goes with them
 struct SplitPath {
     int mode;              // loader walk: 0 everything at run time, 1 per-tap, 2 pointwise, 3 halo ring
-    bool pb;               // weights come as pre-split cells
-    bool cs, dma, deep;    // compute-side split, LDS-DMA loaders, deep DMA ring
+    bool cs, dma, deep;    // compute-side split (the weights come as pre-split cells), LDS-DMA loaders, deep DMA ring
     bool ah2, oh2, h1;     // input in cells, output in cells, the cells are H1 (16-bit tier)
     size_t lds;
 };

@@ -1,7 +1,7 @@
 // DGP loss: forward + backward w.r.t. the two head outputs, as wavefront-reduction kernels (gfx950).
 //
 // Restates dgp_loss (DGP/models/fitdgp.py:946-1076) on [nt, H, W, nj] scoremaps:
-//   mu = soft-argmax(pred)                      fitdgp_util.py:342-402   (kernel in dgp_kernels.hip)
+//   mu = soft-argmax(pred)                      fitdgp_util.py:342-402   (kernel in dgp_ops.hip)
 //   t  = labels for visible markers, mu for hidden ones (no stop_gradient)      fitdgp.py:946-961
 //   G  = exp(-|alpha - t|^2 / 2l^2) / (max G + 1e-5)                           :964-976
 //   visible CE, hidden CE (gm2 in {0,1,2}, gm3 in {0,3})                       :979-1039

@@ -1,4 +1,4 @@
-// gfx950 (MI355X / CDNA4): the non-convolution kernels of the Deep Graph Pose hot path (split off dgp_kernels.hip in round 4).
+// gfx950 (MI355X / CDNA4): the non-convolution kernels of the Deep Graph Pose hot path (the convolutions: dgp_conv_split.hip, dgp_conv_f32.hip).
 //
 //   pack_h3 / pack_h3_all   fp32 weight panels -> fp16 high / low cells (the LDS order of the fp16-split conv kernels)
 //   absmax, reduce_slabs, head_gather, f32 <-> H2 converters, h2_range_check

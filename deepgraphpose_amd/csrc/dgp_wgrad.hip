@@ -178,7 +178,7 @@ __device__ __forceinline__ float rng_scale(const float* slots, int lane) {     /
 }
 
 __device__ __forceinline__ void split_hl(const float4 v, const float s, uint2& ph, uint2& pl) {
-    // same 10-VALU sequence as split2_f16 (dgp_kernels.hip): h = f16(s x) written into its half of the packed register,
+    // same 10-VALU sequence as split2_f16 (dgp_device.h): h = f16(s x) written into its half of the packed register,
     // r = s x - h exact in fp32 with h read as an fp16 operand, l = f16(r) packed
     unsigned h01, h23;
     float r0, r1, r2, r3;

@@ -330,7 +330,7 @@ int  dgp_conv2d(const dgp_conv_desc* d, const float* x, const float* packed_w,
 int  dgp_conv2d_ranged(const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale, const float* bias,
                        const float* residual, float* y, const float* x_absmax, const float* w_absmax, float* y_absmax,
                        void* stream);
-/* Same, with room for the grid-tail K-split (the launch layer of csrc/dgp_kernels.hip: the tiles of an underfull last round split
+/* Same, with room for the grid-tail K-split (plan_tail_ksplit in csrc/dgp_conv_split.hip: the tiles of an underfull last round split
  * their K range over up to 4 workgroups, raw partial sums go to the slab, a fix-up launch sums them in fixed order).  tail_slab: the
  * caller's device memory, tail_slab_bytes < 4 GiB (DGP_ERR_INVALID otherwise); nothing is allocated.  NULL / 0: dgp_conv2d_ranged. */
 int  dgp_conv2d_ranged_slab(const dgp_conv_desc* d, const float* x, const float* packed_w, const float* scale, const float* bias,

@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Compare the device code of two builds of one HIP source, kernel by kernel.
 
-    hipcc -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S csrc/dgp_kernels.hip -o new.s      (same at the parent: old.s)
+    hipcc -O3 --offload-arch=gfx950 -std=c++17 --cuda-device-only -S csrc/dgp_conv_split.hip -o new.s      (same at the parent: old.s)
     python scripts/device_asm_diff.py old.s new.s
     python scripts/device_asm_diff.py old.s -- a.s b.s c.s      (a source split into several: each side is the union of its files)
+    python scripts/device_asm_diff.py --drop-arg conv_igemm_split_ls:6 old.s new.s      (new.s removed the function's 6th template parameter)
 
 Splits each assembly file into its functions, keeps the instruction text (no directives, no comments) and drops the function-index part
 of local labels (.LBB<fn>_<n>, which moves when host-only edits reorder the instantiations).  Prints the functions only one side has
 and the ones whose instructions differ; exit status 1 if there are any.  Metadata (amdhsa.kernels: the order of the entries) is not
-compared.  A function that more than one file of a side defines is reported as well."""
+compared.  A function that more than one file of a side defines is reported as well.  --drop-arg NAME:N removes the N-th (1-based, literal)
+template argument of function NAME from the FIRST side's mangled names before matching."""
 import re
 import sys
 
@@ -45,8 +47,12 @@ def side(paths):
     return out, twice
 
 
-def main(a_paths, b_paths):
+def main(a_paths, b_paths, drop=None):
     (a, a2), (b, b2) = side(a_paths), side(b_paths)
+    if drop:
+        name, n = drop.rsplit(":", 1)
+        arg = re.compile(r"(%d%sI(?:L[^E]*E){%d})L[^E]*E" % (len(name), name, int(n) - 1))
+        a = {arg.sub(r"\1", k): v for k, v in a.items()}
     a_path, b_path = " ".join(a_paths), " ".join(b_paths)
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     differ = sorted(k for k in a if k in b and a[k] != b[k])
@@ -61,5 +67,7 @@ def main(a_paths, b_paths):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    drop = args.pop(args.index("--drop-arg") + 1) if "--drop-arg" in args else None
+    args = [x for x in args if x != "--drop-arg"]
     cut = args.index("--") if "--" in args else 1
-    sys.exit(main(args[:cut], [x for x in args[cut:] if x != "--"]))
+    sys.exit(main(args[:cut], [x for x in args[cut:] if x != "--"], drop))

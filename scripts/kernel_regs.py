@@ -1,5 +1,5 @@
 """Register / spill / occupancy table of one HIP source's kernels (hipcc -Rpass-analysis=kernel-resource-usage).
-Usage: python scripts/kernel_regs.py deepgraphpose_amd/csrc/dgp_kernels.hip [name-regex] [extra hipcc flags ...]"""
+Usage: python scripts/kernel_regs.py deepgraphpose_amd/csrc/dgp_conv_split.hip [name-regex] [extra hipcc flags ...]"""
 import re, subprocess, sys
 src = sys.argv[1]; pat = sys.argv[2] if len(sys.argv) > 2 else "."; extra = sys.argv[3:]
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-c", src, "-o", "/dev/null",

@@ -1,5 +1,5 @@
-"""The grid rules of the conv launch layer restated in plain Python, from the comments in the launcher (csrc/dgp_kernels.hip, "Launch
-layer") and DESIGN.md ("How a conv launch picks its kernel", "XCD-aware launch order") -- not from the code: tests/test_conv_plan_cpu.py
+"""The grid rules of the conv launch layer restated in plain Python, from the comments in the launchers (csrc/dgp_kernels.hip, the
+launch layer; csrc/dgp_conv_split.hip, the split family's plan) and DESIGN.md ("How a conv launch picks its kernel", "XCD-aware launch order") -- not from the code: tests/test_conv_plan_cpu.py
 holds dgp_conv2d_plan to these, tests/test_conv_plan_gpu.py builds its shapes with them.  Three rules, all on integers:
 
   grid tail      With two workgroups of a 128 x 128 split kernel per CU, `slots = 2 n_cu` run at once.  A grid of `tiles` leaves

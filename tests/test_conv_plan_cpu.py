@@ -1,4 +1,4 @@
-"""dgp_conv2d_plan -- the host-side plan of a conv launch (csrc/dgp_kernels.hip, plan_conv) -- against the independent restatement of
+"""dgp_conv2d_plan -- the host-side plan of a conv launch (csrc/dgp_kernels.hip, plan_conv; csrc/dgp_conv_split.hip, plan_split) -- against the independent restatement of
 the grid rules in tests/_conv_plan_ref.py, for explicit numbers of CUs: no GPU is needed.  What a plan decides (the K-split of the
 grid's tail, the supertile order, the deep ring) is otherwise reachable only at full-size grids; a refactor that sends a layer down
 another, still correct kernel is caught here.  The GPU side (tests/test_conv_plan_gpu.py) asserts through the same query that each of
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # K-steps of 32 floats -> a kernel that has them: (KH, KW, Cin), nk = ceil(KH KW Cin / 32); Cin must be 4 * 2^k
 KERNEL_OF_NK = {2: (1, 1, 64), 4: (1, 1, 128), 8: (1, 1, 256), 16: (1, 1, 512), 32: (1, 1, 1024), 64: (1, 1, 2048),
                 9: (3, 3, 32), 18: (3, 3, 64), 36: (3, 3, 128), 72: (3, 3, 256), 47: (47, 1, 32), 48: (3, 1, 512)}
-# tile id -> (K floats per step, columns, compute waves, needs ranges); the 128-row split tiles (TILES in dgp_kernels.hip)
+# tile id -> (K floats per step, columns, compute waves, needs ranges); the 128-row split tiles (TILES in dgp_conv.h)
 SPLIT_TILES = {16: (32, 128, 4, True), 8: (32, 128, 4, False), 10: (16, 128, 4, False), 13: (16, 128, 4, True),
                12: (16, 128, 8, False), 15: (32, 64, 4, True)}
 MB32 = 32 << 20
