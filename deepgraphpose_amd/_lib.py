@@ -172,6 +172,11 @@ SYMBOLS = {
     "dgp_jpeg_entropy_encode": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "dgp_jpeg_forward_scratch_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "dgp_jpeg_forward_u8": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int64, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "dgp_frame_features_u8": (C.c_int, [_vp, _i32, _i32, _i32, C.c_int64] + [_i32] * 7 + [_vp, C.c_int64, _vp]),
+    "dgp_kmeans_scratch_bytes": (_sz, [C.c_int64, _i32, _i32]),
+    "dgp_kmeans_center": (C.c_int, [_vp, C.c_int64, _i32, _vp, _vp, _sz, _vp]),
+    "dgp_kmeans_assign": (C.c_int, [_vp, C.c_int64, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "dgp_kmeans_update": (C.c_int, [_vp, C.c_int64, _i32, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libdgp_hip.so")
 # through DGP_HIP_LIB, by the tests of those paths
 TUNING_LIB = os.path.join(HERE, "libdgp_hip_tuning.so")
 SOURCES = ["dgp_conv_split.hip", "dgp_conv_f32.hip", "dgp_kernels.hip", "dgp_ops.hip", "dgp_chain.hip", "dgp_loss.hip", "dgp_net.hip", "dgp_train.hip", "dgp_wgrad.hip", "dgp_train_pack.hip",
-           "dgp_optim.hip", "dgp_train_layers.hip", "dgp_flow.hip", "dgp_resize.hip", "dgp_targets.hip", "dgp_frames.hip", "dgp_augment.hip", "dgp_jpeg.hip"]
+           "dgp_optim.hip", "dgp_train_layers.hip", "dgp_flow.hip", "dgp_resize.hip", "dgp_targets.hip", "dgp_frames.hip", "dgp_augment.hip", "dgp_jpeg.hip", "dgp_select.hip"]
 HEADERS = ["dgp_internal.h", "dgp_device.h", "dgp_conv.h", "dgp_engine.h", "dgp_train.h", "dgp_jpeg_host.h", os.path.join("..", "..", "include", "dgp_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 

@@ -1378,6 +1378,122 @@ def gather_frames(store, src, patch: Optional[torch.Tensor] = None, out: Optiona
     return out
 
 
+# ---- frame selection (csrc/dgp_select.hip): thumbnails of device frames and the three k-means kernels; frame_selection.py drives them
+
+from .frame_selection import KMEANS_MAX_K, KMEANS_MAX_D, feature_geometry  # noqa: E402  (torch-free: the limits and the thumbnail geometry)
+
+
+def frame_features(frames_u8: torch.Tensor, resizewidth: int = 30, color: bool = False, crop=None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Area-averaged thumbnails of device uint8 frames [N, H, W, 3] (dgp_frame_features_u8; the resize of
+    KmeansbasedFrameselectioncv2, frameselectiontools.py:173-228): float32 [N, D], geometry as feature_geometry, grey = the box mean over
+    pixels and channels laid out [oh, ow], color = one mean per channel laid out [oh, 3, ow] (the reference's hstack, :188).  Integer sums,
+    one division: float32(float64(sum) / count), bit for bit frame_selection.features_host.  `frames_u8` may be a view: each frame
+    contiguous, frames any stride >= H W 3 apart, at any byte offset.  `out`: float32 [N, D] whose rows may be a view into a wider buffer
+    (unit column stride); only the N x D values are written.  One launch on the current stream, no host synchronisation."""
+    lib = _lib.load()
+    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
+        raise _lib.DgpError("frame_features: frames must be a device uint8 tensor")
+    if frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise _lib.DgpError("frame_features: frames must be [N, H, W, 3], got %s" % (tuple(frames_u8.shape),))
+    N, H, W = (int(v) for v in frames_u8.shape[:3])
+    if H < 1 or W < 1:
+        raise ValueError("frame_features: empty frames %s" % (tuple(frames_u8.shape),))
+    x1, x2, y1, y2, oh, ow, D = feature_geometry(H, W, resizewidth, color, crop)
+    if N and not frames_u8[0].is_contiguous():
+        raise _lib.DgpError("frame_features: each frame must be contiguous")
+    fstride = int(frames_u8.stride(0)) if N > 1 else H * W * 3
+    if fstride < H * W * 3:
+        raise _lib.DgpError("frame_features: frames overlap (stride %d < %d bytes)" % (fstride, H * W * 3))
+    dev = frames_u8.device
+    if out is None:
+        out = torch.empty((N, D), dtype=torch.float32, device=dev)
+    else:
+        if not out.is_cuda or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (N, D):
+            raise _lib.DgpError("frame_features: out must be float32 %s on %s, got %s %s on %s" % ((N, D), dev, out.dtype, tuple(out.shape), out.device))
+        if (D > 1 and out.stride(1) != 1) or (N > 1 and out.stride(0) < D):
+            raise _lib.DgpError("frame_features: out needs unit column stride and a row stride >= %d, got %s" % (D, tuple(out.stride())))
+    if N == 0:
+        return out
+    ostride = int(out.stride(0)) if N > 1 else D
+    _lib.check(lib.dgp_frame_features_u8(_ptr(frames_u8), N, H, W, fstride, x1, x2, y1, y2, ow, oh, int(bool(color)), _ptr(out), ostride,
+                                         _stream(dev)), "dgp_frame_features_u8")
+    return out
+
+
+def _kmeans_matrix(X: torch.Tensor, who: str, k: Optional[int] = None) -> Tuple[int, int]:
+    _need_cuda(X, torch.float32, "X")
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("%s: X must be a non-empty [N, D] matrix, got %s" % (who, tuple(X.shape)))
+    N, D = int(X.shape[0]), int(X.shape[1])
+    if D > KMEANS_MAX_D:
+        raise ValueError("%s: D = %d is above the limit of %d columns" % (who, D, KMEANS_MAX_D))
+    if N * D >= 1 << 31:
+        raise ValueError("%s: N x D = %d must stay below 2^31" % (who, N * D))
+    if k is not None and not 1 <= k <= KMEANS_MAX_K:
+        raise ValueError("%s: k = %d is outside 1 .. %d" % (who, k, KMEANS_MAX_K))
+    return N, D
+
+
+def _kmeans_scratch(lib, N: int, D: int, k: int, dev) -> torch.Tensor:
+    return torch.empty((int(lib.dgp_kmeans_scratch_bytes(N, D, k)) + 7) // 8, dtype=torch.float64, device=dev)
+
+
+def kmeans_center(X: torch.Tensor) -> torch.Tensor:
+    """X float32 [N, D] on the device, centred IN PLACE: DATA - DATA.mean(axis=0) (frameselectiontools.py:231).  Column sums in double
+    over fixed slabs of rows combined in slab order, the mean rounded once to fp32, then float32(x - mean32).  -> mean float32 [D].
+    Enqueued on the current stream (dgp_kmeans_center)."""
+    lib = _lib.load()
+    N, D = _kmeans_matrix(X, "kmeans_center")
+    mean = torch.empty(D, dtype=torch.float32, device=X.device)
+    scratch = _kmeans_scratch(lib, N, D, 0, X.device)
+    _lib.check(lib.dgp_kmeans_center(_ptr(X), N, D, _ptr(mean), _ptr(scratch), scratch.numel() * 8, _stream(X.device)), "dgp_kmeans_center")
+    return mean
+
+
+def kmeans_assign(X: torch.Tensor, C_: torch.Tensor, labels: torch.Tensor, dist: torch.Tensor) -> int:
+    """Nearest centre of every row of X [N, D] among C_ [k, D] (dgp_kmeans_assign): labels int32 [N] is read (the previous labels) and
+    overwritten, dist float32 [N] gets the squared distance to the chosen centre, fp32 sums of (x - c)^2 in a fixed order; the lowest
+    index wins a tie.  -> the number of rows whose label changed (an exact integer; reading it synchronises)."""
+    lib = _lib.load()
+    _need_cuda(C_, torch.float32, "C")
+    if C_.dim() != 2:
+        raise ValueError("kmeans_assign: C must be [k, D], got %s" % (tuple(C_.shape),))
+    N, D = _kmeans_matrix(X, "kmeans_assign", int(C_.shape[0]))
+    _need_cuda(labels, torch.int32, "labels")
+    _need_cuda(dist, torch.float32, "dist")
+    if int(C_.shape[1]) != D or tuple(labels.shape) != (N,) or tuple(dist.shape) != (N,):
+        raise ValueError("kmeans_assign: X %s, C %s, labels %s and dist %s do not belong together"
+                         % (tuple(X.shape), tuple(C_.shape), tuple(labels.shape), tuple(dist.shape)))
+    changed = torch.empty(1, dtype=torch.int32, device=X.device)
+    _lib.check(lib.dgp_kmeans_assign(_ptr(X), N, D, _ptr(C_), int(C_.shape[0]), _ptr(labels), _ptr(dist), _ptr(changed), _stream(X.device)),
+               "dgp_kmeans_assign")
+    return int(changed.item())
+
+
+def kmeans_update(X: torch.Tensor, labels: torch.Tensor, C_: torch.Tensor, counts: torch.Tensor) -> None:
+    """Every centre of C_ [k, D] becomes the mean of its members in place (dgp_kmeans_update): double sums in a fixed order, so two calls
+    give the same bits; an empty cluster keeps its centre.  counts int32 [k + 1]: the members of each cluster, and in counts[k] the
+    labels outside [0, k) -- those rows are skipped, and a non-zero count raises ValueError here (which synchronises)."""
+    lib = _lib.load()
+    _need_cuda(C_, torch.float32, "C")
+    if C_.dim() != 2:
+        raise ValueError("kmeans_update: C must be [k, D], got %s" % (tuple(C_.shape),))
+    k = int(C_.shape[0])
+    N, D = _kmeans_matrix(X, "kmeans_update", k)
+    _need_cuda(labels, torch.int32, "labels")
+    _need_cuda(counts, torch.int32, "counts")
+    if int(C_.shape[1]) != D or tuple(labels.shape) != (N,) or tuple(counts.shape) != (k + 1,):
+        raise ValueError("kmeans_update: X %s, C %s, labels %s and counts %s do not belong together"
+                         % (tuple(X.shape), tuple(C_.shape), tuple(labels.shape), tuple(counts.shape)))
+    scratch = _kmeans_scratch(lib, N, D, k, X.device)
+    _lib.check(lib.dgp_kmeans_update(_ptr(X), N, D, _ptr(labels), _ptr(C_), k, _ptr(counts), _ptr(scratch), scratch.numel() * 8,
+                                     _stream(X.device)), "dgp_kmeans_update")
+    bad = int(counts[k].item())
+    if bad:
+        raise ValueError("kmeans_update: %d labels are outside [0, %d)" % (bad, k))
+
+
 # ---- the augmenters of the DGP drivers' labeled frames (csrc/dgp_augment.hip): one frame, one stage, one launch on the current stream
 
 def _aug_pair(src: torch.Tensor, dst: torch.Tensor, who: str):

@@ -132,6 +132,8 @@ def main(argv=None):
     parser.add_argument("--test", action="store_true", default=False)
     parser.add_argument("--frame_store", type=str, default="off", choices=["off", "hip"],
                         help="steps 1 and 2: 'hip' decodes the selected frames once into a device store and gathers every batch there")
+    parser.add_argument("--extract-outliers", action="store_true", default=False,
+                        help="step 4: write the frames the model most likely got wrong, with their machine labels, to labeled-data/<video>/")
     input_params = parser.parse_known_args(argv)[0]
     print(input_params)
     dlcpath, shuffle, dlcsnapshot = input_params.dlcpath, input_params.shuffle, input_params.dlcsnapshot
@@ -200,6 +202,12 @@ def main(argv=None):
             out = plot_dgp(video_file=str(video_file), output_dir=video_pred_path, proj_cfg_file=str(cfg_yaml),
                            dgp_model_file=str(snapshot_path), shuffle=shuffle)
             print("wrote", out, flush=True)
+            if input_params.extract_outliers:
+                # step 4 (opt-in): the frames to label next, from the labels plot_dgp has just written
+                from deepgraphpose_amd.frame_selection import extract_outlier_frames
+                stem = os.path.basename(str(video_file)).rsplit(".", 1)[0]
+                picked = extract_outlier_frames(str(cfg_yaml), str(video_file), label_file=join(video_pred_path, stem + "_labeled.csv"))
+                print("outlier frames", picked, flush=True)
     finally:
         if update_configs:
             return_configs(demo_rel)

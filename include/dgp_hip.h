@@ -779,6 +779,49 @@ int     dgp_jpeg_forward_u8(const uint8_t* src, int32_t B, int32_t H, int32_t W,
                             const uint16_t* d_qt, const int32_t* d_markers, int32_t n_markers, int32_t dotsize, int16_t* d_coef,
                             void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- Frame selection: thumbnails and k-means on the device (replaces the per-frame resize and the clustering of
+ * KmeansbasedFrameselection / KmeansbasedFrameselectioncv2, deeplabcut/utils/frameselectiontools.py:139-246, used by extract_frames and
+ * by extract_outlier_frames' ExtractFramesbasedonPreselection).  No float atomics anywhere: the same input gives the same bits.
+ *
+ * Thumbnails, exact integer area averages.  frames: device uint8, N frames of [H][W][3], frame_stride BYTES apart (at least H W 3), at
+ * ANY byte address.  The window frame[y1:y2, x1:x2] (0 <= x1 < x2 <= W, same for y; Hc = y2 - y1, Wc = x2 - x1) is reduced to oh x ow
+ * values: column box i is [floor(i Wc / ow), floor((i + 1) Wc / ow)), rows alike with oh, and oh MUST be max(1, Hc ow / Wc rounded half
+ * to even) -- the caller states it, it is checked.  ow > Wc (an upsample) is DGP_ERR_INVALID.  color == 0: one value per box, the integer
+ * sum over the box's pixels and three channels / (pixels x 3), out row = [oh][ow]; color != 0: one value per channel, out row =
+ * [oh][3][ow] (the reference's hstack of the three planes).  A value is (float)((double)sum / (double)count), nothing else.  out: device
+ * fp32, row f at out + f out_stride (FLOATS, at least D = oh ow (1 | 3)); only the D values of each row are written.
+ * Limits (DGP_ERR_INVALID before anything is launched): Wc <= 16384, ow <= 1024, and the largest box (ceil(Wc / ow) x ceil(Hc / oh)
+ * pixels) x 3 x 255 must fit 32 bits (5 614 429 pixels), so an all-255 frame cannot overflow a counter.
+ * One workgroup per (frame, output row); 16-byte loads when the address of every row allows it (frames, frame_stride and 3 W multiples
+ * of 16), 4-byte loads likewise, single bytes otherwise; per-column integer counters in LDS (integer LDS atomics: order-independent). */
+int  dgp_frame_features_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, int64_t frame_stride, int32_t x1, int32_t x2,
+                           int32_t y1, int32_t y2, int32_t ow, int32_t oh, int32_t color, float* out, int64_t out_stride, void* stream);
+
+/* Limits of the three k-means entry points: 1 <= k <= DGP_KMEANS_MAX_K, 1 <= D <= DGP_KMEANS_MAX_D (30 x 30 x 3 thumbnails are 2700),
+ * 1 <= N, N D < 2^31.  Rows are grouped in slabs: S = min(DGP_KMEANS_MAX_SLABS, ceil(N / 256)) slabs of ceil(N / S) rows (the last one
+ * shorter); a column sum is one double accumulator per slab walked in row order, and the slabs are added in slab order. */
+enum { DGP_KMEANS_MAX_K = 160, DGP_KMEANS_MAX_D = 8192, DGP_KMEANS_MAX_SLABS = 64 };
+/* Host only: device scratch bytes dgp_kmeans_center (k = 0) or dgp_kmeans_update needs; 0 for arguments they refuse. */
+size_t dgp_kmeans_scratch_bytes(int64_t N, int32_t D, int32_t k);
+/* X: device fp32 [N][D], packed.  mean[d] = (float)(column sum / N) (DATA.mean(axis=0), :231), then X[r][d] = X[r][d] - mean[d] in fp32,
+ * in place.  mean: device fp32 [D].  scratch: device, 8-byte aligned, dgp_kmeans_scratch_bytes(N, D, 0).  Three launches. */
+int  dgp_kmeans_center(float* X, int64_t N, int32_t D, float* mean, void* scratch, size_t scratch_bytes, void* stream);
+/* Nearest centre of every row.  C: device fp32 [k][D].  labels: device int32 [N], read (the previous labels, any values) and
+ * overwritten; dist: device fp32 [N], the squared distance to the chosen centre; changed: device int32, set to the number of rows whose
+ * label differs from the one that was there (an integer counter: exact).  Distances are the direct form sum_d (x_d - c_d)^2 in fp32,
+ * every product and sum rounded on its own, in a FIXED order: D is cut into chunks of DC = min(512, floor(10240 / k) rounded down to a
+ * multiple of 64) columns; inside a chunk lane l of a 64-lane wave adds its columns l, l + 64, ... in that order (columns past D count
+ * as zero), the 64 partial sums are combined by a butterfly (v += v of lane ^ 32, ^ 16, ... ^ 1), and the chunk totals are added in
+ * chunk order.  On an exact tie the lowest centre index wins.  One wave per row, the centres of a chunk staged in LDS (40 KB), the
+ * running sums of a workgroup's 32 rows in LDS as well. */
+int  dgp_kmeans_assign(const float* X, int64_t N, int32_t D, const float* C, int32_t k, int32_t* labels, float* dist, int32_t* changed,
+                       void* stream);
+/* Every centre becomes the mean of its members: (float)(sum / count), the sum as described above (members only, in row order).  An
+ * empty cluster keeps its centre and gets count 0.  counts: device int32 [k + 1]; counts[k] is the number of labels outside [0, k):
+ * such a row indexes nothing, it is skipped and counted.  scratch: dgp_kmeans_scratch_bytes(N, D, k).  Two launches. */
+int  dgp_kmeans_update(const float* X, int64_t N, int32_t D, const int32_t* labels, float* C, int32_t k, int32_t* counts, void* scratch,
+                       size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
