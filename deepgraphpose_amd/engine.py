@@ -562,13 +562,13 @@ def conv2d(x: torch.Tensor, w_hwio: np.ndarray, stride: int = 1, rate: int = 1, 
     return (y, rng[2]) if return_range else y
 
 
-def _conv_out(out, shape, dev):
+def _conv_out(out, shape, dev, dtype=torch.float32):
     """the output tensor of a layer call: the caller's (checked) or a new one"""
     if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-    _need_cuda(out, torch.float32, "out")
+        return torch.empty(shape, dtype=dtype, device=dev)
+    _need_cuda(out, dtype, "out")
     if tuple(out.shape) != tuple(shape) or out.device != dev:
-        raise _lib.DgpError("out must be a float32 tensor of shape %s on %s" % (tuple(shape), dev))
+        raise _lib.DgpError("out must be a %s tensor of shape %s on %s" % (str(dtype).replace("torch.", ""), tuple(shape), dev))
     return out
 
 
@@ -965,9 +965,10 @@ def h1_to_f32(x: torch.Tensor, scale_exp: int) -> torch.Tensor:
 
 def conv2d_h1(x_h1: torch.Tensor, x_exp: int, w_hwio: np.ndarray, stride: int = 1, rate: int = 1, pad_t: int = 0, pad_l: int = 0,
               out_hw: Optional[Tuple[int, int]] = None, scale=None, bias=None, residual: Optional[torch.Tensor] = None,
-              res_stride: int = 0, res_exp: int = 0, relu: bool = False, y_is_h1: bool = True, y_exp: int = 0):
+              res_stride: int = 0, res_exp: int = 0, relu: bool = False, y_is_h1: bool = True, y_exp: int = 0,
+              out: Optional[torch.Tensor] = None):
     """One conv layer on H1 tensors (float16 NHWC with power-of-two scales) through the 16-bit tier's cell kernels.
-    -> (y: float16 H1 cells or fp32, y_absmax_slots)."""
+    -> (y: float16 H1 cells or fp32, y_absmax_slots).  out: as in conv2d (float16 where y_is_h1)."""
     lib = _lib.load()
     _need_cuda(x_h1, torch.float16, "x_h1")
     N, H, W, Cin = x_h1.shape
@@ -981,7 +982,7 @@ def conv2d_h1(x_h1: torch.Tensor, x_exp: int, w_hwio: np.ndarray, stride: int = 
     wp = torch.from_numpy(pack_conv_weights(w_hwio)).to(dev)
     sc = None if scale is None else torch.as_tensor(scale, dtype=torch.float32).contiguous().to(dev)
     bi = None if bias is None else torch.as_tensor(bias, dtype=torch.float32).contiguous().to(dev)
-    y = torch.empty((N, Ho, Wo, cout), dtype=torch.float16 if y_is_h1 else torch.float32, device=dev)
+    y = _conv_out(out, (N, Ho, Wo, cout), dev, torch.float16 if y_is_h1 else torch.float32)
     if residual is not None:
         _need_cuda(residual, torch.float16, "residual")
     rh, rw = (residual.shape[1], residual.shape[2]) if residual is not None else (0, 0)

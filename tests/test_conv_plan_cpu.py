@@ -2,7 +2,9 @@
 the grid rules in tests/_conv_plan_ref.py, for explicit numbers of CUs: no GPU is needed.  What a plan decides (the K-split of the
 grid's tail, the supertile order, the deep ring) is otherwise reachable only at full-size grids; a refactor that sends a layer down
 another, still correct kernel is caught here.  The GPU side (tests/test_conv_plan_gpu.py) asserts through the same query that each of
-its launches takes the plan it is about."""
+its launches takes the plan it is about.  The first sweep runs on 1 x M frames, which the halo ring never takes; a second one
+(_halo_sweep) runs 3 x 3 layers on N x H x W frames around the ring's capacity bounds and holds the fourth rule, with a known-answer
+table and the networks' own 3 x 3 layers at 256 CUs beside it (GPU side: tests/test_halo_walk_gpu.py)."""
 import ctypes as C
 import os
 import subprocess
@@ -116,9 +118,141 @@ def test_plan_query_matches_the_restated_grid_rules_with_the_tail_split_forced_o
     assert r.returncode == 0 and "sweep ok" in r.stdout, r.stdout[-2000:] + r.stderr[-1000:]
 
 
+# ---------------------------------------------------------------- the halo walk: 3 x 3 layers on real N x H x W frames
+def _widths(d):
+    """W = 1, 2, a small one, and the last fit / first miss of both capacity bounds at dilation d (worked out here, not read from the code):
+    default S = 128 + 2 d (W + 1) <= 360 <=> W <= 116 // d - 1; hard d (W - 2) + 128 <= 352 <=> W <= 224 // d + 2"""
+    w_def, w_hard = 116 // d - 1, 224 // d + 2
+    assert 128 + 2 * d * (w_def + 1) <= 360 < 128 + 2 * d * (w_def + 2) and d * (w_hard - 2) + 128 <= 352 < d * (w_hard - 1) + 128
+    return (1, 2, 9, w_def, w_def + 1, w_hard, w_hard + 1)
+
+
+def _frames_for(mtiles, W):
+    """(N, H) with ceil(N H W / 128) == mtiles where some H in 1 .. 40 allows it, else the nearest count from below"""
+    for H in (7, 5, 3, 1, 2, 4, 6) + tuple(range(8, 41)):
+        N = mtiles * 128 // (H * W)
+        if N >= 1 and -(-N * H * W // 128) == mtiles:
+            return N, H
+    return max(1, mtiles * 128 // W), 1
+
+
+def _halo_sweep(lib, halo_env, tail_env=1):
+    """every mismatch between the query and the restatement on 3 x 3 layers, the number of plans compared, and how many took each path"""
+    from deepgraphpose_amd import _lib
+    bad, n, seen = [], 0, {"walk": 0, "deep": 0, "per_tap": 0}
+    for n_cu in (64, 104, 256, 304):
+        for fmt in (1, 2):
+            for d in (1, 2, 3):
+                for W in _widths(d):
+                    for cin in ((32, 128, 512) if fmt == 1 else (64, 128, 512)):
+                        for cout in (64, 128, 512):
+                            bn = 128 if cout >= 128 else 64
+                            ntiles = cout // bn
+                            for mt in sorted({1, 3, n_cu // ntiles - 1, n_cu // ntiles, n_cu // ntiles + 1, 2 * n_cu // ntiles + 3, 5 * n_cu // ntiles + 1} - {0, -1}):
+                                N, H = _frames_for(mt, W)
+                                mtiles = -(-N * H * W // 128)
+                                for pad_l, stride, slab in ((d, 1, 0), (d, 1, MB32), (d + 1, 1, 0), (d, 2, 0)):
+                                    Ho = H if stride == 1 else (H - 1) // 2 + 1
+                                    Wo = W + 2 * (pad_l - d) if stride == 1 else (W - 1) // 2 + 1
+                                    dsc = _lib.DgpConvDesc(N, H, W, cin, cout, 3, 3, stride, d, d, pad_l, Ho, Wo, 1, 0, 0, 0)
+                                    pl = _lib.DgpConvPlan()
+                                    rc = lib.dgp_conv2d_plan(C.byref(dsc), fmt, fmt, 0, 1, 0, slab, -1, n_cu, C.byref(pl))
+                                    mo = -(-N * Ho * Wo // 128)
+                                    nk = 9 * cin // 32
+                                    deep = bn == 128 and R.deep_ring(mo, ntiles, nk, n_cu, dma=True, h1=fmt == 2)
+                                    halo = R.halo_walk(fmt, fmt, (3, 3), stride, d, d, pad_l, (H, W), (Ho, Wo), dma128=bn == 128, deep=deep, halo_env=halo_env)
+                                    ks, n_main, grid = R.tail_ksplit(mo, ntiles, nk, n_cu, slab, cells_in=True, h1=fmt == 2, halo=halo, bn=bn, tail_env=tail_env)
+                                    got = (rc, pl.tile, pl.mode, pl.deep, pl.lds, pl.mtiles, pl.ntiles, pl.tail_ksplit, pl.n_main, pl.grid, pl.st_gn, pl.dma, pl.h1)
+                                    want = (0, 16 if bn == 128 else 15, 3 if halo else 1, int(deep), R.dma_lds_bytes(halo, deep, bn), mo, ntiles, ks, n_main, grid, 0, 1, int(fmt == 2))
+                                    n += 1
+                                    seen["walk" if halo else "deep" if deep else "per_tap"] += 1
+                                    assert not (halo and (ks or deep))
+                                    if got != want and len(bad) < 20:
+                                        bad.append(((n_cu, fmt, d, N, H, W, cin, cout, pad_l, stride, slab), got, want))
+    return bad, n, seen
+
+
+def _halo_sweep_ok(bad, n, seen, halo_env):
+    """nothing differs and the sweep reached every path it is about (no walk at all with the switch off)"""
+    return not bad and n > 20000 and seen["deep"] > 500 and seen["per_tap"] > 5000 and (seen["walk"] > 3000 if halo_env else seen["walk"] == 0)
+
+
+def test_plan_query_matches_the_restated_halo_rule(lib_built):
+    """3 x 3 layers of both cell formats on N x H x W frames, dilation 1 / 2 / 3, widths 1, 2 and on each side of both capacity bounds,
+    one and several channel chunks, 64 / 128 / 512 output channels, tile counts on each side of n_cu, with and without a slab, and beside
+    each stride-1 layer one with another pad and a stride-2 one: mode, deep, lds, tail_ksplit, n_main and grid against the restatement."""
+    from deepgraphpose_amd import _lib
+    bad, n, seen = _halo_sweep(_lib.load(), halo_env=1)
+    print("[conv-plan] halo sweep: %d plans, %r" % (n, seen))
+    assert _halo_sweep_ok(bad, n, seen, 1), (n, seen, bad[:5])
+
+
+@pytest.mark.parametrize("halo_env", [0, 2])
+def test_plan_query_matches_the_restated_halo_rule_with_the_switch_set(lib_built, halo_env):
+    """DGP_HALO=0 (no walk anywhere) and DGP_HALO=2 (the default capacity bound lifted, the hard one kept), read once per process: a child"""
+    env = dict(os.environ, DGP_HALO=str(halo_env), PYTHONPATH=ROOT + os.pathsep + os.path.join(ROOT, "tests"))
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "halo"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    sys.stdout.write(r.stdout[-500:])
+    assert r.returncode == 0 and "halo sweep ok" in r.stdout, r.stdout[-2000:] + r.stderr[-1000:]
+
+
 def _plan(**kw):
     from deepgraphpose_amd import engine
     return engine.conv2d_plan(**kw)
+
+
+def _c3(nhw, cin, cout, d, fmt, n_cu=256):
+    return _plan(x_shape=tuple(nhw) + (cin,), w_shape=(3, 3, cin, cout), rate=d, pad_t=d, pad_l=d, in_fmt=fmt, out_fmt=fmt, n_cu=n_cu)
+
+
+# 3 x 3, 128 -> 512 at 256 CUs, more than 256 tiles: (dilation, (N, H, W)) -> mode at the default switches, mode under DGP_HALO=2
+HALO_KNOWN = [
+    (1, (15, 5, 115), 3, 3), (1, (15, 5, 116), 1, 3),         # default capacity at d 1: S = 360 / 362
+    (2, (30, 5, 57), 3, 3), (2, (30, 5, 58), 1, 3),           # ... at d 2: S = 360 / 364
+    (1, (8, 5, 226), 1, 3), (1, (8, 5, 227), 1, 1),           # hard capacity at d 1: d (W - 2) + 128 = 352 / 353
+    (2, (15, 5, 114), 1, 3), (2, (15, 5, 115), 1, 1),         # ... at d 2: 352 / 354
+    (3, (6, 33, 47), 1, 3),                                   # S = 416, d (W - 2) + 128 = 263
+    (1, (171, 25, 2), 3, 3), (1, (171, 50, 1), 1, 1),         # two pixels per row; one
+    (1, (140, 7, 9), 3, 3),                                   # frames smaller than a tile
+]
+
+
+def _halo_known(halo_env):
+    """the table above and the ResNet-101 layer through the query, both cell formats -> the rows that differ"""
+    bad = []
+    for fmt in (1, 2):
+        rows = HALO_KNOWN + [(2, (16, 45, 80), 1, 3)]
+        for d, nhw, m_def, m_forced in rows:
+            cin, cout = (512, 512) if nhw[1:] == (45, 80) else (128, 512)
+            pl = _c3(nhw, cin, cout, d, fmt)
+            want = dict(mode=(1, m_def, m_forced)[halo_env], deep=0, tail_ksplit=0, st_gn=0, h1=int(fmt == 2), tile=16)
+            if pl["mtiles"] * pl["ntiles"] <= 256 or {k: pl[k] for k in want} != want:
+                bad.append((fmt, d, nhw, pl, want))
+    return bad
+
+
+def test_known_halo_plans_at_256_cus(lib_built):
+    """Each side of both capacity bounds, dilation 3, narrow rows and tiny frames as literal answers, H2 and H1 alike.  With at most
+    one tile per CU every H2 row is on the deep ring instead; H1 keeps the walk."""
+    assert not _halo_known(1), _halo_known(1)[:3]
+    for d, nhw, m_def, _ in HALO_KNOWN:
+        small = (max(1, nhw[0] // 8),) + nhw[1:]
+        _expect(_c3(small, 128, 512, d, 1), mode=1, deep=1, lds=147456, tail_ksplit=0)
+        _expect(_c3(small, 128, 512, d, 2), mode=m_def, deep=0, lds=81920, tail_ksplit=0, h1=1)
+
+
+def test_the_networks_3x3_layers_at_256_cus(lib_built):
+    """ResNet-50 at 640 x 480: block2 / 3 / 4 conv2 (60 x 80 x 128, 30 x 40 x 256, 30 x 40 x 512 at dilation 2) walk the ring at batch 32 on
+    both tiers; at batch 4 (150 / 76 / 152 tiles) the parity tier runs them on the deep ring with the per-tap loaders, the 16-bit tier
+    still on the walk.  ResNet-101 at 1280 x 720 x 16: block4 conv2 (45 x 80 at dilation 2, S = 452) keeps the per-tap loaders."""
+    layers = (((60, 80), 128, 1), ((30, 40), 256, 1), ((30, 40), 512, 2))
+    for hw, c, d in layers:
+        for fmt in (1, 2):
+            _expect(_c3((32,) + hw, c, c, d, fmt), mode=3, deep=0, lds=81920, tail_ksplit=0, st_gn=0, grid=32 * hw[0] * hw[1] // 128 * (c // 128))
+        _expect(_c3((4,) + hw, c, c, d, 1), mode=1, deep=1, lds=147456)
+        _expect(_c3((4,) + hw, c, c, d, 2), mode=3, deep=0, h1=1)
+    for fmt in (1, 2):
+        _expect(_c3((16, 45, 80), 512, 512, 2, fmt), mode=1, deep=0, grid=1800)
 
 
 def _expect(pl, **want):
@@ -221,6 +355,13 @@ def test_what_the_kernels_refuse_is_refused_by_the_query(lib_built):
 
 if __name__ == "__main__":
     from deepgraphpose_amd import _lib as _l
+    if sys.argv[1] == "halo":          # the halo sweep and the known answers under this process's DGP_HALO
+        henv = int(os.environ.get("DGP_HALO", "1"))
+        bad_, n_, seen_ = _halo_sweep(_l.load(), halo_env=henv)
+        known_ = _halo_known(henv)
+        ok_ = _halo_sweep_ok(bad_, n_, seen_, henv) and not known_
+        print("halo sweep ok: %d plans, %r" % (n_, seen_) if ok_ else "halo sweep FAILED: %d plans, %r, %r, %r" % (n_, seen_, bad_[:5], known_[:3]))
+        sys.exit(0 if ok_ else 1)
     bad_, n_ = _sweep(_l.load(), tail_env=int(sys.argv[1]))
     print("sweep ok: %d plans" % n_ if not bad_ and n_ > 100000 else "sweep FAILED: %d plans, %r" % (n_, bad_[:5]))
     sys.exit(1 if bad_ else 0)

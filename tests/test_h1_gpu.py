@@ -54,6 +54,12 @@ H1_CONV_CASES = [
 ]
 
 
+# the cases that walk the halo ring (mode 3): asserted in the test; the ring's edges on this tier are in tests/test_halo_walk_gpu.py
+H1_WALK_CASES = {(1, 15, 20, 128, 128, 3, 1, 2, 0, True), (2, 30, 40, 256, 256, 3, 1, 1, 0, True), (1, 30, 40, 512, 512, 3, 1, 2, 2, True),
+                 (3, 7, 9, 128, 128, 3, 1, 1, 0, True)}
+assert H1_WALK_CASES <= set(H1_CONV_CASES)
+
+
 @pytest.mark.parametrize("case", H1_CONV_CASES)
 def test_conv_on_h1_tensors_matches_float64_on_the_same_fp16_operands(lib_built, case):
     from deepgraphpose_amd import engine
@@ -71,6 +77,16 @@ def test_conv_on_h1_tensors_matches_float64_on_the_same_fp16_operands(lib_built,
     Wo = (W + 2 * pad - keff) // stride + 1 if stride > 1 else W
     if k == 1 and stride > 1:
         pad, Ho, Wo = 0, (H + stride - 1) // stride, (W + stride - 1) // stride
+    # the loader walk, through the plan query: the 16-bit tier has no deep ring, so the four halo-walk cases walk the ring on any chip
+    pl = engine.conv2d_plan((N, H, W, Cin), w.shape, stride=stride, rate=rate, pad_t=pad, pad_l=pad, out_hw=(Ho, Wo), in_fmt=2,
+                            out_fmt=2 if y_h1 else 0, res_fmt=2 if res_kind else 0, res_stride={0: 0, 2: 1, 3: 2}[res_kind],
+                            res_hw={0: (0, 0), 2: (Ho, Wo), 3: (2 * Ho - 1, 2 * Wo)}[res_kind])
+    print("[h1-path] %r mode %d deep %d" % (case, pl["mode"], pl["deep"]))
+    assert pl["h1"] == 1 and pl["deep"] == 0
+    if case in H1_WALK_CASES:
+        assert pl["mode"] == 3, pl
+    if case == (1, 9, 200, 128, 128, 3, 1, 2, 0, True):
+        assert pl["mode"] == 1, pl
     x_exp = engine.h2_exp_for(float(x.abs().max()))
     xh = engine.f32_to_h1(x, x_exp)
     xq = engine.h1_to_f32(xh, x_exp).double()                                  # the activations as the cells hold them
@@ -201,6 +217,7 @@ H1_CHAIN_CASES = [
     (2, 15, 20, 128, 128, 0, 1),      # identity unit of block2
     (2, 8, 10, 128, 256, 0, 2),       # end of block2 -> block3 unit_1's conv1
     (32, 60, 80, 128, 128, 0, 1),     # batch-32 640x480 shape of block2 (1200 tiles over persistent workgroups)
+    (2, 30, 40, 256, 256, 0, 1),      # identity unit of block3: the two-slot ring with five compute waves
 ]
 
 

@@ -48,23 +48,63 @@ H2_CONV_CASES = [
     (32, 30, 40, 1024, 256, 1, 1, 1, 0, True),     # batch-32 block3 conv1: 600 tiles in the pairing order of two column tiles (no tail slab here: tests/test_conv_plan_gpu.py splits it)
     (32, 30, 40, 512, 512, 3, 1, 2, 2, True),      # batch-32 block4 conv2 (+ an H2 residual): the deepest K loop at its real size
     (11, 30, 40, 2048, 512, 1, 1, 1, 0, True),     # block4 conv1 at 11 frames: 416 tiles, K = 2048
-    # round 4, the halo walk (MODE 3 of the dominant kernel: 3x3 / stride 1 on a pixel ring in LDS, taps masked by the compute waves)
-    (3, 7, 9, 128, 128, 3, 1, 1, 0, True),         # case12: frames smaller than a tile -- a 128-pixel window spans three frames; ragged last tile
-    (2, 30, 40, 256, 256, 3, 1, 1, 0, True),       # case13: block3 conv2
-    (1, 60, 80, 128, 128, 3, 1, 1, 2, True),       # case14: block2 conv2 (+ an H2 residual)
-    (1, 20, 118, 128, 128, 3, 1, 2, 0, True),      # case15: d (W - 2) + 128 = HALO_C - 8: the widest row the ring takes
-    (1, 9, 200, 128, 128, 3, 1, 2, 0, True),       # case16: wider than that -> the per-tap loaders (MODE 1)
-    (1, 45, 80, 512, 512, 3, 1, 2, 0, True),       # case17: block4 conv2 of the 1280 x 720 network
-    (2, 5, 2, 128, 128, 3, 1, 1, 0, True),         # case18: two pixels per row (every tap but the centre column masked somewhere)
-    (1, 33, 47, 128, 256, 3, 1, 3, 0, True),       # case19: dilation 3, odd sizes
+    # round 4, shapes of the halo walk (MODE 3 of the dominant kernel: 3x3 / stride 1 on a pixel ring in LDS, taps masked by the compute waves).
+    # The walk takes a launch only where the grid has MORE tiles than the chip has CUs: case12 to case19 have 1 to 116 tiles, so on a
+    # full-size chip (256 CUs) every one of them runs the deep ring with the per-tap loaders (mode 1, deep 1), and only the 1200 tiles of
+    # case10 above walk the ring.  The test asserts the path each case takes on this device through the plan query; the walk's own edges
+    # are the cases of tests/test_halo_walk_gpu.py, which sizes them from the CU count.
+    (3, 7, 9, 128, 128, 3, 1, 1, 0, True),         # case12: frames smaller than a tile -- a 128-pixel window spans three frames; ragged last tile (2 tiles)
+    (2, 30, 40, 256, 256, 3, 1, 1, 0, True),       # case13: block3 conv2 (38 tiles)
+    (1, 60, 80, 128, 128, 3, 1, 1, 2, True),       # case14: block2 conv2 (+ an H2 residual; 38 tiles)
+    (1, 20, 118, 128, 128, 3, 1, 2, 0, True),      # case15: d (W - 2) + 128 = 360, beyond the ring's HALO_C - 8 = 352 (the widest row it takes at d = 2 is W = 114): per-tap loaders everywhere
+    (1, 9, 200, 128, 128, 3, 1, 2, 0, True),       # case16: wider still -> the per-tap loaders
+    (1, 45, 80, 512, 512, 3, 1, 2, 0, True),       # case17: block4 conv2 of the 1280 x 720 network (116 tiles; with more tiles than CUs still per-tap: S = 452 > 360)
+    (2, 5, 2, 128, 128, 3, 1, 1, 0, True),         # case18: two pixels per row (every tap but the centre column masked somewhere; 1 tile)
+    (1, 33, 47, 128, 256, 3, 1, 3, 0, True),       # case19: dilation 3, odd sizes (26 tiles; with more tiles than CUs per-tap: S = 416 > 360)
 ]
+
+
+def _case_geometry(case):
+    """-> pad, Ho, Wo of a case of H2_CONV_CASES"""
+    N, H, W, Cin, Cout, k, stride, rate = case[:8]
+    keff = (k - 1) * rate + 1
+    pad = (keff - 1) // 2
+    Ho = (H + 2 * pad - keff) // stride + 1 if stride > 1 else H
+    Wo = (W + 2 * pad - keff) // stride + 1 if stride > 1 else W
+    if k == 1 and stride > 1:
+        pad, Ho, Wo = 0, (H + stride - 1) // stride, (W + stride - 1) // stride
+    return pad, Ho, Wo
+
+
+def _path_of(case, n_cu, halo_env):
+    """(mode, deep) of a case on n_cu CUs with DGP_HALO = halo_env, from the restated rules (tests/_conv_plan_ref.py): the 128-column tile
+    from 128 output channels on, pointwise walk (2) for 1 x 1 / stride 1, else per-tap (1) or the halo ring (3)"""
+    import _conv_plan_ref as R
+    N, H, W, Cin, Cout, k, stride, rate, _, y_h2 = case
+    pad, Ho, Wo = _case_geometry(case)
+    bn = 128 if Cout >= 128 else 64
+    deep = bn == 128 and R.deep_ring(-(-N * Ho * Wo // 128), Cout // bn, k * k * Cin // 32, n_cu, dma=True)
+    halo = R.halo_walk(1, int(y_h2), (k, k), stride, rate, pad, pad, (H, W), (Ho, Wo), dma128=bn == 128, deep=deep, halo_env=halo_env)
+    return (3 if halo else 2 if (k == 1 and stride == 1) else 1), int(deep)
+
+
+def _path_line(case, path):
+    return "[h2-path] %r mode %d deep %d" % (case, path[0], path[1])
 
 
 @pytest.mark.parametrize("case", H2_CONV_CASES)
 def test_conv_on_h2_tensors_matches_float64(lib_built, case):
+    import os
     from deepgraphpose_amd import engine
     from oracle import dgp_oracle as O
     N, H, W, Cin, Cout, k, stride, rate, res_kind, y_h2 = case
+    # the path this launch takes on this device under this process's DGP_HALO, asserted through the plan query and reported
+    pad_, Ho_, Wo_ = _case_geometry(case)
+    pl = engine.conv2d_plan((N, H, W, Cin), (k, k, Cin, Cout), stride=stride, rate=rate, pad_t=pad_, pad_l=pad_, out_hw=(Ho_, Wo_), in_fmt=1,
+                            out_fmt=int(y_h2), res_fmt=int(res_kind in (2, 3)), res_stride={0: 0, 1: 1, 2: 1, 3: 2}[res_kind],
+                            res_hw={0: (0, 0), 1: (Ho_, Wo_), 2: (Ho_, Wo_), 3: (2 * Ho_ - 1, 2 * Wo_)}[res_kind])
+    print(_path_line(case, (pl["mode"], pl["deep"])))
+    assert (pl["mode"], pl["deep"]) == _path_of(case, pl["n_cu"], int(os.environ.get("DGP_HALO", "1"))), pl
     g = torch.Generator(device="cuda").manual_seed(abs(hash(case)) % (2 ** 31))
     x = torch.relu(torch.randn((N, H, W, Cin), device="cuda", generator=g)) * 3.0
     rngw = np.random.default_rng(abs(hash(case)) % (2 ** 31))
@@ -238,28 +278,44 @@ def test_reported_16_bit_tier_is_an_11_bit_version_of_the_same_network(lib_built
     assert np.abs(mu_a.cpu().numpy() - t["mu"]).max() * 8.0 < 0.25
 
 
-def test_halo_walk_on_strips_longer_than_the_ring_in_a_child_process(lib_built):
-    """DGP_HALO=2 forces the halo walk wherever the ring's capacity rule allows, i.e. also where ONE strip (128 + 2 d (W + 1) pixels) is
-    longer than the 360-pixel ring and the ring slides inside a channel chunk (by default those shapes keep the per-tap loaders)."""
+def _cases_in_a_child(indices, halo_env):
+    """the conv cases `indices` in a child pytest process under DGP_HALO = halo_env (read once per process).  Each case asserts there,
+    through the plan query, the path the restated rules give it; here the path every case REPORTED is held to what the rules give for
+    that switch on this device -- the two sides cannot drift apart.  -> {index: (mode, deep)}"""
     import os, subprocess, sys
+    from deepgraphpose_amd import engine
+    n_cu = engine.conv2d_plan((1, 1, 128, 64), (1, 1, 64, 128))["n_cu"]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DGP_HALO="2", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_h2_gpu.py"), "-q", "-m", "gpu", "-k",
-                        "test_conv_on_h2_tensors_matches_float64 and (case15 or case17 or case19)"], env=env, cwd=root,
+    env = dict(os.environ, DGP_HALO=str(halo_env), PYTHONPATH=root)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_h2_gpu.py"), "-q", "-s", "-m", "gpu", "-p", "no:cacheprovider", "-k",
+                        "test_conv_on_h2_tensors_matches_float64 and (%s)" % " or ".join("case%d" % i for i in indices)], env=env, cwd=root,
                        capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "3 passed" in r.stdout, r.stdout[-1500:] + r.stderr[-500:]
+    assert r.returncode == 0 and "%d passed" % len(indices) in r.stdout and "skipped" not in r.stdout, r.stdout[-1500:] + r.stderr[-500:]
+    paths = {i: _path_of(H2_CONV_CASES[i], n_cu, halo_env) for i in indices}
+    for i, path in paths.items():
+        print(_path_line(H2_CONV_CASES[i], path))
+        assert _path_line(H2_CONV_CASES[i], path) in r.stdout, (i, path, r.stdout[-1500:])
+    return paths, n_cu
+
+
+def test_halo_walk_on_strips_longer_than_the_ring_in_a_child_process(lib_built):
+    """DGP_HALO=2 lifts the default capacity bound: the walk also takes strips (128 + 2 d (W + 1) pixels) longer than the 360-pixel ring,
+    which then slides inside a channel chunk -- where the launch is not on the deep ring and d (W - 2) + 128 <= 352.  Of the three
+    cases, case15 misses the hard bound (360) on any chip; case17 (116 tiles) and case19 (26 tiles) walk the ring only on a chip with fewer
+    CUs than that and run the deep ring with the per-tap loaders on a full-size one, as at the default.  The forced walk at full size:
+    tests/test_halo_walk_gpu.py::test_sliding_ring_with_the_walk_forced."""
+    paths, n_cu = _cases_in_a_child((15, 17, 19), 2)
+    assert paths[15][0] == 1
+    assert paths[17] == ((3, 0) if n_cu < 116 else (1, 1)) and paths[19] == ((3, 0) if n_cu < 26 else (1, 1))
 
 
 def test_per_tap_loaders_of_the_3x3_layers_in_a_child_process(lib_built):
-    """DGP_HALO=0: the 3x3 / stride-1 layers on the per-tap LDS-DMA loaders (MODE 1) they used before the halo walk became the
-    default -- still the path of rows too wide for the pixel ring, of the 16-bit tier and of the A/B switch."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DGP_HALO="0", PYTHONPATH=root)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_h2_gpu.py"), "-q", "-m", "gpu", "-k",
-                        "test_conv_on_h2_tensors_matches_float64 and (case4 or case5 or case12 or case13 or case19)"], env=env, cwd=root,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "5 passed" in r.stdout, r.stdout[-1500:] + r.stderr[-500:]
+    """DGP_HALO=0: no launch walks the ring.  The batch-32 block4 conv2 (case10, 1200 tiles: the walk at the default) runs the
+    three-stage per-tap LDS-DMA kernel (mode 1, deep 0) the 3x3 / stride-1 layers used before the walk became the default; the cases
+    below one tile per CU run the deep per-tap kernel, as they do at the default."""
+    paths, n_cu = _cases_in_a_child((4, 5, 10, 12, 13, 19), 0)
+    assert all(mode == 1 for mode, _ in paths.values())
+    assert paths[10] == ((1, 0) if n_cu < 1200 else (1, 1))
 
 
 def test_extreme_frames_keep_parity(lib_built):
