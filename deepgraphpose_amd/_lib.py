@@ -49,7 +49,7 @@ class DgpConvDesc(C.Structure):
 class DgpConvPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "tile", "family", "mode", "cs", "dma", "deep", "ah2", "oh2", "h1", "lds", "mtiles", "ntiles", "grid",
-        "tail_ksplit", "n_main", "st_gn", "st_mc", "st_mb", "n_cu")] + [("kernel_name", C.c_char * 32)]
+        "tail_ksplit", "n_main", "st_gn", "st_mc", "st_mb", "n_cu")] + [("kernel_name", C.c_char * 32), ("w22", C.c_int32)]
 
 
 # every symbol include/dgp_hip.h declares: name -> (restype, argtypes)

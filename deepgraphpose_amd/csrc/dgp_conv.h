@@ -33,7 +33,7 @@ __device__ __forceinline__ void ls_epilogue(const ConvArgs& p, floatx16 (&acc)[T
     constexpr int LDC = WN + 4;
     const int half = lane >> 5, l31 = lane & 31;
     const int HoWo = p.Ho * p.Wo;
-    float* sC = reinterpret_cast<float*>(smem) + wave * (32 * LDC);
+    float* sC = reinterpret_cast<float*>(smem) + wave * ((M16 ? 32 * TM : 32) * LDC);      // (M16: the caller staged all 32 TM rows)
     // the wave's range slot, read NOW (see ls_epilogue_h2: nothing may wait at the end of the wave)
     unsigned slot_bits = 0u;
     if (p.out_absmax)
@@ -138,7 +138,7 @@ __device__ __forceinline__ void ls_epilogue(const ConvArgs& p, floatx16 (&acc)[T
 #pragma unroll
         for (int u = 0; u < VC; ++u) {
             const int row = my_r0 + (v0 + u) * (64 / C4);
-            const float4 a = *reinterpret_cast<const float4*>(sC + row * LDC + 4 * my_c4);
+            const float4 a = *reinterpret_cast<const float4*>(sC + ((M16 ? 32 * i : 0) + row) * LDC + 4 * my_c4);
             float4 o;
             o.x = a.x * sc4.x + bi4.x + rres[slot][u].x;
             o.y = a.y * sc4.y + bi4.y + rres[slot][u].y;
@@ -193,7 +193,7 @@ __device__ __forceinline__ void ls_store_raw(floatx16 (&acc)[TM][TN], char* smem
     constexpr int C4 = WN / 4;
     constexpr int NV = 32 * C4 / 64;
     const int half = lane >> 5, l31 = lane & 31;
-    float* sC = reinterpret_cast<float*>(smem) + wave * (32 * LDC);
+    float* sC = reinterpret_cast<float*>(smem) + wave * ((M16 ? 32 * TM : 32) * LDC);
     const int my_c4 = lane % C4, my_r0 = lane / C4;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -209,7 +209,7 @@ __device__ __forceinline__ void ls_store_raw(floatx16 (&acc)[TM][TN], char* smem
         for (int v = 0; v < NV; ++v) {
             const int row = my_r0 + v * (64 / C4);
             *reinterpret_cast<float4*>(out + (size_t)(wave_m0 + 32 * i + row) * ld + wave_n0 + 4 * my_c4) =
-                *reinterpret_cast<const float4*>(sC + row * LDC + 4 * my_c4);
+                *reinterpret_cast<const float4*>(sC + ((M16 ? 32 * i : 0) + row) * LDC + 4 * my_c4);
         }
     }
 }

@@ -86,8 +86,9 @@ __device__ __forceinline__ void ls_epilogue_h2(const ConvArgs& p, floatx16 (&acc
     constexpr int CPP = NV / VC, NQ = TM * CPP;
     const int half = lane >> 5, l31 = lane & 31;
     const int HoWo = p.Ho * p.Wo;
-    // (16x16x32 loops: the caller staged the wave's 32 rows; the 32x32x16 loops stage one 32-row pass at a time below)
-    float* sC = reinterpret_cast<float*>(smem) + wave * (32 * LDC);
+    // (16x16x32 loops: the caller staged ALL 32 TM rows of the wave tile; the 32x32x16 loops stage one 32-row pass at a time below)
+    constexpr int SROWS = M16 ? 32 * TM : 32;      // rows of a wave's staging tile
+    float* sC = reinterpret_cast<float*>(smem) + wave * (SROWS * LDC);
     const __amdgpu_buffer_rsrc_t rs_res =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.in), 0, p.res ? (int)p.res_bytes : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
@@ -180,7 +181,7 @@ __device__ __forceinline__ void ls_epilogue_h2(const ConvArgs& p, floatx16 (&acc
 #pragma unroll
         for (int u = 0; u < VC; ++u) {
             const int row = my_r0 + (v0 + u) * RPI;
-            const float* srow = sC + row * LDC + 8 * my_c8;
+            const float* srow = sC + ((M16 ? 32 * i : 0) + row) * LDC + 8 * my_c8;
             const float4 a0 = *reinterpret_cast<const float4*>(srow);
             const float4 a1 = *reinterpret_cast<const float4*>(srow + 4);
             float o[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -294,10 +295,12 @@ __device__ __forceinline__ void ls_epilogue_h2(const ConvArgs& p, floatx16 (&acc
 constexpr int HALO_C = 360;                       // ring capacity in pixels (multiple of 8)
 constexpr int HALO_ZERO = HALO_C * 128;           // 1 KiB of zeros: what masked taps read (k-group constants up to 528, low cell at +256)
 constexpr int HALO_TBL = HALO_ZERO + 1024;        // three stages of the address table: [wave][row & 15][row block] x 4 B = 512 B each (step s: stage s % 3;
-                                                  // written two steps ahead, read one step ahead: the stage being written is never one being read)
+                                                  // written two steps ahead, read one step ahead: the stage being written is never one being read).
+                                                  // 2 x 2 compute waves: [wave row][row & 15][4 row blocks], the same 512 B
 constexpr int HALO_B0 = HALO_TBL + 2048;          // two stages of weight cells behind it: 49 152 + 32 768 = 80 KB, two workgroups per CU
 static_assert(HALO_B0 == 49152, "80 KB per workgroup");
-template <int BM, int BN, int NT, int BK, int CW, int MODE = 0, bool CS = false, bool DMA = false, bool AH2 = false, bool OH2 = false, bool DEEP = false, bool H1 = false>
+template <int BM, int BN, int NT, int BK, int CW, int MODE = 0, bool CS = false, bool DMA = false, bool AH2 = false, bool OH2 = false, bool DEEP = false, bool H1 = false,
+          bool W22 = false>
 __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : ((BK == 16 || NT == 2) ? 4 : 2)) void conv_igemm_split_ls(const ConvArgs p) {
     static_assert(MODE != 3 || (DMA && AH2 && OH2 && BM == 128 && BN == 128 && CW == 4 && !DEEP), "halo walk: H2 / H1 tensors, LDS-DMA, 128 x 128 tiles");
     static_assert(!DEEP || (DMA && BN == 128 && BM == 128), "deep ring: LDS-DMA kernels with 128 x 128 tiles");
@@ -305,9 +308,12 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : ((BK == 16 || NT == 2)
     static_assert(BM == 128, "128-row tiles");
     static_assert(!AH2 || CS, "pre-split A operand: compute-side-split kernels only");
     static_assert(!OH2 || AH2, "H2 output: kernels with H2 input only (the stem writes fp32, the pool converts)");
+    static_assert(!W22 || (CS && AH2 && DMA && BN == 128 && CW == 4), "2 x 2 compute waves: cell input, LDS-DMA image, 128 x 128 tiles");
     // compute waves: 2 x (CW / 2) over the tile; with the compute-side split 4 x 1 (each wave owns 32 rows and ALL columns, so no
-    // two waves split the same A rows -- half the split arithmetic for 25 % more B fragment reads)
-    constexpr int WAVES_M = (CS && CW == 4) ? 4 : 2;
+    // two waves split the same A rows -- half the split arithmetic for 25 % more B fragment reads).  W22 (cell inputs, where that
+    // arithmetic is gone: DGP_SPLIT is a register copy): 2 x 2 again, 64 x 64 wave tiles -- 8 A cells + 8 B fragments per wave and K-step
+    // instead of 4 + 16 for the same 48 MFMAs, a fifth fewer LDS reads (DGP_WAVE_2X2, split_decide)
+    constexpr int WAVES_M = (CS && CW == 4 && !W22) ? 4 : 2;
     constexpr int WAVES_N = CW / WAVES_M;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
     constexpr int TM = WM / 32, TN = WN / 32;
@@ -499,7 +505,8 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : ((BK == 16 || NT == 2)
             };
             if (lw < 3) {
                 // table entry e = [wave w][l15][row block i] <-> tile row 32 w + 16 i + l15; this lane's entry: e = t (waves 0, 1)
-                const int te = t & 127, trow = (te >> 5) * 32 + (te & 1) * 16 + ((te >> 1) & 15);
+                // (W22: [wave row h][l15][row block i] <-> tile row 64 h + 16 i + l15 -- a compute lane's four entries are one 16-byte read)
+                const int te = t & 127, trow = W22 ? (te >> 6) * 64 + (te & 3) * 16 + ((te >> 2) & 15) : (te >> 5) * 32 + (te & 1) * 16 + ((te >> 1) & 15);
                 unsigned tmask = 0;                                      // bit tp: tap tp of this row's pixel lies inside the image
                 if (lw < 2) {
                     const int m = m0 + trow;
@@ -853,10 +860,115 @@ __global__ __launch_bounds__(64 * (CW + 4), CW == 8 ? 6 : ((BK == 16 || NT == 2)
 #endif
     // 16x16x32 MFMAs in the pipelined loop of the 32 x 128 wave tile: the same FLOPs, LDS bytes and register reads as the 32x32x16
     // shape in twice as many, half as long matrix instructions -- +5.3 % end to end (block4 3x3: 0.499 -> 0.453 ms)
-    constexpr bool M16 = CS && TM == 1 && (TN == 4 || (TN == 2 && DMA)) && NT == 2 && BK == 32;      // (32 x 64 wave tiles: DMA images only)
-    static_assert(!DMA || (TM == 1 && (TN == 4 || TN == 2)), "DMA image is read by the pipelined loops only");
+    constexpr bool M16 = CS && ((TM == 1 && (TN == 4 || (TN == 2 && DMA))) || W22) && NT == 2 && BK == 32;      // (32 x 64 wave tiles: DMA images only)
+    static_assert(!DMA || W22 || (TM == 1 && (TN == 4 || TN == 2)), "DMA image is read by the pipelined loops only");
     static_assert(!(DMA && AH2) || M16, "pre-split A + DMA image: 16x16x32 loop only");
-    if constexpr (M16) {
+    if constexpr (W22) {
+        // The 64 x 64 wave tile (cell inputs): 4 x 4 accumulator blocks of 16 x 16.  The step's 8 B fragments (4 column blocks x low / high
+        // plane) stay in registers, the A cells go through a ring of two row blocks: row block i + 1 is read while block i's 12 MFMAs
+        // issue.  Per accumulator and step the products are ah bl, al bh, ah bh (H1: a_odd b_odd, a_even b_even) in the order of the
+        // 32 x 128 loop below, so both layouts give the same bits.  The barrier sits in front of the LAST row block's MFMAs: every LDS
+        // read of the step has been issued (and, behind the barrier's wait, has landed) by then; behind it the next step's first A row
+        // block goes into the free ring slot and its B fragments into their slots as the last row block's MFMAs release them.
+        // MODE 3: the four ring cells of a lane's rows are ONE 16-byte entry of the address table; the table of step s + 1 is read in
+        // step s in front of the barrier (written before barrier s, overwritten behind barrier s + 2) and becomes addresses behind it.
+        static_assert(TM == 2 && TN == 2 && (NSB == 2 || DEEP), "2 x 2 compute waves of 64 x 64");
+        typedef float floatx4 __attribute__((ext_vector_type(4)));
+        const int l15 = lane & 15, g = lane >> 4;
+        floatx4 c[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+        // DMA image: chunk ch of row r in slot ch ^ ((r >> 1) & 7) (the same for r + 16 i); this lane wants chunks 2 g, 2 g + 1
+        const unsigned a_row0 = (unsigned)((wave_m0 + l15) * 128 + (((2 * g) ^ (((wave_m0 + l15) >> 1) & 7)) << 4));
+        unsigned a_cur = a_row0;
+        int sa_c = 0, sb_c = 0, db = B_CELLS;
+        const unsigned lane_c = (unsigned)((g >> 1) * 512 + (g & 1) * 16);       // MODE 3: k-group g's constant (see the 32 x 128 loop)
+        const char* tbl = smem + HALO_TBL + ((wave >> 1) * 64 + l15 * 4) * 4;    // this lane's four entries of a table stage
+        int tst = 1;                                                             // stage of the table to read next
+        u32x4 adr, tq;
+        (void)a_cur; (void)sa_c; (void)sb_c; (void)lane_c; (void)tbl; (void)tst; (void)adr; (void)tq;
+        const uint4* B = sB + wave_n0 + l15 + g * LDB;
+        uint4 ah[2], al[2], bl[4], bh[4];
+        auto mma = [](const uint4& x, const uint4& y, floatx4 cc) {
+            return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, x), __builtin_bit_cast(half8, y), cc, 0, 0, 0);
+        };
+        if constexpr (MODE == 3) {      // (barrier #0 above: the zero cells and the tables of steps 0 and 1 are written)
+            tq = *reinterpret_cast<const u32x4*>(tbl);
+            adr = tq + lane_c;
+        }
+#define DGP_FENCE() __builtin_amdgcn_sched_barrier(0)
+#define DGP_RA(I) do { if constexpr (MODE == 3) {                                                                   \
+            ah[(I) & 1] = *reinterpret_cast<const uint4*>(smem + adr[I]);                                          \
+            al[(I) & 1] = *reinterpret_cast<const uint4*>(smem + adr[I] + 256);                                    \
+        } else {                                                                                                   \
+            ah[(I) & 1] = *reinterpret_cast<const uint4*>(smem + a_cur + (I) * 2048);                              \
+            al[(I) & 1] = *reinterpret_cast<const uint4*>(smem + (a_cur ^ 16u) + (I) * 2048);                      \
+        } } while (0)
+#define DGP_RB(J) do { bl[J] = B[KG * LDB + 16 * (J)]; bh[J] = B[16 * (J)]; } while (0)
+#define DGP_MM(I, J) do {                                                                                           \
+        if constexpr (H1) { c[I][J] = mma(al[(I) & 1], bl[J], c[I][J]); c[I][J] = mma(ah[(I) & 1], bh[J], c[I][J]); }              \
+        else { c[I][J] = mma(ah[(I) & 1], bl[J], c[I][J]); c[I][J] = mma(al[(I) & 1], bh[J], c[I][J]);             \
+               c[I][J] = mma(ah[(I) & 1], bh[J], c[I][J]); } } while (0)
+#define DGP_ROW(I) do { DGP_MM(I, 0); DGP_MM(I, 1); DGP_MM(I, 2); DGP_MM(I, 3); DGP_FENCE(); } while (0)
+        DGP_RA(0);
+        DGP_RB(0); DGP_RB(1); DGP_RB(2); DGP_RB(3);
+        DGP_FENCE();
+        for (int ks = 0; ks < nks; ++ks) {
+            const bool more = ks + 1 < nks;
+            DGP_RA(1); DGP_FENCE();
+            DGP_ROW(0);
+            DGP_RA(2); DGP_FENCE();
+            DGP_ROW(1);
+            DGP_RA(3);
+            if constexpr (MODE == 3) {
+                if (more) { tq = *reinterpret_cast<const u32x4*>(tbl + tst * 512); tst = tst == 2 ? 0 : tst + 1; }
+            }
+            DGP_FENCE();
+            DGP_ROW(2);
+            DIAG_STAMP(e2);
+            __syncthreads();
+            DIAG_STAMP(e3);
+#ifdef DGP_DIAG
+            acc_mf += e2 - e1; acc_ba += e3 - e2; e1 = e3;
+#endif
+            if constexpr (MODE == 3) adr = tq + lane_c;
+            else { sa_c = sa_c == NSA - 1 ? 0 : sa_c + 1; a_cur = a_row0 + (unsigned)(sa_c * (A_CELLS * 16)); }
+            if constexpr (NSB == 2) { B += db; db = -db; } else { B += db; if (++sb_c == NSB) { sb_c = 0; B -= NSB * B_CELLS; } }
+            if (more) DGP_RA(0);
+            DGP_FENCE();
+            DGP_MM(3, 0); DGP_FENCE();
+            if (more) DGP_RB(0);
+            DGP_FENCE();
+            DGP_MM(3, 1); DGP_FENCE();
+            if (more) DGP_RB(1);
+            DGP_FENCE();
+            DGP_MM(3, 2); DGP_FENCE();
+            if (more) DGP_RB(2);
+            DGP_FENCE();
+            DGP_MM(3, 3); DGP_FENCE();
+            if (more) DGP_RB(3);
+            DGP_FENCE();
+        }
+#undef DGP_FENCE
+#undef DGP_RA
+#undef DGP_RB
+#undef DGP_MM
+#undef DGP_ROW
+        {      // stage the wave's 64 rows (the epilogues' M16 contract: block (i, j) register r of lane l = row 16 i + 4 (l >> 4) + r, column 16 j + (l & 15))
+            constexpr int LDCW = WN + 4;
+            float* sCw = reinterpret_cast<float*>(smem) + wave * (64 * LDCW);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sCw[(16 * i + 4 * g + r) * LDCW + 16 * j + l15] = c[i][j][r];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+    } else if constexpr (M16) {
         // One K-step = one MFMA depth (32).  Per step a wave splits its 2 x 16 rows (A: two fp32 chunks per lane and row block ->
         // a_hi / a_lo), and walks 16 B fragments f = (column block j = f / 2, plane: low first) through a ring of four register
         // quads, three fragments ahead of the MFMAs: low plane -> a_hi b_lo for both row blocks, high plane -> a_lo b_hi, a_hi b_hi.
@@ -1385,23 +1497,34 @@ static hipError_t split_decide(const ConvArgs& a, int n_cu, SplitPath& p) {
     p.mode = halo ? 3 : mode;
     p.cs = cs; p.dma = dma; p.deep = deep;
     p.ah2 = ah2; p.oh2 = oh2; p.h1 = h1;
+    // -- compute-wave layout of the cell-input LDS-DMA kernels on 128 x 128 tiles: 2 x 2 waves of 64 x 64 (see the kernel) instead of 4 x 1
+    // waves of 32 x 128.  Same bits either way.  A/B switch DGP_WAVE_2X2=0.  Every walk takes it: measured per layer at batch 32 (one
+    // stream, minimum of three alternating runs per layout, sums of the 128 x 128 launches, 4 x 1 -> 2 x 2): pointwise (19 launches)
+    // 2.789 -> 2.735 ms (-1.9 %; block4 conv3 -2.4 .. -3.7 %, block3 conv1 / conv3 -0.2 .. -4.8 %, block2 conv3+shortcut +0.4 %), halo
+    // walk (12) 2.209 -> 2.197 ms (-0.6 %; single layers -3.0 .. +1.9 %, the spread of a repeated row), per-tap (block2/unit_4 conv2)
+    // 0.0505 -> 0.0494 ms.  No walk is slower, so there is no per-mode rule; end to end +1.6 % at the power cap (EXPERIMENTS.md, W)
+    static const int w22_env = dgp_env("DGP_WAVE_2X2", 1);
+    p.w22 = w22_env && T::CAN_DEEP && dma && ah2;
     // -- LDS: the K loop's stages or the epilogue's staging tile, whichever is larger
     const size_t b_stage = (size_t)T::NP * T::KG * T::BN * 16;
     const size_t lds_loop = halo ? (size_t)HALO_B0 + 2 * b_stage                      // pixel ring + tables, 2 B stages = 80 KB
                           : deep ? (size_t)5 * T::BM * 8 * 16 + 4 * b_stage           // 5 A stages + 4 B stages = 144 KB
                           : dma  ? (size_t)3 * T::BM * 8 * 16 + 2 * b_stage           // 3 A stages + 2 B stages = 80 KB
                                  : (size_t)2 * (T::NP * T::KG * (T::BM + (T::BK == 32 ? 4 : 8)) + T::NP * T::KG * (T::BN + 4)) * 16;
-    const size_t lds_epi = (size_t)T::CW * 32 * (T::BN + 4) * 4;        // (upper bound: 4 x 1 compute-wave layout of the CS kernels)
+    // (staging tiles of the compute waves: 32 rows x all columns on the 4 x 1 layout, which bounds the 2 x (CW / 2) layouts' 32 x BN / 2
+    //  from above; the 2 x 2 waves of 64 x 64 stage all 64 rows)
+    const size_t lds_epi = p.w22 ? (size_t)T::CW * 64 * (T::BN / 2 + 4) * 4 : (size_t)T::CW * 32 * (T::BN + 4) * 4;
     p.lds = lds_loop > lds_epi ? lds_loop : lds_epi;
     return hipSuccess;
 }
 
-// Stage 2: the instantiation of a path.  split_inst is the one spelling of the kernel; split_kernel names
+// Stage 2: the instantiation of a path.  split_inst is the one spelling of the kernel; split_kernel and its helper
+// split_kernel_cells128 (the cell-input LDS-DMA kernels of the 128 x 128 tiles, once per compute-wave layout W22) together name
 // every reachable combination of flags once, walk012 / walk12 the loader walks of one
 struct SplitKernel { ConvKernel fn; hipError_t (*ensure_lds)(size_t); };
-template <class T, int MODE, bool CS = false, bool DMA = false, bool AH2 = false, bool OH2 = false, bool DEEP = false, bool H1 = false>
+template <class T, int MODE, bool CS = false, bool DMA = false, bool AH2 = false, bool OH2 = false, bool DEEP = false, bool H1 = false, bool W22 = false>
 static SplitKernel split_inst() {
-    constexpr ConvKernel k = conv_igemm_split_ls<T::BM, T::BN, T::NT, T::BK, T::CW, MODE, CS, DMA, AH2, OH2, DEEP, H1>;
+    constexpr ConvKernel k = conv_igemm_split_ls<T::BM, T::BN, T::NT, T::BK, T::CW, MODE, CS, DMA, AH2, OH2, DEEP, H1, W22>;
     return {k, &ensure_dynamic_lds<k>};
 }
 template <class T, bool... FLAGS>
@@ -1409,9 +1532,27 @@ static SplitKernel walk012(int mode) { return mode == 2 ? split_inst<T, 2, FLAGS
 template <class T, bool... FLAGS>
 static SplitKernel walk12(int mode) { return mode == 2 ? split_inst<T, 2, FLAGS...>() : split_inst<T, 1, FLAGS...>(); }
 
+// the cell-input LDS-DMA kernels of a 128 x 128 tile on one compute-wave layout (W22: 2 x 2 waves of 64 x 64, else 4 x 1 of 32 x 128)
+template <class T, bool W22>
+static SplitKernel split_kernel_cells128(const SplitPath& p) {
+    constexpr bool Y = true, N = false;                                       // flags: CS DMA AH2 OH2 DEEP H1 W22
+    if (p.h1) {                                                               // 16-bit tier
+        if (!p.oh2) return split_inst<T, 2, Y, Y, Y, N, N, Y, W22>();
+        if (p.mode == 3) return split_inst<T, 3, Y, Y, Y, Y, N, Y, W22>();
+        return walk12<T, Y, Y, Y, Y, N, Y, W22>(p.mode);
+    }
+    if (p.deep) {
+        if (p.oh2) return walk12<T, Y, Y, Y, Y, Y, N, W22>(p.mode);
+        return split_inst<T, 2, Y, Y, Y, N, Y, N, W22>();
+    }
+    if (p.mode == 3) return split_inst<T, 3, Y, Y, Y, Y, N, N, W22>();
+    if (p.oh2) return walk12<T, Y, Y, Y, Y, N, N, W22>(p.mode);
+    return split_inst<T, 2, Y, Y, Y, N, N, N, W22>();
+}
+
 template <class T>
 static SplitKernel split_kernel(const SplitPath& p) {
-    constexpr bool Y = true, N = false;                                       // flags: CS DMA AH2 OH2 DEEP H1
+    constexpr bool Y = true, N = false;                                       // flags: CS DMA AH2 OH2 DEEP H1 (W22: split_kernel_cells128 only)
     if (!p.cs) return walk012<T>(p.mode);                                     // loaders split fp32 operands
     if constexpr (T::CAN_CS) {
         if (!p.dma) {                                                         // compute waves split; global loads through registers
@@ -1419,19 +1560,14 @@ static SplitKernel split_kernel(const SplitPath& p) {
             if (p.oh2)  return walk012<T, Y, N, Y, Y>(p.mode);
             return split_inst<T, 2, Y, N, Y, N>();
         }
+        if constexpr (T::CAN_DEEP) {                                          // cells in, 128 columns: both compute-wave layouts
+            if (p.ah2) return p.w22 ? split_kernel_cells128<T, Y>(p) : split_kernel_cells128<T, N>(p);
+            if (p.deep) return walk12<T, Y, Y, N, N, Y>(p.mode);
+        }
         if constexpr (T::CAN_DMA) {
-            if (p.h1) {                                                       // 16-bit tier
+            if (p.h1) {                                                       // 16-bit tier, 64 columns
                 if (!p.oh2) return split_inst<T, 2, Y, Y, Y, N, N, Y>();
-                if constexpr (T::CAN_DEEP) { if (p.mode == 3) return split_inst<T, 3, Y, Y, Y, Y, N, Y>(); }
                 return walk12<T, Y, Y, Y, Y, N, Y>(p.mode);
-            }
-            if constexpr (T::CAN_DEEP) {
-                if (p.deep) {
-                    if (!p.ah2) return walk12<T, Y, Y, N, N, Y>(p.mode);
-                    if (p.oh2)  return walk12<T, Y, Y, Y, Y, Y>(p.mode);
-                    return split_inst<T, 2, Y, Y, Y, N, Y>();
-                }
-                if (p.mode == 3) return split_inst<T, 3, Y, Y, Y, Y>();
             }
             if (!p.ah2) return walk12<T, Y, Y>(p.mode);
             if (p.oh2)  return walk12<T, Y, Y, Y, Y>(p.mode);

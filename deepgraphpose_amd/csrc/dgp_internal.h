@@ -96,6 +96,7 @@ struct SplitPath {
     int mode;              // loader walk: 0 everything at run time, 1 per-tap, 2 pointwise, 3 halo ring
     bool cs, dma, deep;    // compute-side split (the weights come as pre-split cells), LDS-DMA loaders, deep DMA ring
     bool ah2, oh2, h1;     // input in cells, output in cells, the cells are H1 (16-bit tier)
+    bool w22;              // compute waves 2 x 2 over the tile (64 x 64 wave tiles) instead of 4 x 1 (32 x 128): cell-input LDS-DMA kernels, DGP_WAVE_2X2
     size_t lds;
 };
 

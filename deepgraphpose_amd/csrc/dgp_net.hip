@@ -1558,6 +1558,7 @@ int dgp_conv2d_plan(const dgp_conv_desc* d, int32_t in_fmt, int32_t out_fmt, int
     out->tile = pl.tile; out->family = (int32_t)pl.family;
     out->mode = pl.path.mode; out->cs = pl.path.cs; out->dma = pl.path.dma; out->deep = pl.path.deep;
     out->ah2 = pl.path.ah2; out->oh2 = pl.path.oh2; out->h1 = pl.path.h1; out->lds = (int32_t)pl.path.lds;
+    out->w22 = pl.path.w22;
     out->mtiles = pl.mtiles; out->ntiles = pl.ntiles; out->grid = (int32_t)pl.grid;
     out->tail_ksplit = pl.tail_ksplit; out->n_main = pl.n_main; out->st_gn = pl.st_gn; out->st_mc = pl.st_mc; out->st_mb = pl.st_mb;
     out->n_cu = cus;

@@ -354,6 +354,7 @@ typedef struct dgp_conv_plan {
     int32_t st_gn, st_mc, st_mb;     /* supertile order (st_gn 0: plain): column tiles per group, row tiles per chunk and per band */
     int32_t n_cu;                    /* compute units planned for */
     char    kernel_name[32];
+    int32_t w22;                     /* split family, cell inputs: 1 = 2 x 2 compute waves of 64 x 64, 0 = 4 x 1 of 32 x 128 (DGP_WAVE_2X2) */
 } dgp_conv_plan;
 int  dgp_conv2d_plan(const dgp_conv_desc* d, int32_t in_fmt, int32_t out_fmt, int32_t res_fmt, int32_t have_ranges, int32_t have_cells,
                      size_t slab_bytes, int32_t force_tile, int32_t n_cu, dgp_conv_plan* out);

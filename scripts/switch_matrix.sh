@@ -21,7 +21,7 @@ run() {   # name, env assignments...
   done
 }
 run "defaults" DGP_NOP=1
-for s in DGP_H2=0 DGP_CHAIN=0 DGP_CHAIN_H1=0 DGP_HALO=0 DGP_HALO=2 DGP_FUSE_SHORTCUT=0 DGP_XOUT_SUBSAMPLE=0 DGP_TAIL_SPLIT=0 DGP_TAIL_SPLIT=2 DGP_TRAIN_HEADS_H1=0 \
+for s in DGP_H2=0 DGP_CHAIN=0 DGP_CHAIN_H1=0 DGP_HALO=0 DGP_HALO=2 DGP_WAVE_2X2=0 DGP_FUSE_SHORTCUT=0 DGP_XOUT_SUBSAMPLE=0 DGP_TAIL_SPLIT=0 DGP_TAIL_SPLIT=2 DGP_TRAIN_HEADS_H1=0 \
          DGP_SOFTARGMAX_STREAM=1 DGP_LOSS_STREAM=1 DGP_CONV2D_CELLS=1; do run "$s" $s; done
 if [ "${1:-}" = pairs ]; then
   run "CHAIN=0 HALO=0" DGP_CHAIN=0 DGP_HALO=0
